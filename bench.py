@@ -16,7 +16,10 @@ the same 1080p / 4K frame are dealt round-robin to the ranks, as the reference's
 and textures are the synthetic stand-ins of scenes/gen_assets.py.  --spp overrides the config's spp (a full
 C5 frame is 17 Gsamples).
 
-One JSON line on rank 0; see DESIGN.md "Measurement" for the roofline / cpu_baseline definitions.
+A plain run sets up, warms up, times --steps steps and prints one JSON line on rank 0.  --full adds what takes runs of its
+own: the CPU baseline (cpu_baseline) and, on the default one-GPU line, one full-spp step of C3 / C4 / C5 (other_configs).
+--dump-outputs DIR writes the arrays of the last timed step as DIR/<name>.npy (dump_outputs).  See DESIGN.md "Measurement"
+for the roofline / cpu_baseline definitions.
 """
 import argparse
 import json
@@ -35,6 +38,7 @@ import numpy as np  # noqa: E402
 BYTES_PER_CAST = 144   # ray 2x32 B + hit 2x16 B + path state 2x24 B
 BYTES_PER_SAMPLE = 24  # radiance accumulate read + write
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8 TB/s
+DUMP_BYTES = 64 * 10**6  # --dump-outputs: every array together, .npy headers included
 
 
 CONFIGS = {   # BASELINE.json configs[1..4]
@@ -54,6 +58,23 @@ def frame_size(n_gpus, base_w, base_h, strong=False):
         return base_w, base_h
     s = math.sqrt(n_gpus)
     return int(round(base_w * s)), int(round(base_h * s))
+
+
+def dump_outputs(dirname, frame):
+    """The arrays a caller of the timed path receives from its last step: radiance [H,W,3], first-hit depth [H,W] and samples
+    per pixel [H,W], as float32 DIR/rgb.npy, depth.npy, samples.npy.  A frame beyond DUMP_BYTES (4K) is written as a fixed,
+    seeded sample of its pixels, the same pixels in every array, with their row-major indices in pixel_index.npy (float64)."""
+    rgb, depth, ns = (t.cpu().numpy() for t in frame)
+    arrays = {"rgb": rgb.astype(np.float32), "depth": depth.astype(np.float32), "samples": ns.astype(np.float32)}
+    npix = depth.size
+    if npix * 20 > DUMP_BYTES - 10**6:
+        k = (DUMP_BYTES - 4 * 10**6) // 28   # 20 B of arrays + an 8-byte index per pixel
+        idx = np.sort(np.random.default_rng(0x51A7A7).choice(npix, k, replace=False))
+        arrays = {"rgb": arrays["rgb"].reshape(npix, 3)[idx], "depth": arrays["depth"].reshape(npix)[idx],
+                  "samples": arrays["samples"].reshape(npix)[idx], "pixel_index": idx.astype(np.float64)}
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a))
 
 
 def cpu_baseline(scene_xml, width, height, spp, seed):
@@ -205,7 +226,7 @@ def main():
                     help="integrator for scenes beyond LDS (same bits either way; auto = timed probe, see include/qaray_hip.h)")
     ap.add_argument("--bounce", type=int, default=5)
     ap.add_argument("--seed", type=lambda s: int(s, 0), default=0x51A7A7)
-    ap.add_argument("--cpu-spp", type=int, default=128, help="spp of the bounded CPU-baseline sample (0 = skip)")
+    ap.add_argument("--cpu-spp", type=int, default=128, help="with --full: spp of the bounded CPU-baseline sample (0 = skip)")
     ap.add_argument("--save-png", default=None, help="rank 0: write the last frame through FrameBuffer")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="gloo: rehearsal of the N>1 path on a box with fewer GPUs than ranks (ranks share devices, "
@@ -219,7 +240,12 @@ def main():
                     help="create the process group and run broadcast + gather with ONE rank too (the RCCL path on a one-GPU box; "
                          "launch under torch.distributed.run --nproc-per-node 1)")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the one full-spp step of BASELINE's c3 / c4 / c5 that the default N=1 line carries in 'other_configs'")
+                    help="with --full: skip the one full-spp step of BASELINE's c3 / c4 / c5 that the default N=1 line carries in 'other_configs'")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the CPU baseline ('cpu_baseline') and, on the default N=1 line, "
+                         "BASELINE's c3 / c4 / c5 ('other_configs')")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0: write the arrays of the last timed step as DIR/<name>.npy (float32; a seeded pixel sample beyond 64 MB)")
     args = ap.parse_args()
     cfg = CONFIGS[args.config or "c2"]
     strong = bool(args.config) and cfg["strong"]
@@ -338,6 +364,8 @@ def main():
     samples, casts_n, casts_s = (float(v) for v in local.tolist())
 
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, full)
         msamples = samples / elapsed * 1e-6
         ms_per_step = elapsed / args.steps * 1e3
         # roofline of the dominant (only) kernel, rank 0's launches: ALGORITHMIC bytes per launch /
@@ -404,19 +432,8 @@ def main():
                                                  "the counters also see Infinity-Cache hits; measured on build " + str(best[0].get("build", "?")) + ")")
         if world == 1:
             add_compute_side(out["roofline"], os.path.basename(scene_xml), W, H, args.spp)
-        if world == 1 and args.cpu_spp > 0:
+        if args.full and world == 1 and args.cpu_spp > 0:
             out["cpu_baseline"] = cpu_baseline(scene_xml, W, H, args.cpu_spp, args.seed)
-        # the default one-GPU line also carries ONE full-spp step of BASELINE's other three configs (the driver only runs this command)
-        default_line = (world == 1 and not collective and args.config is None and headline and (args.spp, W, H) == (512, 1920, 1080)
-                        and not args.photon_map and args.pipeline == "auto")
-        if default_line and not args.no_other_configs:
-            subprocess.run([sys.executable, os.path.join(ROOT, "scenes", "gen_assets.py")], check=True, stdout=subprocess.DEVNULL)
-            out["other_configs"] = {}
-            for tag in ("c3", "c4", "c5"):
-                try:
-                    out["other_configs"][tag] = other_config(ctx, tag, args, torch, hip, qd, load_scene_blob, SCENES_DIR, device)
-                except Exception as e:   # never lose the headline line to a side measurement
-                    out["other_configs"][tag] = {"error": repr(e)}
         if collective:
             out["collectives"] = {"backend": args.backend, "world": world, "broadcast": "flat scene blob (uint8)",
                                   "gather": "one flat float32 buffer per rank: rgb | depth | sample counts (Renderer_MPI.cpp:194-207)"}
@@ -433,6 +450,18 @@ def main():
             fb.save_image(args.save_png if args.save_png.endswith(".png") else prefix + "colorBuffer.png")
             fb.save_z_image(prefix + "depthBuffer.png")
             fb.save_sample_count_image(prefix + "sampleBuffer.png")
+        # --full, default one-GPU line: ONE full-spp step of BASELINE's other three configs.  Last, because it uploads other
+        # scenes into ctx, which --check renders again.
+        default_line = (world == 1 and not collective and args.config is None and headline and (args.spp, W, H) == (512, 1920, 1080)
+                        and not args.photon_map and args.pipeline == "auto")
+        if args.full and default_line and not args.no_other_configs:
+            subprocess.run([sys.executable, os.path.join(ROOT, "scenes", "gen_assets.py")], check=True, stdout=subprocess.DEVNULL)
+            out["other_configs"] = {}
+            for tag in ("c3", "c4", "c5"):
+                try:
+                    out["other_configs"][tag] = other_config(ctx, tag, args, torch, hip, qd, load_scene_blob, SCENES_DIR, device)
+                except Exception as e:   # never lose the headline line to a side measurement
+                    out["other_configs"][tag] = {"error": repr(e)}
         print(json.dumps(out), flush=True)
     if collective:
         dist.destroy_process_group()

@@ -7,7 +7,7 @@ mkdir -p $O
 export TMPDIR=/tmp
 cd $R
 python3 scenes/gen_assets.py > /dev/null
-python3 bench.py --steps 5 --warmup 1 > $O/bench_c2.json 2> $O/bench_c2.err
+python3 bench.py --full --steps 5 --warmup 1 > $O/bench_c2.json 2> $O/bench_c2.err
 python3 bench.py --config c3 --steps 2 --warmup 1 --cpu-spp 0 > $O/bench_c3.json 2> /dev/null
 python3 bench.py --config c4 --steps 1 --warmup 1 --cpu-spp 0 > $O/bench_c4.json 2> /dev/null
 echo "c2-c4 done" > $O/progress.txt

@@ -7,11 +7,11 @@ export TMPDIR=/tmp
 cd $R
 python3 scenes/gen_assets.py > /dev/null
 # 1. bench lines (default workload first, then the other configs at their BASELINE spp)
-python3 bench.py --steps 5 --warmup 1 > $O/bench_c2.json 2> $O/bench_c2.err
-python3 bench.py --config c3 --steps 2 --warmup 1 --cpu-spp 2 > $O/bench_c3.json 2> $O/bench_c3.err
-python3 bench.py --config c4 --steps 1 --warmup 1 --cpu-spp 1 > $O/bench_c4.json 2> $O/bench_c4.err
+python3 bench.py --full --steps 5 --warmup 1 > $O/bench_c2.json 2> $O/bench_c2.err
+python3 bench.py --full --config c3 --steps 2 --warmup 1 --cpu-spp 2 > $O/bench_c3.json 2> $O/bench_c3.err
+python3 bench.py --full --config c4 --steps 1 --warmup 1 --cpu-spp 1 > $O/bench_c4.json 2> $O/bench_c4.err
 echo "c2-c4 done" > $O/progress.txt
-python3 bench.py --config c5 --steps 1 --warmup 1 --cpu-spp 1 > $O/bench_c5.json 2> $O/bench_c5.err
+python3 bench.py --full --config c5 --steps 1 --warmup 1 --cpu-spp 1 > $O/bench_c5.json 2> $O/bench_c5.err
 echo "c5 done" >> $O/progress.txt
 python3 bench.py --config c5 --steps 1 --warmup 0 --cpu-spp 0 --spp 256 --pipeline mega > $O/bench_c5_mega_256spp.json 2> /dev/null
 python3 bench.py --config c5 --steps 1 --warmup 0 --cpu-spp 0 --spp 256 --pipeline staged > $O/bench_c5_staged_256spp.json 2> /dev/null
