@@ -7,7 +7,7 @@
 #include <string>
 #include <vector>
 
-#include "qa_scene_dev.h"
+#include "qa_scene_build.h"
 #include "qa_wf_types.h"
 #include "qaray_hip.h"
 
@@ -83,8 +83,8 @@ struct qa_ctx {
   std::vector<unsigned char> hostBlob;
   unsigned char *dBlob = nullptr;
   std::vector<void *> sceneAllocs;  // derived arrays
-  std::vector<DMesh> hostMeshes;    // host copy of the device mesh table
   DScene ds{};
+  ScenePlan plan;                   // what the upload decided (qa_scene_build.h)
   bool haveScene = false;
   float *dHalton = nullptr;
   int haltonCount = 0;
@@ -114,28 +114,18 @@ struct qa_ctx {
   int blocksPerCU = 0, blocksPerCUAuto = 2, threads = QA_BLOCK;  // 0 = use the occupancy-derived value
   void (*kernel)(const DScene, const RenderParams) = nullptr;
   void (*kernelStats)(const DScene, const RenderParams) = nullptr;
-  bool resident = false, textured = false, area = false;
-  int syncAuto = 0;
   bool csMany = false;   // the cooperative kernel's MANY variant (more shadow-casting lights than one batch)
   bool tileOrder = true;        // centre-first tile order (QA_NO_TILE_ORDER=1 turns it off)
   uint32_t *dOrder = nullptr;   // tile launch order of the last region shape
   uint64_t orderKey = 0;
   int syncSamples = -1;  // -1: decide per scene (SelectKernel), 0/1 forced by QA_SYNC
-  uint32_t stackDepth = 32;
-  size_t ldsBytes = 0;
   // photon / caustics maps (qa_photon.hip); valid until the next scene upload or qa_photon_maps_clear
   bool photonReady = false;
   KernelFn kernelPm = nullptr, kernelPmStats = nullptr;
   // the megakernel with cooperative mesh walks (qa_kernel_cs.h): global-memory scenes without area lights
   KernelFn kernelCs = nullptr;
-  bool csFits = false;          // the scene fits qa_integrate_cs's limits (20-bit scene-wide node / triangle indices, <= 256 nodes, ...)
   size_t ldsBytesCs = 0;
-  const uint4 *csNodesDev = nullptr, *csTrisDev = nullptr, *csLeafBoxDev = nullptr;   // scene allocations (freed with the scene)
-  const CsInst *csInstDev = nullptr;
-  const CsCull *csCullDev = nullptr;
-  float csCullS1 = 0, csCullS2 = 0, csCullK3 = 0, csCullK4 = 0;
   bool csCullVariant = false;    // the cooperative kernel chosen tests the nodes' bounds first (SelectKernel)
-  bool csCullOk = false;         // the widening constants are finite (otherwise every instance is visited)
   int blocksPerCUCs = 2;
   int blocksPerCUPm = 2;
   uint32_t stackDepthPm = 0;   // LDS stack entries per lane when the kd-tree gather runs on it
@@ -175,8 +165,8 @@ inline void FreeScene(qa_ctx *c)
   c->haveScene = false;
 }
 
-template <class T>
-inline int DeviceCopy(qa_ctx *c, const std::vector<T> &v, const T **out)
+template <class T, class P>
+inline int DeviceCopy(qa_ctx *c, const std::vector<T> &v, const P **out)
 {
   *out = nullptr;
   if (v.empty()) return QA_OK;
@@ -184,7 +174,7 @@ inline int DeviceCopy(qa_ctx *c, const std::vector<T> &v, const T **out)
   HIP_TRY(hipMalloc(&p, v.size() * sizeof(T)));
   c->sceneAllocs.push_back(p);
   HIP_TRY(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-  *out = static_cast<const T *>(p);
+  *out = static_cast<const P *>(p);
   return QA_OK;
 }
 

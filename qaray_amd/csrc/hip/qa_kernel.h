@@ -38,13 +38,11 @@
 
 namespace qa {
 
-#define QA_BLOCK 256
 #ifndef QA_MIN_WAVES
 #define QA_MIN_WAVES 4          /* waves per SIMD the register allocator must leave room for */
 #endif
 #define QA_BIAS 0.005f         /* src/objects/objects.cpp:19 */
 #define QA_DX 0.01f            /* DiffRay::dx = dy, src/core/ray.cpp:31-32 */
-#define QA_DONE 0xFFFFFFFFu    /* traversal sentinel (has the leaf bit set, never a real node word) */
 // qa_integrate's DCounters are per LANE, reduced by shuffles at the end.  (-DQA_WAVE_TALLIES: the lanes that reach a tally add
 // their number to a wave-uniform count in scalar registers instead - eight vector registers less on paper; measured on the
 // Cornell-box kernel: 101 instead of 87 spilled registers and 12.4 instead of 13.1 Gsamples/s, profiles/round03/experiments.txt.

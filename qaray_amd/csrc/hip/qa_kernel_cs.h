@@ -46,10 +46,7 @@ namespace qa {
 #define QA_FILL(cnt) nullptr
 #endif
 #define QA_CS_SLOT_SHIFT 20             /* pool item = child word | ray slot << 20 (inner: node index; leaf: flag, count - 1, triangle offset) */
-#define QA_CS_INDEX_MASK 0xFFFFFu       /* scene-wide node indices / triangle offsets must fit 20 bits (host check), elements of a mesh too */
 #define QA_CS_SLOT_MASK 0xFFu           /* <= 256 ray slots */
-#define QA_CS_LIGHT_BATCH 4             /* shadow queries are pooled for up to four lights at a time */
-#define QA_CS_EXACT_STACK 64            /* private stack entries of the exact walks (reference trees deeper than this keep qa_integrate) */
 #ifndef QA_CS_LEAF_ROUND
 #define QA_CS_LEAF_ROUND 48u           /* leaf items that make a leaf round go first */
 #endif

@@ -437,8 +437,8 @@ void FreePhotonMaps(qa_ctx *c)
 static int BuildOne(qa_ctx *c, int which, const qa_photon_map_params &mp, uint32_t seed, const int32_t *dSources, int numSources)
 {
   typedef void (*EmitFn)(const DScene, const EmitParams);
-  const EmitFn emit = c->resident ? (c->textured ? (EmitFn) qa_photon_emit<true, true> : (EmitFn) qa_photon_emit<true, false>)
-                                  : (c->textured ? (EmitFn) qa_photon_emit<false, true> : (EmitFn) qa_photon_emit<false, false>);
+  const EmitFn emit = c->plan.resident ? (c->plan.textured ? (EmitFn) qa_photon_emit<true, true> : (EmitFn) qa_photon_emit<true, false>)
+                                  : (c->plan.textured ? (EmitFn) qa_photon_emit<false, true> : (EmitFn) qa_photon_emit<false, false>);
   const uint32_t maxRec = mp.bounce > 1 ? mp.bounce - 1 : 1;   // a photon is stored at hits 1 .. bounce - 1
   const uint32_t batch = 32768;
   Scratch sc;
@@ -468,7 +468,7 @@ static int BuildOne(qa_ctx *c, int which, const qa_photon_map_params &mp, uint32
     ep.max_rec = maxRec;
     ep.counts = dCounts;
     ep.cand = dCand;
-    hipLaunchKernelGGL(emit, dim3(batch / QA_BLOCK), dim3(QA_BLOCK), (unsigned) c->ldsBytes, c->stream, c->ds, ep);
+    hipLaunchKernelGGL(emit, dim3(batch / QA_BLOCK), dim3(QA_BLOCK), (unsigned) c->plan.ldsBytes, c->stream, c->ds, ep);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(qa_photon_pack, dim3(1), dim3(1024), 0, c->stream, dCounts, dCand, batch, maxRec, (uint32_t) first, dMap,
                        mp.size, dState);
@@ -551,9 +551,9 @@ int qa_photon_maps_build(qa_ctx *c, const qa_photon_params *pp, uint32_t seed)
   // the gather walks the kd-tree on the lane's LDS stack: two words per tree level + 1
   uint32_t levels = 1;
   for (uint32_t n = std::max(pp->photon.size, pp->caustics.size); n > 1; n >>= 1) ++levels;
-  const uint32_t needDepth = std::max(c->stackDepth, 2 * (levels + 2));
+  const uint32_t needDepth = std::max(c->ds.stackDepth, 2 * (levels + 2));
   const size_t stackBytes = ((size_t) needDepth + QA_LANE_SLOTS) * QA_BLOCK * sizeof(uint32_t);
-  const size_t imageBytes = c->resident ? (size_t) c->ds.residentVec4 * sizeof(uint4) : 0;
+  const size_t imageBytes = c->plan.resident ? (size_t) c->ds.residentVec4 * sizeof(uint4) : 0;
   if (imageBytes + stackBytes > 64 * 1024) return Fail(QA_EUNSUPPORTED, "photon map too deep for the LDS stack");
 
   Scratch tmp;
@@ -567,8 +567,8 @@ int qa_photon_maps_build(qa_ctx *c, const qa_photon_params *pp, uint32_t seed)
   c->photonParams = *pp;
   c->stackDepthPm = needDepth;
   c->ldsBytesPm = imageBytes + stackBytes;
-  c->kernelPm = PickPmKernel(c->resident, c->textured, c->area, false);
-  c->kernelPmStats = PickPmKernel(c->resident, c->textured, c->area, true);
+  c->kernelPm = PickPmKernel(c->plan.resident, c->plan.textured, c->plan.area, false);
+  c->kernelPmStats = PickPmKernel(c->plan.resident, c->plan.textured, c->plan.area, true);
   int resident = 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&resident, (const void *) c->kernelPm, QA_BLOCK, c->ldsBytesPm) != hipSuccess || resident < 1)
     resident = 1;

@@ -1,0 +1,74 @@
+// qa_scene_build.h — the host-only half of a scene upload: validate a flat blob (include/qa_flat_scene.h), derive every table the
+// kernels read and the decisions that follow from them.  No HIP runtime call and no environment: qa_capi.hip fills the knobs and
+// copies the tables to the device (UploadScene); tests/cpp/scene_build_check.cpp runs the builder under the sanitizers.
+#pragma once
+#include <hip/hip_runtime.h>   // uint4 / float4
+
+#include <cstdio>
+#include <string>
+#include <vector>
+
+#include "qa_scene_dev.h"
+#include "qa_widebvh.h"
+
+namespace qa {
+
+constexpr size_t kMaxLdsPerBlock = 64 * 1024;      // dynamic LDS a workgroup may ask for without opt-in
+constexpr size_t kResidentLdsBudget = 40 * 1024;   // image + stacks: keeps 4 workgroups per CU (160 KB LDS)
+
+// Developer knobs (qa_capi.hip reads them once per upload; the defaults are the product's)
+struct BuildKnobs {
+  bool wide = true;                      // QA_WIDE=0: no 4-wide trees
+  unsigned wideLeaf = 3;                 // QA_WIDE_LEAF: triangles per leaf of the 4-wide trees
+  unsigned fastLeaf = 2;                 // QA_FAST_LEAF: triangles per leaf of the own SAH trees
+  uint32_t fastMaxFaces = 0xFFFFFFFFu;   // QA_FAST_MAXFACES: larger meshes keep the reference tree
+  uint32_t csItems = 576, csSlots = 80;  // QA_CS_ITEMS, QA_CS_SLOTS: qa_integrate_cs's pool items and ray slots per wave
+  FILE *report = nullptr;                // per-mesh tree report ("verbose", QA_FAST_VERBOSE), else null
+};
+
+struct MeshTables {
+  std::vector<DNode> nodes, fnodes;      // reference tree (even count), own SAH tree (qa_fastbvh.h)
+  std::vector<DTri> tris, ftris, wtris;  // element order, own tree's leaf order, 4-wide tree's leaf order
+  std::vector<DTriShade> shade;
+  std::vector<uint32_t> fmap;
+  std::vector<float> vt;                 // 6 floats per element (textured scenes)
+  std::vector<float> normals;            // distinct face normals, 4 floats each (resident image)
+  WideBvh wide;                          // qa_widebvh.h
+};
+
+// What one upload decides; the launch paths read it from qa_ctx::plan
+struct ScenePlan {
+  std::vector<DMesh> meshes;             // the device mesh table, its pointer fields still null
+  std::vector<bool> meshInstanced;       // some scene-graph node shows the mesh
+  std::vector<int32_t> shadowLights;     // table indices of the non-ambient lights
+  bool textured = false, area = false, resident = false;
+  bool csFits = false;                   // the scene fits qa_integrate_cs's limits (20-bit scene-wide indices, <= 256 nodes, ...)
+  bool csCullOk = false;                 // the instance-culling constants are finite (otherwise every instance is visited)
+  int syncAuto = 0;                      // samples of a wave start together unless the frame decides otherwise
+  size_t ldsBytes = 0;                   // dynamic LDS of qa_integrate: resident image + stacks, or stacks
+};
+// a mesh hit without texture vertices keeps the uvw of an earlier, farther hit: history only a sequential walk has
+inline bool MissesTexcoords(const ScenePlan &p, const DMesh &m) { return p.textured && m.num_faces > 0 && !m.hasVT; }
+
+struct SceneTables {
+  ScenePlan plan;
+  DScene ds{};                           // camera, background, counts, LDS and culling constants; no device pointer yet
+  std::vector<MeshTables> mesh;
+  std::vector<DWideNode> csNodes;        // qa_integrate_cs: the 4-wide trees of all meshes (empty unless plan.csFits)
+  std::vector<DTri> csTris;
+  std::vector<float> csLeafBox;
+  std::vector<CsInst> csInst;
+  std::vector<CsCull> csCull;
+  std::vector<DMaterial> materials;
+  std::vector<int32_t> mtlTex;           // textured scenes: texmaps per material, float texels, their offsets, filter taps
+  std::vector<float> texels;
+  std::vector<uint32_t> texOff;
+  std::vector<float> taps;
+  std::vector<uint4> image;              // the resident image (uploaded when plan.resident)
+};
+
+float HaltonF(int index, int base);   // Halton sequence in the reference's fp32 order
+// QA_OK, or a QA_E* code with the reason in *err
+int BuildScene(const unsigned char *blob, size_t nbytes, const BuildKnobs &knobs, SceneTables &out, std::string *err);
+
+}  // namespace qa

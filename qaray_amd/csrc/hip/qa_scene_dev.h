@@ -25,6 +25,13 @@
 #include "qa_flat_scene.h"
 #include "qa_photon.h"
 
+#define QA_BLOCK 256
+#define QA_DONE 0xFFFFFFFFu    /* traversal sentinel (has the leaf bit set, never a real node word) */
+// qa_integrate_cs (qa_kernel_cs.h) limits the host checks too
+#define QA_CS_INDEX_MASK 0xFFFFFu       /* scene-wide node indices / triangle offsets must fit 20 bits (host check), elements of a mesh too */
+#define QA_CS_LIGHT_BATCH 4             /* shadow queries are pooled for up to four lights at a time */
+#define QA_CS_EXACT_STACK 64            /* private stack entries of the exact walks (reference trees deeper than this keep qa_integrate) */
+
 namespace qa {
 
 struct alignas(32) DNode {

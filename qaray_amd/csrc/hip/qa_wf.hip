@@ -104,37 +104,22 @@ void FreeStaged(qa_ctx *c)
 void SelectStaged(qa_ctx *c)
 {
   WfHost &w = c->wf;
-  w.eligible = false;
-  w.numLights = 0;
-  const qa_flat_header *h = reinterpret_cast<const qa_flat_header *>(c->hostBlob.data());
-  const qa_light *light = QA_BLOB_PTR(qa_light, c->hostBlob.data(), h->off_lights);
-  const qa_instance *inst = QA_BLOB_PTR(qa_instance, c->hostBlob.data(), h->off_instances);
-  const qa_mesh *mesh = QA_BLOB_PTR(qa_mesh, c->hostBlob.data(), h->off_meshes);
-  int nl = 0;
-  for (uint32_t i = 0; i < h->num_lights; ++i)
-    if (light[i].type != QA_LIGHT_AMBIENT) {
-      if (nl < QA_WF_MAX_LIGHTS) w.lightIdx[nl] = (int32_t) i;
-      ++nl;
-    }
-  bool ok = !c->resident && !c->area && nl <= QA_WF_MAX_LIGHTS && h->num_instances <= 31;
+  const ScenePlan &p = c->plan;
+  const int nl = (int) p.shadowLights.size();
+  for (int i = 0; i < nl && i < QA_WF_MAX_LIGHTS; ++i) w.lightIdx[i] = p.shadowLights[i];
+  bool ok = !p.resident && !p.area && nl <= QA_WF_MAX_LIGHTS && c->ds.num_inst <= 31;
   bool anyMesh = false;
-  for (uint32_t k = 0; k < h->num_instances && ok; ++k) {
-    if (inst[k].obj_type != QA_OBJ_MESH) continue;
-    anyMesh = true;
-    const qa_mesh &m = mesh[inst[k].mesh];
-    if (m.num_faces >= (1u << 24)) ok = false;
-    // a hit on a mesh without texture vertices keeps the uvw of an earlier, farther hit (the intersectors only
-    // overwrite what they set): that history lives in the megakernel's sequential walk only
-    if (c->textured && m.num_faces > 0) {
-      uint32_t withVT = 0;
-      const qa_face *faces = QA_BLOB_PTR(qa_face, c->hostBlob.data(), m.off_faces);
-      for (uint32_t f = 0; f < m.num_faces; ++f) if (faces[f].vt[0] >= 0 && faces[f].vt[1] >= 0 && faces[f].vt[2] >= 0) ++withVT;
-      if (withVT != m.num_faces) ok = false;
+  for (size_t mi = 0; mi < p.meshes.size(); ++mi) {
+    const DMesh &dm = p.meshes[mi];
+    if (p.meshInstanced[mi]) {
+      anyMesh = true;
+      // a hit on a mesh without texture vertices keeps the uvw of an earlier, farther hit (the intersectors only
+      // overwrite what they set): that history lives in the megakernel's sequential walk only
+      if (dm.num_faces >= (1u << 24) || MissesTexcoords(p, dm)) ok = false;
     }
+    if (dm.num_faces > 0 && !dm.useWide) ok = false;   // the trace stage searches the 4-wide trees only (qa_widebvh.h)
   }
   ok = ok && anyMesh;
-  // the trace stage searches the 4-wide trees only (qa_widebvh.h)
-  for (const DMesh &dm : c->hostMeshes) if (dm.num_faces > 0 && !dm.useWide) ok = false;
   if (!w.modeSet) {     // qa_set_pipeline outlives scene uploads; otherwise the environment decides
     w.mode = QA_PIPE_AUTO;
     if (const char *e = DevEnv("QA_PIPELINE")) {
@@ -164,7 +149,7 @@ int RenderStaged(qa_ctx *c, const DScene &ds, const RenderParams &rp, hipStream_
   // wf_trace's stacks: what the wide trees can need, capped (QA_WF_STACK, default 24): nearest-first walks rarely hold
   // more than a dozen entries, and every LDS kilobyte saved is occupancy; a full stack sends the ray to wf_redo
   uint32_t wideNeed = 2;
-  for (const DMesh &dm : c->hostMeshes) if (dm.useWide) wideNeed = std::max(wideNeed, dm.wideStack);
+  for (const DMesh &dm : c->plan.meshes) if (dm.useWide) wideNeed = std::max(wideNeed, dm.wideStack);
   const uint32_t traceStack = std::min(wideNeed, w.stackCap);
 
   const size_t stackLds = (size_t) ds.stackDepth * QA_BLOCK * sizeof(uint32_t);
@@ -248,7 +233,7 @@ int RenderStaged(qa_ctx *c, const DScene &ds, const RenderParams &rp, hipStream_
         const Shape &sh = shape[gi];
         WfCounters *ctr = g.dCtr + i;
         g.buf.gateOpen = ((iter + i) % w.gate) == 0 ? 1u : 0u;
-        if (c->textured) hipLaunchKernelGGL(wf_logic<true>, dim3(sh.logicBlocks), dim3(QA_BLOCK), 0, g.stream, ds, rp, g.buf, ctr, frameCounters, parity);
+        if (c->plan.textured) hipLaunchKernelGGL(wf_logic<true>, dim3(sh.logicBlocks), dim3(QA_BLOCK), 0, g.stream, ds, rp, g.buf, ctr, frameCounters, parity);
         else hipLaunchKernelGGL(wf_logic<false>, dim3(sh.logicBlocks), dim3(QA_BLOCK), 0, g.stream, ds, rp, g.buf, ctr, frameCounters, parity);
         if (dbg) { HIP_TRY(hipStreamSynchronize(g.stream)); fprintf(stderr, "[wf] group %d pass %lld logic ok\n", gi, iter + i); }
         if (redoAsync) {

@@ -1,12 +1,12 @@
 """AddressSanitizer + UBSan builds of the CPU-side code (the GPU pool does not offer sanitizers):
-the host layer driven through its loaders with good and malformed input, and the oracle rendering
-a small image."""
+the host layer driven through its loaders with good and malformed input, the HIP library's scene
+builder over every scene and over malformed blobs, and the oracle rendering a small image."""
 import os
 import subprocess
 
 import numpy as np
 
-from conftest import ROOT
+from conftest import ROOT, ensure_assets
 
 SAN = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer", "-g", "-O1"]
 ENV = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
@@ -24,6 +24,47 @@ def test_host_layer_under_asan_ubsan(tmp_path):
     r = subprocess.run([exe, os.path.join(ROOT, "scenes"), str(work)], env=ENV, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     assert r.returncode == 0 and "host_sanity: clean" in r.stdout, r.stdout[-3000:]
     assert "runtime error" not in r.stdout and "AddressSanitizer" not in r.stdout, r.stdout[-3000:]
+
+
+# The plan BuildScene makes for the BASELINE configurations C1 - C5 at their frame sizes (the values the upload made before the
+# builder was split out of it): LDS residency, the cooperative kernel's limits, the stack, and per mesh the own SAH tree / 4-wide tree
+BASELINE_PLANS = [
+    ("example_project3_sphere.xml", (256, 256), "resident=1 csFits=0 csCullOk=1 stackNeedMax=1 ldsBytes=23744 useFast= useWide="),
+    ("example_project12_box.xml", (1920, 1080), "resident=1 csFits=0 csCullOk=1 stackNeedMax=8 ldsBytes=31520 useFast=1 useWide=0"),
+    ("example_project7_object.xml", (1920, 1080), "resident=0 csFits=1 csCullOk=1 stackNeedMax=32 ldsBytes=38912 useFast=000 useWide=111"),
+    ("example_project12_caustics_glossy.xml", (3840, 2160), "resident=0 csFits=1 csCullOk=1 stackNeedMax=32 ldsBytes=38912 useFast=0 useWide=1"),
+    ("trc_scene_tower.xml", (3840, 2160), "resident=0 csFits=1 csCullOk=1 stackNeedMax=44 ldsBytes=51200 useFast=000 useWide=111"),
+]
+
+
+def test_scene_builder_under_asan_ubsan(tmp_path):
+    from qaray_amd.host import load_scene_blob
+    hip = os.path.join(ROOT, "qaray_amd", "csrc", "hip")
+    exe = str(tmp_path / "scene_build_check")
+    subprocess.run(["g++", "-std=c++17", *SAN, "-ffp-contract=off", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", f"-I{ROOT}/include",
+                    f"-I{hip}", os.path.join(ROOT, "tests", "cpp", "scene_build_check.cpp"), os.path.join(hip, "qa_scene_build.cpp"), "-o", exe],
+                   check=True)
+    ensure_assets()
+
+    def run(*args):
+        r = subprocess.run([exe, *args], env=ENV, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+        assert r.returncode == 0, r.stdout[-3000:]
+        assert "runtime error" not in r.stdout and "AddressSanitizer" not in r.stdout, r.stdout[-3000:]
+        return r.stdout.splitlines()
+
+    def blob_file(name, size):
+        p = str(tmp_path / f"{name}.{size[0]}x{size[1]}.bin")
+        load_scene_blob(name, size=size).tofile(p)
+        return p
+
+    scenes = sorted(f for f in os.listdir(os.path.join(ROOT, "scenes")) if f.endswith(".xml"))
+    lines = run("plan", *[blob_file(n, (40, 30)) for n in scenes])
+    assert len(lines) == len(scenes) and all(" rc=0 " in ln for ln in lines), "\n".join(lines)
+    lines = run("plan", *[blob_file(n, size) for n, size, _ in BASELINE_PLANS])
+    for ln, (name, size, plan) in zip(lines, BASELINE_PLANS):
+        assert ln.endswith(" rc=0 " + plan), (name, ln)
+    lines = run("malformed", blob_file("custom_textures.xml", (24, 18)))
+    assert len(lines) == 16, "\n".join(lines)
 
 
 def test_oracle_under_asan_ubsan(tmp_path):
