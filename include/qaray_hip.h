@@ -25,6 +25,9 @@
  *                                  power scaling, kd-tree; afterwards qa_render_* shade with
  *                                  Scene::usePhotonMap = true        src/renderers/renderer.cpp:114-291,
  *                                                                       src/materials/MtlBlinn_PhotonMap.cpp:349-458
+ *   qa_progressive_*               Renderer_GUI's progressive display: BeginRender starts the render
+ *                                  threads, the window shows renderImage while it fills, StopRender
+ *                                  signals the stop            src/renderers/Renderer_GUI.cpp:37-97
  *   qa_get_counters                (no counterpart: the reference only prints wall-clock)
  *   qa_get_kernel_time             Renderer::StartTimer/StopTimer       src/renderers/renderer.cpp:42-63
  */
@@ -115,6 +118,36 @@ int qa_photon_maps_download(qa_ctx *ctx, int which, qa_photon *out, uint64_t cap
 int qa_request_stop(qa_ctx *ctx);
 int qa_clear_stop(qa_ctx *ctx);
 
+/* Progressive frames: an image resident in HBM whose sample count is raised in passes (1, 4, 16, ... spp), with a preview
+ * between passes and a stop / resume at any point.  The final image is bit-identical to the one-shot frame of the same
+ * arguments: every pixel takes the same samples in the same order, its state (RNG state, samples taken, running mean and
+ * variance: 32 bytes) waiting in device memory between passes.  One frame per context.
+ *   qa_progressive_begin    validates like qa_render_region (same codes) and allocates the frame's slabs (52 bytes per pixel,
+ *                           4 + 4 per 8x8 tile); renders nothing.  flags: QA_RENDER_STATS.  Ends the previous frame, if any.
+ *   qa_progressive_advance  one launch of the megakernel (never the staged pipeline) that brings every unfinished pixel to
+ *                           min(spp_target, spp_max) samples; a pixel may finish earlier by the adaptive rule of spp_min /
+ *                           spp_max.  Enqueues on hip_stream (NULL = the context's stream, as for qa_render_region_device).  A
+ *                           target at or below the frame's level is a no-op; at or below the last pass's target the call first
+ *                           asks the device for the level (synchronises).  qa_request_stop during a pass: tiles in hand finish
+ *                           the pass, the others keep their level; a later pass to the same or a higher target completes them.
+ *   qa_progressive_read     the preview (synchronises), region-local like qa_render_region: finished pixels' final mean and
+ *   qa_progressive_read_device   sample count, the running mean and the samples so far of the others (rgb 0, ns 0 where none was
+ *                           taken); depth is sample 0's hit distance (1e30 before it).  The device variant only enqueues.
+ *   qa_progressive_status   (synchronises) spp_reached: the lowest level of the frame's tiles; pixels_finished: pixels done
+ *                           for good (spp_max or the adaptive rule); tiles_behind: tiles below the last pass's target (non-zero
+ *                           after a stop).  Any pointer may be NULL.
+ *   qa_progressive_end      frees the frame (also done by qa_ctx_destroy).
+ * qa_scene_upload*, qa_photon_maps_build and qa_photon_maps_clear end the frame: a later advance / read / status returns
+ * QA_EINVAL and qa_last_error says why.  qa_render_* frames between passes do not disturb it, and qa_set_option /
+ * qa_set_pipeline may change between passes (same bits). */
+int qa_progressive_begin(qa_ctx *ctx, int x0, int y0, int x1, int y1, int spp_min, int spp_max, int max_bounce, uint32_t seed,
+                         uint32_t flags);
+int qa_progressive_advance(qa_ctx *ctx, int spp_target, void *hip_stream);
+int qa_progressive_read(qa_ctx *ctx, float *rgb, float *depth, uint32_t *nsamples);
+int qa_progressive_read_device(qa_ctx *ctx, float *d_rgb, float *d_depth, uint32_t *d_nsamples, void *hip_stream);
+int qa_progressive_status(qa_ctx *ctx, int *spp_reached, uint64_t *pixels_finished, uint64_t *tiles_behind);
+int qa_progressive_end(qa_ctx *ctx);
+
 /* Counters accumulated since the last reset (synchronises the context first). */
 int qa_get_counters(qa_ctx *ctx, qa_counters *out);
 int qa_reset_counters(qa_ctx *ctx);
@@ -166,6 +199,7 @@ int qa_set_pipeline(qa_ctx *ctx, int mode);
  *   "chunk_tail"     chunks of this many (0: an eighth of the frame's spp) - so that a frame of few tiles per wave ends on small work
  *                    items; a pixel's state waits in device memory between chunks (same samples in the same order: same bits)
  *   "tile_order"     1 (default) / 0: tiles handed out centre-first
+ *   "progressive_tile_limit"  tests: n > 0 = a progressive pass takes at most n tiles, then ends as if stopped; 0 (default) = none
  *   "staged_groups"  1 (default) .. 8 tile groups of the staged pipeline, each on its own stream; more than one only pays
  *                    when the process started the HIP runtime with GPU_MAX_HW_QUEUES >= 8
  *   "verbose"        1: tree statistics and launch shapes on stderr at upload

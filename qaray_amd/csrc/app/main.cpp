@@ -3,7 +3,8 @@
 //             [-use-photon-map] [-photon-map-size N] [-caustics-map-size N] scene.xml
 // plus what the reference has no flag for: -size W H, -seed S, -device D, -devices N (GPUs 0..N-1 of this node in one
 // process: one host thread and one context per GPU, strips gathered on the first; Renderer::UseDevices), -out PREFIX, -root DIR,
-// -photon-map-radius R, -caustics-map-radius R, -photon-map-bounce N, -caustics-map-bounce N.
+// -photon-map-radius R, -caustics-map-radius R, -photon-map-bounce N, -caustics-map-bounce N, -progressive N (the frame in passes of
+// N spp up to -spp / -sppMax, the images rewritten after each: the batch counterpart of the reference's progressive display).
 // The reference's `-sppMax` sets sppMin by mistake (main.cpp:27-28); here it sets sppMax.
 // Flow: Init -> LoadScene -> ComputeScene -> Render -> Terminate (main.cpp:55-59).
 #include <cstdio>
@@ -22,7 +23,7 @@ int main(int argc, char **argv)
   RendererParam param;
   const char *file = nullptr;
   std::string out, root;
-  int device = 0, w = -1, h = -1, devices = 0;
+  int device = 0, w = -1, h = -1, devices = 0, progressive = 0;
   if (argc < 2) { fprintf(stderr, "Error: insufficient input\n"); return -1; }
   for (int i = 1; i < argc; ++i) {
     const std::string s(argv[i]);
@@ -45,11 +46,13 @@ int main(int argc, char **argv)
     else if (s == "-seed") param.seed = (uint32_t) strtoul(next(), nullptr, 0);
     else if (s == "-device") device = atoi(next());
     else if (s == "-devices") devices = atoi(next());
+    else if (s == "-progressive") progressive = atoi(next());
     else if (s == "-out") out = next();
     else if (s == "-root") root = next();
     else file = argv[i];
   }
   if (!file) { fprintf(stderr, "Error: no scene file\n"); return -1; }
+  if (progressive > 0 && devices > 0) { fprintf(stderr, "Error: -progressive renders on one device and cannot be combined with -devices\n"); return -1; }
   try {
     Renderer renderer(param, device);
     if (devices > 0) {
@@ -66,7 +69,8 @@ int main(int argc, char **argv)
     if (!LoadScene(file, scene)) { fprintf(stderr, "Failed to load %s\n", file); return 1; }
     if (w > 0 && h > 0) { scene.camera.imgWidth = w; scene.camera.imgHeight = h; }
     renderer.ComputeScene(renderImage, scene);
-    renderer.Render();
+    if (progressive > 0) renderer.RenderProgressive((size_t) progressive);
+    else renderer.Render();
     const qa_counters &c = renderer.Counters();
     printf("samples %llu  casts %llu + %llu shadow  %.3f Msamples/s\n", (unsigned long long) c.samples,
            (unsigned long long) c.casts_normal, (unsigned long long) c.casts_shadow, c.samples / renderer.LastSeconds() * 1e-6);

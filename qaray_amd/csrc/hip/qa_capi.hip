@@ -56,6 +56,87 @@ __global__ __launch_bounds__(256, 8) void qa_scrub_scratch(uint32_t pattern, uin
   for (int i = 0; i < 300; ++i) __builtin_amdgcn_s_sleep(127);
   if (a[threadIdx.x] == 0x12345u && pattern != 0x12345u) never[0] = 1;
 }
+
+// ---- progressive frames (qa_progressive_*): the pixel state slab is RenderParams::pix_state's layout, 8 words per pixel at its output
+// index q (row-major in the region): [0] RNG state, [1] samples taken | bit 31 finished, [2..4] running mean, [5..7] running variance
+// qa_progressive_begin: every pixel's fresh state (what qa_integrate's section A sets up for a pixel's first sample), nothing rendered
+__global__ __launch_bounds__(256) void qa_prog_init(uint32_t *state, float *rgb, float *depth, uint32_t *ns, int x0, int y0, uint32_t rw, uint32_t npix,
+                                                    uint32_t width, uint32_t seed)
+{
+  const uint32_t q = blockIdx.x * 256u + threadIdx.x;
+  if (q >= npix) return;
+  const uint32_t px = (uint32_t) x0 + q % rw, py = (uint32_t) y0 + q / rw;
+  uint4 *st = reinterpret_cast<uint4 *>(state) + 2 * (size_t) q;
+  st[0] = make_uint4(qa_pixel_seed(seed, py * width + px), 0u, 0u, 0u);
+  st[1] = make_uint4(0u, 0u, 0u, 0u);
+  rgb[3 * (size_t) q] = 0.f; rgb[3 * (size_t) q + 1] = 0.f; rgb[3 * (size_t) q + 2] = 0.f;
+  depth[q] = QA_BIGFLOAT;
+  ns[q] = 0u;
+}
+// after a pass to `target` samples: the tiles whose pass is complete are at the target now.  tile_progress is indexed by the work item's
+// place in the pass's tile order (qa_integrate, section A: 2 once the item is complete); every word is 1 again for the next pass (its
+// work items are all "chunk 1": the wait for chunk 0 ends at once)
+__global__ __launch_bounds__(256) void qa_prog_levels(uint32_t *progress, const uint32_t *order, uint32_t *level, uint32_t tiles, uint32_t target)
+{
+  const uint32_t p = blockIdx.x * 256u + threadIdx.x;
+  if (p >= tiles) return;
+  if (progress[p] >= 2u) {
+    const uint32_t t = order ? order[p] : p;
+    if (level[t] < target) level[t] = target;
+  }
+  progress[p] = 1u;
+}
+// a pass to a target some tiles already reached (the same target again after a stop): only the tiles below it are handed out, so that
+// no pixel takes a sample beyond the target.  They go, in launch order, to the END of list[tiles], and the pass's work counter starts
+// so that its items are the last min(count, limit) of them.  One wave walks the order (a rare path; the order decides the schedule only)
+__global__ __launch_bounds__(64) void qa_prog_select(const uint32_t *order, const uint32_t *level, uint32_t tiles, uint32_t target, uint32_t limit,
+                                                     uint32_t *list, unsigned int *work)
+{
+  const uint32_t lane = threadIdx.x;
+  uint32_t k = 0;   // tiles selected so far
+  for (uint32_t b = 0; b < tiles; b += 64) {
+    const bool valid = b + lane < tiles;
+    const uint32_t p = valid ? tiles - 1u - (b + lane) : 0u;   // (backwards from the order's end)
+    const uint32_t t = valid ? (order ? order[p] : p) : 0u;
+    const bool need = valid && level[t] < target;
+    const unsigned long long m = __ballot(need);
+    if (need) list[tiles - 1u - (k + (uint32_t) __popcll(m & ((1ull << lane) - 1ull)))] = t;
+    k += (uint32_t) __popcll(m);
+  }
+  if (lane == 0) *work = (2u * tiles - ((limit && limit < k) ? limit : k)) * 64u;
+}
+// the preview: finished pixels' final mean and sample count, the running mean and the samples so far of the others (rgb 0, ns 0 where
+// nothing was taken yet); depth is sample 0's hit distance (1e30 before it)
+__global__ __launch_bounds__(256) void qa_prog_resolve(const uint32_t *state, const float *rgb, const float *depth, const uint32_t *ns, uint32_t npix,
+                                                       float *outRgb, float *outDepth, uint32_t *outNs)
+{
+  const uint32_t q = blockIdx.x * 256u + threadIdx.x;
+  if (q >= npix) return;
+  const uint4 a = reinterpret_cast<const uint4 *>(state)[2 * (size_t) q];
+  const uint32_t mz = state[8 * (size_t) q + 4];
+  if (a.y & 0x80000000u) {
+    outRgb[3 * (size_t) q] = rgb[3 * (size_t) q]; outRgb[3 * (size_t) q + 1] = rgb[3 * (size_t) q + 1]; outRgb[3 * (size_t) q + 2] = rgb[3 * (size_t) q + 2];
+    outNs[q] = ns[q];
+  } else {
+    outRgb[3 * (size_t) q] = __uint_as_float(a.z); outRgb[3 * (size_t) q + 1] = __uint_as_float(a.w); outRgb[3 * (size_t) q + 2] = __uint_as_float(mz);
+    outNs[q] = a.y;
+  }
+  outDepth[q] = depth[q];
+}
+// qa_progressive_status: out[0] finished pixels, out[1] tiles below `target`, out[2] the lowest tile level (zeroed / set to ~0 before)
+__global__ __launch_bounds__(256) void qa_prog_status(const uint32_t *state, uint32_t npix, const uint32_t *level, uint32_t tiles, uint32_t target,
+                                                      unsigned long long *out)
+{
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  const bool fin = i < npix && (state[8 * (size_t) i + 1] & 0x80000000u);
+  const bool behind = i < tiles && level[i] < target;
+  const unsigned long long mf = __ballot(fin), mb = __ballot(behind);
+  if (__lane_id() == 0) {
+    if (mf) atomicAdd(&out[0], (unsigned long long) __popcll(mf));
+    if (mb) atomicAdd(&out[1], (unsigned long long) __popcll(mb));
+  }
+  if (i < tiles) atomicMin(&out[2], (unsigned long long) level[i]);
+}
 }  // namespace qa
 
 static const char *kStagedName = "staged: wf_logic + wf_cull + wf_trace + wf_redo";
@@ -91,6 +172,14 @@ static KernelFn PickCs(bool lights, bool tex, bool cull, bool many, bool area)
       {(KernelFn) qa_integrate_cs<true, false, true, false, true>, (KernelFn) qa_integrate_cs<true, true, true, false, true>}};
   return k[area ? 5 : many ? 4 : 2 * cull + lights][tex];
 }
+// ... their untextured rows as chunk-capable instances (qa_integrate_cs_resume): the passes of progressive frames
+static KernelFn PickCsResume(bool lights, bool cull, bool many, bool area)
+{
+  static const KernelFn k[6] = {(KernelFn) qa_integrate_cs_resume<false, false, false, false>, (KernelFn) qa_integrate_cs_resume<true, false, false, false>,
+                                (KernelFn) qa_integrate_cs_resume<false, false, true, false>, (KernelFn) qa_integrate_cs_resume<true, false, true, false>,
+                                (KernelFn) qa_integrate_cs_resume<true, false, true, true>, (KernelFn) qa_integrate_cs_resume<true, false, true, false, true>};
+  return k[area ? 5 : many ? 4 : 2 * cull + lights];
+}
 
 // where the upload report goes ("verbose", QA_FAST_VERBOSE), else null
 static FILE *Report(const qa_ctx *c) { return (c->optVerbose || DevEnv("QA_FAST_VERBOSE")) ? stderr : nullptr; }
@@ -111,6 +200,7 @@ static int SelectKernel(qa_ctx *c)
   // (any number of lights: their shadow queries are pooled QA_CS_LIGHT_BATCH = 4 lights at a time; with more than one batch the
   // surface waits in the slab DScene::csSurf between batches, qa_kernel_cs.h; area lights: the AREA variants)
   c->kernelCs = nullptr;
+  c->kernelCsResume = nullptr;
   c->csMany = false;
   const char *e = DevEnv("QA_COOP");
   const size_t shadowLights = p.shadowLights.size();
@@ -125,6 +215,11 @@ static int SelectKernel(qa_ctx *c)
     int n = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void *) c->kernelCs, QA_BLOCK, c->ldsBytesCs) != hipSuccess || n < 1) n = 2;
     c->blocksPerCUCs = n > 8 ? 8 : n;
+    if (!p.textured) {
+      c->kernelCsResume = PickCsResume(lights, c->csCullVariant, c->csMany, p.area);
+      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void *) c->kernelCsResume, QA_BLOCK, c->ldsBytesCs) != hipSuccess || n < 1) n = 2;
+      c->blocksPerCUCsResume = n > 8 ? 8 : n;
+    }
   }
   SetKernelName(c);
   if (FILE *report = Report(c))
@@ -212,8 +307,8 @@ static int OwnTileRows(int y0, int y1, int tile_row0, int tile_row_step)
   return (tilesY - tile_row0 + tile_row_step - 1) / tile_row_step;
 }
 
-static int Render(qa_ctx *c, int x0, int y0, int x1, int y1, int tile_row0, int tile_row_step, int spp_min, int spp_max,
-                  int max_bounce, uint32_t seed, uint32_t flags, float *d_rgb, float *d_depth, uint32_t *d_ns, hipStream_t s)
+// What qa_render_* and qa_progressive_begin refuse alike
+static int CheckFrame(qa_ctx *c, int x0, int y0, int x1, int y1, int spp_min, int spp_max, int max_bounce)
 {
   if (!c->haveScene) return Fail(QA_ENOSCENE, "no scene uploaded");
   if (x0 < 0 || y0 < 0 || x1 > c->ds.cam.width || y1 > c->ds.cam.height || x1 <= x0 || y1 <= y0)
@@ -221,28 +316,32 @@ static int Render(qa_ctx *c, int x0, int y0, int x1, int y1, int tile_row0, int 
   // sppMin = 0 would mean "no sample at all" (SuperSamplerHalton::Loop, src/scene/scene.cpp:92-97): refused
   if (spp_min < 1 || spp_max < spp_min || max_bounce < 0) return Fail(QA_EINVAL, "bad spp / bounce");
   if (c->plan.area && max_bounce + 1 > QA_MAX_PATH) return Fail(QA_EUNSUPPORTED, "area lights: maxBounce must be <= 7");
-  if (!d_rgb || !d_depth || !d_ns) return Fail(QA_EINVAL, "null output buffer");
-  int rc = EnsureHalton(c, spp_max);
-  if (rc != QA_OK) return rc;
-  c->ds.halton = c->dHalton;
-  c->ds.halton_count = c->haltonCount;
+  return QA_OK;
+}
 
-  if (tile_row0 < 0 || tile_row_step < 1) return Fail(QA_EINVAL, "bad strip partition");
-  const int ownRows = OwnTileRows(y0, y1, tile_row0, tile_row_step);
-  if (ownRows == 0) return QA_OK;  // nothing to do for this rank
-  const bool whole = (tile_row0 == 0 && tile_row_step == 1);
-  const size_t npix = (size_t) (x1 - x0) * (whole ? (size_t) (y1 - y0) : (size_t) ownRows * 8);
-  // pixels skipped by a stop request (and the padding rows of a ragged last strip) read as "not rendered"
-  HIP_TRY(hipMemsetAsync(d_ns, 0, npix * sizeof(uint32_t), s));
-  unsigned int *work = c->dWork + c->workNext;
-  c->workNext = (c->workNext + 1) % qa_ctx::kCounterRing;
-  HIP_TRY(hipMemsetAsync(work, 0, sizeof(unsigned int), s));
+// One launch of the megakernel as LaunchSetup plans it
+struct Launch {
+  RenderParams rp;
+  DScene ds;
+  KernelFn kernel = nullptr;
+  size_t ldsBytes = 0;
+  long long blocks = 1;
+  unsigned tiles = 0;
+  bool cs = false, pmOn = false, csResume = false;
+};
 
+// The part of a launch one-shot frames and progressive passes share: the wait for the context's last frame, the render parameters
+// (without the chunk fields), the tile order, the photon maps, the kernel variant and the grid.  resume: a progressive pass - every
+// work item resumes a pixel, so the cooperative kernel's untextured variants run as their chunk-capable instances
+static int LaunchSetup(qa_ctx *c, Launch &L, int x0, int y0, int x1, int y1, int tile_row0, int tile_row_step, int ownRows, int spp_min,
+                       int spp_max, int max_bounce, uint32_t seed, uint32_t flags, float *d_rgb, float *d_depth, uint32_t *d_ns,
+                       unsigned int *work, hipStream_t s, bool resume)
+{
   // one frame at a time per context (its device slabs are one per context): a frame on another stream than the last one waits for it
   if (!c->chunkEv) HIP_TRY(hipEventCreateWithFlags(&c->chunkEv, hipEventDisableTiming));
   if (c->chunkEvSet && s != c->lastStream) HIP_TRY(hipStreamWaitEvent(s, c->chunkEv, 0));
 
-  RenderParams rp;
+  RenderParams &rp = L.rp;
   rp.x0 = x0; rp.y0 = y0; rp.x1 = x1; rp.y1 = y1;
   rp.spp_min = spp_min; rp.spp_max = spp_max; rp.max_bounce = max_bounce;
   rp.seed = seed;
@@ -295,7 +394,8 @@ static int Render(qa_ctx *c, int x0, int y0, int x1, int y1, int tile_row0, int 
     }
     rp.heap = static_cast<uint2 *>(c->dHeap);
   }
-  DScene ds = c->ds;
+  DScene &ds = L.ds;
+  ds = c->ds;
   if (pmOn) ds.stackDepth = c->stackDepthPm;
   const bool cs = c->kernelCs && !pmOn && !(flags & QA_RENDER_STATS);
   // the cooperative kernel's third way between "a lane starts its next sample at once" (0) and "when the whole wave is between samples"
@@ -307,23 +407,98 @@ static int Render(qa_ctx *c, int x0, int y0, int x1, int y1, int tile_row0, int 
   ds.csForceExact = c->optCsForceExact;
   ds.walkZeroTerms = c->optWalkZeroTerms;
   ds.csPoolLimit = DevEnv("QA_CS_POOL") ? (uint32_t) std::max(64, atoi(DevEnv("QA_CS_POOL"))) : c->optCsPool;
-  const size_t ldsBytes = pmOn ? c->ldsBytesPm : (cs ? c->ldsBytesCs : c->plan.ldsBytes);
-  const KernelFn kernel = pmOn ? ((flags & QA_RENDER_STATS) ? c->kernelPmStats : c->kernelPm)
-                               : ((flags & QA_RENDER_STATS) ? c->kernelStats : (cs ? c->kernelCs : c->kernel));
+  L.ldsBytes = pmOn ? c->ldsBytesPm : (cs ? c->ldsBytesCs : c->plan.ldsBytes);
+  // (the textured cooperative variants carry the chunk code already: a progressive pass runs them as they are)
+  L.csResume = cs && resume && !c->plan.textured;
+  const KernelFn csKernel = L.csResume ? c->kernelCsResume : c->kernelCs;
+  L.kernel = pmOn ? ((flags & QA_RENDER_STATS) ? c->kernelPmStats : c->kernelPm)
+                  : ((flags & QA_RENDER_STATS) ? c->kernelStats : (cs ? csKernel : c->kernel));
 
-  const unsigned tiles = (unsigned) ((x1 - x0 + 7) / 8) * (unsigned) ownRows;
-  const long long needBlocks = ((long long) tiles * 64 + QA_BLOCK - 1) / QA_BLOCK;
-  long long blocks = (long long) c->numCUs * (c->blocksPerCU > 0 ? c->blocksPerCU : (pmOn ? c->blocksPerCUPm : (cs ? c->blocksPerCUCs : c->blocksPerCUAuto)));
-  if (pmOn && blocks > (long long) c->numCUs * 8) blocks = (long long) c->numCUs * 8;   // the heap scratch is sized for this
-  if (blocks > needBlocks) blocks = needBlocks;
-  if (blocks < 1) blocks = 1;
+  L.tiles = (unsigned) ((x1 - x0 + 7) / 8) * (unsigned) ownRows;
+  const long long needBlocks = ((long long) L.tiles * 64 + QA_BLOCK - 1) / QA_BLOCK;
+  const int csBlocks = L.csResume ? c->blocksPerCUCsResume : c->blocksPerCUCs;
+  L.blocks = (long long) c->numCUs * (c->blocksPerCU > 0 ? c->blocksPerCU : (pmOn ? c->blocksPerCUPm : (cs ? csBlocks : c->blocksPerCUAuto)));
+  if (pmOn && L.blocks > (long long) c->numCUs * 8) L.blocks = (long long) c->numCUs * 8;   // the heap scratch is sized for this
+  if (L.blocks > needBlocks) L.blocks = needBlocks;
+  if (L.blocks < 1) L.blocks = 1;
+  L.cs = cs;
+  L.pmOn = pmOn;
+  rp.chunk_spp = 0; rp.chunk_tail = 0; rp.num_chunks = 1; rp.chunk_pad = 0; rp.tile_progress = nullptr; rp.pix_state = nullptr;
+  return QA_OK;
+}
+
+// Launch what LaunchSetup planned (or the staged integrator), time it and record what ran
+static int LaunchFrame(qa_ctx *c, Launch &L, uint32_t flags, bool staged, hipStream_t s)
+{
+  EventPair ev;
+  if (!c->freeEvents.empty()) { ev = c->freeEvents.back(); c->freeEvents.pop_back(); }
+  else { HIP_TRY(hipEventCreate(&ev.a)); HIP_TRY(hipEventCreate(&ev.b)); }
+  HIP_TRY(hipEventRecord(ev.a, s));
+  if (staged) {
+    // one event pair around the whole frame of the staged integrator (qa_wf.h)
+    const int rc = RenderStaged(c, L.ds, L.rp, s, L.rp.counters);
+    if (rc != QA_OK) { c->freeEvents.push_back(ev); return rc; }
+  } else {
+    hipLaunchKernelGGL(L.kernel, dim3((unsigned) L.blocks), dim3(QA_BLOCK), (unsigned) L.ldsBytes, s, L.ds, L.rp);
+    HIP_TRY(hipGetLastError());
+  }
+  HIP_TRY(hipEventRecord(c->chunkEv, s));
+  c->chunkEvSet = true;
+  c->lastStream = s;
+  HIP_TRY(hipEventRecord(ev.b, s));
+  {
+    // the kernel this frame really ran on
+    if (staged) c->launchedName = c->kernelName;
+    else {
+      c->launchedName = MegaName(c, L.cs);
+      if (L.csResume) c->launchedName.replace(0, strlen("qa_integrate_cs"), "qa_integrate_cs_resume");
+      if (L.pmOn) c->launchedName += " + photon-map gathers (PHOTON=1)";
+      if (flags & QA_RENDER_STATS) c->launchedName += " counting variant (STATS=1, reference tree)";
+    }
+  }
+  c->pending.push_back(ev);
+  c->launches++;
+  // a caller that never asks for timers or counters must not grow the event list without bound
+  if (c->pending.size() > 256) return DrainEvents(c);
+  return QA_OK;
+}
+
+static int Render(qa_ctx *c, int x0, int y0, int x1, int y1, int tile_row0, int tile_row_step, int spp_min, int spp_max,
+                  int max_bounce, uint32_t seed, uint32_t flags, float *d_rgb, float *d_depth, uint32_t *d_ns, hipStream_t s)
+{
+  int rc = CheckFrame(c, x0, y0, x1, y1, spp_min, spp_max, max_bounce);
+  if (rc != QA_OK) return rc;
+  if (!d_rgb || !d_depth || !d_ns) return Fail(QA_EINVAL, "null output buffer");
+  rc = EnsureHalton(c, spp_max);
+  if (rc != QA_OK) return rc;
+  c->ds.halton = c->dHalton;
+  c->ds.halton_count = c->haltonCount;
+
+  if (tile_row0 < 0 || tile_row_step < 1) return Fail(QA_EINVAL, "bad strip partition");
+  const int ownRows = OwnTileRows(y0, y1, tile_row0, tile_row_step);
+  if (ownRows == 0) return QA_OK;  // nothing to do for this rank
+  const bool whole = (tile_row0 == 0 && tile_row_step == 1);
+  const size_t npix = (size_t) (x1 - x0) * (whole ? (size_t) (y1 - y0) : (size_t) ownRows * 8);
+  // pixels skipped by a stop request (and the padding rows of a ragged last strip) read as "not rendered"
+  HIP_TRY(hipMemsetAsync(d_ns, 0, npix * sizeof(uint32_t), s));
+  unsigned int *work = c->dWork + c->workNext;
+  c->workNext = (c->workNext + 1) % qa_ctx::kCounterRing;
+  HIP_TRY(hipMemsetAsync(work, 0, sizeof(unsigned int), s));
+
+  Launch L;
+  rc = LaunchSetup(c, L, x0, y0, x1, y1, tile_row0, tile_row_step, ownRows, spp_min, spp_max, max_bounce, seed, flags, d_rgb, d_depth, d_ns,
+                   work, s, false);
+  if (rc != QA_OK) return rc;
+  RenderParams &rp = L.rp;
+  const bool cs = L.cs;
+  const unsigned tiles = L.tiles;
+  const long long blocks = L.blocks;
 
   // ---- tiles in sample chunks (qa_kernel.h, section A): the per-lane kernels and the cooperative kernel's textured variants (in the
   // untextured ones the code costs more than their 4K frames' tails: 31 tiles per wave).  Per frame: when a wave gets fewer than 16 tiles, a tile's samples are handed out in chunks, so that
   // the frame ends on work items an eighth the size: half of them first, then eighths, where a wave's lanes start their samples
   // together (they also reach a chunk's end together); three quarters first where they do not (every hand-over then waits for the
   // tile's slowest pixel).  Cornell box 1080p @ 512 spp: 81.3 -> 72.5 ms (profiles/round03/chunk_sweep.txt).
-  rp.chunk_spp = 0; rp.chunk_tail = 0; rp.num_chunks = 1; rp.chunk_pad = 0; rp.tile_progress = nullptr; rp.pix_state = nullptr;
   if ((!cs || c->plan.textured) && !(c->wf.mode == QA_PIPE_STAGED) && c->optChunkSpp != 0) {   // (cooperative kernel: the textured variants carry the code)
     uint32_t chunk = 0, tail = 0;
     if (c->optChunkSpp > 0) chunk = (uint32_t) c->optChunkSpp;
@@ -354,37 +529,7 @@ static int Render(qa_ctx *c, int x0, int y0, int x1, int y1, int tile_row0, int 
   // the cooperative walks the megakernel is the faster one on every scene measured, and round 2's timed probe between the
   // two is gone.
   const bool staged = c->wf.mode == QA_PIPE_STAGED && StagedTakes(c, flags, spp_max, max_bounce, (size_t) tiles * 64);
-
-  EventPair ev;
-  if (!c->freeEvents.empty()) { ev = c->freeEvents.back(); c->freeEvents.pop_back(); }
-  else { HIP_TRY(hipEventCreate(&ev.a)); HIP_TRY(hipEventCreate(&ev.b)); }
-  HIP_TRY(hipEventRecord(ev.a, s));
-  if (staged) {
-    // one event pair around the whole frame of the staged integrator (qa_wf.h)
-    rc = RenderStaged(c, ds, rp, s, rp.counters);
-    if (rc != QA_OK) { c->freeEvents.push_back(ev); return rc; }
-  } else {
-    hipLaunchKernelGGL(kernel, dim3((unsigned) blocks), dim3(QA_BLOCK), (unsigned) ldsBytes, s, ds, rp);
-    HIP_TRY(hipGetLastError());
-  }
-  HIP_TRY(hipEventRecord(c->chunkEv, s));
-  c->chunkEvSet = true;
-  c->lastStream = s;
-  HIP_TRY(hipEventRecord(ev.b, s));
-  {
-    // the kernel this frame really ran on
-    if (staged) c->launchedName = c->kernelName;
-    else {
-      c->launchedName = MegaName(c, cs);
-      if (pmOn) c->launchedName += " + photon-map gathers (PHOTON=1)";
-      if (flags & QA_RENDER_STATS) c->launchedName += " counting variant (STATS=1, reference tree)";
-    }
-  }
-  c->pending.push_back(ev);
-  c->launches++;
-  // a caller that never asks for timers or counters must not grow the event list without bound
-  if (c->pending.size() > 256) return DrainEvents(c);
-  return QA_OK;
+  return LaunchFrame(c, L, flags, staged, s);
 }
 
 static int DrainEvents(qa_ctx *c)
@@ -528,6 +673,7 @@ int qa_ctx_destroy(qa_ctx *c)
   if (c->dPixState) (void) hipFree(c->dPixState);
   if (c->dTileProgress) (void) hipFree(c->dTileProgress);
   if (c->chunkEv) (void) hipEventDestroy(c->chunkEv);
+  if (c->prog.done) (void) hipEventDestroy(c->prog.done);
   if (c->dCounters) (void) hipFree(c->dCounters);
   if (c->hStop) (void) hipHostFree(c->hStop);
   if (c->dRgb) (void) hipFree(c->dRgb);
@@ -749,6 +895,7 @@ int qa_set_option(qa_ctx *c, const char *name, long long value)
   else if (n == "cs_pool_limit") c->optCsPool = value > 0 ? (uint32_t) std::max<long long>(64, value) : 0u;
   else if (n == "sync_samples") c->syncSamples = value < 0 ? -1 : (value > 64 ? 64 : (int) value);
   else if (n == "tile_order") c->tileOrder = value != 0;
+  else if (n == "progressive_tile_limit") c->optProgTileLimit = value > 0 ? (uint32_t) std::min<long long>(value, 0x7FFFFFFF) : 0u;
   else if (n == "staged_groups") {
     c->wf.numGroups = (int) std::max<long long>(1, std::min<long long>(value, WfHost::kMaxGroups));
     if (c->haveScene) SetKernelName(c);
@@ -775,6 +922,177 @@ int qa_debug_scrub_scratch(qa_ctx *c, uint32_t pattern)
     HIP_TRY(hipGetLastError());
   }
   HIP_TRY(hipDeviceSynchronize());
+  return QA_OK;
+}
+
+// ---- progressive frames ---------------------------------------------------------------------------------------------------------
+static int ProgActive(qa_ctx *c)
+{
+  if (!c) return Fail(QA_EINVAL, "null context");
+  if (!c->prog.active) return Fail(QA_EINVAL, c->prog.ended.empty() ? "no progressive frame: qa_progressive_begin first" : c->prog.ended);
+  return QA_OK;
+}
+
+int qa_progressive_begin(qa_ctx *c, int x0, int y0, int x1, int y1, int spp_min, int spp_max, int max_bounce, uint32_t seed, uint32_t flags)
+{
+  if (!c) return Fail(QA_EINVAL, "null context");
+  HIP_TRY(hipSetDevice(c->device));
+  int rc = CheckFrame(c, x0, y0, x1, y1, spp_min, spp_max, max_bounce);
+  if (rc != QA_OK) return rc;
+  if (flags & ~QA_RENDER_STATS) return Fail(QA_EINVAL, "unknown flags");
+  const unsigned tiles = (unsigned) ((x1 - x0 + 7) / 8) * (unsigned) ((y1 - y0 + 7) / 8);
+  // a pass's work counter runs from tiles * 64 to 2 * tiles * 64 (plus 64 per exiting wave) in 32 bits
+  if ((unsigned long long) tiles * 64ull * 2ull >= 0xF0000000ull) return Fail(QA_EINVAL, "region too large for a progressive frame");
+  EndProgressive(c, nullptr);
+  qa_ctx::Progressive &f = c->prog;
+  f.ended.clear();
+  const size_t npix = (size_t) (x1 - x0) * (size_t) (y1 - y0);
+  hipError_t e = hipSuccess;
+  if ((e = hipMalloc((void **) &f.dState, npix * 8 * sizeof(uint32_t))) != hipSuccess || (e = hipMalloc((void **) &f.dLevel, tiles * sizeof(uint32_t))) != hipSuccess ||
+      (e = hipMalloc((void **) &f.dProgress, tiles * sizeof(uint32_t))) != hipSuccess || (e = hipMalloc((void **) &f.dRgb, npix * 3 * sizeof(float))) != hipSuccess ||
+      (e = hipMalloc((void **) &f.dDepth, npix * sizeof(float))) != hipSuccess || (e = hipMalloc((void **) &f.dNs, npix * sizeof(uint32_t))) != hipSuccess ||
+      (e = hipMalloc((void **) &f.dStatus, 3 * sizeof(unsigned long long))) != hipSuccess || (e = hipMalloc((void **) &f.dList, tiles * sizeof(uint32_t))) != hipSuccess) {
+    EndProgressive(c, nullptr);
+    return Fail(e == hipErrorOutOfMemory ? QA_ENOMEM : QA_EHIP, std::string("progressive frame slabs: ") + hipGetErrorString(e));
+  }
+  if (!f.done) HIP_TRY(hipEventCreateWithFlags(&f.done, hipEventDisableTiming));
+  hipLaunchKernelGGL(qa::qa_prog_init, dim3((unsigned) ((npix + 255) / 256)), dim3(256), 0, c->stream, f.dState, f.dRgb, f.dDepth, f.dNs, x0, y0,
+                     (uint32_t) (x1 - x0), (uint32_t) npix, (uint32_t) c->ds.cam.width, seed);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemsetAsync(f.dLevel, 0, tiles * sizeof(uint32_t), c->stream));
+  HIP_TRY(hipMemsetD32Async((hipDeviceptr_t) f.dProgress, 1, tiles, c->stream));
+  HIP_TRY(hipEventRecord(f.done, c->stream));
+  f.x0 = x0; f.y0 = y0; f.x1 = x1; f.y1 = y1;
+  f.sppMin = spp_min; f.sppMax = spp_max; f.maxBounce = max_bounce;
+  f.seed = seed; f.flags = flags;
+  f.tiles = tiles;
+  f.npix = npix;
+  f.target = f.top = 0;
+  f.active = true;
+  return QA_OK;
+}
+
+// the frame's status on the context's stream (synchronises)
+static int ProgStatus(qa_ctx *c, int *reached, uint64_t *finished, uint64_t *behind)
+{
+  qa_ctx::Progressive &f = c->prog;
+  HIP_TRY(hipStreamWaitEvent(c->stream, f.done, 0));
+  HIP_TRY(hipMemsetAsync(f.dStatus, 0, 2 * sizeof(unsigned long long), c->stream));
+  HIP_TRY(hipMemsetAsync(f.dStatus + 2, 0xFF, sizeof(unsigned long long), c->stream));
+  const size_t n = std::max(f.npix, (size_t) f.tiles);
+  hipLaunchKernelGGL(qa::qa_prog_status, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, c->stream, f.dState, (uint32_t) f.npix, f.dLevel, f.tiles,
+                     (uint32_t) f.target, f.dStatus);
+  HIP_TRY(hipGetLastError());
+  unsigned long long h[3];
+  HIP_TRY(hipMemcpyAsync(h, f.dStatus, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (reached) *reached = (int) h[2];
+  if (finished) *finished = h[0];
+  if (behind) *behind = h[1];
+  return QA_OK;
+}
+
+int qa_progressive_advance(qa_ctx *c, int spp_target, void *hip_stream)
+{
+  int rc = ProgActive(c);
+  if (rc != QA_OK) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  if (spp_target < 1) return Fail(QA_EINVAL, "bad spp target");
+  qa_ctx::Progressive &f = c->prog;
+  const int target = std::min(spp_target, f.sppMax);
+  // Every unfinished pixel of a tile has exactly the tile's level in samples (a tile in hand always completes its pass).  Above every
+  // earlier target, no pixel has the target yet; at or below the highest, some tiles may have it (a stop left others behind): the
+  // pass then hands out the tiles below the target alone - or nothing happens when there are none (this asks the device)
+  const bool reissue = target <= f.top;
+  if (reissue) {
+    int reached = 0;
+    if ((rc = ProgStatus(c, &reached, nullptr, nullptr)) != QA_OK) return rc;
+    if (reached >= target) return QA_OK;
+  }
+  hipStream_t s = hip_stream ? (hipStream_t) hip_stream : c->stream;
+  rc = EnsureHalton(c, f.sppMax);   // (a one-shot frame in between may have reallocated the table)
+  if (rc != QA_OK) return rc;
+  c->ds.halton = c->dHalton;
+  c->ds.halton_count = c->haltonCount;
+  HIP_TRY(hipStreamWaitEvent(s, f.done, 0));   // the frame's setup / last pass, on whatever stream it ran
+  unsigned int *work = c->dWork + c->workNext;
+  c->workNext = (c->workNext + 1) % qa_ctx::kCounterRing;
+  Launch L;
+  rc = LaunchSetup(c, L, f.x0, f.y0, f.x1, f.y1, 0, 1, (f.y1 - f.y0 + 7) / 8, f.sppMin, f.sppMax, f.maxBounce, f.seed, f.flags, f.dRgb, f.dDepth,
+                   f.dNs, work, s, true);
+  if (rc != QA_OK) return rc;
+  // every work item is "chunk 1" of its tile: the counter starts past chunk 0 (qa_integrate, section A), so every pixel resumes from its
+  // state and ends its chunk on chunk_spp + 1 * chunk_tail = target samples.  progressive_tile_limit (tests): only the last n items are
+  // left, as if stopped
+  const uint32_t limit = c->optProgTileLimit;
+  if (reissue) {
+    hipLaunchKernelGGL(qa::qa_prog_select, dim3(1), dim3(64), 0, s, L.rp.tile_order, f.dLevel, f.tiles, (uint32_t) target, limit, f.dList, work);
+    HIP_TRY(hipGetLastError());
+    L.rp.tile_order = f.dList;
+  } else {
+    const unsigned take = (limit && limit < f.tiles) ? limit : f.tiles;
+    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t) work, (int) ((2u * f.tiles - take) * 64u), 1, s));
+  }
+  L.rp.chunk_spp = (uint32_t) target; L.rp.chunk_tail = 0; L.rp.num_chunks = 2;
+  L.rp.tile_progress = f.dProgress; L.rp.pix_state = f.dState;
+  if ((rc = LaunchFrame(c, L, f.flags, false, s)) != QA_OK) return rc;
+  hipLaunchKernelGGL(qa::qa_prog_levels, dim3((f.tiles + 255) / 256), dim3(256), 0, s, f.dProgress, L.rp.tile_order, f.dLevel, f.tiles, (uint32_t) target);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(f.done, s));
+  f.target = target;
+  f.top = std::max(f.top, target);
+  return QA_OK;
+}
+
+int qa_progressive_read_device(qa_ctx *c, float *d_rgb, float *d_depth, uint32_t *d_ns, void *hip_stream)
+{
+  int rc = ProgActive(c);
+  if (rc != QA_OK) return rc;
+  if (!d_rgb || !d_depth || !d_ns) return Fail(QA_EINVAL, "null output buffer");
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t s = hip_stream ? (hipStream_t) hip_stream : c->stream;
+  const qa_ctx::Progressive &f = c->prog;
+  HIP_TRY(hipStreamWaitEvent(s, f.done, 0));
+  hipLaunchKernelGGL(qa::qa_prog_resolve, dim3((unsigned) ((f.npix + 255) / 256)), dim3(256), 0, s, f.dState, f.dRgb, f.dDepth, f.dNs, (uint32_t) f.npix,
+                     d_rgb, d_depth, d_ns);
+  HIP_TRY(hipGetLastError());
+  return QA_OK;
+}
+
+int qa_progressive_read(qa_ctx *c, float *rgb, float *depth, uint32_t *ns)
+{
+  int rc = ProgActive(c);
+  if (rc != QA_OK) return rc;
+  if (!rgb || !depth || !ns) return Fail(QA_EINVAL, "null argument");
+  HIP_TRY(hipSetDevice(c->device));
+  qa_ctx::Progressive &f = c->prog;
+  if (!f.dPrevRgb) {
+    HIP_TRY(hipMalloc((void **) &f.dPrevRgb, f.npix * 3 * sizeof(float)));
+    HIP_TRY(hipMalloc((void **) &f.dPrevDepth, f.npix * sizeof(float)));
+    HIP_TRY(hipMalloc((void **) &f.dPrevNs, f.npix * sizeof(uint32_t)));
+  }
+  if ((rc = qa_progressive_read_device(c, f.dPrevRgb, f.dPrevDepth, f.dPrevNs, nullptr)) != QA_OK) return rc;
+  HIP_TRY(hipMemcpyAsync(rgb, f.dPrevRgb, f.npix * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(depth, f.dPrevDepth, f.npix * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(ns, f.dPrevNs, f.npix * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return QA_OK;
+}
+
+int qa_progressive_status(qa_ctx *c, int *spp_reached, uint64_t *pixels_finished, uint64_t *tiles_behind)
+{
+  int rc = ProgActive(c);
+  if (rc != QA_OK) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  return ProgStatus(c, spp_reached, pixels_finished, tiles_behind);
+}
+
+int qa_progressive_end(qa_ctx *c)
+{
+  if (!c) return Fail(QA_EINVAL, "null context");
+  HIP_TRY(hipSetDevice(c->device));
+  EndProgressive(c, nullptr);
+  c->prog.ended.clear();
   return QA_OK;
 }
 

@@ -124,6 +124,8 @@ struct qa_ctx {
   KernelFn kernelPm = nullptr, kernelPmStats = nullptr;
   // the megakernel with cooperative mesh walks (qa_kernel_cs.h): global-memory scenes without area lights
   KernelFn kernelCs = nullptr;
+  KernelFn kernelCsResume = nullptr;   // ... its chunk-capable instance where kernelCs carries no chunk code (progressive passes)
+  int blocksPerCUCsResume = 2;
   size_t ldsBytesCs = 0;
   bool csCullVariant = false;    // the cooperative kernel chosen tests the nodes' bounds first (SelectKernel)
   int blocksPerCUCs = 2;
@@ -146,6 +148,28 @@ struct qa_ctx {
   uint32_t optCsForceExact = 0; // "cs_force_exact": tests of the exact walks (bit 0 closest-hit, bit 1 shadow queries)
   uint32_t optCsPool = 0;       // "cs_pool_limit": upper bound for the walks' pool capacity (tests force the overflow path)
   bool optVerbose = false;      // "verbose": tree / launch-shape report on stderr at upload
+  uint32_t optProgTileLimit = 0; // "progressive_tile_limit": tests - a progressive pass takes at most n tiles, then ends as if stopped
+  // the progressive frame (qa_progressive_*): its slabs are its own, apart from the one-shot frames' dPixState / dTileProgress
+  struct Progressive {
+    bool active = false;
+    std::string ended;            // why the last frame ended early (a scene upload, the photon maps built or cleared): qa_last_error
+    int x0 = 0, y0 = 0, x1 = 0, y1 = 0, sppMin = 1, sppMax = 1, maxBounce = 0;
+    uint32_t seed = 0, flags = 0;
+    unsigned tiles = 0;
+    size_t npix = 0;
+    int target = 0;               // the last pass's target, min(S, spp_max)
+    int top = 0;                  // the highest target so far: no tile's level is above it
+    uint32_t *dState = nullptr;   // 8 words per pixel (output index): RNG state, samples taken | bit 31 finished, running mean, variance
+    uint32_t *dLevel = nullptr;   // per tile: the samples every unfinished pixel of it has
+    uint32_t *dList = nullptr;    // per tile: the tile order of a pass that re-issues a target (qa_prog_select)
+    uint32_t *dProgress = nullptr;   // per tile: the pass's tile_progress (1 before a pass, 2 once the tile's pass is complete)
+    float *dRgb = nullptr, *dDepth = nullptr;   // finished pixels' outputs; depth of sample 0
+    uint32_t *dNs = nullptr;
+    float *dPrevRgb = nullptr, *dPrevDepth = nullptr;   // qa_progressive_read's preview (made on first use)
+    uint32_t *dPrevNs = nullptr;
+    unsigned long long *dStatus = nullptr;   // qa_progressive_status: finished pixels, tiles behind, lowest level
+    hipEvent_t done = nullptr;    // end of the last pass
+  } prog;
 };
 
 void FreePhotonMaps(qa_ctx *c);  // qa_photon.hip
@@ -155,8 +179,24 @@ void SelectStaged(qa_ctx *c);
 bool StagedTakes(const qa_ctx *c, uint32_t flags, int spp_max, int max_bounce, size_t slots);
 int RenderStaged(qa_ctx *c, const DScene &ds, const RenderParams &rp, hipStream_t s, DCounters *frameCounters);
 
+// Ends the progressive frame, if any, and frees its slabs; a later qa_progressive_advance / read returns QA_EINVAL with `why`
+inline void EndProgressive(qa_ctx *c, const char *why)
+{
+  qa_ctx::Progressive &f = c->prog;
+  if (f.active && why) f.ended = why;
+  f.active = false;
+  void *slabs[] = {f.dState, f.dLevel, f.dList, f.dProgress, f.dRgb, f.dDepth, f.dNs, f.dPrevRgb, f.dPrevDepth, f.dPrevNs, f.dStatus};
+  if (f.dState) (void) hipDeviceSynchronize();   // (a pass may still run on a stream of the caller's)
+  for (void *p : slabs)
+    if (p) (void) hipFree(p);
+  f.dState = f.dLevel = f.dList = f.dProgress = f.dNs = f.dPrevNs = nullptr;
+  f.dRgb = f.dDepth = f.dPrevRgb = f.dPrevDepth = nullptr;
+  f.dStatus = nullptr;
+}
+
 inline void FreeScene(qa_ctx *c)
 {
+  EndProgressive(c, "the progressive frame ended: a new scene was uploaded");
   FreePhotonMaps(c);
   for (void *p : c->sceneAllocs) (void) hipFree(p);
   c->sceneAllocs.clear();

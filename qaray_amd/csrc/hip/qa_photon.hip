@@ -524,6 +524,7 @@ int qa_photon_maps_clear(qa_ctx *c)
   if (!c) return Fail(QA_EINVAL, "null context");
   HIP_TRY(hipSetDevice(c->device));
   HIP_TRY(hipStreamSynchronize(c->stream));
+  EndProgressive(c, "the progressive frame ended: the photon maps were cleared");
   FreePhotonMaps(c);
   return QA_OK;
 }
@@ -534,6 +535,7 @@ int qa_photon_maps_build(qa_ctx *c, const qa_photon_params *pp, uint32_t seed)
   if (!c->haveScene) return Fail(QA_ENOSCENE, "no scene uploaded");
   HIP_TRY(hipSetDevice(c->device));
   HIP_TRY(hipStreamSynchronize(c->stream));
+  EndProgressive(c, "the progressive frame ended: photon maps were built");
   FreePhotonMaps(c);
   const qa_photon_map_params *mps[2] = {&pp->photon, &pp->caustics};
   for (const qa_photon_map_params *mp : mps) {

@@ -1,6 +1,7 @@
 // renderer.cpp — see renderer.h.
 #include "renderer.h"
 
+#include <algorithm>
 #include <chrono>
 #include <cstdio>
 #include <cstring>
@@ -222,6 +223,50 @@ void Renderer::ThreadRender()
 void Renderer::Render()
 {
   ThreadRender();
+  image->ComputeZBufferImage();
+  image->ComputeSampleCountImage();
+  image->SaveImage((outputPrefix + "colorBuffer.png").c_str());
+  image->SaveZImage((outputPrefix + "depthBuffer.png").c_str());
+  image->SaveSampleCountImage((outputPrefix + "sampleBuffer.png").c_str());
+}
+
+// The batch counterpart of Renderer_GUI's progressive display (src/renderers/Renderer_GUI.cpp:37-97, which shows renderImage while
+// the render threads fill it): the frame stays resident on the GPU (qa_progressive_*) and its samples are raised in passes of
+// passSpp up to sppMax; after each pass the FrameBuffer is filled from the preview and the three images are written again.  The
+// last pass leaves the one-shot frame's images, byte for byte.
+void Renderer::RenderProgressive(size_t passSpp)
+{
+  if (!multi.empty() || mpiSize != 1) throw std::runtime_error("-progressive renders on one device and cannot be combined with -devices");
+  if (passSpp < 1) throw std::runtime_error("-progressive needs passes of at least one sample");
+  StartTimer();
+  printf("\nRunning on HIP device %d, progressive passes of %zu spp\n", device, passSpp);
+  const int W = (int) pixelW, H = (int) pixelH;
+  if (tasking::has_stop_signal()) qa_request_stop(ctx);
+  else qa_clear_stop(ctx);
+  qa_reset_counters(ctx);
+  if (qa_progressive_begin(ctx, 0, 0, W, H, (int) param.sppMin, (int) param.sppMax, Material::maxBounce, param.seed, 0) != QA_OK)
+    throw std::runtime_error(std::string("qa_progressive_begin: ") + qa_last_error());
+  std::vector<float> rgb((size_t) 3 * W * H), depth((size_t) W * H);
+  std::vector<uint32_t> ns((size_t) W * H);
+  for (size_t spp = 0; spp < param.sppMax;) {
+    spp = std::min(spp + passSpp, param.sppMax);
+    const auto t0 = std::chrono::system_clock::now();
+    if (qa_progressive_advance(ctx, (int) spp, nullptr) != QA_OK || qa_progressive_read(ctx, rgb.data(), depth.data(), ns.data()) != QA_OK)
+      throw std::runtime_error(std::string("qa_progressive: ") + qa_last_error());
+    const std::chrono::duration<double, std::milli> ms = std::chrono::system_clock::now() - t0;
+    int reached = 0;
+    qa_progressive_status(ctx, &reached, nullptr, nullptr);
+    printf("pass to %zu spp: %d spp reached, %.3f ms\n", spp, reached, ms.count());
+    image->Deposit(0, 0, W, H, rgb.data(), depth.data(), ns.data(), (int) param.sppMax, param.useSRGB);
+    SaveImages();
+  }
+  qa_progressive_end(ctx);
+  qa_get_counters(ctx, &counters);
+  StopTimer();
+}
+
+void Renderer::SaveImages()
+{
   image->ComputeZBufferImage();
   image->ComputeSampleCountImage();
   image->SaveImage((outputPrefix + "colorBuffer.png").c_str());

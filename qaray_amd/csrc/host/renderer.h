@@ -57,6 +57,7 @@ class Renderer {
   void ComputeScene(FrameBuffer &renderImage, Scene &scene);  // camera frame, fb, scene upload, photon maps
   virtual void Render();                                // ThreadRender + image dumps (batch mode)
   void ThreadRender();                                  // the hot path: one HIP call
+  void RenderProgressive(size_t passSpp);               // Render in passes of passSpp samples, images rewritten after each
   virtual void StartTimer();
   virtual void StopTimer();
   virtual void KillTimer();
@@ -76,6 +77,7 @@ class Renderer {
   std::vector<int> multi;                               // UseDevices: empty = the single-context path
   std::vector<qa_ctx *> ctxs;                           // one per entry of `multi`
   void ThreadRenderMulti();
+  void SaveImages();                                    // the three PNGs of the FrameBuffer
   double lastSeconds = 0, avgSeconds = 0;
   int numFrames = -1;
   qa_counters counters{};

@@ -87,6 +87,12 @@ def lib():
         L.qa_get_kernel_name.argtypes = [C.c_void_p]
         L.qa_get_kernel_name.restype = C.c_char_p
         L.qa_get_staged_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        L.qa_progressive_begin.argtypes = [C.c_void_p] + [C.c_int] * 7 + [C.c_uint32, C.c_uint32]
+        L.qa_progressive_advance.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.qa_progressive_read.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.qa_progressive_read_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.qa_progressive_status.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.qa_progressive_end.argtypes = [C.c_void_p]
         L.qa_photon_maps_build.argtypes = [C.c_void_p, C.POINTER(PhotonParams), C.c_uint32]
         L.qa_photon_maps_clear.argtypes = [C.c_void_p]
         L.qa_photon_maps_info.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
@@ -174,6 +180,17 @@ class Context:
                                       ns.ctypes.data))
         return rgb, depth, ns
 
+    def progressive(self, region, spp, spp_max=None, max_bounce=5, seed=DEFAULT_SEED, stats=False):
+        """Begin a progressive frame (qa_progressive_begin): a resident image whose samples are raised in passes
+        (Progressive.advance), with a preview between passes.  spp is spp_min; spp_max defaults to it.  The final frame
+        is bit-identical to render_region with the same arguments.  One frame per context: a new one ends the last."""
+        spp_max = spp if spp_max is None else spp_max
+        x0, y0, x1, y1 = region
+        _check(lib().qa_progressive_begin(self._h, x0, y0, x1, y1, spp, spp_max, max_bounce, seed,
+                                          QA_RENDER_STATS if stats else 0))
+        self._prog = Progressive(self, region)
+        return self._prog
+
     def render_region_device(self, region, spp, rgb, depth, ns, max_bounce=5, seed=DEFAULT_SEED, spp_max=None,
                              stats=False, stream=None):
         """Asynchronous render into torch CUDA tensors (float32 [h,w,3], float32 [h,w], int32/uint32 [h,w]).
@@ -248,7 +265,8 @@ class Context:
         _check(lib().qa_set_pipeline(self._h, self.PIPELINES[mode]))
 
     def set_option(self, name, value):
-        """qa_set_option: 'coop', 'cs_cull', 'cs_force_exact', 'walk_zero_terms', 'cs_pool_limit', 'chunk_spp', 'chunk_tail', 'sync_samples', 'tile_order', 'staged_groups', 'verbose'."""
+        """qa_set_option: 'coop', 'cs_cull', 'cs_force_exact', 'walk_zero_terms', 'cs_pool_limit', 'chunk_spp', 'chunk_tail', 'sync_samples', 'tile_order', 'staged_groups', 'verbose',
+        'progressive_tile_limit'."""
         _check(lib().qa_set_option(self._h, name.encode(), int(value)))
 
     def kernel_name(self):
@@ -287,3 +305,58 @@ class Context:
             self.close()
         except Exception:
             pass
+
+
+class Progressive:
+    """A progressive frame of a Context (Context.progressive).  advance() enqueues a pass, read() returns the preview
+    (finished pixels' final values, the running mean and samples so far of the others), status() how far it got."""
+
+    def __init__(self, ctx, region):
+        self._ctx = ctx
+        self.region = tuple(region)
+
+    def advance(self, spp_target, stream=None):
+        """Bring every unfinished pixel to min(spp_target, spp_max) samples (one megakernel launch, enqueued on `stream`,
+        a HIP stream handle; None = the context's own stream)."""
+        _check(lib().qa_progressive_advance(self._ctx._h, int(spp_target), C.c_void_p(stream) if stream else None))
+
+    def read(self):
+        """-> (rgb[h,w,3] f32, depth[h,w] f32, ns[h,w] u32), as render_region returns them; synchronises."""
+        x0, y0, x1, y1 = self.region
+        h, w = y1 - y0, x1 - x0
+        rgb = np.zeros((h, w, 3), np.float32)
+        depth = np.zeros((h, w), np.float32)
+        ns = np.zeros((h, w), np.uint32)
+        _check(lib().qa_progressive_read(self._ctx._h, rgb.ctypes.data, depth.ctypes.data, ns.ctypes.data))
+        return rgb, depth, ns
+
+    def read_device(self, rgb, depth, ns, stream=None):
+        """The preview into torch CUDA tensors (float32 [h,w,3], float32 [h,w], int32/uint32 [h,w]); only enqueues (see
+        Context.render_region_device for the stream)."""
+        x0, y0, x1, y1 = self.region
+        n = (x1 - x0) * (y1 - y0)
+        assert rgb.is_cuda and rgb.is_contiguous() and rgb.numel() == 3 * n and rgb.element_size() == 4
+        assert depth.is_cuda and depth.is_contiguous() and depth.numel() == n and depth.element_size() == 4
+        assert ns.is_cuda and ns.is_contiguous() and ns.numel() == n and ns.element_size() == 4
+        sptr = Context._stream_arg(stream, rgb)
+        _check(lib().qa_progressive_read_device(self._ctx._h, rgb.data_ptr(), depth.data_ptr(), ns.data_ptr(), sptr))
+
+    def status(self):
+        """-> dict(spp_reached, pixels_finished, tiles_behind); synchronises."""
+        r, f, b = C.c_int(), C.c_uint64(), C.c_uint64()
+        _check(lib().qa_progressive_status(self._ctx._h, C.byref(r), C.byref(f), C.byref(b)))
+        return {"spp_reached": r.value, "pixels_finished": f.value, "tiles_behind": b.value}
+
+    def close(self):
+        """End the frame (qa_progressive_end) unless a newer frame of the context has replaced it."""
+        if self._ctx is not None and self._ctx._h and getattr(self._ctx, "_prog", None) is self:
+            _check(lib().qa_progressive_end(self._ctx._h))
+            self._ctx._prog = None
+        self._ctx = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
