@@ -143,7 +143,8 @@ static const char *kStagedName = "staged: wf_logic + wf_cull + wf_trace + wf_red
 static std::string MegaName(const qa_ctx *c, bool cs)
 {
   char name[160];
-  if (cs) snprintf(name, sizeof(name), "qa_integrate_cs<LIGHTS=%d,TEX=%d,CULL=%d%s>", (int) (c->ds.num_lights > 0), (int) c->plan.textured, (int) c->csCullVariant, c->plan.area ? ",AREA=1" : "");
+  if (cs) snprintf(name, sizeof(name), "qa_integrate_cs<LIGHTS=%d,TEX=%d,CULL=%d%s%s>", (int) (c->ds.num_lights > 0), (int) c->plan.textured, (int) c->csCullVariant,
+                   c->csMany ? ",MANY=1" : "", c->plan.area ? ",AREA=1" : "");
   else snprintf(name, sizeof(name), "qa_integrate<RES=%d,LIGHTS=%d,TEX=%d,AREA=%d>", (int) c->plan.resident, (int) (c->ds.num_lights > 0), (int) c->plan.textured, (int) c->plan.area);
   return name;
 }
@@ -559,16 +560,20 @@ __global__ void qa_math_probe(int fn, const float *x, const float *y, int n, flo
     case 0: out[i] = qsinf(x[i]); break;
     case 1: out[i] = qcosf(x[i]); break;
     case 2: out[i] = qpowf(x[i], y[i]); break;
-    default: out[i] = qexpf(x[i]); break;
+    case 3: out[i] = qexpf(x[i]); break;
+    case 4: out[i] = qasinf(x[i]); break;
+    case 5: out[i] = sphereU(x[i], y[i]); break;
+    default: out[i] = sphereV(x[i], y[i]); break;
   }
 }
 
 extern "C" {
 
-// the device build of qa_device_math.h: fn 0 sinf, 1 cosf, 2 powf(x, y), 3 expf (host arrays in / out)
+// the device build of qa_device_math.h: fn 0 sinf, 1 cosf, 2 powf(x, y), 3 expf, 4 asinf; and of the sphere's texture
+// coordinates (qa_texture_dev.h): 5 u from (p.x = x, p.y = y), 6 v from (p.z = x, rcp_l = y) (host arrays in / out)
 int qa_test_math_device(int fn, const float *x, const float *y, int n, float *out)
 {
-  if (!x || !out || n <= 0 || fn < 0 || fn > 3 || (fn == 2 && !y)) return Fail(QA_EINVAL, "bad argument");
+  if (!x || !out || n <= 0 || fn < 0 || fn > 6 || ((fn == 2 || fn == 5 || fn == 6) && !y)) return Fail(QA_EINVAL, "bad argument");
   float *dx = nullptr, *dy = nullptr, *dout = nullptr;
   HIP_TRY(hipMalloc((void **) &dx, n * sizeof(float)));
   HIP_TRY(hipMalloc((void **) &dy, n * sizeof(float)));
@@ -608,6 +613,9 @@ int qa_test_math_host(int fn, const float *x, const float *y, int n, float *out)
       case 1: out[i] = qcosf(x[i]); break;
       case 2: out[i] = qpowf(x[i], y ? y[i] : 1.f); break;
       case 3: out[i] = qexpf(x[i]); break;
+      case 4: out[i] = qasinf(x[i]); break;
+      case 5: if (!y) return QA_EINVAL; out[i] = sphereU(x[i], y[i]); break;
+      case 6: if (!y) return QA_EINVAL; out[i] = sphereV(x[i], y[i]); break;
       default: return QA_EINVAL;
     }
   }

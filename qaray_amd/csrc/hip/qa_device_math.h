@@ -5,9 +5,10 @@
 // the same order and this library is built with -ffp-contract=off and correctly rounded
 // divide/sqrt, so +,-,*,/ and sqrt give the reference's bits.  The only places where bits can
 // differ are libm calls (sinf, cosf, powf, expf, asinf, tanf and the double asin/atan2 of the
-// sphere's texture coordinates): glibc's float routines are evaluated in double and are correctly
-// rounded for the vast majority of arguments, so the device versions below also evaluate in fp64
-// (MI355X runs fp64 vector math at half the fp32 rate) and round once to fp32.
+// sphere's texture coordinates).  sinf, cosf, expf, powf and asinf restate the algorithms of the
+// glibc the reference links, so that they return its bits (tests/test_device_math.py pins the host
+// build of this file to libm, tests/test_gpu_device_math.py the device build to the host build);
+// tanf is evaluated in fp64 and rounded once.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -281,7 +282,47 @@ __host__ __device__ __forceinline__ float qpowf(float x, float y)
   e = __builtin_fma(zz, rr2, e);
   return (float) (e * s);
 }
-__host__ __device__ __forceinline__ float qasinf(float x) { return (float) asin((double) x); }
+
+// ---------------------------------------------------------------------------------------------
+// asinf: glibc's single-precision routine (fdlibm's e_asinf.c as glibc ships it; x86-64 has no FMA
+// variant of it), evaluated entirely in fp32: asin(x) = x + x*t*P(t), t = x^2, on |x| < 0.5;
+// pi/2 - 2*asin(sqrt((1 - |x|)/2)) above, with a split of the square root (w, c) between 0.5 and
+// 0.975.  P is a degree-4 polynomial, Horner order, every operation rounded (no FMA).  A correctly
+// rounded (float) asin((double) x) differs from it by 1 ulp on ~4.6e6 of the 2.1e9 floats in [-1, 1].
+// tests/test_device_math.py compares the host build with libm, tests/test_gpu_device_math.py the
+// device build with the host build.  Not inlined: it runs once per escaped ray, and inlined its
+// branches cost the textured cooperative kernel (C3) registers and ~4 % of its speed.
+// ---------------------------------------------------------------------------------------------
+__host__ __device__ inline __noinline__ float qasinf(float x)
+{
+  const float pio2_hi = 0x1.921fb6p+0f, pio2_lo = -0x1.777a5cp-25f, pio4_hi = 0x1.921fb6p-1f;
+  const float p0 = 0x1.5555c8p-3f, p1 = 0x1.3301e4p-4f, p2 = 0x1.747e4ap-5f, p3 = 0x1.8c283cp-6f, p4 = 0x1.596d28p-5f;
+  const uint32_t hx = qa_asuint(x), ix = hx & 0x7fffffffu;
+  if (ix == 0x3f800000u) return x * pio2_hi + x * pio2_lo;  // asin(+-1)
+  if (ix > 0x3f800000u) return (x - x) / (x - x);           // |x| > 1 or NaN
+  if (ix < 0x3f000000u) {                                   // |x| < 0.5
+    if (ix < 0x32000000u) return x;                         // |x| < 2^-27
+    const float t = x * x;
+    const float w = t * (p0 + t * (p1 + t * (p2 + t * (p3 + t * p4))));
+    return x + x * w;
+  }
+  const float t = (1.0f - __builtin_fabsf(x)) * 0.5f;
+  const float p = t * (p0 + t * (p1 + t * (p2 + t * (p3 + t * p4))));
+  const float s = qsqrt(t);
+  float r;
+  if (ix >= 0x3f79999au) {  // |x| > 0.975
+    r = pio2_hi - (2.0f * (s + s * p) - pio2_lo);
+  } else {
+    const uint32_t iw = qa_asuint(s) & 0xfffff000u;
+    float w;
+    __builtin_memcpy(&w, &iw, 4);
+    const float c = (t - w * w) / (s + w);
+    const float pp = 2.0f * s * p - (pio2_lo - 2.0f * c);
+    const float q = pio4_hi - 2.0f * w;
+    r = pio4_hi - (pp - q);
+  }
+  return (int32_t) hx > 0 ? r : -r;
+}
 __host__ __device__ __forceinline__ float qtanf(float x) { return (float) tan((double) x); }
 
 }  // namespace qa

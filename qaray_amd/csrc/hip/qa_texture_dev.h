@@ -34,13 +34,17 @@ struct TexTables {
 };
 
 // ---- texture coordinates --------------------------------------------------------------------
-// Sphere_TexCoord (objects.cpp:48-53): C's double atan2/asin, rounded when the Point3 is built
-__device__ __forceinline__ f3 sphereTexCoord(f3 p, float rcp_l)
+// Sphere_TexCoord (objects.cpp:48-53): C's double atan2/asin, rounded when the Point3 is built.  Host and device
+// builds of the two coordinates are compared bit for bit (qa_test_math_host / _device, fn 5 and 6)
+__host__ __device__ __forceinline__ float sphereU(float px, float py)
 {
-  const double u = 0.5 - atan2((double) p.x, (double) p.y) * (double) QA_RCP_2PI;
-  const double v = 0.5 + asin((double) (p.z * rcp_l)) * (double) QA_RCP_PI;
-  return F3((float) u, (float) v, 0.f);
+  return (float) (0.5 - atan2((double) px, (double) py) * (double) QA_RCP_2PI);
 }
+__host__ __device__ __forceinline__ float sphereV(float pz, float rcp_l)
+{
+  return (float) (0.5 + asin((double) (pz * rcp_l)) * (double) QA_RCP_PI);
+}
+__device__ __forceinline__ f3 sphereTexCoord(f3 p, float rcp_l) { return F3(sphereU(p.x, p.y), sphereV(p.z, rcp_l), 0.f); }
 __device__ __forceinline__ f3 planeTexCoord(f3 p) { return F3((p.x + 1.f) * 0.5f, (p.y + 1.f) * 0.5f, 0.f); }
 
 // Sphere::IntersectRay's texture block (objects.cpp:96-118); p, N: the accepted local hit

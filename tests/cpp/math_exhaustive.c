@@ -2,7 +2,8 @@
  * host inside libqaray_hip.so, entry point qa_test_math_host) against the host libm, bit for bit.
  *   math_exhaustive <libqaray_hip.so> 0 [stride]   expf over every stride-th float bit pattern
  *   math_exhaustive <libqaray_hip.so> 1 [stride]   powf over positive bases below 2 x 17 exponents + random pairs
- * stride 1 = the full sweep (4.3e9 / 3.9e9 evaluations, ~30 s on 8 cores); the test suite uses a larger stride. */
+ *   math_exhaustive <libqaray_hip.so> 2 [stride]   asinf over every stride-th float in [-1, 1]
+ * stride 1 = the full sweep (4.3e9 / 3.9e9 / 2.1e9 evaluations, ~30 s on 8 cores); the test suite uses a larger stride. */
 #define _GNU_SOURCE
 #include <dlfcn.h>
 #include <math.h>
@@ -35,6 +36,32 @@ int main(int argc, char **argv)
           uint32_t a, b; memcpy(&a, &e, 4); memcpy(&b, &o[i], 4);
           total++;
           if (a != b) { if (bad < 5) fprintf(stderr, "expf(%a) libm %a mine %a\n", x[i], e, o[i]); bad++; }
+        }
+      }
+    }
+  } else if (mode == 2) {  // asinf over [-1, 1]: the bit patterns 0 .. 0x3f800000 of either sign
+#pragma omp parallel reduction(+ : bad, total)
+    {
+      const int CH = 1 << 16;
+      const long long per_sign = (0x3f800000LL + CH) / CH;   // chunks of 65536 patterns up to and including 1.0
+      float *x = malloc(CH * 4), *o = malloc(CH * 4);
+#pragma omp for schedule(dynamic, 64)
+      for (long long c = 0; c < 2 * per_sign; c += stride) {
+        const uint32_t sign = c < per_sign ? 0u : 0x80000000u;
+        const long long c0 = c < per_sign ? c : c - per_sign;
+        int n = 0;
+        for (int i = 0; i < CH; ++i) {
+          const long long u = c0 * CH + i;
+          if (u > 0x3f800000LL) break;
+          const uint32_t b = (uint32_t) u | sign;
+          memcpy(&x[n++], &b, 4);
+        }
+        f(4, x, NULL, n, o);
+        for (int i = 0; i < n; ++i) {
+          float e = asinf(x[i]);
+          uint32_t a, b; memcpy(&a, &e, 4); memcpy(&b, &o[i], 4);
+          total++;
+          if (a != b) { if (bad < 5) fprintf(stderr, "asinf(%a) libm %a mine %a\n", x[i], e, o[i]); bad++; }
         }
       }
     }

@@ -7,7 +7,10 @@ Tolerances (fp32 radiance, written here as the contract asks):
     (Cornell box = BASELINE config[1]) are bit-identical to the reference.  Elsewhere the kernel sums
     the reference's recursive radiance formula front-to-back (a throughput product instead of nested
     multiplications), which moves results by a few ulp: per-image RMSE <= 1e-6 and max abs error
-    <= 1e-4 (north_star: RMSE < 1e-4).  sinf/cosf/expf/powf return glibc's bits (tests/test_device_math.py).
+    <= 1e-4 (north_star: RMSE < 1e-4).  sinf/cosf/expf/powf/asinf return glibc's bits: their host builds
+    against libm in tests/test_device_math.py (with the sphere's double-atan2/asin uv against the oracle's
+    expressions), their device builds against the host builds in tests/test_gpu_device_math.py (sin/cos:
+    test_device_sincos_equals_host_libm below).  Every shipped kernel instance: tests/test_gpu_variant_census.py.
 """
 import os
 
