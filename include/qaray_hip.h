@@ -223,6 +223,19 @@ int qa_test_sincosf_device(const float *x, int n, float *s, float *c);
 int qa_test_math_device(int fn, const float *x, const float *y, int n, float *out);
 int qa_test_math_host(int fn, const float *x, const float *y, int n, float *out);
 
+/* Self-test hooks for the texture path (qaray_amd/csrc/hip/qa_texture_dev.h): n queries of one op, 16 floats in and 9 out per query.
+ * in: [0..2] a, [3..5] b, [6..8] c, [9..11] d, [12..14] e, [15] flag; out: three vectors r0, r1, r2 (zero where an op has fewer).
+ *   op 0 tileClamp(a)                          4 mtlSample(hit {uvw a, duvw b, c, hasTexture flag}, colour d, texmap index)
+ *   op 1 textureSample(texture index, a)       5 sampleEnvironment(colour b, texmap index, direction a)
+ *   op 2 textureSampleFiltered(index, a, b, c) 6 texPlane(o a, dx b, dy c, p d) -> uvw, duvw0, duvw1
+ *   op 3 texColorSample(colour b, texmap index, uvw a)   7 texSphere(o a, dx b, dy c, p d, N e) -> uvw, duvw0, duvw1
+ *   op 8 texTriangle(element index & 0xFFFFF of mesh index >> 20, o a, dx b, dy c, barycentrics d.x, d.y) -> uvw, duvw0, duvw1
+ *   op 9 the float -> int conversion of the texel lookups (x86 semantics) of a.x: the int's bits in r0.x
+ * The device hook reads the tables of the scene uploaded into ctx, the host hook builds them from blob on the CPU (no GPU needed;
+ * ops 0 and 9 read no table, and blob may be null). */
+int qa_test_texture_device(qa_ctx *ctx, int op, int index, int n, const float *in, float *out);
+int qa_test_texture_host(const void *blob, int op, int index, int n, const float *in, float *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -60,6 +60,7 @@ def lib():
         L.qa_oracle_halton.restype = C.c_float
         L.qa_oracle_rng_stream.argtypes = [C.c_uint32, C.c_uint32, C.c_int, C.c_void_p]
         L.qa_oracle_rng_stream.restype = None
+        L.qa_oracle_texture_probe.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -111,4 +112,16 @@ def halton(i, base):
 def rng_stream(seed, pixel, n):
     out = np.zeros(n, np.float32)
     lib().qa_oracle_rng_stream(seed, pixel, n, out.ctypes.data)
+    return out
+
+
+def texture_probe(blob, op, index, queries):
+    """The oracle's texture functions on n queries of one op (include/qaray_hip.h qa_test_texture_host: the same op numbers and
+    layout): queries float32 [n, 16] -> float32 [n, 9]."""
+    blob = np.ascontiguousarray(blob, dtype=np.uint8)
+    q = np.ascontiguousarray(queries, np.float32).reshape(-1, 16)
+    out = np.zeros((len(q), 9), np.float32)
+    rc = lib().qa_oracle_texture_probe(blob.ctypes.data, op, index, len(q), q.ctypes.data, out.ctypes.data)
+    if rc != 0:
+        raise RuntimeError(f"qa_oracle_texture_probe failed: {rc}")
     return out

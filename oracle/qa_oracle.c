@@ -318,6 +318,23 @@ static v3 sphere_texcoord(v3 p, float rcp_l)
   return V3((float) (0.5f - atan2(p.x, p.y) * kRCP_2PI), (float) (0.5f + asin(p.z * rcp_l) * kRCP_PI), 0.f);
 }
 
+/* the differential block of src/objects/objects.cpp:96-118 (hc->uvw set) */
+static void sphere_diff(const diffray_t *dr, v3 p, v3 N, hit_t *hc, diffhit_t *dh)
+{
+  const float pz_x = vdot(vsub(dr->x.p, p), N);
+  const float pz_y = vdot(vsub(dr->y.p, p), N);
+  const float dz_x = vdot(dr->x.dir, N);
+  const float dz_y = vdot(dr->y.dir, N);
+  const float t_x = -pz_x / dz_x;
+  const float t_y = -pz_y / dz_y;
+  const v3 p_x = vadd(dr->x.p, vscale(dr->x.dir, t_x));
+  const v3 p_y = vadd(dr->y.p, vscale(dr->y.dir, t_y));
+  dh->x.z = t_x; dh->x.p = p_x; dh->x.N = vnormalize(p_x);
+  dh->y.z = t_y; dh->y.p = p_y; dh->y.N = vnormalize(p_y);
+  hc->duvw[0] = vscale(vsub(sphere_texcoord(p_x, 1.f / vlength(p_x)), hc->uvw), kRDX);
+  hc->duvw[1] = vscale(vsub(sphere_texcoord(p_y, 1.f / vlength(p_y)), hc->uvw), kRDX);
+}
+
 /* src/objects/objects.cpp:55-141; dr == NULL is a shadow query */
 static int sphere_intersect(const ray_t *ray, hit_t *hc, const diffray_t *dr, diffhit_t *dh)
 {
@@ -352,18 +369,7 @@ static int sphere_intersect(const ray_t *ray, hit_t *hc, const diffray_t *dr, di
       hc->hasTexture = 1;
       hc->uvw = sphere_texcoord(p, 1.f);
       if (dr->hasDiffRay) {
-        const float pz_x = vdot(vsub(dr->x.p, p), N);
-        const float pz_y = vdot(vsub(dr->y.p, p), N);
-        const float dz_x = vdot(dr->x.dir, N);
-        const float dz_y = vdot(dr->y.dir, N);
-        const float t_x = -pz_x / dz_x;
-        const float t_y = -pz_y / dz_y;
-        const v3 p_x = vadd(dr->x.p, vscale(dr->x.dir, t_x));
-        const v3 p_y = vadd(dr->y.p, vscale(dr->y.dir, t_y));
-        dh->x.z = t_x; dh->x.p = p_x; dh->x.N = vnormalize(p_x);
-        dh->y.z = t_y; dh->y.p = p_y; dh->y.N = vnormalize(p_y);
-        hc->duvw[0] = vscale(vsub(sphere_texcoord(p_x, 1.f / vlength(p_x)), hc->uvw), kRDX);
-        hc->duvw[1] = vscale(vsub(sphere_texcoord(p_y, 1.f / vlength(p_y)), hc->uvw), kRDX);
+        sphere_diff(dr, p, N, hc, dh);
       } else {
         dh->x.z = t; dh->x.p = p; dh->x.N = N;
         dh->y.z = t; dh->y.p = p; dh->y.N = N;
@@ -378,6 +384,24 @@ static int sphere_intersect(const ray_t *ray, hit_t *hc, const diffray_t *dr, di
 
 /* src/objects/objects.cpp:144-147 */
 static inline v3 plane_texcoord(v3 p) { return V3((p.x + 1.f) * 0.5f, (p.y + 1.f) * 0.5f, 0.f); }
+
+/* the differential block of src/objects/objects.cpp:168-192 (hc->uvw set) */
+static void plane_diff(const diffray_t *dr, hit_t *hc, diffhit_t *dh)
+{
+  const v3 N = V3(0, 0, 1);
+  const float pz_x = vdot(dr->x.p, N);
+  const float pz_y = vdot(dr->y.p, N);
+  const float dz_x = vdot(dr->x.dir, N);
+  const float dz_y = vdot(dr->y.dir, N);
+  const float t_x = -pz_x / dz_x;
+  const float t_y = -pz_y / dz_y;
+  const v3 p_x = vadd(dr->x.p, vscale(dr->x.dir, t_x));
+  const v3 p_y = vadd(dr->y.p, vscale(dr->y.dir, t_y));
+  dh->x.z = t_x; dh->x.p = p_x; dh->x.N = N;
+  dh->y.z = t_y; dh->y.p = p_y; dh->y.N = N;
+  hc->duvw[0] = vscale(vsub(plane_texcoord(p_x), hc->uvw), kRDX);
+  hc->duvw[1] = vscale(vsub(plane_texcoord(p_y), hc->uvw), kRDX);
+}
 
 /* src/objects/objects.cpp:149-208 */
 static int plane_intersect(const ray_t *ray, hit_t *hc, const diffray_t *dr, diffhit_t *dh)
@@ -400,18 +424,7 @@ static int plane_intersect(const ray_t *ray, hit_t *hc, const diffray_t *dr, dif
       hc->hasTexture = 1;
       hc->uvw = plane_texcoord(p);
       if (dr->hasDiffRay) {
-        const float pz_x = vdot(dr->x.p, N);
-        const float pz_y = vdot(dr->y.p, N);
-        const float dz_x = vdot(dr->x.dir, N);
-        const float dz_y = vdot(dr->y.dir, N);
-        const float t_x = -pz_x / dz_x;
-        const float t_y = -pz_y / dz_y;
-        const v3 p_x = vadd(dr->x.p, vscale(dr->x.dir, t_x));
-        const v3 p_y = vadd(dr->y.p, vscale(dr->y.dir, t_y));
-        dh->x.z = t_x; dh->x.p = p_x; dh->x.N = N;
-        dh->y.z = t_y; dh->y.p = p_y; dh->y.N = N;
-        hc->duvw[0] = vscale(vsub(plane_texcoord(p_x), hc->uvw), kRDX);
-        hc->duvw[1] = vscale(vsub(plane_texcoord(p_y), hc->uvw), kRDX);
+        plane_diff(dr, hc, dh);
       } else {
         dh->x.z = t; dh->x.p = p; dh->x.N = N;
         dh->y.z = t; dh->y.p = p; dh->y.N = N;
@@ -460,6 +473,32 @@ static inline v3 tri_texcoord(const meshview_t *mv, const qa_face *f, v3 bc)
 {
   const float *t0 = mv->VT + 2 * f->vt[0], *t1 = mv->VT + 2 * f->vt[1], *t2 = mv->VT + 2 * f->vt[2];
   return V3(t0[0] * bc.x + t1[0] * bc.y + t2[0] * bc.z, t0[1] * bc.x + t1[1] * bc.y + t2[1] * bc.z, 0.f);
+}
+
+/* the differential block of src/objects/objects.cpp:256-294 (hc->uvw, hc->N set) */
+static void triangle_diff(const meshview_t *mv, const qa_face *f, v3 A, v3 B, v3 C, v3 N, int axis, float s, int hasVT,
+                          const diffray_t *dr, hit_t *hc, diffhit_t *dh)
+{
+  const float pz_x = vdot(vsub(dr->x.p, A), N);
+  const float pz_y = vdot(vsub(dr->y.p, A), N);
+  const float dz_x = vdot(dr->x.dir, N);
+  const float dz_y = vdot(dr->y.dir, N);
+  const float t_x = -pz_x / dz_x;
+  const float t_y = -pz_y / dz_y;
+  const v3 p_x = vadd(dr->x.p, vscale(dr->x.dir, t_x));
+  const v3 p_y = vadd(dr->y.p, vscale(dr->y.dir, t_y));
+  const float axx = tri_area(axis, p_x, B, C) * s;
+  const float bxx = tri_area(axis, p_x, C, A) * s;
+  const float cxx = 1.f - axx - bxx;
+  const float ayy = tri_area(axis, p_y, B, C) * s;
+  const float byy = tri_area(axis, p_y, C, A) * s;
+  const float cyy = 1.f - ayy - byy;
+  dh->x.z = t_x; dh->x.p = p_x; dh->x.N = hc->N;
+  dh->y.z = t_y; dh->y.p = p_y; dh->y.N = hc->N;
+  if (hasVT) {
+    hc->duvw[0] = vscale(vsub(tri_texcoord(mv, f, V3(axx, bxx, cxx)), hc->uvw), kRDX);
+    hc->duvw[1] = vscale(vsub(tri_texcoord(mv, f, V3(ayy, byy, cyy)), hc->uvw), kRDX);
+  }
 }
 
 /* src/objects/objects.cpp:212-306 */
@@ -517,26 +556,7 @@ static int triangle_intersect(const meshview_t *mv, const ray_t *ray, hit_t *hc,
         hc->uvw = tri_texcoord(mv, f, bc);
       }
       if (dr->hasDiffRay) {
-        const float pz_x = vdot(vsub(dr->x.p, A), N);
-        const float pz_y = vdot(vsub(dr->y.p, A), N);
-        const float dz_x = vdot(dr->x.dir, N);
-        const float dz_y = vdot(dr->y.dir, N);
-        const float t_x = -pz_x / dz_x;
-        const float t_y = -pz_y / dz_y;
-        const v3 p_x = vadd(dr->x.p, vscale(dr->x.dir, t_x));
-        const v3 p_y = vadd(dr->y.p, vscale(dr->y.dir, t_y));
-        const float axx = tri_area(axis, p_x, B, C) * s;
-        const float bxx = tri_area(axis, p_x, C, A) * s;
-        const float cxx = 1.f - axx - bxx;
-        const float ayy = tri_area(axis, p_y, B, C) * s;
-        const float byy = tri_area(axis, p_y, C, A) * s;
-        const float cyy = 1.f - ayy - byy;
-        dh->x.z = t_x; dh->x.p = p_x; dh->x.N = hc->N;
-        dh->y.z = t_y; dh->y.p = p_y; dh->y.N = hc->N;
-        if (hasVT) {
-          hc->duvw[0] = vscale(vsub(tri_texcoord(mv, f, V3(axx, bxx, cxx)), hc->uvw), kRDX);
-          hc->duvw[1] = vscale(vsub(tri_texcoord(mv, f, V3(ayy, byy, cyy)), hc->uvw), kRDX);
-        }
+        triangle_diff(mv, f, A, B, C, N, axis, s, hasVT, dr, hc, dh);
       } else {
         dh->x.z = t; dh->x.p = p; dh->x.N = hc->N;
         dh->y.z = t; dh->y.p = p; dh->y.N = hc->N;
@@ -1541,5 +1561,80 @@ int qa_oracle_render_pm(const void *blob, int x0, int y0, int x1, int y1, int sp
     }
   }
   if (counters) *counters = total;
+  return 0;
+}
+
+/* Texture probes: the same op numbers, in / out layout and index encoding as qa_test_texture_host (include/qaray_hip.h), evaluated
+ * by this file's own functions.  op 8 rebuilds the triangle's normal, axis and 1/area as triangle_intersect does; op 9 is the plain
+ * (int) cast as this x86-64 build executes it (cvttss2si). */
+int qa_oracle_texture_probe(const void *blob, int op, int index, int n, const float *in, float *out)
+{
+  scene_t s;
+  if (scene_bind(&s, blob) != 0 || n < 0 || op < 0 || op > 9) return -1;
+  if ((op == 1 || op == 2) && (index < 0 || (uint32_t) index >= s.h->num_textures)) return -1;
+  if (op >= 3 && op <= 5 && index >= (int) s.h->num_texmaps) return -1;
+  const int mi = index >> 20, el = index & 0xFFFFF;
+  if (op == 8 && (index < 0 || (uint32_t) mi >= s.h->num_meshes || (uint32_t) el >= s.mesh[mi].num_faces)) return -1;
+  for (int i = 0; i < n; ++i) {
+    const float *q = in + 16 * (size_t) i;
+    float *o = out + 9 * (size_t) i;
+    const v3 a = v3p(q), b = v3p(q + 3), c = v3p(q + 6), d = v3p(q + 9), e = v3p(q + 12);
+    diffray_t dr;
+    dr.x.p = a; dr.x.dir = b;
+    dr.y.p = a; dr.y.dir = c;
+    dr.c = dr.x;
+    dr.hasDiffRay = 1;
+    diffhit_t dh;
+    hit_init(&dh);
+    hit_t *hc = &dh.c;
+    hc->uvw = V3(0, 0, 0);
+    switch (op) {
+      case 0: hc->uvw = tile_clamp(a); break;
+      case 1: hc->uvw = texture_sample(&s, &s.tex[index], a); break;
+      case 2: {
+        const v3 du[2] = {b, c};
+        hc->uvw = texture_sample_filtered(&s, &s.tex[index], a, du);
+        break;
+      }
+      case 3: case 5: {
+        const qa_texcolor tc = {{b.x, b.y, b.z}, index};
+        hc->uvw = op == 3 ? texcolor_sample(&s, &tc, a) : sample_environment(&s, &tc, a);
+        break;
+      }
+      case 4: {
+        const qa_texcolor tc = {{d.x, d.y, d.z}, index};
+        hc->uvw = a; hc->duvw[0] = b; hc->duvw[1] = c;
+        hc->hasTexture = q[15] != 0.f;
+        const v3 r = mtl_sample(&s, &dh, &tc);
+        hc->uvw = r; hc->duvw[0] = V3(0, 0, 0); hc->duvw[1] = V3(0, 0, 0);
+        break;
+      }
+      case 6: hc->uvw = plane_texcoord(d); plane_diff(&dr, hc, &dh); break;
+      case 7: hc->uvw = sphere_texcoord(d, 1.f); sphere_diff(&dr, d, e, hc, &dh); break;
+      case 8: {
+        const meshview_t mv = mesh_view(&s, mi);
+        const qa_face *f = &mv.faces[mv.elements[el]];
+        const v3 A = v3p(mv.V + 3 * f->v[0]), B = v3p(mv.V + 3 * f->v[1]), C = v3p(mv.V + 3 * f->v[2]);
+        const v3 N = vnormalize(vcross(vsub(B, A), vsub(C, A)));
+        int axis;
+        const float ax_ = QABS(N.x), ay_ = QABS(N.y), az_ = QABS(N.z);
+        if (ax_ > ay_ && ax_ > az_) axis = 0;
+        else if (ay_ > az_) axis = 1;
+        else axis = 2;
+        const float sa = 1.f / tri_area(axis, A, B, C);
+        hc->N = V3(0, 0, 0);
+        hc->uvw = tri_texcoord(&mv, f, V3(q[9], q[10], 1.f - q[9] - q[10]));
+        triangle_diff(&mv, f, A, B, C, N, axis, sa, 1, &dr, hc, &dh);
+        break;
+      }
+      default: {
+        const int k = (int) a.x;
+        memcpy(&hc->uvw.x, &k, 4);
+        break;
+      }
+    }
+    const v3 r[3] = {hc->uvw, hc->duvw[0], hc->duvw[1]};
+    for (int k = 0; k < 3; ++k) { o[3 * k] = r[k].x; o[3 * k + 1] = r[k].y; o[3 * k + 2] = r[k].z; }
+  }
   return 0;
 }

@@ -52,6 +52,9 @@ int qa_oracle_render_pm(const void *blob, int x0, int y0, int x1, int y1, int sp
 /* Small pieces exposed for unit tests. */
 float qa_oracle_halton(int index, int base);
 void  qa_oracle_rng_stream(uint32_t seed, uint32_t pixel, int n, float *out);
+/* The texture path's pieces, n queries of one op: the op numbers and the in / out layout of qa_test_texture_host (include/qaray_hip.h).
+ * Returns 0, or -1 on a bad op, table index or blob. */
+int   qa_oracle_texture_probe(const void *blob, int op, int index, int n, const float *in, float *out);
 
 #ifdef __cplusplus
 }

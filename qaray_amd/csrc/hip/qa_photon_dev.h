@@ -9,7 +9,9 @@
 
 namespace qa {
 
-// Photon::SetPower + SetDirection packed into the record's last three dwords
+// Photon::SetPower + SetDirection packed into the record's last three dwords.  The plain (int) casts agree with the reference's x86
+// ones (cvttss2si; qa_texture_dev.h qa_f2i_x86): their operands lie in [0, 255] or in (-0x7FFF, 0x7FFF), or are NaN, whose INT_MIN
+// there and 0 here keep the same low 8 / 16 bits: 0.
 __device__ __forceinline__ void photonPack(f3 power, f3 dir, float &maxPower, uint32_t &w4, uint32_t &w5)
 {
   float pw = power.x;

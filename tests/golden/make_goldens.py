@@ -44,6 +44,12 @@ CASES = [
     ("c3_object_1080p_crop_256spp", "example_project7_object.xml", (1920, 1080), (860, 570, 868, 578), 256, 256, 5),
     ("c4_caustics_4k_crop_1024spp", "example_project12_caustics_glossy.xml", (3840, 2160), (1920, 1310, 1928, 1318), 1024, 1024, 5),
     ("c5_tower_4k_crop_2048spp", "trc_scene_tower.xml", (3840, 2160), (1820, 1010, 1828, 1018), 2048, 2048, 5),
+    # texture lookups at their edges (tests/golden/texedge/, its own assets): a floor whose texture map scales uv by 2e10, so that
+    # the lookups cross +-2^31 inside the frame, a checker wall seen at grazing angles, a textured sphere, a textured mesh
+    # (LDS-resident: small; global memory: big), textured background and environment.  One path segment (bounce 0): the colours
+    # reach 1e21, where the kernels' front-to-back sum of the segments and the reference's nested one round differently.
+    ("texedge_small_48x36_2spp_bounce0", "../tests/golden/texedge/texedge_small.xml", (48, 36), None, 2, 2, 0),
+    ("texedge_big_48x36_2spp_bounce0", "../tests/golden/texedge/texedge_big.xml", (48, 36), None, 2, 2, 0),
 ]
 SEED = 0x51A7A7
 
@@ -77,11 +83,13 @@ def main():
             continue
         with tempfile.TemporaryDirectory() as td:
             out = os.path.join(td, "g")
-            cmd = [HARNESS, scene, "--size", str(w), str(h), "--spp-min", str(smin), "--spp-max", str(smax),
+            # the reference opens asset files relative to its working directory: a scene's own directory
+            where = os.path.dirname(os.path.join(SCENES, scene))
+            cmd = [HARNESS, os.path.basename(scene), "--size", str(w), str(h), "--spp-min", str(smin), "--spp-max", str(smax),
                    "--bounce", str(bounce), "--seed", str(SEED), "--threads", "8", "--out", out]
             if crop:
                 cmd += ["--crop"] + [str(c) for c in crop]
-            subprocess.run(cmd, cwd=SCENES, check=True, stdout=subprocess.DEVNULL)
+            subprocess.run(cmd, cwd=where, check=True, stdout=subprocess.DEVNULL)
             meta = json.load(open(out + ".json"))
             x0, y0, x1, y1 = meta["crop"]
             ch, cw = y1 - y0, x1 - x0
