@@ -28,6 +28,10 @@
  *   qa_progressive_*               Renderer_GUI's progressive display: BeginRender starts the render
  *                                  threads, the window shows renderImage while it fills, StopRender
  *                                  signals the stop            src/renderers/Renderer_GUI.cpp:37-97
+ *   qa_display_device,             renderImage's 8-bit products: the tail of PixelRender (LinearToSRGB, clamp, round) and
+ *   qa_progressive_display*        FrameBuffer::ComputeZBufferImage / ComputeSampleCountImage, computed where the frame
+ *                                  is; what Renderer_GUI shows of renderImage   src/fb/framebuffer.cpp:62-107,
+ *                                                                       src/renderers/renderer.cpp:34-39,347-365
  *   qa_get_counters                (no counterpart: the reference only prints wall-clock)
  *   qa_get_kernel_time             Renderer::StartTimer/StopTimer       src/renderers/renderer.cpp:42-63
  */
@@ -148,6 +152,35 @@ int qa_progressive_read_device(qa_ctx *ctx, float *d_rgb, float *d_depth, uint32
 int qa_progressive_status(qa_ctx *ctx, int *spp_reached, uint64_t *pixels_finished, uint64_t *tiles_behind);
 int qa_progressive_end(qa_ctx *ctx);
 
+/* The FrameBuffer's 8-bit products of a frame of float results, computed on the device: byte for byte what the host FrameBuffer
+ * (Deposit + ComputeZBufferImage + ComputeSampleCountImage) makes of the same floats.  Per pixel:
+ *   color     3 bytes: LinearToSRGB when use_srgb, MIN(1, .), MAX(0, .), roundf(c * 255)
+ *   count     (uint8_t) (255.f * ns / spp_max)
+ *   zimg      0 where depth == 1e30, else (uint8_t) ((zmax - z) / (zmax - zmin) * 255)
+ *   countimg  (uint8_t) (255 * (count - smin) / (smax - smin)) in integers; 0 everywhere when smax == smin
+ *   mask      ns != 0
+ * A float becomes a byte as the host library's x86-64 build does it: NaN and |x| >= 2^31 give 0, else the low byte of the truncated
+ * int.  A pixel with ns == 0 was skipped (stop request): colour 0, count 0, mask 0 and depth 0.0f, as FrameBuffer::Init leaves it.
+ * stats: zmin (from 1e30 down) and zmax (from 0 up) over the depths other than 1e30, NaNs never counting; smin (from 255) and smax
+ * (from 0) over the count bytes; a zero zmin is reported as +0.
+ *   qa_display_device               npix pixels of plain device buffers -> device buffers.  Only enqueues on hip_stream (NULL = the
+ *                                   context's stream, as for qa_render_region_device): a statistics kernel and an encode kernel.
+ *   qa_progressive_display          the progressive frame's products straight from its slabs - finished pixels' outputs, the running
+ *   qa_progressive_display_device   mean and samples so far of the others, exactly the floats qa_progressive_read returns, which are
+ *                                   never written out.  spp_max is the frame's.  The host variant copies back 3 + 1 + 1 + 1 + 1
+ *                                   bytes per pixel at most, and synchronises; the device variant only enqueues.
+ * Every output pointer may be NULL (not wanted).  QA_EINVAL: npix == 0, spp_max < 1, a null source buffer; on a frame that has
+ * ended, what the other qa_progressive_* calls return.  The frame is not changed.  The statistics block (32 bytes) and the host
+ * variant's staging are allocated on first use and freed with the context. */
+typedef struct qa_display_stats { float zmin, zmax; uint32_t smin, smax; } qa_display_stats;
+int qa_display_device(qa_ctx *ctx, const float *d_rgb, const float *d_depth, const uint32_t *d_nsamples, uint64_t npix, int spp_max,
+                      int use_srgb, uint8_t *d_color, uint8_t *d_count, uint8_t *d_zimg, uint8_t *d_countimg, uint8_t *d_mask,
+                      qa_display_stats *d_stats, void *hip_stream);
+int qa_progressive_display(qa_ctx *ctx, int use_srgb, uint8_t *color, uint8_t *count, uint8_t *zimg, uint8_t *countimg, uint8_t *mask,
+                           qa_display_stats *stats);
+int qa_progressive_display_device(qa_ctx *ctx, int use_srgb, uint8_t *d_color, uint8_t *d_count, uint8_t *d_zimg, uint8_t *d_countimg,
+                                  uint8_t *d_mask, qa_display_stats *d_stats, void *hip_stream);
+
 /* Counters accumulated since the last reset (synchronises the context first). */
 int qa_get_counters(qa_ctx *ctx, qa_counters *out);
 int qa_reset_counters(qa_ctx *ctx);
@@ -235,6 +268,11 @@ int qa_test_math_host(int fn, const float *x, const float *y, int n, float *out)
  * ops 0 and 9 read no table, and blob may be null). */
 int qa_test_texture_device(qa_ctx *ctx, int op, int index, int n, const float *in, float *out);
 int qa_test_texture_host(const void *blob, int op, int index, int n, const float *in, float *out);
+
+/* Self-test hook for the 8-bit products (qaray_amd/csrc/hip/qa_display_dev.h): the source of qa_display_device's kernels compiled
+ * for the host, pixel after pixel over host arrays (no GPU and no context needed). */
+int qa_test_display_host(const float *rgb, const float *depth, const uint32_t *nsamples, uint64_t npix, int spp_max, int use_srgb,
+                         uint8_t *color, uint8_t *count, uint8_t *zimg, uint8_t *countimg, uint8_t *mask, qa_display_stats *stats);
 
 #ifdef __cplusplus
 }

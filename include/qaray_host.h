@@ -56,6 +56,12 @@ void qa_fb_destroy(qa_fb *fb);
  * (src/renderers/renderer.cpp:347-365). */
 int qa_fb_deposit(qa_fb *fb, int x0, int y0, int x1, int y1, const float *rgb, const float *depth,
                   const uint32_t *nsamples, int spp_max, int use_srgb);
+/* FrameBuffer::AdoptProducts: the whole frame's 8-bit products computed elsewhere (include/qaray_hip.h qa_display_device /
+ * qa_progressive_display) become the FrameBuffer's, as qa_fb_deposit of the same floats over the whole frame would leave them;
+ * depth (may be NULL) is stored where mask is set.  (qa_fb_z_image / qa_fb_sample_count_image compute their images again from
+ * the z buffer and the count bytes.) */
+int qa_fb_adopt_products(qa_fb *fb, const uint8_t *color, const uint8_t *count, const uint8_t *zimg, const uint8_t *countimg,
+                         const uint8_t *mask, const float *depth);
 const uint8_t *qa_fb_pixels(const qa_fb *fb);        /* RGB8 */
 const float *qa_fb_zbuffer(const qa_fb *fb);
 const uint8_t *qa_fb_sample_count(const qa_fb *fb);

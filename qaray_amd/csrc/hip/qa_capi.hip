@@ -810,6 +810,9 @@ int qa_ctx_destroy(qa_ctx *c)
   if (c->dRgb) (void) hipFree(c->dRgb);
   if (c->dDepth) (void) hipFree(c->dDepth);
   if (c->dNs) (void) hipFree(c->dNs);
+  if (c->dDisplay) (void) hipFree(c->dDisplay);
+  if (c->dDisplayStage) (void) hipFree(c->dDisplayStage);
+  if (c->displayEv) (void) hipEventDestroy(c->displayEv);
   if (c->stream) (void) hipStreamDestroy(c->stream);
   delete c;
   return QA_OK;
@@ -1057,13 +1060,6 @@ int qa_debug_scrub_scratch(qa_ctx *c, uint32_t pattern)
 }
 
 // ---- progressive frames ---------------------------------------------------------------------------------------------------------
-static int ProgActive(qa_ctx *c)
-{
-  if (!c) return Fail(QA_EINVAL, "null context");
-  if (!c->prog.active) return Fail(QA_EINVAL, c->prog.ended.empty() ? "no progressive frame: qa_progressive_begin first" : c->prog.ended);
-  return QA_OK;
-}
-
 int qa_progressive_begin(qa_ctx *c, int x0, int y0, int x1, int y1, int spp_min, int spp_max, int max_bounce, uint32_t seed, uint32_t flags)
 {
   if (!c) return Fail(QA_EINVAL, "null context");

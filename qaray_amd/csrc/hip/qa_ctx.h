@@ -1,5 +1,5 @@
 // qa_ctx.h — internals shared by the translation units of libqaray_hip.so (qa_capi.hip: context,
-// scene, render launches; qa_photon.hip: photon / caustics maps).  Not part of the C ABI.
+// scene, render launches; qa_photon.hip: photon / caustics maps; qa_display.hip: the 8-bit products).  Not part of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -170,6 +170,14 @@ struct qa_ctx {
     unsigned long long *dStatus = nullptr;   // qa_progressive_status: finished pixels, tiles behind, lowest level
     hipEvent_t done = nullptr;    // end of the last pass
   } prog;
+  // the 8-bit products (qa_display.hip): the statistics block (4 working words, then their initial values) and the staging of
+  // qa_progressive_display's host variant are made on first use and live as long as the context
+  uint32_t *dDisplay = nullptr;
+  hipEvent_t displayEv = nullptr;      // end of the last display: the block is one per context ...
+  bool displayEvSet = false;
+  hipStream_t displayStream = nullptr; // ... a display on another stream waits for it
+  uint8_t *dDisplayStage = nullptr;
+  size_t displayStageBytes = 0;
 };
 
 void FreePhotonMaps(qa_ctx *c);  // qa_photon.hip
@@ -192,6 +200,14 @@ inline void EndProgressive(qa_ctx *c, const char *why)
   f.dState = f.dLevel = f.dList = f.dProgress = f.dNs = f.dPrevNs = nullptr;
   f.dRgb = f.dDepth = f.dPrevRgb = f.dPrevDepth = nullptr;
   f.dStatus = nullptr;
+}
+
+// What every qa_progressive_* call on a frame says when there is none (or why the last one ended)
+inline int ProgActive(qa_ctx *c)
+{
+  if (!c) return Fail(QA_EINVAL, "null context");
+  if (!c->prog.active) return Fail(QA_EINVAL, c->prog.ended.empty() ? "no progressive frame: qa_progressive_begin first" : c->prog.ended);
+  return QA_OK;
 }
 
 inline void FreeScene(qa_ctx *c)

@@ -116,6 +116,21 @@ void FrameBuffer::Deposit(int x0, int y0, int x1, int y1, const float *rgb, cons
   IncrementNumRenderPixel((x1 > x0 && y1 > y0) ? cw * (y1 - y0) : 0);
 }
 
+void FrameBuffer::AdoptProducts(const uint8_t *color, const uint8_t *count, const uint8_t *zimg, const uint8_t *countimg, const uint8_t *maskIn,
+                                const float *depth)
+{
+  const size_t n = (size_t) width * height;
+  img.assign(color, color + 3 * n);
+  sampleCount.assign(count, count + n);
+  zbufferImg.assign(zimg, zimg + n);
+  sampleCountImg.assign(countimg, countimg + n);
+  mask.assign(maskIn, maskIn + n);
+  if (depth)
+    for (size_t i = 0; i < n; ++i)
+      if (mask[i]) zbuffer[i] = depth[i];
+  IncrementNumRenderPixel((int) n);
+}
+
 bool StripRowRange(int height, int world, int rank, int k, int &y0, int &y1)
 {
   if (height <= 0 || world < 1 || rank < 0 || rank >= world || k < 0) return false;

@@ -46,6 +46,14 @@ class FrameBuffer {
   void Deposit(int x0, int y0, int x1, int y1, const float *rgb, const float *depth,
                const uint32_t *nsamples, int sppMax, bool useSRGB);
 
+  // The whole frame's 8-bit products made elsewhere (include/qaray_hip.h qa_display_device / qa_progressive_display: the same
+  // bytes, computed where the frame is): colour, sample-count byte, z image, sample-count image and mask become the members as
+  // Deposit(0, 0, w, h, ...) + ComputeZBufferImage + ComputeSampleCountImage on a fresh FrameBuffer would leave them, and the
+  // rendered pixels are counted as Deposit counts them.  depth (may be null: the z buffer keeps its floats) is stored where mask
+  // is set, as Deposit stores it.
+  void AdoptProducts(const uint8_t *color, const uint8_t *count, const uint8_t *zimg, const uint8_t *countimg, const uint8_t *maskIn,
+                     const float *depth);
+
  private:
   unsigned width = 0, height = 0;
   std::vector<uint8_t> img, mask, sampleCount, zbufferImg, sampleCountImg;

@@ -99,6 +99,13 @@ int qa_fb_deposit(qa_fb *fb, int x0, int y0, int x1, int y1, const float *rgb, c
   fb->fb.Deposit(x0, y0, x1, y1, rgb, depth, nsamples, spp_max, use_srgb != 0);
   return QA_OK;
 }
+int qa_fb_adopt_products(qa_fb *fb, const uint8_t *color, const uint8_t *count, const uint8_t *zimg, const uint8_t *countimg, const uint8_t *mask,
+                         const float *depth)
+{
+  if (!fb || !color || !count || !zimg || !countimg || !mask) return Fail(QA_EINVAL, "null argument");
+  fb->fb.AdoptProducts(color, count, zimg, countimg, mask, depth);
+  return QA_OK;
+}
 const uint8_t *qa_fb_pixels(const qa_fb *fb) { return fb ? fb->fb.GetPixels() : nullptr; }
 const float *qa_fb_zbuffer(const qa_fb *fb) { return fb ? fb->fb.GetZBuffer() : nullptr; }
 const uint8_t *qa_fb_sample_count(const qa_fb *fb) { return fb ? fb->fb.GetSampleCount() : nullptr; }

@@ -223,17 +223,14 @@ void Renderer::ThreadRender()
 void Renderer::Render()
 {
   ThreadRender();
-  image->ComputeZBufferImage();
-  image->ComputeSampleCountImage();
-  image->SaveImage((outputPrefix + "colorBuffer.png").c_str());
-  image->SaveZImage((outputPrefix + "depthBuffer.png").c_str());
-  image->SaveSampleCountImage((outputPrefix + "sampleBuffer.png").c_str());
+  SaveImages();
 }
 
 // The batch counterpart of Renderer_GUI's progressive display (src/renderers/Renderer_GUI.cpp:37-97, which shows renderImage while
 // the render threads fill it): the frame stays resident on the GPU (qa_progressive_*) and its samples are raised in passes of
-// passSpp up to sppMax; after each pass the FrameBuffer is filled from the preview and the three images are written again.  The
-// last pass leaves the one-shot frame's images, byte for byte.
+// passSpp up to sppMax; after each pass the FrameBuffer adopts the 8-bit products the device made of the frame where it lies
+// (qa_progressive_display: 7 bytes per pixel come back instead of 20, and no powf runs on the host) and the three images are written
+// again.  The float depth is read after the last pass only.  The last pass leaves the one-shot frame's images, byte for byte.
 void Renderer::RenderProgressive(size_t passSpp)
 {
   if (!multi.empty() || mpiSize != 1) throw std::runtime_error("-progressive renders on one device and cannot be combined with -devices");
@@ -246,19 +243,29 @@ void Renderer::RenderProgressive(size_t passSpp)
   qa_reset_counters(ctx);
   if (qa_progressive_begin(ctx, 0, 0, W, H, (int) param.sppMin, (int) param.sppMax, Material::maxBounce, param.seed, 0) != QA_OK)
     throw std::runtime_error(std::string("qa_progressive_begin: ") + qa_last_error());
-  std::vector<float> rgb((size_t) 3 * W * H), depth((size_t) W * H);
-  std::vector<uint32_t> ns((size_t) W * H);
+  const size_t n = (size_t) W * H;
+  std::vector<uint8_t> color(3 * n), count(n), zimg(n), countimg(n), mask(n);
   for (size_t spp = 0; spp < param.sppMax;) {
     spp = std::min(spp + passSpp, param.sppMax);
+    const bool last = spp >= param.sppMax;
     const auto t0 = std::chrono::system_clock::now();
-    if (qa_progressive_advance(ctx, (int) spp, nullptr) != QA_OK || qa_progressive_read(ctx, rgb.data(), depth.data(), ns.data()) != QA_OK)
+    if (qa_progressive_advance(ctx, (int) spp, nullptr) != QA_OK ||
+        qa_progressive_display(ctx, param.useSRGB ? 1 : 0, color.data(), count.data(), zimg.data(), countimg.data(), mask.data(), nullptr) != QA_OK)
       throw std::runtime_error(std::string("qa_progressive: ") + qa_last_error());
     const std::chrono::duration<double, std::milli> ms = std::chrono::system_clock::now() - t0;
     int reached = 0;
     qa_progressive_status(ctx, &reached, nullptr, nullptr);
     printf("pass to %zu spp: %d spp reached, %.3f ms\n", spp, reached, ms.count());
-    image->Deposit(0, 0, W, H, rgb.data(), depth.data(), ns.data(), (int) param.sppMax, param.useSRGB);
-    SaveImages();
+    std::vector<float> rgb, depth;
+    std::vector<uint32_t> ns;
+    if (last) {   // FrameBuffer::zbuffer ends as Deposit leaves it
+      rgb.resize(3 * n); depth.resize(n); ns.resize(n);
+      if (qa_progressive_read(ctx, rgb.data(), depth.data(), ns.data()) != QA_OK) throw std::runtime_error(std::string("qa_progressive_read: ") + qa_last_error());
+    }
+    image->AdoptProducts(color.data(), count.data(), zimg.data(), countimg.data(), mask.data(), last ? depth.data() : nullptr);
+    image->SaveImage((outputPrefix + "colorBuffer.png").c_str());
+    image->SaveZImage((outputPrefix + "depthBuffer.png").c_str());
+    image->SaveSampleCountImage((outputPrefix + "sampleBuffer.png").c_str());
   }
   qa_progressive_end(ctx);
   qa_get_counters(ctx, &counters);

@@ -1,6 +1,7 @@
 """ctypes binding of libqaray_hip.so (include/qaray_hip.h) - the MI355X integrator.
 
 There is no CPU fallback: creating a context without the library or without a GPU raises."""
+import collections
 import ctypes as C
 import os
 
@@ -35,6 +36,18 @@ class PhotonParams(C.Structure):
 # qa_photon: byte-compatible with the reference's cy::PhotonMap::Photon (24 bytes)
 PHOTON_DTYPE = np.dtype([("pos", np.float32, 3), ("power", np.float32), ("rgb", np.uint8, 3), ("plane_dirz", np.uint8),
                          ("dirx", np.int16), ("diry", np.int16)])
+
+
+class DisplayStats(C.Structure):   # qa_display_stats
+    _fields_ = [("zmin", C.c_float), ("zmax", C.c_float), ("smin", C.c_uint32), ("smax", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+# Progressive.display(): numpy arrays shaped like the region (color [h,w,3], the others [h,w], uint8) and the statistics as a dict
+Display = collections.namedtuple("Display", "color count zimg countimg mask stats")
+DISPLAY_STATS_DTYPE = np.dtype([("zmin", np.float32), ("zmax", np.float32), ("smin", np.uint32), ("smax", np.uint32)])
 
 
 class HipError(RuntimeError):
@@ -93,6 +106,10 @@ def lib():
         L.qa_progressive_read_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.qa_progressive_status.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.qa_progressive_end.argtypes = [C.c_void_p]
+        L.qa_display_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int] + [C.c_void_p] * 7
+        L.qa_progressive_display.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.POINTER(DisplayStats)]
+        L.qa_progressive_display_device.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 7
+        L.qa_test_display_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int] + [C.c_void_p] * 6
         L.qa_photon_maps_build.argtypes = [C.c_void_p, C.POINTER(PhotonParams), C.c_uint32]
         L.qa_photon_maps_clear.argtypes = [C.c_void_p]
         L.qa_photon_maps_info.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
@@ -104,6 +121,46 @@ def lib():
 def _check(rc):
     if rc != 0:
         raise HipError(rc, lib().qa_last_error().decode())
+
+
+def display_host(rgb, depth, ns, spp_max, srgb=True):
+    """qa_test_display_host: the 8-bit products of a frame of float results (any shape; rgb has 3 floats per pixel) on the CPU,
+    from the source the device kernels are compiled from -> Display of flat uint8 arrays and the statistics.  No GPU needed."""
+    rgb = np.ascontiguousarray(rgb, dtype=np.float32)
+    depth = np.ascontiguousarray(depth, dtype=np.float32)
+    ns = np.ascontiguousarray(ns, dtype=np.uint32)
+    n = depth.size
+    assert rgb.size == 3 * n and ns.size == n
+    out = [np.zeros(3 * n if k == 0 else n, np.uint8) for k in range(5)]
+    st = DisplayStats()
+    _check(lib().qa_test_display_host(rgb.ctypes.data, depth.ctypes.data, ns.ctypes.data, n, int(spp_max), int(bool(srgb)),
+                                      *(a.ctypes.data for a in out), C.addressof(st)))
+    return Display(*out, st.as_dict())
+
+
+def _display_outputs(n, device, want, given):
+    """The device outputs of a display call: names in `want` are allocated (torch uint8; stats: 4 words), `given` overrides;
+    -> (dict name -> tensor or None, list of pointers in the C ABI's order)."""
+    import torch
+    out = {}
+    for name in ("color", "count", "zimg", "countimg", "mask", "stats"):
+        t = given.get(name)
+        if t is None and name in want:
+            t = torch.empty(4, dtype=torch.int32, device=device) if name == "stats" else \
+                torch.empty(3 * n if name == "color" else n, dtype=torch.uint8, device=device)
+        if t is not None:
+            assert t.is_cuda and t.is_contiguous() and t.numel() * t.element_size() == (16 if name == "stats" else 3 * n if name == "color" else n)
+        out[name] = t
+    return out, [out[k].data_ptr() if out[k] is not None else None for k in ("color", "count", "zimg", "countimg", "mask", "stats")]
+
+
+DISPLAY_ALL = ("color", "count", "zimg", "countimg", "mask", "stats")
+
+
+def stats_from_tensor(t):
+    """The statistics a display call wrote to the device (4 words) -> dict(zmin, zmax, smin, smax)."""
+    a = t.cpu().numpy().view(DISPLAY_STATS_DTYPE)[0]
+    return {k: a[k].item() for k in DISPLAY_STATS_DTYPE.names}
 
 
 def strip_count(y0, y1, first_strip, strip_step):
@@ -207,6 +264,22 @@ class Context:
         _check(lib().qa_render_region_device(self._h, x0, y0, x1, y1, spp, spp_max, max_bounce, seed,
                                              QA_RENDER_STATS if stats else 0, rgb.data_ptr(), depth.data_ptr(),
                                              ns.data_ptr(), sptr))
+
+    def display_device(self, rgb, depth, ns, spp_max, srgb=True, stream=None, want=DISPLAY_ALL, **given):
+        """qa_display_device: the FrameBuffer's 8-bit products of a frame of float results in torch CUDA tensors (float32 [..,3],
+        float32, int32/uint32, as render_region_device fills them), computed on the device.  want: the products to make, of
+        color / count / zimg / countimg / mask / stats; a tensor passed by that name is written instead of a new one (uint8;
+        stats: 16 bytes).  -> dict name -> tensor (None where not wanted); stats_from_tensor() reads the statistics.  Only
+        enqueues (see render_region_device for the stream)."""
+        n = depth.numel()
+        assert rgb.is_cuda and rgb.is_contiguous() and rgb.numel() == 3 * n and rgb.element_size() == 4
+        assert depth.is_cuda and depth.is_contiguous() and depth.element_size() == 4
+        assert ns.is_cuda and ns.is_contiguous() and ns.numel() == n and ns.element_size() == 4
+        out, ptrs = _display_outputs(n, rgb.device, want, given)
+        sptr = self._stream_arg(stream, rgb)
+        _check(lib().qa_display_device(self._h, rgb.data_ptr(), depth.data_ptr(), ns.data_ptr(), n, int(spp_max), int(bool(srgb)),
+                                       *ptrs, sptr))
+        return out
 
     def render_strips_device(self, region, first_strip, strip_step, spp, rgb, depth, ns, max_bounce=5,
                              seed=DEFAULT_SEED, spp_max=None, stats=False, stream=None):
@@ -340,6 +413,32 @@ class Progressive:
         assert ns.is_cuda and ns.is_contiguous() and ns.numel() == n and ns.element_size() == 4
         sptr = Context._stream_arg(stream, rgb)
         _check(lib().qa_progressive_read_device(self._ctx._h, rgb.data_ptr(), depth.data_ptr(), ns.data_ptr(), sptr))
+
+    def display(self, srgb=True):
+        """qa_progressive_display: the frame's 8-bit products as the host FrameBuffer would make them of read(), computed on
+        the device from the frame's own slabs (7 bytes per pixel come back) -> Display(color[h,w,3], count, zimg, countimg,
+        mask [h,w] uint8, stats dict); synchronises."""
+        x0, y0, x1, y1 = self.region
+        h, w = y1 - y0, x1 - x0
+        out = [np.zeros((h, w, 3) if k == 0 else (h, w), np.uint8) for k in range(5)]
+        st = DisplayStats()
+        _check(lib().qa_progressive_display(self._ctx._h, int(bool(srgb)), *(a.ctypes.data for a in out), C.byref(st)))
+        return Display(*out, st.as_dict())
+
+    def display_device(self, srgb=True, stream=None, want=DISPLAY_ALL, **given):
+        """qa_progressive_display_device: the same products into torch CUDA tensors on the context's device (see
+        Context.display_device for want / given and the result); only enqueues."""
+        import torch
+        device = torch.device("cuda", self._ctx.device_id)
+        x0, y0, x1, y1 = self.region
+        out, ptrs = _display_outputs((x1 - x0) * (y1 - y0), device, want, given)
+        if stream:
+            sptr = C.c_void_p(stream)
+        else:
+            torch.cuda.current_stream(device).synchronize()
+            sptr = None
+        _check(lib().qa_progressive_display_device(self._ctx._h, int(bool(srgb)), *ptrs, sptr))
+        return out
 
     def status(self):
         """-> dict(spp_reached, pixels_finished, tiles_behind); synchronises."""

@@ -35,6 +35,7 @@ def lib():
         L.qa_fb_destroy.restype = None
         L.qa_fb_deposit.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_int, C.c_int]
+        L.qa_fb_adopt_products.argtypes = [C.c_void_p] + [C.c_void_p] * 6
         for name, rt in (("qa_fb_pixels", C.POINTER(C.c_uint8)), ("qa_fb_zbuffer", C.POINTER(C.c_float)),
                          ("qa_fb_sample_count", C.POINTER(C.c_uint8)), ("qa_fb_mask", C.POINTER(C.c_uint8)),
                          ("qa_fb_z_image", C.POINTER(C.c_uint8)), ("qa_fb_sample_count_image", C.POINTER(C.c_uint8))):
@@ -132,6 +133,17 @@ class FrameBuffer:
         assert rgb.size == 3 * n and depth.size == n and nsamples.size == n
         _check(lib().qa_fb_deposit(self._h, x0, y0, x1, y1, rgb.ctypes.data, depth.ctypes.data,
                                    nsamples.ctypes.data, int(spp_max), int(bool(use_srgb))))
+
+    def adopt_products(self, color, count, zimg, countimg, mask, depth=None):
+        """FrameBuffer::AdoptProducts: the whole frame's 8-bit products computed elsewhere (hip.Context.display_device,
+        hip.Progressive.display) become this FrameBuffer's; depth (optional) is stored where mask is set."""
+        n = self.width * self.height
+        arrs = [np.ascontiguousarray(a, dtype=np.uint8) for a in (color, count, zimg, countimg, mask)]
+        assert arrs[0].size == 3 * n and all(a.size == n for a in arrs[1:])
+        if depth is not None:
+            depth = np.ascontiguousarray(depth, dtype=np.float32)
+            assert depth.size == n
+        _check(lib().qa_fb_adopt_products(self._h, *(a.ctypes.data for a in arrs), depth.ctypes.data if depth is not None else None))
 
     def place_strips(self, world, rank, rgb, depth, nsamples, spp_max, use_srgb=True):
         """Deposit rank `rank`'s PACKED strips (8-row strips rank, rank + world, ...) into the rows they belong to -> strips placed."""
