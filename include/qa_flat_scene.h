@@ -152,6 +152,14 @@ typedef struct qa_flat_header {
   uint64_t reserved[5];
 } qa_flat_header;
 
+/* The header's camera block by name (scene edits, include/qaray_hip.h qa_scene_edit_camera; the host layer hands it out,
+ * include/qaray_host.h qa_host_scene_camera).  The image size is not part of it. */
+typedef struct qa_camera {
+  float screenA[3], screenU[3], screenV[3], screenX[3], screenY[3];
+  float cam_pos[3];
+  float dof;
+} qa_camera;
+
 #define QA_BLOB_PTR(type, blob, off) ((const type *) ((const unsigned char *) (blob) + (off)))
 
 #ifdef __cplusplus

@@ -13,6 +13,8 @@
  *   qa_scene_upload_device         same, blob already in HBM (after an RCCL broadcast); the
  *                                  reference instead re-parses the XML on every rank
  *                                                                       src/renderers/Renderer_MPI.cpp:54
+ *   qa_scene_edit_*, qa_scene_download   (no counterpart: the reference loads a scene once per process; what a viewer built on
+ *                                  Renderer_GUI would need to move the camera or a light without a reload)
  *   qa_render_region[_device]      Renderer::ThreadRender -> PixelRender over a pixel region:
  *                                  camera ray, Scene::TraceNodeNormal, Material::Shade,
  *                                  Light::Illuminate/GenLight::Shadow, SuperSamplerHalton
@@ -40,6 +42,7 @@
 
 #include <stdint.h>
 
+#include "qa_flat_scene.h" /* the records qa_scene_edit_* take */
 #include "qa_photon.h"
 #include "qaray_host.h" /* QA_OK / QA_E* */
 
@@ -68,6 +71,41 @@ int qa_ctx_destroy(qa_ctx *ctx);
  * already sits in device memory.  Replaces any previous scene of the context. */
 int qa_scene_upload(qa_ctx *ctx, const void *host_blob, uint64_t nbytes);
 int qa_scene_upload_device(qa_ctx *ctx, const void *device_blob, uint64_t nbytes);
+
+/* Scene edits: the camera, lights, materials and node transforms of the resident scene, rewritten in place.  After an edit the
+ * context is in the state qa_scene_upload of the edited blob would leave it in - same kernel plan, same qa_get_kernel_name, same
+ * bits in every later frame - but no mesh or texture table is rebuilt, copied or reallocated: the edited records go into the
+ * resident blob (host and device copy) and the few tables derived from them are built again on the host (qa_scene_build.h
+ * RebuildSceneSide) and copied over their device copies.  Records are those of include/qa_flat_scene.h; `first`, `n` select
+ * records [first, first + n) of the blob's table.
+ *   qa_scene_edit_camera     the header's camera block (screenA/U/V/X/Y, cam_pos, dof).  The image size cannot change.
+ *   qa_scene_edit_lights     every field may change (a point light may become an area light, any light an ambient one ...)
+ *   qa_scene_edit_materials  colours, glossiness, ior, absorption, kill.  QA_EINVAL when a record's texmap references differ
+ *                            from the resident ones (texture tables are not rebuilt)
+ *   qa_scene_edit_instances  tm, itm, pos.  QA_EINVAL when a record changes obj_type, mesh, mtlset, parent, subtree_end or depth
+ * An edit that changes the plan (area lights appear or go, the shadow-casting lights cross QA_CS_LIGHT_BATCH, the root node
+ * stops being the identity ...) selects the integrator again, and allocates the per-thread slab the new plan needs if no earlier
+ * plan of this scene did; no other edit allocates device memory.  An edit that a fresh upload would refuse returns that upload's
+ * code; QA_EINVAL: null argument, first + n beyond the table; QA_ENOSCENE: no scene.  A refused edit changes nothing.
+ * Edits are ordered with the context's stream and never wait for the device: the copies leave pinned staging asynchronously and
+ * the scene record is passed by value at launch, so a frame already enqueued renders the old scene and the next one the new.
+ * (The staging is a ring: an edit waits for an earlier EDIT's copies only when the ring wraps.)
+ * A progressive frame becomes stale: qa_progressive_advance returns QA_EINVAL until qa_progressive_restart or a new
+ * qa_progressive_begin, while read / display / status keep serving the old frame's pixels.  The photon maps do not depend on
+ * the camera: qa_scene_edit_camera keeps them; the other edits drop them as an upload does (their memory is released by the next
+ * upload, build, clear or qa_ctx_destroy).
+ *   qa_scene_download        the resident blob as it now stands (nbytes: its size, also when out is NULL or capacity too small,
+ *                            which returns QA_EINVAL)
+ *   qa_get_scene_stats       [0] mesh-table builds (calls of the per-mesh builder) since the context was created, [1] scene
+ *                            device allocations since then, [2] bytes copied to the device by the last upload or edit,
+ *                            [3] edits applied since the last upload
+ * No reference counterpart: the reference loads a scene once per process (Renderer_GUI has no scene editing). */
+int qa_scene_edit_camera(qa_ctx *ctx, const qa_camera *camera);
+int qa_scene_edit_lights(qa_ctx *ctx, uint32_t first, uint32_t n, const qa_light *lights);
+int qa_scene_edit_materials(qa_ctx *ctx, uint32_t first, uint32_t n, const qa_material *materials);
+int qa_scene_edit_instances(qa_ctx *ctx, uint32_t first, uint32_t n, const qa_instance *instances);
+int qa_scene_download(qa_ctx *ctx, void *out, uint64_t capacity, uint64_t *nbytes);
+int qa_get_scene_stats(qa_ctx *ctx, uint64_t out[4]);
 
 /* Render pixels [x0,x1) x [y0,y1) of the scene's image.  Outputs are region-local, row-major:
  * rgb (y1-y0)*(x1-x0)*3 floats of LINEAR mean radiance (sRGB/quantisation stay in FrameBuffer),
@@ -141,7 +179,11 @@ int qa_clear_stop(qa_ctx *ctx);
  *                           for good (spp_max or the adaptive rule); tiles_behind: tiles below the last pass's target (non-zero
  *                           after a stop).  Any pointer may be NULL.
  *   qa_progressive_end      frees the frame (also done by qa_ctx_destroy).
- * qa_scene_upload*, qa_photon_maps_build and qa_photon_maps_clear end the frame: a later advance / read / status returns
+ *   qa_progressive_restart  starts the current frame again after a scene edit (or at any time): same region, spp, bounce, seed,
+ *                           flags and slabs, every pixel's state fresh and every tile at level 0, as after qa_progressive_begin.
+ *                           Validates like qa_progressive_begin against the edited scene; frees and allocates nothing; only
+ *                           enqueues on the context's stream.
+ * qa_scene_upload*,qa_photon_maps_build and qa_photon_maps_clear end the frame: a later advance / read / status returns
  * QA_EINVAL and qa_last_error says why.  qa_render_* frames between passes do not disturb it, and qa_set_option /
  * qa_set_pipeline may change between passes (same bits). */
 int qa_progressive_begin(qa_ctx *ctx, int x0, int y0, int x1, int y1, int spp_min, int spp_max, int max_bounce, uint32_t seed,
@@ -151,6 +193,7 @@ int qa_progressive_read(qa_ctx *ctx, float *rgb, float *depth, uint32_t *nsample
 int qa_progressive_read_device(qa_ctx *ctx, float *d_rgb, float *d_depth, uint32_t *d_nsamples, void *hip_stream);
 int qa_progressive_status(qa_ctx *ctx, int *spp_reached, uint64_t *pixels_finished, uint64_t *tiles_behind);
 int qa_progressive_end(qa_ctx *ctx);
+int qa_progressive_restart(qa_ctx *ctx);
 
 /* The FrameBuffer's 8-bit products of a frame of float results, computed on the device: byte for byte what the host FrameBuffer
  * (Deposit + ComputeZBufferImage + ComputeSampleCountImage) makes of the same floats.  Per pixel:

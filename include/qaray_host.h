@@ -9,6 +9,8 @@
  * Reference interfaces replaced (paths in the reference repo):
  *   qa_host_scene_load      LoadScene(const char*)                    src/parser/xmlload.h:16-18
  *   qa_host_scene_set_size  (no CLI flag exists; the oracle harness pokes scene.camera.imgWidth)
+ *   qa_host_scene_set_camera, qa_host_scene_camera   LoadScene's <camera> block + Renderer::ComputeScene's camera frame
+ *                                                                     src/parser/xmlload.cpp, src/renderers/renderer.cpp:76-93
  *   qa_host_scene_flatten   Renderer::ComputeScene + scene graph      src/renderers/renderer.cpp:71-113
  *   qa_fb_*                 FrameBuffer                               src/fb/framebuffer.h:35-95
  *   qa_tasking_*            tasking::signal_start/stop, thread count  src/tasking/parallel_for.h:59-68
@@ -19,6 +21,8 @@
 #define QARAY_HOST_H
 
 #include <stdint.h>
+
+#include "qa_flat_scene.h" /* qa_camera */
 
 #ifdef __cplusplus
 extern "C" {
@@ -42,6 +46,13 @@ void qa_host_scene_destroy(qa_host_scene *scene);
 /* Override <camera><width>/<height> (BASELINE configs render the reference scenes at other sizes). */
 int qa_host_scene_set_size(qa_host_scene *scene, int width, int height);
 int qa_host_scene_get_size(const qa_host_scene *scene, int *width, int *height);
+/* Move the camera: what loading an XML whose <camera> has this <position>, <target>, <up>, <fov>, <focaldist> and <dof> gives
+ * (the loader's orthonormalisation included), the image size kept.  fov <= 0, focaldist <= 0 and dof < 0 keep the current value.
+ * qa_host_scene_camera: the camera block the next flatten would put into the blob's header, without flattening - what
+ * qa_scene_edit_camera (include/qaray_hip.h) takes. */
+int qa_host_scene_set_camera(qa_host_scene *scene, const float pos[3], const float target[3], const float up[3], float fov,
+                             float focaldist, float dof);
+int qa_host_scene_camera(const qa_host_scene *scene, qa_camera *out);
 /* Flatten into one relocatable blob (include/qa_flat_scene.h); release with qa_host_free. */
 int qa_host_scene_flatten(const qa_host_scene *scene, unsigned char **blob, uint64_t *nbytes);
 void qa_host_free(void *p);

@@ -4,6 +4,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstring>
 #include <new>
@@ -229,7 +230,25 @@ static int SelectKernel(qa_ctx *c)
   return QA_OK;
 }
 
-// Copy the built tables to the device: the only place a scene allocates device memory
+// The per-thread slab c->plan needs, if any, made on first need and kept with the scene; c->ds points at the one the plan uses
+static int EnsurePlanSlab(qa_ctx *c)
+{
+  const size_t threads = (size_t) c->numCUs * 8 * QA_BLOCK;
+  const bool area = c->plan.area, many = !area && c->plan.shadowLights.size() > QA_CS_LIGHT_BATCH;
+  float **slab = area ? &c->dAreaSlab : many ? &c->dSurfSlab : nullptr;
+  if (slab && !*slab) {
+    void *p = nullptr;
+    HIP_TRY(hipMalloc(&p, threads * (area ? QA_MAX_PATH * QA_REC_FLOATS : 13) * sizeof(float)));
+    c->sceneAllocs.push_back(p);
+    c->statSceneAllocs++;
+    *slab = static_cast<float *>(p);
+  }
+  c->ds.areaScratch = area ? c->dAreaSlab : nullptr;
+  c->ds.csSurf = many ? c->dSurfSlab : nullptr;
+  return QA_OK;
+}
+
+// Copy the built tables to the device: the only place a scene allocates device memory (but for the slab of a plan an edit brings)
 static int UploadScene(qa_ctx *c, const SceneTables &t)
 {
   const qa_flat_header *h = reinterpret_cast<const qa_flat_header *>(c->hostBlob.data());
@@ -257,14 +276,7 @@ static int UploadScene(qa_ctx *c, const SceneTables &t)
     return rc;
   // per-thread slabs of the largest grid: the AREA variants' hit log (QA_MAX_PATH x 19 floats), and the surface qa_integrate_cs
   // parks between batches when there are more shadow-casting lights than one batch
-  const size_t threads = (size_t) c->numCUs * 8 * QA_BLOCK;
-  const size_t slabFloats = t.plan.area ? QA_MAX_PATH * QA_REC_FLOATS : t.plan.shadowLights.size() > QA_CS_LIGHT_BATCH ? 13 : 0;
-  if (slabFloats) {
-    void *p = nullptr;
-    HIP_TRY(hipMalloc(&p, threads * slabFloats * sizeof(float)));
-    c->sceneAllocs.push_back(p);
-    (t.plan.area ? ds.areaScratch : ds.csSurf) = static_cast<float *>(p);
-  }
+  if ((rc = EnsurePlanSlab(c)) != QA_OK) return rc;
   if ((rc = DeviceCopy(c, t.mtlTex, &ds.mtlTex)) || (rc = DeviceCopy(c, t.texels, &ds.texels)) || (rc = DeviceCopy(c, t.texOff, &ds.texOff)) ||
       (rc = DeviceCopy(c, t.taps, &ds.texFilter)))
     return rc;
@@ -289,11 +301,17 @@ static int PrepareScene(qa_ctx *c)
   k.csItems = env("QA_CS_ITEMS", k.csItems);
   k.csSlots = env("QA_CS_SLOTS", k.csSlots);
   k.report = Report(c);
-  SceneTables t;
+  SceneTables &t = c->tables;
   std::string err;
   int rc = BuildScene(c->hostBlob.data(), c->hostBlob.size(), k, t, &err);
+  c->statMeshBuilds += t.meshBuilds;
   if (rc != QA_OK) return Fail(rc, err);
   if ((rc = UploadScene(c, t)) != QA_OK) return rc;
+  // scene edits build the scene-side tables again from these (qa_scene_edit_*): the mesh side is on the device now
+  DropMeshSide(t);
+  c->knobs = k;
+  c->knobs.report = nullptr;
+  c->statEdits = 0;
   c->haveScene = true;
   SelectStaged(c);
   return SelectKernel(c);
@@ -341,6 +359,7 @@ static int LaunchSetup(qa_ctx *c, Launch &L, int x0, int y0, int x1, int y1, int
   // one frame at a time per context (its device slabs are one per context): a frame on another stream than the last one waits for it
   if (!c->chunkEv) HIP_TRY(hipEventCreateWithFlags(&c->chunkEv, hipEventDisableTiming));
   if (c->chunkEvSet && s != c->lastStream) HIP_TRY(hipStreamWaitEvent(s, c->chunkEv, 0));
+  if (c->editEvSet && s != c->stream) HIP_TRY(hipStreamWaitEvent(s, c->editEv, 0));   // a scene edit's copies run on the context's stream
 
   RenderParams &rp = L.rp;
   rp.x0 = x0; rp.y0 = y0; rp.x1 = x1; rp.y1 = y1;
@@ -804,6 +823,8 @@ int qa_ctx_destroy(qa_ctx *c)
   if (c->dPixState) (void) hipFree(c->dPixState);
   if (c->dTileProgress) (void) hipFree(c->dTileProgress);
   if (c->chunkEv) (void) hipEventDestroy(c->chunkEv);
+  if (c->editEv) (void) hipEventDestroy(c->editEv);
+  if (c->hEditStage) (void) hipHostFree(c->hEditStage);
   if (c->prog.done) (void) hipEventDestroy(c->prog.done);
   if (c->dCounters) (void) hipFree(c->dCounters);
   if (c->hStop) (void) hipHostFree(c->hStop);
@@ -828,7 +849,9 @@ int qa_scene_upload(qa_ctx *c, const void *host_blob, uint64_t nbytes)
     c->hostBlob.assign((const unsigned char *) host_blob, (const unsigned char *) host_blob + nbytes);
   } catch (const std::bad_alloc &) { return Fail(QA_ENOMEM, "out of memory"); }
   HIP_TRY(hipMalloc((void **) &c->dBlob, nbytes));
+  c->statSceneAllocs++;
   HIP_TRY(hipMemcpy(c->dBlob, host_blob, nbytes, hipMemcpyHostToDevice));
+  c->statBytesCopied = nbytes;
   const int rc = PrepareScene(c);
   if (rc != QA_OK) FreeScene(c);
   return rc;
@@ -842,11 +865,187 @@ int qa_scene_upload_device(qa_ctx *c, const void *device_blob, uint64_t nbytes)
   FreeScene(c);
   try { c->hostBlob.resize(nbytes); } catch (const std::bad_alloc &) { return Fail(QA_ENOMEM, "out of memory"); }
   HIP_TRY(hipMalloc((void **) &c->dBlob, nbytes));
+  c->statSceneAllocs++;
   HIP_TRY(hipMemcpy(c->dBlob, device_blob, nbytes, hipMemcpyDeviceToDevice));
+  c->statBytesCopied = nbytes;
   HIP_TRY(hipMemcpy(c->hostBlob.data(), device_blob, nbytes, hipMemcpyDeviceToHost));
   const int rc = PrepareScene(c);
   if (rc != QA_OK) FreeScene(c);
   return rc;
+}
+
+}  // extern "C"
+
+// ---- scene edits (qa_scene_edit_*) ----------------------------------------------------------------------------------------------
+// c->tables (rebuilt from the edited host blob) -> the context's plan and scene record, device pointers kept; the slab the plan needs
+static int ApplySceneSide(qa_ctx *c)
+{
+  const SceneTables &t = c->tables;
+  std::vector<DMesh> meshes = std::move(c->plan.meshes);   // (the device copies' pointers live here; no edit changes a DMesh)
+  c->plan = t.plan;
+  c->plan.meshes = std::move(meshes);
+  DScene &ds = c->ds;
+  ds.cam = t.ds.cam;
+  ds.rootIdentity = t.ds.rootIdentity;
+  ds.csCullS1 = t.ds.csCullS1; ds.csCullS2 = t.ds.csCullS2; ds.csCullK3 = t.ds.csCullK3; ds.csCullK4 = t.ds.csCullK4;
+  memcpy(ds.instv, t.ds.instv, sizeof(ds.instv));
+  return EnsurePlanSlab(c);
+}
+
+struct EditCopy { const void *dst; const void *src; size_t bytes; };
+
+// The copies of one edit: through the pinned ring, asynchronously on the context's stream
+static int EnqueueEditCopies(qa_ctx *c, const std::vector<EditCopy> &copies)
+{
+  size_t need = 0;
+  for (const EditCopy &k : copies) need += (k.bytes + 63) & ~(size_t) 63;
+  if (!c->editEv) HIP_TRY(hipEventCreateWithFlags(&c->editEv, hipEventDisableTiming));
+  if (need > c->editStageBytes) {
+    if (c->editEvSet) HIP_TRY(hipEventSynchronize(c->editEv));
+    if (c->hEditStage) (void) hipHostFree(c->hEditStage);
+    c->hEditStage = nullptr;
+    c->editStageBytes = c->editStageUsed = 0;
+    const size_t bytes = std::max<size_t>(256 * 1024, 8 * need);
+    HIP_TRY(hipHostMalloc((void **) &c->hEditStage, bytes, hipHostMallocDefault));
+    c->editStageBytes = bytes;
+  }
+  if (c->editStageUsed + need > c->editStageBytes) {   // the ring wraps: the copies of the edits before this one must have left it
+    if (c->editEvSet) HIP_TRY(hipEventSynchronize(c->editEv));
+    c->editStageUsed = 0;
+  }
+  // a frame on a stream of the caller's may still read the tables
+  if (c->chunkEvSet && c->lastStream != c->stream) HIP_TRY(hipStreamWaitEvent(c->stream, c->chunkEv, 0));
+  if (c->prog.done && c->prog.active) HIP_TRY(hipStreamWaitEvent(c->stream, c->prog.done, 0));
+  c->statBytesCopied = 0;
+  for (const EditCopy &k : copies) {
+    if (!k.bytes || !k.dst) continue;
+    unsigned char *stage = c->hEditStage + c->editStageUsed;
+    memcpy(stage, k.src, k.bytes);
+    HIP_TRY(hipMemcpyAsync(const_cast<void *>(k.dst), stage, k.bytes, hipMemcpyHostToDevice, c->stream));
+    c->editStageUsed += (k.bytes + 63) & ~(size_t) 63;
+    c->statBytesCopied += k.bytes;
+  }
+  HIP_TRY(hipEventRecord(c->editEv, c->stream));
+  c->editEvSet = true;
+  return QA_OK;
+}
+
+enum EditKind { kEditCamera, kEditLights, kEditMaterials, kEditInstances };
+
+// Writes `bytes` at `off` of the resident blob, rebuilds the scene side and brings the context to the state an upload of the
+// edited blob would leave; a refusal leaves everything as it was
+static int ApplyEdit(qa_ctx *c, EditKind kind, size_t off, const void *src, size_t bytes)
+{
+  HIP_TRY(hipSetDevice(c->device));
+  unsigned char *at = c->hostBlob.data() + off;
+  std::vector<unsigned char> old(at, at + bytes);
+  memcpy(at, src, bytes);
+  std::string err;
+  int rc = RebuildSceneSide(c->hostBlob.data(), c->hostBlob.size(), c->knobs, c->tables, &err);
+  if (rc != QA_OK) Fail(rc, err);
+  else rc = ApplySceneSide(c);
+  if (rc != QA_OK) {
+    const std::string why = g_err;
+    memcpy(at, old.data(), bytes);
+    if (RebuildSceneSide(c->hostBlob.data(), c->hostBlob.size(), c->knobs, c->tables, &err) == QA_OK) (void) ApplySceneSide(c);
+    return Fail(rc, why);
+  }
+  const SceneTables &t = c->tables;
+  std::vector<EditCopy> copies;
+  copies.push_back({c->dBlob + off, at, bytes});
+  if (kind == kEditMaterials) {
+    copies.push_back({c->ds.mtl, t.materials.data(), t.materials.size() * sizeof(DMaterial)});
+    if (c->plan.resident) copies.push_back({c->ds.resident, t.image.data(), t.image.size() * sizeof(uint4)});
+  } else if (kind == kEditInstances) {
+    copies.push_back({c->ds.csInst, t.csInst.data(), t.csInst.size() * sizeof(CsInst)});
+    copies.push_back({c->ds.csCull, t.csCull.data(), t.csCull.size() * sizeof(CsCull)});
+  }
+  if ((rc = EnqueueEditCopies(c, copies)) != QA_OK) return rc;
+  if (kind == kEditCamera) SetKernelName(c);   // (the plan cannot change; the name is the plan's again, as after an upload)
+  else {
+    // Scene::usePhotonMap ends as with an upload; the maps' memory goes with the next upload, build, clear or the context
+    // (releasing it here would wait for the device)
+    c->photonReady = false;
+    SelectStaged(c);
+    if ((rc = SelectKernel(c)) != QA_OK) return rc;
+  }
+  if (c->prog.active) c->prog.stale = true;
+  c->statEdits++;
+  return QA_OK;
+}
+
+static int EditArgs(qa_ctx *c, const void *records, uint32_t first, uint32_t n, uint32_t count)
+{
+  if (!c) return Fail(QA_EINVAL, "null context");
+  if (!c->haveScene) return Fail(QA_ENOSCENE, "no scene uploaded");
+  if (!records) return Fail(QA_EINVAL, "null argument");
+  if (first > count || n > count - first) return Fail(QA_EINVAL, "records beyond the scene's table");
+  return QA_OK;
+}
+
+extern "C" {
+
+int qa_scene_edit_camera(qa_ctx *c, const qa_camera *cam)
+{
+  int rc = EditArgs(c, cam, 0, 0, 0);
+  if (rc != QA_OK) return rc;
+  static_assert(offsetof(qa_flat_header, dof) + sizeof(float) - offsetof(qa_flat_header, screenA) == sizeof(qa_camera), "qa_camera is the header's camera block");
+  return ApplyEdit(c, kEditCamera, offsetof(qa_flat_header, screenA), cam, sizeof(qa_camera));
+}
+
+int qa_scene_edit_lights(qa_ctx *c, uint32_t first, uint32_t n, const qa_light *lights)
+{
+  int rc = EditArgs(c, lights, first, n, c && c->haveScene ? reinterpret_cast<const qa_flat_header *>(c->hostBlob.data())->num_lights : 0);
+  if (rc != QA_OK || n == 0) return rc;
+  const qa_flat_header *h = reinterpret_cast<const qa_flat_header *>(c->hostBlob.data());
+  return ApplyEdit(c, kEditLights, h->off_lights + (size_t) first * sizeof(qa_light), lights, (size_t) n * sizeof(qa_light));
+}
+
+int qa_scene_edit_materials(qa_ctx *c, uint32_t first, uint32_t n, const qa_material *materials)
+{
+  int rc = EditArgs(c, materials, first, n, c && c->haveScene ? reinterpret_cast<const qa_flat_header *>(c->hostBlob.data())->num_materials : 0);
+  if (rc != QA_OK || n == 0) return rc;
+  const qa_flat_header *h = reinterpret_cast<const qa_flat_header *>(c->hostBlob.data());
+  const qa_material *cur = QA_BLOB_PTR(qa_material, c->hostBlob.data(), h->off_materials) + first;
+  for (uint32_t i = 0; i < n; ++i) {
+    const qa_material &a = cur[i], &b = materials[i];
+    if (a.diffuse.texmap != b.diffuse.texmap || a.specular.texmap != b.specular.texmap || a.reflection.texmap != b.reflection.texmap ||
+        a.refraction.texmap != b.refraction.texmap || a.emission.texmap != b.emission.texmap)
+      return Fail(QA_EINVAL, "a material edit cannot change texture-map references (texture tables are not rebuilt): upload the scene instead");
+  }
+  return ApplyEdit(c, kEditMaterials, h->off_materials + (size_t) first * sizeof(qa_material), materials, (size_t) n * sizeof(qa_material));
+}
+
+int qa_scene_edit_instances(qa_ctx *c, uint32_t first, uint32_t n, const qa_instance *instances)
+{
+  int rc = EditArgs(c, instances, first, n, c && c->haveScene ? reinterpret_cast<const qa_flat_header *>(c->hostBlob.data())->num_instances : 0);
+  if (rc != QA_OK || n == 0) return rc;
+  const qa_flat_header *h = reinterpret_cast<const qa_flat_header *>(c->hostBlob.data());
+  const qa_instance *cur = QA_BLOB_PTR(qa_instance, c->hostBlob.data(), h->off_instances) + first;
+  for (uint32_t i = 0; i < n; ++i) {
+    const qa_instance &a = cur[i], &b = instances[i];
+    if (a.obj_type != b.obj_type || a.mesh != b.mesh || a.mtlset != b.mtlset || a.parent != b.parent || a.subtree_end != b.subtree_end ||
+        a.depth != b.depth)
+      return Fail(QA_EINVAL, "an instance edit can change tm, itm and pos only (object, mesh, material set and place in the graph stay): upload the scene instead");
+  }
+  return ApplyEdit(c, kEditInstances, h->off_instances + (size_t) first * sizeof(qa_instance), instances, (size_t) n * sizeof(qa_instance));
+}
+
+int qa_scene_download(qa_ctx *c, void *out, uint64_t capacity, uint64_t *nbytes)
+{
+  if (!c) return Fail(QA_EINVAL, "null context");
+  if (!c->haveScene) return Fail(QA_ENOSCENE, "no scene uploaded");
+  if (nbytes) *nbytes = c->hostBlob.size();
+  if (!out || capacity < c->hostBlob.size()) return Fail(QA_EINVAL, "output smaller than the scene blob");
+  memcpy(out, c->hostBlob.data(), c->hostBlob.size());
+  return QA_OK;
+}
+
+int qa_get_scene_stats(qa_ctx *c, uint64_t out[4])
+{
+  if (!c || !out) return Fail(QA_EINVAL, "null argument");
+  out[0] = c->statMeshBuilds; out[1] = c->statSceneAllocs; out[2] = c->statBytesCopied; out[3] = c->statEdits;
+  return QA_OK;
 }
 
 int qa_render_region_device(qa_ctx *c, int x0, int y0, int x1, int y1, int spp_min, int spp_max, int max_bounce,
@@ -1096,6 +1295,26 @@ int qa_progressive_begin(qa_ctx *c, int x0, int y0, int x1, int y1, int spp_min,
   f.npix = npix;
   f.target = f.top = 0;
   f.active = true;
+  f.stale = false;
+  return QA_OK;
+}
+
+int qa_progressive_restart(qa_ctx *c)
+{
+  int rc = ProgActive(c);
+  if (rc != QA_OK) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  qa_ctx::Progressive &f = c->prog;
+  if ((rc = CheckFrame(c, f.x0, f.y0, f.x1, f.y1, f.sppMin, f.sppMax, f.maxBounce)) != QA_OK) return rc;   // (the edited scene may refuse the frame: area lights, bounce > 7)
+  HIP_TRY(hipStreamWaitEvent(c->stream, f.done, 0));   // the last pass, on whatever stream it ran
+  hipLaunchKernelGGL(qa::qa_prog_init, dim3((unsigned) ((f.npix + 255) / 256)), dim3(256), 0, c->stream, f.dState, f.dRgb, f.dDepth, f.dNs, f.x0, f.y0,
+                     (uint32_t) (f.x1 - f.x0), (uint32_t) f.npix, (uint32_t) c->ds.cam.width, f.seed);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemsetAsync(f.dLevel, 0, f.tiles * sizeof(uint32_t), c->stream));
+  HIP_TRY(hipMemsetD32Async((hipDeviceptr_t) f.dProgress, 1, f.tiles, c->stream));
+  HIP_TRY(hipEventRecord(f.done, c->stream));
+  f.target = f.top = 0;
+  f.stale = false;
   return QA_OK;
 }
 
@@ -1126,6 +1345,7 @@ int qa_progressive_advance(qa_ctx *c, int spp_target, void *hip_stream)
   HIP_TRY(hipSetDevice(c->device));
   if (spp_target < 1) return Fail(QA_EINVAL, "bad spp target");
   qa_ctx::Progressive &f = c->prog;
+  if (f.stale) return Fail(QA_EINVAL, "the scene was edited since this progressive frame began: qa_progressive_restart or qa_progressive_begin first");
   const int target = std::min(spp_target, f.sppMax);
   // Every unfinished pixel of a tile has exactly the tile's level in samples (a tile in hand always completes its pass).  Above every
   // earlier target, no pixel has the target yet; at or below the highest, some tiles may have it (a stop left others behind): the

@@ -86,6 +86,17 @@ struct qa_ctx {
   DScene ds{};
   ScenePlan plan;                   // what the upload decided (qa_scene_build.h)
   bool haveScene = false;
+  // scene edits (qa_scene_edit_*): the host tables of the upload without their mesh side (DropMeshSide), the knobs they were
+  // built with, the per-thread slabs a plan may need (made by the upload or by the first edit whose plan asks for one), and
+  // pinned staging the edits' copies leave from: a bump arena, waited for only when it wraps
+  SceneTables tables;
+  BuildKnobs knobs;
+  float *dAreaSlab = nullptr, *dSurfSlab = nullptr;
+  unsigned char *hEditStage = nullptr;
+  size_t editStageBytes = 0, editStageUsed = 0;
+  hipEvent_t editEv = nullptr;        // end of the last edit's copies (on the context's stream)
+  bool editEvSet = false;
+  uint64_t statMeshBuilds = 0, statSceneAllocs = 0, statBytesCopied = 0, statEdits = 0;   // qa_get_scene_stats
   float *dHalton = nullptr;
   int haltonCount = 0;
   // launch plumbing
@@ -152,7 +163,8 @@ struct qa_ctx {
   // the progressive frame (qa_progressive_*): its slabs are its own, apart from the one-shot frames' dPixState / dTileProgress
   struct Progressive {
     bool active = false;
-    std::string ended;            // why the last frame ended early (a scene upload, the photon maps built or cleared): qa_last_error
+    bool stale = false;           // the scene was edited since the frame's pixels were made: qa_progressive_restart before the next pass
+    std::string ended;           // why the last frame ended early (a scene upload, the photon maps built or cleared): qa_last_error
     int x0 = 0, y0 = 0, x1 = 0, y1 = 0, sppMin = 1, sppMax = 1, maxBounce = 0;
     uint32_t seed = 0, flags = 0;
     unsigned tiles = 0;
@@ -218,6 +230,8 @@ inline void FreeScene(qa_ctx *c)
   c->sceneAllocs.clear();
   if (c->dBlob) (void) hipFree(c->dBlob);
   c->dBlob = nullptr;
+  c->dAreaSlab = c->dSurfSlab = nullptr;   // (they were among sceneAllocs)
+  c->tables = SceneTables{};
   c->haveScene = false;
 }
 
@@ -229,7 +243,9 @@ inline int DeviceCopy(qa_ctx *c, const std::vector<T> &v, const P **out)
   void *p = nullptr;
   HIP_TRY(hipMalloc(&p, v.size() * sizeof(T)));
   c->sceneAllocs.push_back(p);
+  c->statSceneAllocs++;
   HIP_TRY(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+  c->statBytesCopied += v.size() * sizeof(T);
   *out = static_cast<const P *>(p);
   return QA_OK;
 }

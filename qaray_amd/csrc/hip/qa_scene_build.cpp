@@ -380,6 +380,7 @@ void BuildMeshes(const Blob &b, const BuildKnobs &k, SceneTables &out, uint32_t 
     MeshBuild mb{b, m, k, out.mesh[mi], dm, b.at<qa_bvh_node>(m.off_bvh_nodes), b.at<uint32_t>(m.off_elements), b.at<qa_face>(m.off_faces),
                  b.at<float>(m.off_vertices)};
     const uint32_t stackNeedRef = mb.Run(mi, totalFaces, plan.textured);
+    ++out.meshBuilds;
     *stackNeedMax = std::max(*stackNeedMax, dm.stackNeed);
     if (m.num_faces > QA_CS_INDEX_MASK) plan.csFits = false;     // a key holds instance << 20 | element (qa_kernel_cs.h)
     if (stackNeedRef > QA_CS_EXACT_STACK) plan.csFits = false;   // private stacks of the exact walks
@@ -644,6 +645,31 @@ void PlanScene(const Blob &b, const BuildKnobs &k, uint32_t stackNeedMax, SceneT
   ds.num_materials = (int) h->num_materials;
 }
 
+// what follows from the lights and the root node alone
+void PlanLightsAndRoot(const Blob &b, SceneTables &out)
+{
+  const qa_flat_header *h = b.h;
+  ScenePlan &plan = out.plan;
+  const qa_light *light = b.at<qa_light>(h->off_lights);
+  plan.area = false;
+  plan.shadowLights.clear();
+  for (uint32_t i = 0; i < h->num_lights; ++i) {
+    if ((light[i].type == QA_LIGHT_POINT || light[i].type == QA_LIGHT_SPOT) && light[i].size > 0.01f) plan.area = true;
+    if (light[i].type != QA_LIGHT_AMBIENT) plan.shadowLights.push_back((int32_t) i);
+  }
+  const qa_instance *inst = b.at<qa_instance>(h->off_instances);
+  static const float I9[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, Z3[3] = {0, 0, 0};
+  out.ds.rootIdentity = (memcmp(inst[0].tm, I9, 36) == 0 && memcmp(inst[0].itm, I9, 36) == 0 && memcmp(inst[0].pos, Z3, 12) == 0) ? 1 : 0;
+}
+
+// Without reflective / refractive lobes a path is at most camera ray + one diffuse bounce: starting
+// the samples of a wave together keeps its coherent camera rays apart from the incoherent bounce
+// rays (+21 % on the Cornell box).  Long specular chains would make lanes wait for the longest path.
+// Textured scenes also start samples together: the 32-tap filtered lookups of camera hits are the
+// expensive part of their shading and stay coherent that way (+18 % on project7_object, whereas the
+// untextured glossy-caustics scene loses 14 % to waiting for its long specular chains).
+int SyncAuto(const ScenePlan &plan, bool anySpecularLobes) { return (!anySpecularLobes || plan.textured) ? 1 : 0; }
+
 }  // namespace
 
 // core/sampler.cpp:31-40, evaluated on the host in the reference's fp32 order
@@ -667,16 +693,10 @@ int BuildScene(const unsigned char *blob, size_t nbytes, const BuildKnobs &knobs
     CheckHeader(b);
     const qa_flat_header *h = b.h;
     ScenePlan &plan = out.plan;
-    const qa_light *light = b.at<qa_light>(h->off_lights);
-    for (uint32_t i = 0; i < h->num_lights; ++i) {
-      if ((light[i].type == QA_LIGHT_POINT || light[i].type == QA_LIGHT_SPOT) && light[i].size > 0.01f) plan.area = true;
-      if (light[i].type != QA_LIGHT_AMBIENT) plan.shadowLights.push_back((int32_t) i);
-    }
+    PlanLightsAndRoot(b, out);
     const qa_instance *inst = b.at<qa_instance>(h->off_instances);
     plan.meshInstanced.assign(h->num_meshes, false);
     for (uint32_t k = 0; k < h->num_instances; ++k) if (inst[k].obj_type == QA_OBJ_MESH) plan.meshInstanced[inst[k].mesh] = true;
-    static const float I9[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, Z3[3] = {0, 0, 0};
-    out.ds.rootIdentity = (memcmp(inst[0].tm, I9, 36) == 0 && memcmp(inst[0].itm, I9, 36) == 0 && memcmp(inst[0].pos, Z3, 12) == 0) ? 1 : 0;
     plan.textured = h->num_texmaps > 0;
     plan.csFits = true;
     uint32_t stackNeedMax = 1;
@@ -684,14 +704,9 @@ int BuildScene(const unsigned char *blob, size_t nbytes, const BuildKnobs &knobs
     const bool anySpecularLobes = BuildMaterials(b, out);
     BuildImage(out);
     BuildCsTrees(b, out);
+    out.csFitsMeshes = plan.csFits;
     BuildCsInstances(b, out);
-    // Without reflective / refractive lobes a path is at most camera ray + one diffuse bounce: starting
-    // the samples of a wave together keeps its coherent camera rays apart from the incoherent bounce
-    // rays (+21 % on the Cornell box).  Long specular chains would make lanes wait for the longest path.
-    // Textured scenes also start samples together: the 32-tap filtered lookups of camera hits are the
-    // expensive part of their shading and stay coherent that way (+18 % on project7_object, whereas the
-    // untextured glossy-caustics scene loses 14 % to waiting for its long specular chains).
-    plan.syncAuto = (!anySpecularLobes || plan.textured) ? 1 : 0;
+    plan.syncAuto = SyncAuto(plan, anySpecularLobes);
     if (plan.textured) BuildTextures(b, out);
     PlanScene(b, knobs, stackNeedMax, out);
   } catch (const Refused &r) {
@@ -702,6 +717,49 @@ int BuildScene(const unsigned char *blob, size_t nbytes, const BuildKnobs &knobs
     return QA_ENOMEM;
   }
   return QA_OK;
+}
+
+}  // namespace qa
+
+namespace qa {
+
+int RebuildSceneSide(const unsigned char *blob, size_t nbytes, const BuildKnobs &knobs, SceneTables &out, std::string *err)
+{
+  try {
+    const Blob b{blob, nbytes, reinterpret_cast<const qa_flat_header *>(blob)};
+    CheckHeader(b);   // (the only stage below that can refuse: nothing is changed before it has passed)
+    const qa_flat_header *h = b.h;
+    if (h->num_instances != out.csInst.size() || h->num_materials != out.materials.size() || h->num_meshes != out.plan.meshes.size() ||
+        (int) h->num_lights != out.ds.num_lights || (int) h->width != out.ds.cam.width || (int) h->height != out.ds.cam.height)
+      Refuse(QA_EINVAL, "not an edit of the blob these tables were built from (counts or image size differ)");
+    ScenePlan &plan = out.plan;
+    PlanLightsAndRoot(b, out);
+    plan.csFits = out.csFitsMeshes;
+    const bool anySpecularLobes = BuildMaterials(b, out);
+    // the resident image ends with the material table (BuildImage); everything before it is mesh data
+    const size_t mtlVec4 = (out.materials.size() * sizeof(DMaterial) + 15) / 16;
+    if (out.image.size() >= mtlVec4 && mtlVec4) memcpy(out.image.data() + (out.image.size() - mtlVec4), out.materials.data(), out.materials.size() * sizeof(DMaterial));
+    BuildCsInstances(b, out);
+    plan.syncAuto = SyncAuto(plan, anySpecularLobes);
+    PlanScene(b, knobs, out.ds.stackNeed, out);
+  } catch (const Refused &r) {
+    *err = r.msg;
+    return r.code;
+  } catch (const std::bad_alloc &) {
+    *err = "out of memory";
+    return QA_ENOMEM;
+  }
+  return QA_OK;
+}
+
+void DropMeshSide(SceneTables &t)
+{
+  for (MeshTables &m : t.mesh) m = MeshTables{};
+  std::vector<DWideNode>().swap(t.csNodes);
+  std::vector<DTri>().swap(t.csTris);
+  std::vector<float>().swap(t.csLeafBox);
+  std::vector<float>().swap(t.texels);
+  if (!t.plan.resident) std::vector<uint4>().swap(t.image);
 }
 
 }  // namespace qa

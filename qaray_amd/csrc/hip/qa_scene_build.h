@@ -65,10 +65,22 @@ struct SceneTables {
   std::vector<uint32_t> texOff;
   std::vector<float> taps;
   std::vector<uint4> image;              // the resident image (uploaded when plan.resident)
+  // what RebuildSceneSide needs of the mesh-side stages beside the tables above
+  bool csFitsMeshes = false;             // plan.csFits as BuildMeshes and BuildCsTrees left it (the node transforms may still veto)
+  uint32_t meshBuilds = 0;               // calls of the per-mesh builder this BuildScene made
 };
 
 float HaltonF(int index, int base);   // Halton sequence in the reference's fp32 order
 // QA_OK, or a QA_E* code with the reason in *err
 int BuildScene(const unsigned char *blob, size_t nbytes, const BuildKnobs &knobs, SceneTables &out, std::string *err);
+// Scene edits (qa_scene_edit_*): `blob` is the blob `tables` was built from with its camera, light, material and instance records
+// rewritten (same counts, same mesh / texture side).  Runs every stage again that reads them - the light plan, BuildMaterials,
+// BuildCsInstances, PlanScene, and the material table at the end of the resident image - and leaves `tables` as BuildScene(blob)
+// would, without a mesh build: BuildMeshes, BuildCsTrees and BuildTextures keep their results.  QA_OK or a QA_E* code with the
+// reason in *err; a refused blob leaves `tables` as it was.
+int RebuildSceneSide(const unsigned char *blob, size_t nbytes, const BuildKnobs &knobs, SceneTables &tables, std::string *err);
+// Drops the vectors RebuildSceneSide never reads (a context calls it once the tables are on the device: mesh arrays, scene-wide
+// trees, texels, and the image of a scene that is not LDS-resident)
+void DropMeshSide(SceneTables &tables);
 
 }  // namespace qa

@@ -58,6 +58,37 @@ int qa_host_scene_get_size(const qa_host_scene *scene, int *width, int *height)
   return QA_OK;
 }
 
+// what LoadScene makes of a <camera> element's position / target / up (xmlload.cpp): the direction and the up vector orthonormalised
+int qa_host_scene_set_camera(qa_host_scene *scene, const float pos[3], const float target[3], const float up[3], float fov, float focaldist,
+                             float dof)
+{
+  if (!scene || !pos || !target || !up) return Fail(QA_EINVAL, "null argument");
+  Camera &c = scene->scene.camera;
+  c.pos = Point3(pos[0], pos[1], pos[2]);
+  c.dir = Point3(target[0], target[1], target[2]);
+  c.up = Point3(up[0], up[1], up[2]);
+  if (fov > 0) c.fovy = fov;
+  if (focaldist > 0) c.focalDistance = focaldist;
+  if (dof >= 0) c.depthOfField = dof;
+  c.dir -= c.pos;
+  c.dir = normalize(c.dir);
+  const Point3 x = cross(c.dir, c.up);
+  c.up = normalize(cross(x, c.dir));
+  return QA_OK;
+}
+
+int qa_host_scene_camera(const qa_host_scene *scene, qa_camera *out)
+{
+  if (!scene || !out) return Fail(QA_EINVAL, "null argument");
+  const CameraFrame cf = ComputeCameraFrame(scene->scene.camera);
+  const Point3 *v[6] = {&cf.screenA, &cf.screenU, &cf.screenV, &cf.screenX, &cf.screenY, &scene->scene.camera.pos};
+  float *o[6] = {out->screenA, out->screenU, out->screenV, out->screenX, out->screenY, out->cam_pos};
+  for (int k = 0; k < 6; ++k)
+    for (int i = 0; i < 3; ++i) o[k][i] = (*v[k])[i];
+  out->dof = cf.dof;
+  return QA_OK;
+}
+
 int qa_host_scene_flatten(const qa_host_scene *scene, unsigned char **blob, uint64_t *nbytes)
 {
   if (!scene || !blob || !nbytes) return Fail(QA_EINVAL, "null argument");

@@ -38,6 +38,39 @@ PHOTON_DTYPE = np.dtype([("pos", np.float32, 3), ("power", np.float32), ("rgb", 
                          ("dirx", np.int16), ("diry", np.int16)])
 
 
+# the records of include/qa_flat_scene.h that Context.edit_* take (and blob_table views of a blob)
+CAMERA_DTYPE = np.dtype([("screenA", np.float32, 3), ("screenU", np.float32, 3), ("screenV", np.float32, 3), ("screenX", np.float32, 3),
+                         ("screenY", np.float32, 3), ("cam_pos", np.float32, 3), ("dof", np.float32)])
+TEXCOLOR_DTYPE = np.dtype([("color", np.float32, 3), ("texmap", np.int32)])
+LIGHT_DTYPE = np.dtype([("type", np.int32), ("intensity", np.float32, 3), ("position", np.float32, 3), ("direction", np.float32, 3),
+                        ("size", np.float32), ("inner", np.float32), ("outer", np.float32), ("pad", np.int32, 3)])
+MATERIAL_DTYPE = np.dtype([("diffuse", TEXCOLOR_DTYPE), ("specular", TEXCOLOR_DTYPE), ("reflection", TEXCOLOR_DTYPE),
+                           ("refraction", TEXCOLOR_DTYPE), ("emission", TEXCOLOR_DTYPE), ("absorption", np.float32, 3),
+                           ("ior", np.float32), ("kill", np.float32), ("gloss_spec", np.float32), ("gloss_refl", np.float32),
+                           ("gloss_refr", np.float32)])
+INSTANCE_DTYPE = np.dtype([("tm", np.float32, 9), ("itm", np.float32, 9), ("pos", np.float32, 3), ("obj_type", np.int32),
+                           ("mesh", np.int32), ("mtlset", np.int32), ("parent", np.int32), ("subtree_end", np.int32),
+                           ("depth", np.int32), ("pad", np.int32)])
+assert (CAMERA_DTYPE.itemsize, LIGHT_DTYPE.itemsize, MATERIAL_DTYPE.itemsize, INSTANCE_DTYPE.itemsize) == (76, 64, 112, 112)
+# qa_flat_header: byte offsets of the counts and table offsets the views below need
+_HEADER = {"camera": 16, "instances": (136, 168), "materials": (148, 192), "lights": (152, 200)}
+_TABLE_DTYPES = {"instances": INSTANCE_DTYPE, "materials": MATERIAL_DTYPE, "lights": LIGHT_DTYPE}
+
+
+def blob_camera(blob):
+    """The camera block of a flat scene blob (numpy uint8) as a writable 0-d view of CAMERA_DTYPE (cam[...] = record)."""
+    return blob[16:16 + CAMERA_DTYPE.itemsize].view(CAMERA_DTYPE).reshape(())
+
+
+def blob_table(blob, which):
+    """The 'lights' / 'materials' / 'instances' table of a flat scene blob (numpy uint8) as a writable structured view."""
+    at_count, at_off = _HEADER[which]
+    n = int(blob[at_count:at_count + 4].view(np.uint32)[0])
+    off = int(blob[at_off:at_off + 8].view(np.uint64)[0])
+    dt = _TABLE_DTYPES[which]
+    return blob[off:off + n * dt.itemsize].view(dt)
+
+
 class DisplayStats(C.Structure):   # qa_display_stats
     _fields_ = [("zmin", C.c_float), ("zmax", C.c_float), ("smin", C.c_uint32), ("smax", C.c_uint32)]
 
@@ -110,6 +143,12 @@ def lib():
         L.qa_progressive_display.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.POINTER(DisplayStats)]
         L.qa_progressive_display_device.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 7
         L.qa_test_display_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int] + [C.c_void_p] * 6
+        L.qa_scene_edit_camera.argtypes = [C.c_void_p, C.c_void_p]
+        for name in ("qa_scene_edit_lights", "qa_scene_edit_materials", "qa_scene_edit_instances"):
+            getattr(L, name).argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+        L.qa_scene_download.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+        L.qa_get_scene_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        L.qa_progressive_restart.argtypes = [C.c_void_p]
         L.qa_photon_maps_build.argtypes = [C.c_void_p, C.POINTER(PhotonParams), C.c_uint32]
         L.qa_photon_maps_clear.argtypes = [C.c_void_p]
         L.qa_photon_maps_info.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
@@ -196,6 +235,44 @@ class Context:
         # qa_flat_header: width/height follow magic,version(8) total_bytes(8) 6 vec3 (72) dof (4)
         w, h = np.frombuffer(bytes(bytearray(blob_head[92:100])), dtype=np.uint32)
         self.size = (int(w), int(h))
+
+    # -- scene edits (qa_scene_edit_*): the context ends up as after upload_scene(edited blob), without a mesh rebuild ---------
+    def edit_camera(self, cam):
+        """cam: a record of CAMERA_DTYPE (host.HostScene.camera(), blob_camera(blob)).  Keeps the photon maps."""
+        cam = np.ascontiguousarray(cam, dtype=CAMERA_DTYPE).reshape(1)
+        _check(lib().qa_scene_edit_camera(self._h, cam.ctypes.data))
+
+    def _edit_table(self, fn, first, records, dtype):
+        records = np.ascontiguousarray(records, dtype=dtype).reshape(-1)
+        _check(fn(self._h, int(first), records.size, records.ctypes.data))
+        self._photon_sizes = None   # as an upload: the photon maps are dropped
+
+    def edit_lights(self, first, lights):
+        """lights: structured array of LIGHT_DTYPE replacing lights [first, first + len)."""
+        self._edit_table(lib().qa_scene_edit_lights, first, lights, LIGHT_DTYPE)
+
+    def edit_materials(self, first, materials):
+        """materials: structured array of MATERIAL_DTYPE; texture-map references must stay as they are."""
+        self._edit_table(lib().qa_scene_edit_materials, first, materials, MATERIAL_DTYPE)
+
+    def edit_instances(self, first, instances):
+        """instances: structured array of INSTANCE_DTYPE; only tm, itm and pos may differ from the resident records."""
+        self._edit_table(lib().qa_scene_edit_instances, first, instances, INSTANCE_DTYPE)
+
+    def download_scene(self):
+        """-> the resident scene blob as it now stands (numpy uint8), edits included."""
+        n = C.c_uint64()
+        lib().qa_scene_download(self._h, None, 0, C.byref(n))
+        out = np.zeros(max(int(n.value), 1), np.uint8)
+        _check(lib().qa_scene_download(self._h, out.ctypes.data, out.size, C.byref(n)))
+        return out[:n.value]
+
+    def scene_stats(self):
+        """-> [mesh-table builds, scene device allocations (both since the context was created), bytes copied to the device by
+        the last upload or edit, edits since the last upload]."""
+        v = (C.c_uint64 * 4)()
+        _check(lib().qa_get_scene_stats(self._h, v))
+        return [int(x) for x in v]
 
     # -- photon / caustics maps (the reference's -use-photon-map) ---------------------------------
     def build_photon_maps(self, photon=(10000, 20, 0.2), caustics=(1000, 20, 1.0), seed=DEFAULT_SEED):
@@ -445,6 +522,10 @@ class Progressive:
         r, f, b = C.c_int(), C.c_uint64(), C.c_uint64()
         _check(lib().qa_progressive_status(self._ctx._h, C.byref(r), C.byref(f), C.byref(b)))
         return {"spp_reached": r.value, "pixels_finished": f.value, "tiles_behind": b.value}
+
+    def restart(self):
+        """qa_progressive_restart: the same frame from level 0 again (after a scene edit); nothing is freed or allocated."""
+        _check(lib().qa_progressive_restart(self._ctx._h))
 
     def close(self):
         """End the frame (qa_progressive_end) unless a newer frame of the context has replaced it."""

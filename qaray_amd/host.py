@@ -28,6 +28,8 @@ def lib():
         L.qa_host_scene_set_size.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.qa_host_scene_get_size.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.qa_host_scene_flatten.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+        L.qa_host_scene_set_camera.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float]
+        L.qa_host_scene_camera.argtypes = [C.c_void_p, C.c_void_p]
         L.qa_host_free.argtypes = [C.c_void_p]
         L.qa_host_free.restype = None
         L.qa_fb_create.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_void_p)]
@@ -55,6 +57,11 @@ def lib():
         L.qa_tasking_signal_stop.restype = None
         _lib = L
     return _lib
+
+
+# qa_camera (include/qa_flat_scene.h): the camera block of the blob's header, bytes 16..92
+CAMERA_DTYPE = np.dtype([("screenA", np.float32, 3), ("screenU", np.float32, 3), ("screenV", np.float32, 3), ("screenX", np.float32, 3),
+                         ("screenY", np.float32, 3), ("cam_pos", np.float32, 3), ("dof", np.float32)])
 
 
 class HostError(RuntimeError):
@@ -85,6 +92,21 @@ class HostScene:
         w, h = C.c_int(), C.c_int()
         _check(lib().qa_host_scene_get_size(self._h, C.byref(w), C.byref(h)))
         return w.value, h.value
+
+    def set_camera(self, pos, target, up=(0, 1, 0), fov=None, focaldist=None, dof=None):
+        """Move the camera as an XML <camera> with this position / target / up / fov / focaldist / dof would place it (image size
+        kept); None keeps the current fov / focaldist / dof."""
+        v = [np.ascontiguousarray(a, dtype=np.float32) for a in (pos, target, up)]
+        assert all(a.shape == (3,) for a in v)
+        keep = lambda x, none: none if x is None else float(x)   # noqa: E731
+        _check(lib().qa_host_scene_set_camera(self._h, v[0].ctypes.data, v[1].ctypes.data, v[2].ctypes.data, keep(fov, 0.0),
+                                              keep(focaldist, 0.0), keep(dof, -1.0)))
+
+    def camera(self):
+        """-> the camera block flatten() would write (numpy record of CAMERA_DTYPE): what hip.Context.edit_camera takes."""
+        out = np.zeros(1, CAMERA_DTYPE)
+        _check(lib().qa_host_scene_camera(self._h, out.ctypes.data))
+        return out[0]
 
     def flatten(self):
         """-> numpy uint8 array holding the relocatable scene blob (include/qa_flat_scene.h)."""
