@@ -1,5 +1,5 @@
-// qa_ctx.h — internals shared by the translation units of libqaray_hip.so (qa_capi.hip: context,
-// scene, render launches; qa_photon.hip: photon / caustics maps; qa_display.hip: the 8-bit products).  Not part of the C ABI.
+// qa_ctx.h — internals shared by the translation units of libqaray_hip.so (the README's layout line says which unit holds what).
+// Only qa_mega.hip, qa_coop.hip, qa_photon.hip and qa_wf.hip include the kernel headers.  Not part of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -14,6 +14,13 @@
 using namespace qa;
 
 typedef void (*KernelFn)(const DScene, const RenderParams);
+// What crosses from qa_mega.hip and qa_coop.hip: the pickers, and three sizes of the kernel headers the host needs
+KernelFn PickKernel(bool resident, bool lights, bool tex, bool area, bool stats);
+KernelFn PickCs(bool lights, bool tex, bool cull, bool many, bool area);
+KernelFn PickCsResume(bool lights, bool cull, bool many, bool area);   // (untextured rows only)
+extern const int kMaxPath;             // QA_MAX_PATH: hits per path an AREA variant can log
+extern const size_t kAreaLogFloats;    // ... x QA_REC_FLOATS: the floats of a thread's log
+size_t CsLdsBytes(uint32_t items, uint32_t slots);   // CsLdsWords: dynamic LDS of a workgroup of the cooperative kernels
 
 inline thread_local std::string g_err;
 inline int Fail(int code, const std::string &msg) { g_err = msg; return code; }
@@ -37,6 +44,63 @@ inline const char *DevEnv(const char *name)
 }
 
 struct EventPair { hipEvent_t a, b; };
+
+// One integrator a frame can launch.  The STATS slots carry their plain sibling's LDS size and workgroups per CU.  stackDepth is
+// the scene's at SelectKernel (the photon maps' own for kPm): whatever changes DScene::stackDepth runs SelectKernel again
+struct Integrator { KernelFn fn = nullptr; size_t ldsBytes = 0; int blocksPerCU = 2; uint32_t stackDepth = 0; };
+enum Slot { kMega, kMegaStats, kCs, kCsResume, kPm, kPmStats, kNumSlots };
+inline Slot PickSlot(bool photon, bool stats, bool coop, bool resume)
+{
+  return photon ? (stats ? kPmStats : kPm) : stats ? kMegaStats : coop ? (resume ? kCsResume : kCs) : kMega;
+}
+// Workgroups per CU that are resident at once, at most 8; `fallback` when the runtime cannot say
+inline int OccupancyBlocks(KernelFn fn, size_t ldsBytes, int fallback = 2)
+{
+  int n = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void *) fn, QA_BLOCK, ldsBytes) != hipSuccess || n < 1) n = fallback;
+  return n > 8 ? 8 : n;
+}
+
+// "The last X ended here": work on another stream that shares X's memory waits for it.  The event is made on first use
+struct StreamFence {
+  hipEvent_t ev = nullptr;
+  bool set = false;
+  hipStream_t stream = nullptr;
+  hipError_t WaitOn(hipStream_t s) const { return (set && s != stream) ? hipStreamWaitEvent(s, ev, 0) : hipSuccess; }
+  hipError_t Record(hipStream_t s)
+  {
+    hipError_t e = ev ? hipSuccess : hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+    if (e == hipSuccess && (e = hipEventRecord(ev, s)) == hipSuccess) { set = true; stream = s; }
+    return e;
+  }
+};
+
+// A device buffer that only grows.  Before the old one is freed, the whole device or the given stream is waited for, if asked
+struct DevBuf {
+  void *p = nullptr;
+  size_t cap = 0;
+  hipError_t Reserve(size_t bytes, bool syncDevice = false, hipStream_t syncStream = nullptr)
+  {
+    if (bytes <= cap) return hipSuccess;
+    hipError_t e = !p ? hipSuccess : syncDevice ? hipDeviceSynchronize() : syncStream ? hipStreamSynchronize(syncStream) : hipSuccess;
+    if (e != hipSuccess) return e;
+    Free();
+    if ((e = hipMalloc(&p, bytes)) == hipSuccess) cap = bytes;
+    return e;
+  }
+  void Free() { if (p) (void) hipFree(p); p = nullptr; cap = 0; }
+};
+
+// One frame as its caller describes it (qa_render_*, qa_progressive_begin)
+struct FrameArgs {
+  int x0 = 0, y0 = 0, x1 = 0, y1 = 0;
+  int tileRow0 = 0, tileRowStep = 1;   // strip partition: this call's tile rows are tileRow0, + tileRowStep, ...
+  int sppMin = 1, sppMax = 1, maxBounce = 0;
+  uint32_t seed = 0, flags = 0;
+  float *rgb = nullptr, *depth = nullptr;   // outputs (device)
+  uint32_t *ns = nullptr;
+  hipStream_t stream = nullptr;
+};
 
 // Host side of the staged integrator (qa_wf.hip): buffers are kept between frames
 struct WfHost {
@@ -94,8 +158,7 @@ struct qa_ctx {
   float *dAreaSlab = nullptr, *dSurfSlab = nullptr;
   unsigned char *hEditStage = nullptr;
   size_t editStageBytes = 0, editStageUsed = 0;
-  hipEvent_t editEv = nullptr;        // end of the last edit's copies (on the context's stream)
-  bool editEvSet = false;
+  StreamFence lastEdit;             // end of the last edit's copies (on the context's stream)
   uint64_t statMeshBuilds = 0, statSceneAllocs = 0, statBytesCopied = 0, statEdits = 0;   // qa_get_scene_stats
   float *dHalton = nullptr;
   int haltonCount = 0;
@@ -103,11 +166,8 @@ struct qa_ctx {
   static const int kCounterRing = 64;
   unsigned int *dWork = nullptr;  // ring of work counters
   // tiles in sample chunks (qa_integrate, RenderParams::chunk_spp): per-pixel state between chunks, per-tile progress
-  uint32_t *dPixState = nullptr, *dTileProgress = nullptr;
-  size_t pixStateWords = 0, tileProgressWords = 0;
-  hipEvent_t chunkEv = nullptr;   // end of the last frame: the slabs (this one, the area-light log, the many-light surface slab) are one per context
-  bool chunkEvSet = false;
-  hipStream_t lastStream = nullptr;   // ... a frame on another stream waits for it
+  DevBuf pixState, tileProgress;
+  StreamFence lastFrame;          // the slabs (these, the area-light log, the many-light surface slab) are one per context: a frame on another stream waits
   int optChunkSpp = -1;           // "chunk_spp": -1 per frame (few tiles per wave), 0 off, n samples of a tile's first chunk
   int optChunkTail = 0;           // "chunk_tail": samples of every further chunk (0: an eighth of the frame's spp)
   int workNext = 0;
@@ -115,34 +175,22 @@ struct qa_ctx {
   int *dStopAlias = nullptr;
   DCounters *dCounters = nullptr;
   // host-variant staging
-  float *dRgb = nullptr, *dDepth = nullptr;
-  uint32_t *dNs = nullptr;
-  size_t stagePixels = 0;
+  DevBuf stageRgb, stageDepth, stageNs;
   // timing
   std::vector<EventPair> pending, freeEvents;
   double totalMs = 0;
   uint64_t launches = 0;
-  int blocksPerCU = 0, blocksPerCUAuto = 2, threads = QA_BLOCK;  // 0 = use the occupancy-derived value
-  void (*kernel)(const DScene, const RenderParams) = nullptr;
-  void (*kernelStats)(const DScene, const RenderParams) = nullptr;
-  bool csMany = false;   // the cooperative kernel's MANY variant (more shadow-casting lights than one batch)
+  // the integrators of the uploaded scene (SelectKernel; kPm / kPmStats: qa_photon_maps_build).  kCs: the megakernel with cooperative
+  // mesh walks (qa_kernel_cs.h), fn null where the scene or "coop" rules it out, ldsBytes set by the upload; kCsResume: its
+  // chunk-capable instance where kCs carries no chunk code (progressive passes)
+  Integrator integ[kNumSlots];
+  int optBlocksPerCU = 0;       // qa_set_launch_config: workgroups per CU of every slot (0 = the slot's own)
   bool tileOrder = true;        // centre-first tile order (QA_NO_TILE_ORDER=1 turns it off)
   uint32_t *dOrder = nullptr;   // tile launch order of the last region shape
   uint64_t orderKey = 0;
   int syncSamples = -1;  // -1: decide per scene (SelectKernel), 0/1 forced by QA_SYNC
   // photon / caustics maps (qa_photon.hip); valid until the next scene upload or qa_photon_maps_clear
   bool photonReady = false;
-  KernelFn kernelPm = nullptr, kernelPmStats = nullptr;
-  // the megakernel with cooperative mesh walks (qa_kernel_cs.h): global-memory scenes without area lights
-  KernelFn kernelCs = nullptr;
-  KernelFn kernelCsResume = nullptr;   // ... its chunk-capable instance where kernelCs carries no chunk code (progressive passes)
-  int blocksPerCUCsResume = 2;
-  size_t ldsBytesCs = 0;
-  bool csCullVariant = false;    // the cooperative kernel chosen tests the nodes' bounds first (SelectKernel)
-  int blocksPerCUCs = 2;
-  int blocksPerCUPm = 2;
-  uint32_t stackDepthPm = 0;   // LDS stack entries per lane when the kd-tree gather runs on it
-  size_t ldsBytesPm = 0;
   void *dPhotons[2] = {nullptr, nullptr};      // qa_photon records (what qa_photon_maps_download returns)
   void *dPmTables[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};   // DPhotonMap node / dir / power
   void *dHeap = nullptr;
@@ -160,13 +208,12 @@ struct qa_ctx {
   uint32_t optCsPool = 0;       // "cs_pool_limit": upper bound for the walks' pool capacity (tests force the overflow path)
   bool optVerbose = false;      // "verbose": tree / launch-shape report on stderr at upload
   uint32_t optProgTileLimit = 0; // "progressive_tile_limit": tests - a progressive pass takes at most n tiles, then ends as if stopped
-  // the progressive frame (qa_progressive_*): its slabs are its own, apart from the one-shot frames' dPixState / dTileProgress
+  // the progressive frame (qa_progressive_*): its slabs are its own, apart from the one-shot frames' pixState / tileProgress
   struct Progressive {
     bool active = false;
     bool stale = false;           // the scene was edited since the frame's pixels were made: qa_progressive_restart before the next pass
     std::string ended;           // why the last frame ended early (a scene upload, the photon maps built or cleared): qa_last_error
-    int x0 = 0, y0 = 0, x1 = 0, y1 = 0, sppMin = 1, sppMax = 1, maxBounce = 0;
-    uint32_t seed = 0, flags = 0;
+    FrameArgs args;               // as qa_progressive_begin got them; rgb / depth / ns: the frame's slabs of finished pixels' outputs, depth of sample 0
     unsigned tiles = 0;
     size_t npix = 0;
     int target = 0;               // the last pass's target, min(S, spp_max)
@@ -175,24 +222,28 @@ struct qa_ctx {
     uint32_t *dLevel = nullptr;   // per tile: the samples every unfinished pixel of it has
     uint32_t *dList = nullptr;    // per tile: the tile order of a pass that re-issues a target (qa_prog_select)
     uint32_t *dProgress = nullptr;   // per tile: the pass's tile_progress (1 before a pass, 2 once the tile's pass is complete)
-    float *dRgb = nullptr, *dDepth = nullptr;   // finished pixels' outputs; depth of sample 0
-    uint32_t *dNs = nullptr;
-    float *dPrevRgb = nullptr, *dPrevDepth = nullptr;   // qa_progressive_read's preview (made on first use)
-    uint32_t *dPrevNs = nullptr;
+    DevBuf prevRgb, prevDepth, prevNs;   // qa_progressive_read's preview (made on first use)
     unsigned long long *dStatus = nullptr;   // qa_progressive_status: finished pixels, tiles behind, lowest level
-    hipEvent_t done = nullptr;    // end of the last pass
+    StreamFence done;             // end of the frame's setup / last pass, on whatever stream it ran
   } prog;
   // the 8-bit products (qa_display.hip): the statistics block (4 working words, then their initial values) and the staging of
   // qa_progressive_display's host variant are made on first use and live as long as the context
   uint32_t *dDisplay = nullptr;
-  hipEvent_t displayEv = nullptr;      // end of the last display: the block is one per context ...
-  bool displayEvSet = false;
-  hipStream_t displayStream = nullptr; // ... a display on another stream waits for it
-  uint8_t *dDisplayStage = nullptr;
-  size_t displayStageBytes = 0;
+  StreamFence lastDisplay;      // the block is one per context: a display on another stream waits
+  DevBuf displayStage;
 };
 
 void FreePhotonMaps(qa_ctx *c);  // qa_photon.hip
+// qa_frame.hip: the integrators of the uploaded scene and the name qa_get_kernel_name gives before a frame has run; what all frames
+// share of a launch.  Launch: one launch of the megakernel as LaunchSetup plans it (without the chunk fields of rp)
+int SelectKernel(qa_ctx *c);
+void SetKernelName(qa_ctx *c);
+struct Launch { RenderParams rp; DScene ds; Slot slot = kMega; long long blocks = 1; unsigned tiles = 0; };
+int EnsureHalton(qa_ctx *c, int count);
+int CheckFrame(qa_ctx *c, const FrameArgs &a);
+int LaunchSetup(qa_ctx *c, Launch &L, const FrameArgs &a, int ownRows, unsigned int *work, bool resume);
+int LaunchFrame(qa_ctx *c, Launch &L, bool staged, hipStream_t s);
+int DrainEvents(qa_ctx *c);
 // qa_wf.hip
 void FreeStaged(qa_ctx *c);
 void SelectStaged(qa_ctx *c);
@@ -205,14 +256,26 @@ inline void EndProgressive(qa_ctx *c, const char *why)
   qa_ctx::Progressive &f = c->prog;
   if (f.active && why) f.ended = why;
   f.active = false;
-  void *slabs[] = {f.dState, f.dLevel, f.dList, f.dProgress, f.dRgb, f.dDepth, f.dNs, f.dPrevRgb, f.dPrevDepth, f.dPrevNs, f.dStatus};
+  void *slabs[] = {f.dState, f.dLevel, f.dList, f.dProgress, f.args.rgb, f.args.depth, f.args.ns, f.dStatus};
   if (f.dState) (void) hipDeviceSynchronize();   // (a pass may still run on a stream of the caller's)
   for (void *p : slabs)
     if (p) (void) hipFree(p);
-  f.dState = f.dLevel = f.dList = f.dProgress = f.dNs = f.dPrevNs = nullptr;
-  f.dRgb = f.dDepth = f.dPrevRgb = f.dPrevDepth = nullptr;
+  f.dState = f.dLevel = f.dList = f.dProgress = f.args.ns = nullptr;
+  f.args.rgb = f.args.depth = nullptr;
   f.dStatus = nullptr;
+  f.prevRgb.Free(); f.prevDepth.Free(); f.prevNs.Free();
 }
+
+// What most entries begin with, and the stream they work on: the caller's or the context's
+inline int Enter(qa_ctx *c)
+{
+  if (!c) return Fail(QA_EINVAL, "null context");
+  HIP_TRY(hipSetDevice(c->device));
+  return QA_OK;
+}
+inline hipStream_t StreamOf(qa_ctx *c, void *hip_stream) { return hip_stream ? (hipStream_t) hip_stream : c->stream; }
+// where the upload report goes ("verbose", QA_FAST_VERBOSE), else null
+inline FILE *Report(const qa_ctx *c) { return (c->optVerbose || DevEnv("QA_FAST_VERBOSE")) ? stderr : nullptr; }
 
 // What every qa_progressive_* call on a frame says when there is none (or why the last one ended)
 inline int ProgActive(qa_ctx *c)

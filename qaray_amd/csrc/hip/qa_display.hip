@@ -19,7 +19,7 @@
 namespace qa {
 
 // state = null: the plain buffers.  Else the progressive frame: 8 words per pixel ([1] samples taken | bit 31 finished, [2..4] the
-// running mean), rgb / ns hold the finished pixels' outputs and depth sample 0's hit distance (qa_capi.hip, qa_prog_resolve)
+// running mean), rgb / ns hold the finished pixels' outputs and depth sample 0's hit distance (qa_progressive.hip, qa_prog_resolve)
 struct DisplaySrc {
   const float *rgb, *depth;
   const uint32_t *ns, *state;
@@ -172,9 +172,8 @@ static int Display(qa_ctx *c, const DisplaySrc &src, uint64_t npix, int spp_max,
     const DisplayAcc a = displayAccInit();
     const uint32_t init[8] = {0, 0, 0, 0, displayKey(a.zmin), displayKey(a.zmax), a.smin, a.smax};
     HIP_TRY(hipMemcpy(c->dDisplay, init, sizeof(init), hipMemcpyHostToDevice));
-    HIP_TRY(hipEventCreateWithFlags(&c->displayEv, hipEventDisableTiming));
   }
-  if (c->displayEvSet && s != c->displayStream) HIP_TRY(hipStreamWaitEvent(s, c->displayEv, 0));
+  HIP_TRY(c->lastDisplay.WaitOn(s));
   HIP_TRY(hipMemcpyAsync(c->dDisplay, c->dDisplay + 4, 4 * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
   // the 16-byte loads and the dword stores want aligned buffers; otherwise every pixel takes the one-by-one path
   const bool vec = Aligned(src.rgb, 16) && Aligned(src.depth, 16) && Aligned(src.ns, 16) && Aligned(out.color, 4) && Aligned(out.count, 4) &&
@@ -189,9 +188,7 @@ static int Display(qa_ctx *c, const DisplaySrc &src, uint64_t npix, int spp_max,
   hipLaunchKernelGGL(prog ? qa::qa_display_encode<true> : qa::qa_display_encode<false>, dim3(blocks), dim3(256), 0, s, src, n, groups, spp_max, use_srgb,
                      c->dDisplay, out);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(c->displayEv, s));
-  c->displayEvSet = true;
-  c->displayStream = s;
+  HIP_TRY(c->lastDisplay.Record(s));
   return QA_OK;
 }
 
@@ -201,11 +198,10 @@ int qa_display_device(qa_ctx *c, const float *d_rgb, const float *d_depth, const
                       uint8_t *d_color, uint8_t *d_count, uint8_t *d_zimg, uint8_t *d_countimg, uint8_t *d_mask, qa_display_stats *d_stats,
                       void *hip_stream)
 {
-  if (!c) return Fail(QA_EINVAL, "null context");
-  HIP_TRY(hipSetDevice(c->device));
+  if (int rc = Enter(c)) return rc;
   const DisplaySrc src = {d_rgb, d_depth, d_ns, nullptr};
   const DisplayOut out = {d_color, d_count, d_zimg, d_countimg, d_mask, d_stats};
-  return Display(c, src, npix, spp_max, use_srgb, out, hip_stream ? (hipStream_t) hip_stream : c->stream);
+  return Display(c, src, npix, spp_max, use_srgb, out, StreamOf(c, hip_stream));
 }
 
 int qa_progressive_display_device(qa_ctx *c, int use_srgb, uint8_t *d_color, uint8_t *d_count, uint8_t *d_zimg, uint8_t *d_countimg,
@@ -214,12 +210,12 @@ int qa_progressive_display_device(qa_ctx *c, int use_srgb, uint8_t *d_color, uin
   int rc = ProgActive(c);
   if (rc != QA_OK) return rc;
   HIP_TRY(hipSetDevice(c->device));
-  hipStream_t s = hip_stream ? (hipStream_t) hip_stream : c->stream;
+  hipStream_t s = StreamOf(c, hip_stream);
   const qa_ctx::Progressive &f = c->prog;
-  HIP_TRY(hipStreamWaitEvent(s, f.done, 0));
-  const DisplaySrc src = {f.dRgb, f.dDepth, f.dNs, f.dState};
+  HIP_TRY(f.done.WaitOn(s));
+  const DisplaySrc src = {f.args.rgb, f.args.depth, f.args.ns, f.dState};
   const DisplayOut out = {d_color, d_count, d_zimg, d_countimg, d_mask, d_stats};
-  return Display(c, src, f.npix, f.sppMax, use_srgb, out, s);
+  return Display(c, src, f.npix, f.args.sppMax, use_srgb, out, s);
 }
 
 int qa_progressive_display(qa_ctx *c, int use_srgb, uint8_t *color, uint8_t *count, uint8_t *zimg, uint8_t *countimg, uint8_t *mask,
@@ -230,12 +226,8 @@ int qa_progressive_display(qa_ctx *c, int use_srgb, uint8_t *color, uint8_t *cou
   HIP_TRY(hipSetDevice(c->device));
   // the products' staging belongs to the context and only grows: [colour | count | z image | count image | mask | statistics]
   const size_t n = c->prog.npix, slot = (n + 15) & ~(size_t) 15, need = 3 * slot + 4 * slot + 16;
-  if (need > c->displayStageBytes) {
-    if (c->dDisplayStage) { HIP_TRY(hipStreamSynchronize(c->stream)); (void) hipFree(c->dDisplayStage); c->dDisplayStage = nullptr; c->displayStageBytes = 0; }
-    HIP_TRY(hipMalloc((void **) &c->dDisplayStage, need));
-    c->displayStageBytes = need;
-  }
-  uint8_t *d = c->dDisplayStage;
+  HIP_TRY(c->displayStage.Reserve(need, false, c->stream));
+  uint8_t *d = static_cast<uint8_t *>(c->displayStage.p);
   uint8_t *dv[5] = {color ? d : nullptr, count ? d + 3 * slot : nullptr, zimg ? d + 4 * slot : nullptr, countimg ? d + 5 * slot : nullptr,
                     mask ? d + 6 * slot : nullptr};
   qa_display_stats *ds = stats ? reinterpret_cast<qa_display_stats *>(d + 7 * slot) : nullptr;

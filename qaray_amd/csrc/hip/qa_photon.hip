@@ -567,14 +567,13 @@ int qa_photon_maps_build(qa_ctx *c, const qa_photon_params *pp, uint32_t seed)
     if (rc != QA_OK) { FreePhotonMaps(c); return rc; }
   }
   c->photonParams = *pp;
-  c->stackDepthPm = needDepth;
-  c->ldsBytesPm = imageBytes + stackBytes;
-  c->kernelPm = PickPmKernel(c->plan.resident, c->plan.textured, c->plan.area, false);
-  c->kernelPmStats = PickPmKernel(c->plan.resident, c->plan.textured, c->plan.area, true);
-  int resident = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&resident, (const void *) c->kernelPm, QA_BLOCK, c->ldsBytesPm) != hipSuccess || resident < 1)
-    resident = 1;
-  c->blocksPerCUPm = resident > 8 ? 8 : resident;
+  Integrator &pm = c->integ[kPm];
+  pm.fn = PickPmKernel(c->plan.resident, c->plan.textured, c->plan.area, false);
+  pm.ldsBytes = imageBytes + stackBytes;
+  pm.blocksPerCU = OccupancyBlocks(pm.fn, pm.ldsBytes, 1);
+  pm.stackDepth = needDepth;   // LDS stack entries per lane when the kd-tree gather runs on it
+  c->integ[kPmStats] = pm;
+  c->integ[kPmStats].fn = PickPmKernel(c->plan.resident, c->plan.textured, c->plan.area, true);
   // nearest-photon heaps: QA_PHOTON_GATHER + 1 slots per thread of the largest grid
   const size_t threads = (size_t) c->numCUs * 8 * QA_BLOCK;
   const hipError_t e = hipMalloc(&c->dHeap, threads * (QA_PHOTON_GATHER + 1) * sizeof(uint2));

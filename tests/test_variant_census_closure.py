@@ -1,5 +1,5 @@
 """The census table of tests/test_gpu_variant_census.py against the built objects (no GPU): its rows name exactly the integrator
-kernels that qa_capi.o, qa_photon.o and qa_wf.o hold.  A variant added to a picker without a census row fails here."""
+kernels that qa_mega.o, qa_coop.o, qa_photon.o and qa_wf.o hold.  A variant added to a picker without a census row fails here."""
 import os
 import sys
 
@@ -9,6 +9,7 @@ from test_gpu_variant_census import ROWS
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OBJ = os.path.join(ROOT, "qaray_amd", "lib", "obj")
+OBJECTS = ("qa_mega.o", "qa_coop.o", "qa_photon.o", "qa_wf.o")   # the units that include the kernel headers
 
 
 def _shipped_integrators():
@@ -18,7 +19,7 @@ def _shipped_integrators():
     finally:
         sys.path.pop(0)
     names = []
-    for o in ("qa_capi.o", "qa_photon.o", "qa_wf.o"):
+    for o in OBJECTS:
         names += demangle([k["name"] for k in kernels_of(os.path.join(OBJ, o))])
     out = set()
     for n in names:
@@ -30,7 +31,7 @@ def _shipped_integrators():
 
 
 def test_census_rows_are_exactly_the_shipped_integrator_kernels():
-    if not all(os.path.exists(os.path.join(OBJ, o)) for o in ("qa_capi.o", "qa_photon.o", "qa_wf.o")):
+    if not all(os.path.exists(os.path.join(OBJ, o)) for o in OBJECTS):
         pytest.skip("no objects (run __graft_entry__.build())")
     shipped = _shipped_integrators()
     listed = [i for r in ROWS for i in r.instances]

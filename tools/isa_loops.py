@@ -1,7 +1,7 @@
 """Loop-level statistics of a kernel's gfx950 assembly (no GPU needed): where the spills, scalar loads and waits sit.
-   hipcc ... --save-temps -c qa_capi.hip     (writes qa_capi-hip-amdgcn-amd-amdhsa-gfx950.s)
+   hipcc ... --save-temps -c qa_coop.hip     (writes qa_coop-hip-amdgcn-amd-amdhsa-gfx950.s; qa_mega.hip: the per-lane kernels)
    python tools/isa_loops.py FILE.s SUBSTRING_OF_MANGLED_NAME [min_len]
-e.g. python tools/isa_loops.py /tmp/isa/qa_capi-hip-amdgcn-amd-amdhsa-gfx950.s integrate_csILb1ELb0E"""
+e.g. python tools/isa_loops.py /tmp/isa/qa_coop-hip-amdgcn-amd-amdhsa-gfx950.s integrate_csILb1ELb0E"""
 import re
 import sys
 

@@ -1,5 +1,5 @@
 """Where a kernel's scratch traffic sits, by source line and loop depth (no GPU needed).
-   hipcc ... -gline-tables-only --save-temps --cuda-device-only -c qa_capi.hip
+   hipcc ... -gline-tables-only --save-temps --cuda-device-only -c qa_mega.hip   (or qa_coop.hip, qa_photon.hip, qa_wf.hip: the units that hold integrators)
    python tools/isa_spill_sites.py FILE.s SUBSTRING_OF_MANGLED_NAME [rows]
 Every scratch_load / scratch_store is attributed to the last .loc before it and to the number of loops (backward branches)
 that enclose it; v_readlane / v_writelane (spilled SGPRs) are counted per depth."""

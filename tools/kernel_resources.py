@@ -1,5 +1,5 @@
 """Register / spill / scratch / LDS use of every gfx950 kernel in built objects (no GPU needed).
-   python tools/kernel_resources.py [qaray_amd/lib/obj/qa_capi.o ...] [--grep qa_integrate_cs]
+   python tools/kernel_resources.py [qaray_amd/lib/obj/qa_mega.o qaray_amd/lib/obj/qa_coop.o ...] [--grep qa_integrate_cs]
 Unbundles the device code object from each host object and reads the AMDGPU metadata note."""
 import os, re, subprocess, sys, tempfile
 
