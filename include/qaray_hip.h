@@ -83,6 +83,7 @@ int qa_scene_upload_device(qa_ctx *ctx, const void *device_blob, uint64_t nbytes
  *   qa_scene_edit_materials  colours, glossiness, ior, absorption, kill.  QA_EINVAL when a record's texmap references differ
  *                            from the resident ones (texture tables are not rebuilt)
  *   qa_scene_edit_instances  tm, itm, pos.  QA_EINVAL when a record changes obj_type, mesh, mtlset, parent, subtree_end or depth
+ * (Texmaps, texture colours, texels and the backdrop colours: the texture edits below.)
  * An edit that changes the plan (area lights appear or go, the shadow-casting lights cross QA_CS_LIGHT_BATCH, the root node
  * stops being the identity ...) selects the integrator again, and allocates the per-thread slab the new plan needs if no earlier
  * plan of this scene did; no other edit allocates device memory.  An edit that a fresh upload would refuse returns that upload's
@@ -106,6 +107,42 @@ int qa_scene_edit_materials(qa_ctx *ctx, uint32_t first, uint32_t n, const qa_ma
 int qa_scene_edit_instances(qa_ctx *ctx, uint32_t first, uint32_t n, const qa_instance *instances);
 int qa_scene_download(qa_ctx *ctx, void *out, uint64_t capacity, uint64_t *nbytes);
 int qa_get_scene_stats(qa_ctx *ctx, uint64_t out[4]);
+
+/* Texture edits of the resident scene: the same contract as the edits above - afterwards the context is where qa_scene_upload of
+ * the edited blob would leave it (same plan, same qa_get_kernel_name, same bits in every later frame, qa_scene_download returns the
+ * edited blob byte for byte), no mesh tree is rebuilt, no table reallocated, and a refused edit changes nothing.  The kernels read
+ * qa_texmap and qa_texture records straight from the resident device blob and get the two backdrop colours by value at launch, so
+ * the record edits are blob writes; the one derived table, the float texels (16 bytes per texel, byte / 255.0f), is recomputed for
+ * the edited rectangle on the device.
+ *   qa_scene_edit_texmaps   itm, pos and texture.  texture must be in -1 .. num_textures - 1 (QA_EINVAL otherwise, as an upload
+ *                           says): this is how a viewer swaps the image a map shows among the resident textures - the material
+ *                           side keeps its texmap references (qa_scene_edit_materials)
+ *   qa_scene_edit_textures  color1 and color2 (a checker's colours).  QA_EINVAL when a record changes type, width, height or
+ *                           off_texels: the texel table is not laid out again
+ *   qa_scene_edit_backdrop  the colours of the header's background and environment; either pointer may be NULL (stays as it
+ *                           is).  QA_EINVAL when a record's texmap differs from the resident one
+ *   qa_scene_edit_texels    texels [x0, x1) x [y0, y1) of file texture `texture` <- rows of RGB8, row_stride_bytes apart.  The
+ *                           bytes go into the resident blob (host and device copy) and the rectangle's float entries are made
+ *                           again by a kernel.  The source leaves through the pinned edit ring in slices of 64 KB (the ring does
+ *                           not grow with the texture): 3 bytes per texel cross the link.  Only enqueues on the context's stream;
+ *                           waits for an earlier edit only when the ring wraps.  QA_EINVAL: a checker texture, a texture beyond
+ *                           the table, an empty rectangle or one beyond the texture, a stride below 3 * (x1 - x0), a null source
+ *   qa_scene_edit_texels_device   the same with the source in device memory: nothing crosses the link.  hip_stream is the stream
+ *                           the source was produced on (NULL: the caller guarantees that it is ready): the context's stream waits
+ *                           for it before the kernel runs, and hip_stream waits for the kernel afterwards, so the caller may
+ *                           overwrite the source on that stream right after the call.  The host copy of the blob is brought up
+ *                           to date lazily: qa_scene_download first fetches the bytes of the textures edited this way from the
+ *                           device blob (and then synchronises); nothing else reads texels on the host
+ * Side effects as for the other non-camera edits: a progressive frame goes stale until qa_progressive_restart, the photon maps
+ * are dropped (photon tracing samples textures), and a frame on a stream of the caller's is ordered behind the edit.
+ * qa_get_scene_stats [2] after a texel edit: the RGB8 bytes staged (host variant), 0 (device variant).
+ * No reference counterpart (the reference loads its textures once per process). */
+int qa_scene_edit_texmaps(qa_ctx *ctx, uint32_t first, uint32_t n, const qa_texmap *texmaps);
+int qa_scene_edit_textures(qa_ctx *ctx, uint32_t first, uint32_t n, const qa_texture *textures);
+int qa_scene_edit_backdrop(qa_ctx *ctx, const qa_texcolor *background, const qa_texcolor *environment);
+int qa_scene_edit_texels(qa_ctx *ctx, uint32_t texture, int x0, int y0, int x1, int y1, const uint8_t *rgb8, uint64_t row_stride_bytes);
+int qa_scene_edit_texels_device(qa_ctx *ctx, uint32_t texture, int x0, int y0, int x1, int y1, const uint8_t *d_rgb8,
+                                uint64_t row_stride_bytes, void *hip_stream);
 
 /* Render pixels [x0,x1) x [y0,y1) of the scene's image.  Outputs are region-local, row-major:
  * rgb (y1-y0)*(x1-x0)*3 floats of LINEAR mean radiance (sRGB/quantisation stay in FrameBuffer),
@@ -316,6 +353,11 @@ int qa_test_texture_host(const void *blob, int op, int index, int n, const float
  * for the host, pixel after pixel over host arrays (no GPU and no context needed). */
 int qa_test_display_host(const float *rgb, const float *depth, const uint32_t *nsamples, uint64_t npix, int spp_max, int use_srgb,
                          uint8_t *color, uint8_t *count, uint8_t *zimg, uint8_t *countimg, uint8_t *mask, qa_display_stats *stats);
+
+/* Self-test hook for the texel conversion (qaray_amd/csrc/hip/qa_texel_dev.h): the source of qa_scene_edit_texels' kernel and of an
+ * upload's texel table compiled for the host: h rows of w RGB8 texels, `stride` bytes apart -> w * h entries {r, g, b, 0} / 255.0f
+ * of 4 floats (no GPU and no context needed). */
+int qa_test_texels_host(const uint8_t *rgb8, int w, int h, uint64_t stride, float *out4);
 
 #ifdef __cplusplus
 }

@@ -1,5 +1,6 @@
 // qa_capi.hip — the context of libqaray_hip.so's C ABI (include/qaray_hip.h): create / destroy, scene upload (blob -> device
-// tables), download and edits, options, counters and timing.  Frames: qa_frame.hip, qa_progressive.hip.
+// tables), download and edits, options, counters and timing.  Frames: qa_frame.hip, qa_progressive.hip; texel edits and their
+// kernel: qa_texture_edit.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -155,7 +156,7 @@ int qa_ctx_destroy(qa_ctx *c)
   for (void *p : {(void *) c->hEditStage, (void *) c->hStop})
     if (p) (void) hipHostFree(p);
   for (DevBuf *b : {&c->pixState, &c->tileProgress, &c->stageRgb, &c->stageDepth, &c->stageNs, &c->displayStage}) b->Free();
-  for (StreamFence *f : {&c->lastFrame, &c->lastEdit, &c->lastDisplay, &c->prog.done})
+  for (StreamFence *f : {&c->lastFrame, &c->lastEdit, &c->lastDisplay, &c->texSource, &c->prog.done})
     if (f->ev) (void) hipEventDestroy(f->ev);
   if (c->stream) (void) hipStreamDestroy(c->stream);
   delete c;
@@ -195,6 +196,8 @@ static int ApplySceneSide(qa_ctx *c)
   c->plan.meshes = std::move(meshes);
   DScene &ds = c->ds;
   ds.cam = t.ds.cam;
+  memcpy(ds.background, t.ds.background, sizeof(ds.background));
+  memcpy(ds.environment, t.ds.environment, sizeof(ds.environment));
   ds.rootIdentity = t.ds.rootIdentity;
   ds.csCullS1 = t.ds.csCullS1; ds.csCullS2 = t.ds.csCullS2; ds.csCullK3 = t.ds.csCullK3; ds.csCullK4 = t.ds.csCullK4;
   memcpy(ds.instv, t.ds.instv, sizeof(ds.instv));
@@ -203,11 +206,11 @@ static int ApplySceneSide(qa_ctx *c)
 
 struct EditCopy { const void *dst; const void *src; size_t bytes; };
 
-// The copies of one edit: through the pinned ring, asynchronously on the context's stream
-static int EnqueueEditCopies(qa_ctx *c, const std::vector<EditCopy> &copies)
+// `need` bytes of the pinned ring (64-byte aligned), valid until a later edit wraps the ring - which first waits for lastEdit, so
+// whoever reads them on the device records lastEdit behind that work
+int EditStageReserve(qa_ctx *c, size_t need, unsigned char **at)
 {
-  size_t need = 0;
-  for (const EditCopy &k : copies) need += (k.bytes + 63) & ~(size_t) 63;
+  need = (need + 63) & ~(size_t) 63;
   if (need > c->editStageBytes) {
     if (c->lastEdit.set) HIP_TRY(hipEventSynchronize(c->lastEdit.ev));
     if (c->hEditStage) (void) hipHostFree(c->hEditStage);
@@ -221,23 +224,55 @@ static int EnqueueEditCopies(qa_ctx *c, const std::vector<EditCopy> &copies)
     if (c->lastEdit.set) HIP_TRY(hipEventSynchronize(c->lastEdit.ev));
     c->editStageUsed = 0;
   }
-  // a frame on a stream of the caller's may still read the tables
+  *at = c->hEditStage + c->editStageUsed;
+  c->editStageUsed += need;
+  return QA_OK;
+}
+
+// What an edit's device work waits for: a frame on a stream of the caller's may still read the tables
+int EditBegin(qa_ctx *c)
+{
   HIP_TRY(c->lastFrame.WaitOn(c->stream));
   if (c->prog.active) HIP_TRY(c->prog.done.WaitOn(c->stream));
   c->statBytesCopied = 0;
+  return QA_OK;
+}
+
+// The copies of one edit: through the pinned ring, asynchronously on the context's stream
+static int EnqueueEditCopies(qa_ctx *c, const std::vector<EditCopy> &copies)
+{
+  size_t need = 0;
+  for (const EditCopy &k : copies) need += (k.bytes + 63) & ~(size_t) 63;
+  unsigned char *stage = nullptr;
+  int rc = EditStageReserve(c, need, &stage);
+  if (rc != QA_OK || (rc = EditBegin(c)) != QA_OK) return rc;
   for (const EditCopy &k : copies) {
     if (!k.bytes || !k.dst) continue;
-    unsigned char *stage = c->hEditStage + c->editStageUsed;
     memcpy(stage, k.src, k.bytes);
     HIP_TRY(hipMemcpyAsync(const_cast<void *>(k.dst), stage, k.bytes, hipMemcpyHostToDevice, c->stream));
-    c->editStageUsed += (k.bytes + 63) & ~(size_t) 63;
+    stage += (k.bytes + 63) & ~(size_t) 63;
     c->statBytesCopied += k.bytes;
   }
   HIP_TRY(c->lastEdit.Record(c->stream));
   return QA_OK;
 }
 
-enum EditKind { kEditCamera, kEditLights, kEditMaterials, kEditInstances };
+// What every edit ends with.  The photon maps do not depend on the camera; every other edit ends Scene::usePhotonMap as an upload
+// does (the maps' memory goes with the next upload, build, clear or the context: releasing it here would wait for the device)
+int EditEnd(qa_ctx *c, bool keepsPhotonMaps)
+{
+  if (keepsPhotonMaps) SetKernelName(c);   // (the plan cannot change; the name is the plan's again, as after an upload)
+  else {
+    c->photonReady = false;
+    SelectStaged(c);
+    if (int rc = SelectKernel(c)) return rc;
+  }
+  if (c->prog.active) c->prog.stale = true;
+  c->statEdits++;
+  return QA_OK;
+}
+
+enum EditKind { kEditCamera, kEditLights, kEditMaterials, kEditInstances, kEditTexmaps, kEditTextures, kEditBackdrop };
 
 // Writes `bytes` at `off` of the resident blob, rebuilds the scene side and brings the context to the state an upload of the
 // edited blob would leave; a refusal leaves everything as it was
@@ -267,18 +302,9 @@ static int ApplyEdit(qa_ctx *c, EditKind kind, size_t off, const void *src, size
     copies.push_back({c->ds.csInst, t.csInst.data(), t.csInst.size() * sizeof(CsInst)});
     copies.push_back({c->ds.csCull, t.csCull.data(), t.csCull.size() * sizeof(CsCull)});
   }
+  // (texmaps, texture colours, backdrop: the kernels read the records in the device blob, the two colours travel in DScene)
   if ((rc = EnqueueEditCopies(c, copies)) != QA_OK) return rc;
-  if (kind == kEditCamera) SetKernelName(c);   // (the plan cannot change; the name is the plan's again, as after an upload)
-  else {
-    // Scene::usePhotonMap ends as with an upload; the maps' memory goes with the next upload, build, clear or the context
-    // (releasing it here would wait for the device)
-    c->photonReady = false;
-    SelectStaged(c);
-    if ((rc = SelectKernel(c)) != QA_OK) return rc;
-  }
-  if (c->prog.active) c->prog.stale = true;
-  c->statEdits++;
-  return QA_OK;
+  return EditEnd(c, kind == kEditCamera);
 }
 
 // What every edit checks first; *h: the resident blob's header, whose `count` says how many records the edited table has
@@ -342,12 +368,41 @@ int qa_scene_edit_instances(qa_ctx *c, uint32_t first, uint32_t n, const qa_inst
   return ApplyEdit(c, kEditInstances, h->off_instances + (size_t) first * sizeof(qa_instance), instances, (size_t) n * sizeof(qa_instance));
 }
 
+int qa_scene_edit_texmaps(qa_ctx *c, uint32_t first, uint32_t n, const qa_texmap *texmaps)
+{
+  const qa_flat_header *h;
+  int rc = EditArgs(c, texmaps, first, n, &qa_flat_header::num_texmaps, &h);
+  if (rc != QA_OK || n == 0) return rc;
+  // (a texture index out of range: RebuildSceneSide validates the records as an upload does)
+  return ApplyEdit(c, kEditTexmaps, h->off_texmaps + (size_t) first * sizeof(qa_texmap), texmaps, (size_t) n * sizeof(qa_texmap));
+}
+
+int qa_scene_edit_textures(qa_ctx *c, uint32_t first, uint32_t n, const qa_texture *textures)
+{
+  const qa_flat_header *h;
+  int rc = EditArgs(c, textures, first, n, &qa_flat_header::num_textures, &h);
+  if (rc != QA_OK || n == 0) return rc;
+  // (a record of another type, size or texel offset: RebuildSceneSide refuses it)
+  return ApplyEdit(c, kEditTextures, h->off_textures + (size_t) first * sizeof(qa_texture), textures, (size_t) n * sizeof(qa_texture));
+}
+
+int qa_scene_edit_backdrop(qa_ctx *c, const qa_texcolor *background, const qa_texcolor *environment)
+{
+  const qa_flat_header *h;
+  int rc = EditArgs(c, c, 0, 0, nullptr, &h);
+  if (rc != QA_OK || (!background && !environment)) return rc;
+  static_assert(offsetof(qa_flat_header, environment) == offsetof(qa_flat_header, background) + sizeof(qa_texcolor), "the header's two backdrop colours are adjacent");
+  const qa_texcolor both[2] = {background ? *background : h->background, environment ? *environment : h->environment};
+  return ApplyEdit(c, kEditBackdrop, offsetof(qa_flat_header, background), both, sizeof(both));
+}
+
 int qa_scene_download(qa_ctx *c, void *out, uint64_t capacity, uint64_t *nbytes)
 {
   if (!c) return Fail(QA_EINVAL, "null context");
   if (!c->haveScene) return Fail(QA_ENOSCENE, "no scene uploaded");
   if (nbytes) *nbytes = c->hostBlob.size();
   if (!out || capacity < c->hostBlob.size()) return Fail(QA_EINVAL, "output smaller than the scene blob");
+  if (int rc = FetchDeviceTexels(c)) return rc;   // (textures edited from device memory: qa_texture_edit.hip)
   memcpy(out, c->hostBlob.data(), c->hostBlob.size());
   return QA_OK;
 }

@@ -159,6 +159,9 @@ struct qa_ctx {
   unsigned char *hEditStage = nullptr;
   size_t editStageBytes = 0, editStageUsed = 0;
   StreamFence lastEdit;             // end of the last edit's copies (on the context's stream)
+  StreamFence texSource;            // qa_scene_edit_texels_device: the caller's stream when its source was handed over
+  std::vector<uint32_t> texOnDevice;   // file textures whose texels were edited from device memory: the host blob's bytes of
+                                    // these are behind the device blob's until FetchDeviceTexels (qa_scene_download)
   uint64_t statMeshBuilds = 0, statSceneAllocs = 0, statBytesCopied = 0, statEdits = 0;   // qa_get_scene_stats
   float *dHalton = nullptr;
   int haltonCount = 0;
@@ -244,6 +247,13 @@ int CheckFrame(qa_ctx *c, const FrameArgs &a);
 int LaunchSetup(qa_ctx *c, Launch &L, const FrameArgs &a, int ownRows, unsigned int *work, bool resume);
 int LaunchFrame(qa_ctx *c, Launch &L, bool staged, hipStream_t s);
 int DrainEvents(qa_ctx *c);
+// qa_capi.hip, for the edits that live elsewhere (qa_texture_edit.hip): bytes of the pinned edit ring; the waits an edit's device
+// work begins with (and statBytesCopied = 0); what every edit ends with
+int EditStageReserve(qa_ctx *c, size_t need, unsigned char **at);
+int EditBegin(qa_ctx *c);
+int EditEnd(qa_ctx *c, bool keepsPhotonMaps);
+// qa_texture_edit.hip: brings the host blob's texels up to the device blob's (synchronises when there is something to fetch)
+int FetchDeviceTexels(qa_ctx *c);
 // qa_wf.hip
 void FreeStaged(qa_ctx *c);
 void SelectStaged(qa_ctx *c);
@@ -295,6 +305,7 @@ inline void FreeScene(qa_ctx *c)
   c->dBlob = nullptr;
   c->dAreaSlab = c->dSurfSlab = nullptr;   // (they were among sceneAllocs)
   c->tables = SceneTables{};
+  c->texOnDevice.clear();
   c->haveScene = false;
 }
 

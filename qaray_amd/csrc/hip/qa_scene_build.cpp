@@ -8,6 +8,7 @@
 
 #include "qa_device_math.h"
 #include "qa_fastbvh.h"
+#include "qa_texel_dev.h"
 #include "qaray_host.h"
 
 namespace qa {
@@ -554,12 +555,7 @@ void BuildTextures(const Blob &b, SceneTables &out)
     const unsigned char *px = b.p + tx.off_texels;
     const size_t at = tex4.size();
     tex4.resize(at + 4 * n);
-    for (size_t t = 0; t < n; ++t) {
-      tex4[at + 4 * t + 0] = px[3 * t + 0] / 255.0f;
-      tex4[at + 4 * t + 1] = px[3 * t + 1] / 255.0f;
-      tex4[at + 4 * t + 2] = px[3 * t + 2] / 255.0f;
-      tex4[at + 4 * t + 3] = 0.f;
-    }
+    texelsTabulateHost(px, n, 1, 3 * n, tex4.data() + at);   // (qa_texel_dev.h: a texel edit recomputes entries from the same source)
   }
   if (tex4.size() / 4 > 0xFFFFFFFFull) Refuse(QA_EUNSUPPORTED, "more than 2^32 texels");
   if (tex4.empty()) tex4.assign(4, 0.f);
@@ -662,6 +658,15 @@ void PlanLightsAndRoot(const Blob &b, SceneTables &out)
   out.ds.rootIdentity = (memcmp(inst[0].tm, I9, 36) == 0 && memcmp(inst[0].itm, I9, 36) == 0 && memcmp(inst[0].pos, Z3, 12) == 0) ? 1 : 0;
 }
 
+// what a scene edit must leave alone of the texture records: the float texel table is laid out by them (RebuildSceneSide)
+void KeepTexLayout(const Blob &b, SceneTables &out)
+{
+  const qa_texture *textures = b.at<qa_texture>(b.h->off_textures);
+  out.texLayout.resize(b.h->num_textures);
+  for (uint32_t i = 0; i < b.h->num_textures; ++i)
+    out.texLayout[i] = TexLayout{textures[i].type, textures[i].width, textures[i].height, 0, textures[i].off_texels};
+}
+
 // Without reflective / refractive lobes a path is at most camera ray + one diffuse bounce: starting
 // the samples of a wave together keeps its coherent camera rays apart from the incoherent bounce
 // rays (+21 % on the Cornell box).  Long specular chains would make lanes wait for the longest path.
@@ -698,6 +703,7 @@ int BuildScene(const unsigned char *blob, size_t nbytes, const BuildKnobs &knobs
     plan.meshInstanced.assign(h->num_meshes, false);
     for (uint32_t k = 0; k < h->num_instances; ++k) if (inst[k].obj_type == QA_OBJ_MESH) plan.meshInstanced[inst[k].mesh] = true;
     plan.textured = h->num_texmaps > 0;
+    KeepTexLayout(b, out);
     plan.csFits = true;
     uint32_t stackNeedMax = 1;
     BuildMeshes(b, knobs, out, &stackNeedMax);
@@ -732,6 +738,18 @@ int RebuildSceneSide(const unsigned char *blob, size_t nbytes, const BuildKnobs 
     if (h->num_instances != out.csInst.size() || h->num_materials != out.materials.size() || h->num_meshes != out.plan.meshes.size() ||
         (int) h->num_lights != out.ds.num_lights || (int) h->width != out.ds.cam.width || (int) h->height != out.ds.cam.height)
       Refuse(QA_EINVAL, "not an edit of the blob these tables were built from (counts or image size differ)");
+    // texture side: the texmap records, the textures' colours and the two header colours are read in place (by the kernels, or by
+    // PlanScene below); what lays out the texel table, and which map the backdrop shows, stays
+    if (h->num_textures != out.texLayout.size() || (h->num_texmaps > 0) != out.plan.textured)
+      Refuse(QA_EINVAL, "not an edit of the blob these tables were built from (texture counts differ)");
+    const qa_texture *textures = b.at<qa_texture>(h->off_textures);
+    for (uint32_t i = 0; i < h->num_textures; ++i) {
+      const TexLayout &l = out.texLayout[i];
+      if (textures[i].type != l.type || textures[i].width != l.width || textures[i].height != l.height || textures[i].off_texels != l.off_texels)
+        Refuse(QA_EINVAL, "a texture edit can change color1 and color2 only (type, size and texel offset stay: the texel table is not laid out again): upload the scene instead");
+    }
+    if (h->background.texmap != out.ds.bgTexmap || h->environment.texmap != out.ds.envTexmap)
+      Refuse(QA_EINVAL, "a backdrop edit can change the two colours only (their texture maps stay): upload the scene instead");
     ScenePlan &plan = out.plan;
     PlanLightsAndRoot(b, out);
     plan.csFits = out.csFitsMeshes;

@@ -50,6 +50,9 @@ struct ScenePlan {
 // a mesh hit without texture vertices keeps the uvw of an earlier, farther hit: history only a sequential walk has
 inline bool MissesTexcoords(const ScenePlan &p, const DMesh &m) { return p.textured && m.num_faces > 0 && !m.hasVT; }
 
+// type, size and texel offset of a qa_texture as the texel table was laid out with them
+struct TexLayout { int32_t type, width, height, pad; uint64_t off_texels; };
+
 struct SceneTables {
   ScenePlan plan;
   DScene ds{};                           // camera, background, counts, LDS and culling constants; no device pointer yet
@@ -64,6 +67,7 @@ struct SceneTables {
   std::vector<float> texels;
   std::vector<uint32_t> texOff;
   std::vector<float> taps;
+  std::vector<TexLayout> texLayout;      // per texture, textured or not: what no edit may change
   std::vector<uint4> image;              // the resident image (uploaded when plan.resident)
   // what RebuildSceneSide needs of the mesh-side stages beside the tables above
   bool csFitsMeshes = false;             // plan.csFits as BuildMeshes and BuildCsTrees left it (the node transforms may still veto)
@@ -74,10 +78,14 @@ float HaltonF(int index, int base);   // Halton sequence in the reference's fp32
 // QA_OK, or a QA_E* code with the reason in *err
 int BuildScene(const unsigned char *blob, size_t nbytes, const BuildKnobs &knobs, SceneTables &out, std::string *err);
 // Scene edits (qa_scene_edit_*): `blob` is the blob `tables` was built from with its camera, light, material and instance records
-// rewritten (same counts, same mesh / texture side).  Runs every stage again that reads them - the light plan, BuildMaterials,
+// rewritten (same counts, same mesh side), and of its texture side the texmap records, the textures' colours, the texels and the
+// colours of the header's background / environment.  Runs every stage again that reads them - the light plan, BuildMaterials,
 // BuildCsInstances, PlanScene, and the material table at the end of the resident image - and leaves `tables` as BuildScene(blob)
-// would, without a mesh build: BuildMeshes, BuildCsTrees and BuildTextures keep their results.  QA_OK or a QA_E* code with the
-// reason in *err; a refused blob leaves `tables` as it was.
+// would, without a mesh build: BuildMeshes, BuildCsTrees and BuildTextures keep their results (no table is derived from a texmap
+// or a texture colour; SceneTables::texels, the one table derived from the texels, is the caller's to keep up: on a context it
+// lives on the device only, qa_texture_edit.hip).  A texture whose type, size or texel offset differs, or a backdrop that shows
+// another texmap, is refused with QA_EINVAL.  QA_OK or a QA_E* code with the reason in *err; a refused blob leaves `tables` as
+// it was.
 int RebuildSceneSide(const unsigned char *blob, size_t nbytes, const BuildKnobs &knobs, SceneTables &tables, std::string *err);
 // Drops the vectors RebuildSceneSide never reads (a context calls it once the tables are on the device: mesh arrays, scene-wide
 // trees, texels, and the image of a scene that is not LDS-resident)

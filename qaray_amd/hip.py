@@ -51,10 +51,17 @@ MATERIAL_DTYPE = np.dtype([("diffuse", TEXCOLOR_DTYPE), ("specular", TEXCOLOR_DT
 INSTANCE_DTYPE = np.dtype([("tm", np.float32, 9), ("itm", np.float32, 9), ("pos", np.float32, 3), ("obj_type", np.int32),
                            ("mesh", np.int32), ("mtlset", np.int32), ("parent", np.int32), ("subtree_end", np.int32),
                            ("depth", np.int32), ("pad", np.int32)])
+TEXMAP_DTYPE = np.dtype([("itm", np.float32, 9), ("pos", np.float32, 3), ("texture", np.int32), ("pad", np.int32, 3)])
+TEXTURE_DTYPE = np.dtype([("type", np.int32), ("width", np.int32), ("height", np.int32), ("pad0", np.int32), ("color1", np.float32, 3),
+                          ("color2", np.float32, 3), ("off_texels", np.uint64), ("pad1", np.uint64)])
 assert (CAMERA_DTYPE.itemsize, LIGHT_DTYPE.itemsize, MATERIAL_DTYPE.itemsize, INSTANCE_DTYPE.itemsize) == (76, 64, 112, 112)
+assert (TEXCOLOR_DTYPE.itemsize, TEXMAP_DTYPE.itemsize, TEXTURE_DTYPE.itemsize) == (16, 64, 56)
+QA_TEX_CHECKER, QA_TEX_FILE = 0, 1
 # qa_flat_header: byte offsets of the counts and table offsets the views below need
-_HEADER = {"camera": 16, "instances": (136, 168), "materials": (148, 192), "lights": (152, 200)}
-_TABLE_DTYPES = {"instances": INSTANCE_DTYPE, "materials": MATERIAL_DTYPE, "lights": LIGHT_DTYPE}
+_HEADER = {"camera": 16, "backdrop": 104, "instances": (136, 168), "materials": (148, 192), "lights": (152, 200), "texmaps": (156, 208),
+           "textures": (160, 216)}
+_TABLE_DTYPES = {"instances": INSTANCE_DTYPE, "materials": MATERIAL_DTYPE, "lights": LIGHT_DTYPE, "texmaps": TEXMAP_DTYPE,
+                 "textures": TEXTURE_DTYPE}
 
 
 def blob_camera(blob):
@@ -62,8 +69,24 @@ def blob_camera(blob):
     return blob[16:16 + CAMERA_DTYPE.itemsize].view(CAMERA_DTYPE).reshape(())
 
 
+def blob_backdrop(blob):
+    """The header's background and environment of a flat scene blob (numpy uint8) -> two writable 0-d views of TEXCOLOR_DTYPE."""
+    at = _HEADER["backdrop"]
+    both = blob[at:at + 2 * TEXCOLOR_DTYPE.itemsize].view(TEXCOLOR_DTYPE)
+    return both[0:1].reshape(()), both[1:2].reshape(())
+
+
+def blob_texels(blob, i):
+    """The texels of file texture i of a flat scene blob (numpy uint8) as a writable (height, width, 3) uint8 view."""
+    t = blob_table(blob, "textures")[i]
+    assert t["type"] == QA_TEX_FILE, "a checker texture has no texels"
+    w, h, off = int(t["width"]), int(t["height"]), int(t["off_texels"])
+    return blob[off:off + 3 * w * h].reshape(h, w, 3)
+
+
 def blob_table(blob, which):
-    """The 'lights' / 'materials' / 'instances' table of a flat scene blob (numpy uint8) as a writable structured view."""
+    """The 'lights' / 'materials' / 'instances' / 'texmaps' / 'textures' table of a flat scene blob (numpy uint8) as a writable
+    structured view."""
     at_count, at_off = _HEADER[which]
     n = int(blob[at_count:at_count + 4].view(np.uint32)[0])
     off = int(blob[at_off:at_off + 8].view(np.uint64)[0])
@@ -146,6 +169,12 @@ def lib():
         L.qa_scene_edit_camera.argtypes = [C.c_void_p, C.c_void_p]
         for name in ("qa_scene_edit_lights", "qa_scene_edit_materials", "qa_scene_edit_instances"):
             getattr(L, name).argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+        for name in ("qa_scene_edit_texmaps", "qa_scene_edit_textures"):
+            getattr(L, name).argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+        L.qa_scene_edit_backdrop.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.qa_scene_edit_texels.argtypes = [C.c_void_p, C.c_uint32] + [C.c_int] * 4 + [C.c_void_p, C.c_uint64]
+        L.qa_scene_edit_texels_device.argtypes = [C.c_void_p, C.c_uint32] + [C.c_int] * 4 + [C.c_void_p, C.c_uint64, C.c_void_p]
+        L.qa_test_texels_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_void_p]
         L.qa_scene_download.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
         L.qa_get_scene_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
         L.qa_progressive_restart.argtypes = [C.c_void_p]
@@ -175,6 +204,24 @@ def display_host(rgb, depth, ns, spp_max, srgb=True):
     _check(lib().qa_test_display_host(rgb.ctypes.data, depth.ctypes.data, ns.ctypes.data, n, int(spp_max), int(bool(srgb)),
                                       *(a.ctypes.data for a in out), C.addressof(st)))
     return Display(*out, st.as_dict())
+
+
+def texels_host(rgb8):
+    """qa_test_texels_host: the float texel table's entries of an (h, w, 3) uint8 image (rows may be strided) on the CPU, from the
+    source an upload and the texel-edit kernel are compiled from -> float32 (h, w, 4).  No GPU needed."""
+    rgb8 = _rgb8_rows(rgb8)
+    h, w = rgb8.shape[:2]
+    out = np.zeros((h, w, 4), np.float32)
+    _check(lib().qa_test_texels_host(rgb8.ctypes.data, w, h, rgb8.strides[0], out.ctypes.data))
+    return out
+
+
+def _rgb8_rows(a):
+    """An (h, w, 3) uint8 numpy array whose rows are contiguous (a row stride is kept; anything else is copied)."""
+    assert a.dtype == np.uint8 and a.ndim == 3 and a.shape[2] == 3 and a.shape[0] > 0 and a.shape[1] > 0, "rgb8 must be (h, w, 3) uint8"
+    if a.strides[2] != 1 or a.strides[1] != 3 or a.strides[0] < 3 * a.shape[1]:
+        a = np.ascontiguousarray(a)
+    return a
 
 
 def _display_outputs(n, device, want, given):
@@ -258,6 +305,41 @@ class Context:
     def edit_instances(self, first, instances):
         """instances: structured array of INSTANCE_DTYPE; only tm, itm and pos may differ from the resident records."""
         self._edit_table(lib().qa_scene_edit_instances, first, instances, INSTANCE_DTYPE)
+
+    def edit_texmaps(self, first, texmaps):
+        """texmaps: structured array of TEXMAP_DTYPE replacing texmaps [first, first + len): itm, pos and the texture a map shows
+        (-1 .. number of textures - 1) may change."""
+        self._edit_table(lib().qa_scene_edit_texmaps, first, texmaps, TEXMAP_DTYPE)
+
+    def edit_textures(self, first, textures):
+        """textures: structured array of TEXTURE_DTYPE; only color1 and color2 may differ from the resident records."""
+        self._edit_table(lib().qa_scene_edit_textures, first, textures, TEXTURE_DTYPE)
+
+    def edit_backdrop(self, background=None, environment=None):
+        """background / environment: records of TEXCOLOR_DTYPE (blob_backdrop(blob)) or None (stays); the colours may change."""
+        recs = [None if r is None else np.ascontiguousarray(r, dtype=TEXCOLOR_DTYPE).reshape(1) for r in (background, environment)]
+        _check(lib().qa_scene_edit_backdrop(self._h, *(None if r is None else r.ctypes.data for r in recs)))
+        self._photon_sizes = None
+
+    def edit_texels(self, texture, rgb8, origin=(0, 0), stream=None):
+        """Replace the texels of file texture `texture` from (x, y) = origin on with rgb8: a numpy (h, w, 3) uint8 array (contiguous
+        rows; a row stride is allowed), or a torch uint8 tensor of that shape on the context's device, which is consumed where it
+        is (qa_scene_edit_texels_device; stream: the HIP stream handle it was produced on - None: torch's current stream is
+        waited for first, as for render_region_device).  Only enqueues."""
+        x0, y0 = int(origin[0]), int(origin[1])
+        if isinstance(rgb8, np.ndarray):
+            rgb8 = _rgb8_rows(rgb8)
+            h, w = rgb8.shape[:2]
+            _check(lib().qa_scene_edit_texels(self._h, int(texture), x0, y0, x0 + w, y0 + h, rgb8.ctypes.data, rgb8.strides[0]))
+        else:
+            import torch
+            assert rgb8.is_cuda and rgb8.dtype == torch.uint8 and rgb8.dim() == 3 and rgb8.shape[2] == 3 and rgb8.numel() > 0
+            if rgb8.stride(2) != 1 or rgb8.stride(1) != 3 or rgb8.stride(0) < 3 * rgb8.shape[1]:
+                rgb8 = rgb8.contiguous()
+            h, w = rgb8.shape[:2]
+            sptr = self._stream_arg(stream, rgb8)
+            _check(lib().qa_scene_edit_texels_device(self._h, int(texture), x0, y0, x0 + w, y0 + h, rgb8.data_ptr(), rgb8.stride(0), sptr))
+        self._photon_sizes = None
 
     def download_scene(self):
         """-> the resident scene blob as it now stands (numpy uint8), edits included."""
