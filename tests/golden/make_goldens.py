@@ -5,7 +5,11 @@ data (float32 radiance / depth / sample counts + cast counters) and travel with 
 
 Every fixture records: scene file (under scenes/), image size, crop, spp range, max bounce, seed.
 The per-pixel RNG stream is include/qa_seed.h's qa_pixel_seed(seed, j*W+i).
+
+`make_goldens.py scene_fuzz` records tests/golden/scene_fuzz/manifest.json instead: the reference's results (hashes and
+counters only) on every generated scene of tests/scene_fuzz_util.py.
 """
+import hashlib
 import json
 import os
 import subprocess
@@ -73,7 +77,55 @@ PHOTON_DTYPE = np.dtype([("pos", np.float32, 3), ("power", np.float32), ("rgb", 
                          ("dirx", np.int16), ("diry", np.int16)])   # cy::PhotonMap::Photon, 24 bytes
 
 
+def sha(b):
+    return hashlib.sha256(b).hexdigest()
+
+
+def scene_fuzz():
+    """One manifest entry per (family, seed) of tests/scene_fuzz_util.py: hashes of the generated files, the frame, and the
+    reference's radiance / depth / sample-count hashes and counters.  A case the reference crashes on or does not finish in
+    60 s keeps its file hashes and gets "dropped": the reason (the tests skip it; at most one per family)."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import scene_fuzz_util as fz
+    entries = []
+    for family, seed in fz.cases():
+        with tempfile.TemporaryDirectory() as td:
+            xml = fz.write_scene(td, family, seed)
+            p = fz.params(family, seed)
+            names = [os.path.basename(xml)] + fz.asset_names(family)
+            e = dict(family=family, seed=seed, files={n: sha(open(os.path.join(td, n), "rb").read()) for n in names},
+                     render_seed=SEED, **p)
+            out = os.path.join(td, "g")
+            cmd = [HARNESS, os.path.basename(xml), "--size", str(p["width"]), str(p["height"]), "--spp-min", str(p["spp_min"]),
+                   "--spp-max", str(p["spp_max"]), "--bounce", str(p["bounce"]), "--seed", str(SEED), "--threads", "8", "--out", out]
+            try:
+                r = subprocess.run(cmd, cwd=td, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=60)
+                if r.returncode != 0:
+                    e["dropped"] = "the reference exits with status %d" % r.returncode
+            except subprocess.TimeoutExpired:
+                e["dropped"] = "the reference does not finish in 60 s"
+            if "dropped" not in e:
+                meta = json.load(open(out + ".json"))
+                rgb = np.fromfile(out + ".rgb.f32", np.float32).reshape(-1, 3)
+                e.update(rgb_sha256=sha(rgb.tobytes()), depth_sha256=sha(open(out + ".depth.f32", "rb").read()),
+                         ns_sha256=sha(open(out + ".ns.u32", "rb").read()), samples=meta["samples"],
+                         casts_normal=meta["casts_normal"], casts_shadow=meta["casts_shadow"],
+                         nonfinite_rgb_pixels=int((~np.isfinite(rgb).all(axis=1)).sum()))
+        entries.append(e)
+        print(family, seed, e.get("dropped", "samples=%s casts=%s+%s nonfinite=%s"
+                                  % (e.get("samples"), e.get("casts_normal"), e.get("casts_shadow"), e.get("nonfinite_rgb_pixels"))))
+    os.makedirs(os.path.join(HERE, "scene_fuzz"), exist_ok=True)
+    with open(os.path.join(HERE, "scene_fuzz", "manifest.json"), "w") as f:
+        json.dump(dict(producer="oracle/_ref/ref_harness (reference code) on the scenes of tests/scene_fuzz_util.py",
+                       cases=entries), f, indent=1)
+        f.write("\n")
+
+
 def main():
+    if sys.argv[1:2] == ["scene_fuzz"]:
+        if not os.path.exists(HARNESS):
+            sys.exit(f"{HARNESS} missing: run `make -C oracle ref` in the dev container")
+        return scene_fuzz()
     subprocess.run([sys.executable, os.path.join(SCENES, "gen_assets.py")], check=True, stdout=subprocess.DEVNULL)
     if not os.path.exists(HARNESS):
         sys.exit(f"{HARNESS} missing: run `make -C oracle ref` in the dev container")

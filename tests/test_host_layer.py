@@ -66,11 +66,13 @@ def flatten_ref_nodes(node, out, parent=-1, depth=0):
 @pytest.mark.parametrize("name", ["example_project12_box", "custom_textures", "custom_softshadow", "trc_scene_xmas"])
 def test_flattened_scene_equals_reference_loader(name):
     ref = json.load(open(os.path.join(GOLDEN, f"scene_dump_{name}.json")))
-    if name == "trc_scene_xmas":
-        # its OBJ assets are not shipped with the reference: nodes/lights/camera are still comparable
-        pass
+    # trc_scene_xmas: its OBJ assets are not shipped with the reference: nodes/lights/camera are still comparable
     blob = load_scene_blob(name + ".xml")
-    s = parse_blob(blob)
+    assert_blob_equals_dump(parse_blob(blob), ref, all_meshes=(name != "trc_scene_xmas"))
+
+
+def assert_blob_equals_dump(s, ref, all_meshes=True):
+    """s: parse_blob() of a flattened scene; ref: what ref_harness --dump-scene wrote for the same file.  Bit for bit."""
     assert (s["width"], s["height"]) == (ref["width"], ref["height"])
     assert np.array_equal(s["cam"][:15].view(np.uint32), np.array(ref["camera_frame"][:15], np.uint32))
     nodes = []
@@ -92,7 +94,7 @@ def test_flattened_scene_equals_reference_loader(name):
             assert mine["mesh"] == n["mesh"]
         assert (mine["mtlset"] >= 0) == (n["material"] != "")
     assert s["counts"]["lights"] == ref["num_lights"]
-    if name != "trc_scene_xmas":
+    if all_meshes:
         assert len(s["meshes"]) == len(ref["meshes"])
     for mine, r in zip(s["meshes"], ref["meshes"]):
         assert (mine["nf"], mine["nv"], mine["nn"], mine["nt"]) == (r["nf"], r["nv"], r["nvn"], r["nvt"])
