@@ -34,6 +34,8 @@
  *   qa_progressive_display*        FrameBuffer::ComputeZBufferImage / ComputeSampleCountImage, computed where the frame
  *                                  is; what Renderer_GUI shows of renderImage   src/fb/framebuffer.cpp:62-107,
  *                                                                       src/renderers/renderer.cpp:34-39,347-365
+ *   qa_denoise_device,             (no counterpart: the reference shows its previews unfiltered; an edge-avoiding a-trous
+ *   qa_progressive_denoise*        filter for the few-sample previews of an interactive session)
  *   qa_get_counters                (no counterpart: the reference only prints wall-clock)
  *   qa_get_kernel_time             Renderer::StartTimer/StopTimer       src/renderers/renderer.cpp:42-63
  */
@@ -261,6 +263,40 @@ int qa_progressive_display(qa_ctx *ctx, int use_srgb, uint8_t *color, uint8_t *c
 int qa_progressive_display_device(qa_ctx *ctx, int use_srgb, uint8_t *d_color, uint8_t *d_count, uint8_t *d_zimg, uint8_t *d_countimg,
                                   uint8_t *d_mask, qa_display_stats *d_stats, void *hip_stream);
 
+/* A filtered copy of a frame of float results: an edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) guided by the frame's
+ * own colour and by sample 0's hit distance, for the 1 - 8 spp previews between a scene edit and a converged frame.  The header
+ * comment of qaray_amd/csrc/hip/qa_denoise_dev.h is its specification.  Per pixel:
+ *   void   ns == 0, or a colour component or the depth not finite: weighs nothing, comes out as it went in (its bits)
+ *   miss   depth == 1e30: filtered among miss pixels only
+ *   hit    everything else: filtered among hit pixels, the weight falling with the depth difference measured in local slopes
+ * and in every class with the luma difference measured in standard deviations of the 3x3 neighbourhood.  `iterations` passes of a
+ * 5x5 kernel at steps 1, 2, 4, ...; iterations == 0 copies the input's bits.  qa_denoise_params_default: iterations 5,
+ * sigma_color 4, sigma_depth 1, flags 0.  The result is for display only: no rendered frame changes, and the filter never
+ * writes its inputs or the progressive frame's slabs.
+ *   qa_denoise_device               width x height pixels of plain device buffers (row-major, as qa_render_region_device fills them)
+ *                                   -> d_out_rgb, 3 floats per pixel; d_out_rgb == d_rgb is allowed.  Only enqueues on hip_stream
+ *                                   (NULL = the context's stream, as for qa_render_region_device): a guide kernel and one kernel
+ *                                   per iteration.
+ *   qa_progressive_denoise          the progressive frame's preview filtered straight from its slabs: exactly the floats
+ *   qa_progressive_denoise_device   qa_progressive_read returns go in, which are never written out.  The host variant copies back
+ *                                   12 bytes per pixel and synchronises; the device variant only enqueues.  A stale frame (after a
+ *                                   scene edit) is served as qa_progressive_read serves it.  As for qa_progressive_display_device
+ *                                   and _read_device, a call on a stream of the caller's waits for the frame's last pass, but a
+ *                                   later advance / restart / read on another stream does not wait for the filter: the caller
+ *                                   orders it behind that stream (with iterations == 0 the call also writes the frame's preview
+ *                                   buffers for depth and sample count, which qa_progressive_read fills on the context's stream).
+ * QA_EINVAL: a null buffer or params, width or height < 1, iterations outside 0 .. 6, a sigma that is not finite or not positive,
+ * flags other than 0; on a frame that has ended, what the other qa_progressive_* calls return.  The working planes (40 bytes per
+ * pixel of the largest frame filtered so far) are allocated on first use, grow when a larger frame arrives (the call that grows
+ * them waits for the device) and are freed with the context; they are not scene memory and qa_get_scene_stats does not count
+ * them.  The 8-bit picture of a filtered preview is qa_display_device of the result with the frame's depth and sample counts. */
+typedef struct qa_denoise_params { int iterations; float sigma_color, sigma_depth; uint32_t flags; } qa_denoise_params;
+int qa_denoise_params_default(qa_denoise_params *params);
+int qa_denoise_device(qa_ctx *ctx, const float *d_rgb, const float *d_depth, const uint32_t *d_nsamples, int width, int height,
+                      const qa_denoise_params *params, float *d_out_rgb, void *hip_stream);
+int qa_progressive_denoise(qa_ctx *ctx, const qa_denoise_params *params, float *rgb);
+int qa_progressive_denoise_device(qa_ctx *ctx, const qa_denoise_params *params, float *d_rgb, void *hip_stream);
+
 /* Counters accumulated since the last reset (synchronises the context first). */
 int qa_get_counters(qa_ctx *ctx, qa_counters *out);
 int qa_reset_counters(qa_ctx *ctx);
@@ -358,6 +394,11 @@ int qa_test_display_host(const float *rgb, const float *depth, const uint32_t *n
  * upload's texel table compiled for the host: h rows of w RGB8 texels, `stride` bytes apart -> w * h entries {r, g, b, 0} / 255.0f
  * of 4 floats (no GPU and no context needed). */
 int qa_test_texels_host(const uint8_t *rgb8, int w, int h, uint64_t stride, float *out4);
+
+/* Self-test hook for the filter (qaray_amd/csrc/hip/qa_denoise_dev.h): the source of qa_denoise_device's kernels compiled for the
+ * host, pixel after pixel over host arrays (no GPU and no context needed); out_rgb == rgb is allowed. */
+int qa_test_denoise_host(const float *rgb, const float *depth, const uint32_t *nsamples, int width, int height,
+                         const qa_denoise_params *params, float *out_rgb);
 
 #ifdef __cplusplus
 }

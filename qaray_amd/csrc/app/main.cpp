@@ -4,7 +4,11 @@
 // plus what the reference has no flag for: -size W H, -seed S, -device D, -devices N (GPUs 0..N-1 of this node in one
 // process: one host thread and one context per GPU, strips gathered on the first; Renderer::UseDevices), -out PREFIX, -root DIR,
 // -photon-map-radius R, -caustics-map-radius R, -photon-map-bounce N, -caustics-map-bounce N, -progressive N (the frame in passes of
-// N spp up to -spp / -sppMax, the images rewritten after each: the batch counterpart of the reference's progressive display).
+// N spp up to -spp / -sppMax, the images rewritten after each: the batch counterpart of the reference's progressive display),
+// -denoise [N] (a fourth image, <prefix>denoisedBuffer.png: the frame filtered on the device with N iterations - default the
+// library's - and encoded as colorBuffer.png is; with -progressive rewritten after each pass; the other three images do not change.
+// N is optional: an argument made of digits alone right after -denoise is taken as N, so a scene file with such a name goes elsewhere
+// on the line or is written ./123).
 // The reference's `-sppMax` sets sppMin by mistake (main.cpp:27-28); here it sets sppMax.
 // Flow: Init -> LoadScene -> ComputeScene -> Render -> Terminate (main.cpp:55-59).
 #include <cstdio>
@@ -23,7 +27,8 @@ int main(int argc, char **argv)
   RendererParam param;
   const char *file = nullptr;
   std::string out, root;
-  int device = 0, w = -1, h = -1, devices = 0, progressive = 0;
+  int device = 0, w = -1, h = -1, devices = 0, progressive = 0, denoiseIterations = -1;
+  bool denoise = false;
   if (argc < 2) { fprintf(stderr, "Error: insufficient input\n"); return -1; }
   for (int i = 1; i < argc; ++i) {
     const std::string s(argv[i]);
@@ -47,14 +52,22 @@ int main(int argc, char **argv)
     else if (s == "-device") device = atoi(next());
     else if (s == "-devices") devices = atoi(next());
     else if (s == "-progressive") progressive = atoi(next());
+    else if (s == "-denoise") {   // the iteration count is optional: taken when the next argument is a number
+      denoise = true;
+      if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9' && std::string(argv[i + 1]).find_first_not_of("0123456789") == std::string::npos)
+        denoiseIterations = atoi(argv[++i]);
+    }
     else if (s == "-out") out = next();
     else if (s == "-root") root = next();
     else file = argv[i];
   }
   if (!file) { fprintf(stderr, "Error: no scene file\n"); return -1; }
   if (progressive > 0 && devices > 0) { fprintf(stderr, "Error: -progressive renders on one device and cannot be combined with -devices\n"); return -1; }
+  if (denoise && devices > 0) { fprintf(stderr, "Error: -denoise filters on one device and cannot be combined with -devices\n"); return -1; }
   try {
     Renderer renderer(param, device);
+    renderer.denoise = denoise;
+    renderer.denoiseIterations = denoiseIterations;
     if (devices > 0) {
       std::vector<int> ids;
       for (int d = 0; d < devices; ++d) ids.push_back(device + d);

@@ -234,6 +234,9 @@ struct qa_ctx {
   uint32_t *dDisplay = nullptr;
   StreamFence lastDisplay;      // the block is one per context: a display on another stream waits
   DevBuf displayStage;
+  // the denoiser's working planes (qa_denoise.hip): 40 bytes per pixel of the largest frame filtered so far, made on first use
+  DevBuf denoisePlanes;
+  StreamFence lastDenoise;      // the planes are one per context: a filter on another stream waits
 };
 
 void FreePhotonMaps(qa_ctx *c);  // qa_photon.hip

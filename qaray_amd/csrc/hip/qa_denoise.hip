@@ -1,0 +1,266 @@
+// qa_denoise.hip — the edge-avoiding a-trous filter of qa_denoise_dev.h on the device (qa_denoise_device, qa_progressive_denoise*)
+// and the same source on the host (qa_test_denoise_host).  A guide kernel (pass 0) fills the context's working planes - colour and
+// variance (16 bytes per pixel, two of them: the iterations go from one to the other), depth and slope (8 bytes) - from plain
+// buffers or from the progressive frame's slabs; one kernel per iteration follows, the last of which writes the caller's rgb.
+//
+// Per pixel and iteration 16 + 8 bytes are read and 16 written once (12 by the last): 40 bytes of algorithmic traffic; the 24 other
+// taps are re-reads of neighbours' entries.  Steps 1 and 2 stage a 16x16 tile and its halo of 2s (20x20 / 24x24 entries, 9.4 / 13.5 KB)
+// in LDS, where the tile's taps overlap almost wholly; from step 4 on a lane's taps are 4+ pixels apart, the halo would be 32x32
+// entries and more for 256 pixels, and the taps are loaded directly (16 + 8 bytes each; neighbouring lanes share the lines).
+// tools/gpu_denoise_cost.py puts the traffic beside the measured times.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+#include <vector>
+
+#include "qa_ctx.h"
+#include "qa_denoise_dev.h"
+
+namespace qa {
+
+static_assert(sizeof(DenoiseColor) == 16 && sizeof(DenoiseGuide) == 8, "the planes are read with 16- and 8-byte loads");
+#define QA_DENOISE_TILE 16
+
+// state = null: the plain buffers.  Else the progressive frame's slabs, resolved as qa_prog_resolve does (qa_progressive.hip): the
+// running mean and samples so far of an unfinished pixel, the outputs of a finished one
+struct DenoiseSrc {
+  const float *rgb, *depth;
+  const uint32_t *ns, *state;
+  int W;
+  __device__ __forceinline__ DenoisePixel operator()(int x, int y) const
+  {
+    const size_t q = (size_t) y * (size_t) W + (size_t) x;
+    DenoisePixel p;
+    p.z = depth[q];
+    if (state) {
+      const uint4 a = reinterpret_cast<const uint4 *>(state)[2 * q];
+      if (!(a.y & 0x80000000u)) {
+        p.r = __uint_as_float(a.z); p.g = __uint_as_float(a.w); p.b = __uint_as_float(state[8 * q + 4]);
+        p.ns = a.y;
+        return p;
+      }
+    }
+    p.r = rgb[3 * q]; p.g = rgb[3 * q + 1]; p.b = rgb[3 * q + 2];
+    p.ns = ns[q];
+    return p;
+  }
+};
+
+__global__ __launch_bounds__(256) void qa_denoise_guide(DenoiseSrc src, int W, int H, DenoiseColor *color, DenoiseGuide *guide)
+{
+  const int x = (int) (blockIdx.x * QA_DENOISE_TILE + (threadIdx.x & 15u)), y = (int) (blockIdx.y * QA_DENOISE_TILE + (threadIdx.x >> 4));
+  if (x >= W || y >= H) return;
+  DenoiseColor c;
+  DenoiseGuide g;
+  denoiseGuide(src, x, y, W, H, c, g);
+  const size_t q = (size_t) y * (size_t) W + (size_t) x;
+  color[q] = c;
+  guide[q] = g;
+}
+
+// the planes in global memory / a window of them in LDS whose entry (0, 0) is pixel (ox, oy)
+struct DenoiseTapGlobal {
+  const DenoiseColor *color;
+  const DenoiseGuide *guide;
+  int W;
+  __device__ __forceinline__ void operator()(int x, int y, DenoiseColor &c, DenoiseGuide &g) const
+  {
+    const size_t q = (size_t) y * (size_t) W + (size_t) x;
+    c = color[q];
+    g = guide[q];
+  }
+};
+struct DenoiseTapLds {
+  const DenoiseColor *color;
+  const DenoiseGuide *guide;
+  int ox, oy, pitch;
+  __device__ __forceinline__ void operator()(int x, int y, DenoiseColor &c, DenoiseGuide &g) const
+  {
+    const int i = (y - oy) * pitch + (x - ox);
+    c = color[i];
+    g = guide[i];
+  }
+};
+
+__device__ __forceinline__ void denoiseStore(const DenoiseColor &o, size_t q, DenoiseColor *outColor, float *outRgb)
+{
+  if (outRgb) { outRgb[3 * q] = o.r; outRgb[3 * q + 1] = o.g; outRgb[3 * q + 2] = o.b; }
+  else outColor[q] = o;
+}
+
+// One iteration at step S = 1 or 2 over a 16x16 tile staged with its halo of 2 S.  Entries outside the image are not loaded and
+// never read (denoiseIterate skips those taps).  outRgb != null: the last iteration, which writes the caller's frame
+template <int S>
+__global__ __launch_bounds__(256) void qa_denoise_iterate_lds(const DenoiseColor *color, const DenoiseGuide *guide, int W, int H, float sigmaColor,
+                                                              float sigmaDepth, DenoiseColor *outColor, float *outRgb)
+{
+  constexpr int SIDE = QA_DENOISE_TILE + 4 * S;
+  __shared__ DenoiseColor tc[SIDE * SIDE];
+  __shared__ DenoiseGuide tg[SIDE * SIDE];
+  const int ox = (int) (blockIdx.x * QA_DENOISE_TILE) - 2 * S, oy = (int) (blockIdx.y * QA_DENOISE_TILE) - 2 * S;
+  for (int i = (int) threadIdx.x; i < SIDE * SIDE; i += 256) {
+    const int gx = ox + i % SIDE, gy = oy + i / SIDE;
+    if (gx >= 0 && gy >= 0 && gx < W && gy < H) {
+      const size_t q = (size_t) gy * (size_t) W + (size_t) gx;
+      tc[i] = color[q];
+      tg[i] = guide[q];
+    }
+  }
+  __syncthreads();
+  const int x = ox + 2 * S + (int) (threadIdx.x & 15u), y = oy + 2 * S + (int) (threadIdx.x >> 4);
+  if (x >= W || y >= H) return;
+  const DenoiseTapLds tap = {tc, tg, ox, oy, SIDE};
+  denoiseStore(denoiseIterate(tap, x, y, W, H, S, sigmaColor, sigmaDepth), (size_t) y * (size_t) W + (size_t) x, outColor, outRgb);
+}
+
+// One iteration at any step, the taps loaded directly
+__global__ __launch_bounds__(256) void qa_denoise_iterate_direct(const DenoiseColor *color, const DenoiseGuide *guide, int W, int H, int s, float sigmaColor,
+                                                                 float sigmaDepth, DenoiseColor *outColor, float *outRgb)
+{
+  const int x = (int) (blockIdx.x * QA_DENOISE_TILE + (threadIdx.x & 15u)), y = (int) (blockIdx.y * QA_DENOISE_TILE + (threadIdx.x >> 4));
+  if (x >= W || y >= H) return;
+  const DenoiseTapGlobal tap = {color, guide, W};
+  denoiseStore(denoiseIterate(tap, x, y, W, H, s, sigmaColor, sigmaDepth), (size_t) y * (size_t) W + (size_t) x, outColor, outRgb);
+}
+
+}  // namespace qa
+
+static int CheckParams(const qa_denoise_params *p, int width, int height)
+{
+  if (!p) return Fail(QA_EINVAL, "null parameters");
+  if (width < 1 || height < 1) return Fail(QA_EINVAL, "bad frame size");
+  if ((uint64_t) width * (uint64_t) height > 0x7FFFFFFFull) return Fail(QA_EINVAL, "too many pixels");
+  if (p->iterations < 0 || p->iterations > QA_DENOISE_MAX_ITERATIONS) return Fail(QA_EINVAL, "iterations outside 0 .. 6");
+  if (!std::isfinite(p->sigma_color) || !(p->sigma_color > 0.f) || !std::isfinite(p->sigma_depth) || !(p->sigma_depth > 0.f))
+    return Fail(QA_EINVAL, "a sigma that is not finite and positive");
+  if (p->flags != 0u) return Fail(QA_EINVAL, "unknown flags");
+  return QA_OK;
+}
+
+// The guide kernel and the iterations on s.  The working planes (40 bytes per pixel: [colour A | colour B | guide]) are one per
+// context and only grow; a call on another stream than the last one waits for it
+static int Denoise(qa_ctx *c, const DenoiseSrc &src, int W, int H, const qa_denoise_params &p, float *out, hipStream_t s)
+{
+  const size_t n = (size_t) W * (size_t) H;
+  if (p.iterations == 0) {   // the input's bits (a progressive frame still has to be resolved: its callers never get here)
+    if (out != src.rgb) HIP_TRY(hipMemcpyAsync(out, src.rgb, n * 3 * sizeof(float), hipMemcpyDeviceToDevice, s));
+    return QA_OK;
+  }
+  HIP_TRY(c->denoisePlanes.Reserve(n * 40, true));   // (the old planes may be in use on a stream of the caller's)
+  HIP_TRY(c->lastDenoise.WaitOn(s));
+  DenoiseColor *plane[2] = {static_cast<DenoiseColor *>(c->denoisePlanes.p), static_cast<DenoiseColor *>(c->denoisePlanes.p) + n};
+  DenoiseGuide *guide = reinterpret_cast<DenoiseGuide *>(plane[1] + n);
+  const dim3 grid((unsigned) ((W + QA_DENOISE_TILE - 1) / QA_DENOISE_TILE), (unsigned) ((H + QA_DENOISE_TILE - 1) / QA_DENOISE_TILE)), block(256);
+  hipLaunchKernelGGL(qa::qa_denoise_guide, grid, block, 0, s, src, W, H, plane[0], guide);
+  HIP_TRY(hipGetLastError());
+  for (int i = 0; i < p.iterations; ++i) {
+    const DenoiseColor *from = plane[i & 1];
+    DenoiseColor *to = plane[(i + 1) & 1];
+    float *rgb = (i == p.iterations - 1) ? out : nullptr;
+    if (i == 0) hipLaunchKernelGGL(qa::qa_denoise_iterate_lds<1>, grid, block, 0, s, from, guide, W, H, p.sigma_color, p.sigma_depth, to, rgb);
+    else if (i == 1) hipLaunchKernelGGL(qa::qa_denoise_iterate_lds<2>, grid, block, 0, s, from, guide, W, H, p.sigma_color, p.sigma_depth, to, rgb);
+    else hipLaunchKernelGGL(qa::qa_denoise_iterate_direct, grid, block, 0, s, from, guide, W, H, 1 << i, p.sigma_color, p.sigma_depth, to, rgb);
+    HIP_TRY(hipGetLastError());
+  }
+  HIP_TRY(c->lastDenoise.Record(s));
+  return QA_OK;
+}
+
+extern "C" {
+
+int qa_denoise_params_default(qa_denoise_params *p)
+{
+  if (!p) return Fail(QA_EINVAL, "null parameters");
+  p->iterations = QA_DENOISE_DEFAULT_ITERATIONS;
+  p->sigma_color = QA_DENOISE_DEFAULT_SIGMA_COLOR;
+  p->sigma_depth = QA_DENOISE_DEFAULT_SIGMA_DEPTH;
+  p->flags = 0u;
+  return QA_OK;
+}
+
+int qa_denoise_device(qa_ctx *c, const float *d_rgb, const float *d_depth, const uint32_t *d_ns, int width, int height, const qa_denoise_params *p,
+                      float *d_out_rgb, void *hip_stream)
+{
+  if (int rc = Enter(c)) return rc;
+  if (!d_rgb || !d_depth || !d_ns || !d_out_rgb) return Fail(QA_EINVAL, "null buffer");
+  if (int rc = CheckParams(p, width, height)) return rc;
+  const DenoiseSrc src = {d_rgb, d_depth, d_ns, nullptr, width};
+  return Denoise(c, src, width, height, *p, d_out_rgb, StreamOf(c, hip_stream));
+}
+
+int qa_progressive_denoise_device(qa_ctx *c, const qa_denoise_params *p, float *d_rgb, void *hip_stream)
+{
+  int rc = ProgActive(c);
+  if (rc != QA_OK) return rc;
+  if (!d_rgb) return Fail(QA_EINVAL, "null buffer");
+  const qa_ctx::Progressive &f = c->prog;
+  const int W = f.args.x1 - f.args.x0, H = f.args.y1 - f.args.y0;
+  if ((rc = CheckParams(p, W, H)) != QA_OK) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t s = StreamOf(c, hip_stream);
+  HIP_TRY(f.done.WaitOn(s));
+  if (p->iterations == 0) {   // the preview itself; depth and sample counts go to the frame's preview buffers
+    qa_ctx::Progressive &g = c->prog;
+    HIP_TRY(g.prevDepth.Reserve(f.npix * sizeof(float)));
+    HIP_TRY(g.prevNs.Reserve(f.npix * sizeof(uint32_t)));
+    return qa_progressive_read_device(c, d_rgb, (float *) g.prevDepth.p, (uint32_t *) g.prevNs.p, hip_stream);
+  }
+  const DenoiseSrc src = {f.args.rgb, f.args.depth, f.args.ns, f.dState, W};
+  return Denoise(c, src, W, H, *p, d_rgb, s);
+}
+
+int qa_progressive_denoise(qa_ctx *c, const qa_denoise_params *p, float *rgb)
+{
+  int rc = ProgActive(c);
+  if (rc != QA_OK) return rc;
+  if (!rgb) return Fail(QA_EINVAL, "null buffer");
+  HIP_TRY(hipSetDevice(c->device));
+  qa_ctx::Progressive &f = c->prog;
+  HIP_TRY(f.prevRgb.Reserve(f.npix * 3 * sizeof(float)));   // (the preview's buffer: the frame's size is fixed, it never grows)
+  if ((rc = qa_progressive_denoise_device(c, p, (float *) f.prevRgb.p, nullptr)) != QA_OK) return rc;
+  HIP_TRY(hipMemcpyAsync(rgb, f.prevRgb.p, f.npix * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return QA_OK;
+}
+
+// the same source on the CPU, pixel after pixel (no GPU, no context)
+int qa_test_denoise_host(const float *rgb, const float *depth, const uint32_t *ns, int width, int height, const qa_denoise_params *p, float *out_rgb)
+{
+  if (!rgb || !depth || !ns || !out_rgb) return Fail(QA_EINVAL, "null buffer");
+  if (int rc = CheckParams(p, width, height)) return rc;
+  const int W = width, H = height;
+  const size_t n = (size_t) W * (size_t) H;
+  if (p->iterations == 0) {
+    if (out_rgb != rgb) memcpy(out_rgb, rgb, n * 3 * sizeof(float));
+    return QA_OK;
+  }
+  std::vector<DenoiseColor> plane[2] = {std::vector<DenoiseColor>(n), std::vector<DenoiseColor>(n)};
+  std::vector<DenoiseGuide> guide(n);
+  const auto src = [=](int x, int y) {
+    const size_t q = (size_t) y * (size_t) W + (size_t) x;
+    DenoisePixel px;
+    px.r = rgb[3 * q]; px.g = rgb[3 * q + 1]; px.b = rgb[3 * q + 2]; px.z = depth[q]; px.ns = ns[q];
+    return px;
+  };
+  for (int y = 0; y < H; ++y)
+    for (int x = 0; x < W; ++x) denoiseGuide(src, x, y, W, H, plane[0][(size_t) y * W + x], guide[(size_t) y * W + x]);
+  for (int i = 0; i < p->iterations; ++i) {
+    const DenoiseColor *from = plane[i & 1].data();
+    const DenoiseGuide *gd = guide.data();
+    const auto tap = [=](int x, int y, DenoiseColor &c, DenoiseGuide &g) {
+      const size_t q = (size_t) y * (size_t) W + (size_t) x;
+      c = from[q];
+      g = gd[q];
+    };
+    std::vector<DenoiseColor> &to = plane[(i + 1) & 1];
+    for (int y = 0; y < H; ++y)
+      for (int x = 0; x < W; ++x) to[(size_t) y * W + x] = denoiseIterate(tap, x, y, W, H, 1 << i, p->sigma_color, p->sigma_depth);
+  }
+  const std::vector<DenoiseColor> &last = plane[p->iterations & 1];
+  for (size_t q = 0; q < n; ++q) { out_rgb[3 * q] = last[q].r; out_rgb[3 * q + 1] = last[q].g; out_rgb[3 * q + 2] = last[q].b; }
+  return QA_OK;
+}
+
+}  // extern "C"

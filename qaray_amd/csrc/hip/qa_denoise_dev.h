@@ -1,0 +1,163 @@
+// qa_denoise_dev.h — an edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) for a frame of float results, guided by the
+// frame's own colour and by sample 0's hit distance.  No reference counterpart: the reference shows its previews unfiltered.
+// Every function here is compiled for the host too: qa_test_denoise_host and the kernels of qa_denoise.hip run the same source
+// (tests/test_gpu_denoise.py: equal bit for bit); tests/denoise_util.py restates THIS COMMENT in float64 numpy.
+//
+// SPECIFICATION.  All arithmetic is fp32 in the order written, without contraction; / and sqrtf are correctly rounded; exp is qexpf.
+//
+// Input: W x H pixels, row-major: rgb[3], depth, ns.   Parameters: iterations 0 .. 6, sigma_color, sigma_depth (finite, > 0), flags 0.
+// Defaults: iterations 5, sigma_color 4, sigma_depth 1  (chosen on the 4-spp box frame of tests/test_denoise_host.py: DESIGN 4g).
+//
+// Classes.   VOID: ns == 0, or a colour component or the depth is not finite.  (The depth is an addition to the rule for the
+//                  colours: no frame of the renderer holds such a depth, and with it every weight below is a number.)
+//            MISS: not void and depth == 1e30.       HIT: everything else.
+// A void pixel weighs 0 as a neighbour and its output is its input's bits.  Two pixels of different classes weigh 0 for each other.
+// iterations == 0: the output is the input's bits.
+//
+// luma(c) = 0.2126f * r + 0.7152f * g + 0.0722f * b, summed left to right (the reference's ColorLuma).
+//
+// Pass 0, per non-void pixel p -> colour c_p, var_p, slope_p:
+//   members = the pixels of the 3x3 window around p that lie in the image, are not void and have p's class (p is one), visited
+//             row-major; n = their number.
+//   mean = (sum of luma over the members) / n;   var_p = n > 1 ? (sum of (luma - mean)^2 over the members) / n : 0
+//             (the biased variance in its two-pass form: never negative, and 0 on a constant window whatever its level)
+//   slope_p (hit pixels; 0 for a miss): per axis, the differences |z_p - z_n| to the two neighbours on that axis that lie in the
+//             image and are hit pixels; the axis gives the SMALLER of the two, the one there is when there is only one, else 0.
+//             slope_p = max(max(axis x, axis y), 1e-3f * |z_p|).
+//             (On a slanted plane both differences of an axis agree and this is the largest over the 4-neighbours.  At a depth step
+//             the largest would be the step itself, which would then weigh e^(-1 / sigma_depth) for the pixels on its edge; the
+//             smaller one is the slope of the surface p lies on.)
+//
+// Iteration i = 0 .. iterations - 1, step s = 1 << i, per non-void pixel p, from the colours and variances of iteration i - 1
+// (pass 0 for i = 0); slope, depth and class stay pass 0's:
+//   l_p = luma(c_p);   den_l = sigma_color * sqrtf(var_p) + 1e-4f;   den_z = sigma_depth * slope_p * (float) s
+//   the 25 taps q = p + s * (dx, dy), dx, dy in -2 .. 2, row-major in (dy, dx); a tap outside the image, a void tap and a tap of
+//   the other class are skipped.  h = (1/16, 1/4, 3/8, 1/4, 1/16); k = max(|dx|, |dy|).
+//     centre tap: w = 9/64
+//     else        e = |l_p - luma(c_q)| / den_l;   hit pixels with z_p != z_q: e = e + |z_p - z_q| / (den_z * (float) k)
+//                 w = (h[dx + 2] * h[dy + 2]) * qexpf(-e)         (one exponential for w_z * w_l)
+//     sw += w;   sc += w * (c_q - c_p) per component;   sv += (w * w) * var_q
+//   c'_p = c_p + sc / sw   (= sum(w c_q) / sum(w), written around the centre: a constant neighbourhood stays constant exactly)
+//   var'_p = sv / (sw * sw)
+// The output is the colour after the last iteration.  sw >= 9/64: no division by zero.
+#pragma once
+#include "qa_device_math.h"
+
+namespace qa {
+
+#define QA_DENOISE_MISS 1.0e30f
+#define QA_DENOISE_MAX_ITERATIONS 6
+#define QA_DENOISE_DEFAULT_ITERATIONS 5
+#define QA_DENOISE_DEFAULT_SIGMA_COLOR 4.0f
+#define QA_DENOISE_DEFAULT_SIGMA_DEPTH 1.0f
+
+struct DenoisePixel {
+  float r, g, b, z;
+  uint32_t ns;
+};
+// what the iterations work on.  Colour plane: r, g, b, variance.  Guide plane: depth and slope; slope < 0 marks a void pixel
+struct DenoiseColor { float r, g, b, var; };
+struct DenoiseGuide { float z, slope; };
+
+__host__ __device__ __forceinline__ bool denoiseFinite(float x) { return (qa_asuint(x) & 0x7f800000u) != 0x7f800000u; }
+__host__ __device__ __forceinline__ bool denoiseVoid(const DenoisePixel &p)
+{
+  return p.ns == 0u || !denoiseFinite(p.r) || !denoiseFinite(p.g) || !denoiseFinite(p.b) || !denoiseFinite(p.z);
+}
+__host__ __device__ __forceinline__ float denoiseLuma(float r, float g, float b) { return 0.2126f * r + 0.7152f * g + 0.0722f * b; }
+
+// Pass 0 of pixel (x, y).  src(x, y) -> DenoisePixel, called for pixels inside the image only
+template <class Src>
+__host__ __device__ __forceinline__ void denoiseGuide(const Src &src, int x, int y, int W, int H, DenoiseColor &c, DenoiseGuide &g)
+{
+  const DenoisePixel p = src(x, y);
+  c.r = p.r; c.g = p.g; c.b = p.b; c.var = 0.f;
+  g.z = 0.f; g.slope = -1.f;
+  if (denoiseVoid(p)) return;
+  const bool miss = p.z == QA_DENOISE_MISS;
+  float l[9];
+  int n = 0;
+  float sum = 0.f;
+  for (int dy = -1; dy <= 1; ++dy)
+    for (int dx = -1; dx <= 1; ++dx) {
+      const int qx = x + dx, qy = y + dy;
+      if (qx < 0 || qy < 0 || qx >= W || qy >= H) continue;
+      const DenoisePixel q = src(qx, qy);
+      if (denoiseVoid(q) || (q.z == QA_DENOISE_MISS) != miss) continue;
+      l[n] = denoiseLuma(q.r, q.g, q.b);
+      sum += l[n];
+      ++n;
+    }
+  if (n > 1) {
+    const float mean = sum / (float) n;
+    float dev = 0.f;
+    for (int k = 0; k < n; ++k) dev += (l[k] - mean) * (l[k] - mean);
+    c.var = dev / (float) n;
+  }
+  g.z = p.z; g.slope = 0.f;
+  if (miss) return;
+  float slope = 0.f;
+  for (int axis = 0; axis < 2; ++axis) {
+    float d = 0.f;
+    bool have = false;
+    for (int side = -1; side <= 1; side += 2) {
+      const int qx = axis ? x : x + side, qy = axis ? y + side : y;
+      if (qx < 0 || qy < 0 || qx >= W || qy >= H) continue;
+      const DenoisePixel q = src(qx, qy);
+      if (denoiseVoid(q) || q.z == QA_DENOISE_MISS) continue;
+      const float dz = qabs(p.z - q.z);
+      d = have ? qmin(d, dz) : dz;
+      have = true;
+    }
+    slope = qmax(slope, d);
+  }
+  g.slope = qmax(slope, 1e-3f * qabs(p.z));
+}
+
+// One iteration of pixel (x, y) at step s.  tap(x, y, c, g) fetches a pixel's planes, called for pixels inside the image only
+template <class Tap>
+__host__ __device__ __forceinline__ DenoiseColor denoiseIterate(const Tap &tap, int x, int y, int W, int H, int s, float sigmaColor, float sigmaDepth)
+{
+  DenoiseColor P;
+  DenoiseGuide GP;
+  tap(x, y, P, GP);
+  if (GP.slope < 0.f) return P;
+  const bool miss = GP.z == QA_DENOISE_MISS;
+  const float lp = denoiseLuma(P.r, P.g, P.b);
+  const float denL = sigmaColor * qsqrt(P.var) + 1e-4f;
+  const float denZ = sigmaDepth * GP.slope * (float) s;
+  const float h[5] = {0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f};
+  float sw = 0.f, sr = 0.f, sg = 0.f, sb = 0.f, sv = 0.f;
+#pragma unroll
+  for (int dy = -2; dy <= 2; ++dy) {
+#pragma unroll
+    for (int dx = -2; dx <= 2; ++dx) {
+      if (dx == 0 && dy == 0) {
+        const float w = 0.140625f;
+        sw += w; sv += (w * w) * P.var;
+        continue;
+      }
+      const int qx = x + s * dx, qy = y + s * dy;
+      if (qx < 0 || qy < 0 || qx >= W || qy >= H) continue;
+      DenoiseColor Q;
+      DenoiseGuide GQ;
+      tap(qx, qy, Q, GQ);
+      if (GQ.slope < 0.f || (GQ.z == QA_DENOISE_MISS) != miss) continue;
+      float e = qabs(lp - denoiseLuma(Q.r, Q.g, Q.b)) / denL;
+      if (!miss && GP.z != GQ.z) {
+        const int ax = dx < 0 ? -dx : dx, ay = dy < 0 ? -dy : dy;
+        e = e + qabs(GP.z - GQ.z) / (denZ * (float) (ax > ay ? ax : ay));
+      }
+      const float w = (h[dx + 2] * h[dy + 2]) * qexpf(-e);
+      sw += w;
+      sr += w * (Q.r - P.r); sg += w * (Q.g - P.g); sb += w * (Q.b - P.b);
+      sv += (w * w) * Q.var;
+    }
+  }
+  DenoiseColor o;
+  o.r = P.r + sr / sw; o.g = P.g + sg / sw; o.b = P.b + sb / sw;
+  o.var = sv / (sw * sw);
+  return o;
+}
+
+}  // namespace qa

@@ -10,6 +10,8 @@
 
 #include <hip/hip_runtime_api.h>
 
+#include "image.h"
+
 namespace qaray_hip {
 
 static std::chrono::time_point<std::chrono::system_clock> g_start;
@@ -179,7 +181,23 @@ void Renderer::ThreadRender()
   if (tasking::has_stop_signal()) qa_request_stop(ctx);
   else qa_clear_stop(ctx);
   qa_reset_counters(ctx);
-  if (mpiSize == 1) {
+  if (denoise) {
+    // the frame stays on the device for the filter (Render: SaveDenoised, after the timer has stopped); the FrameBuffer gets the
+    // same floats qa_render_region would have copied back
+    if (!multi.empty() || mpiSize != 1) throw std::runtime_error("-denoise filters on one device and cannot be combined with -devices");
+    const size_t n = (size_t) W * H;
+    denoiseFrame.Alloc(n);
+    if (qa_render_region_device(ctx, 0, 0, W, H, (int) param.sppMin, (int) param.sppMax, Material::maxBounce, param.seed, 0, denoiseFrame.rgb,
+                                denoiseFrame.depth, denoiseFrame.ns, nullptr) != QA_OK)
+      throw std::runtime_error(std::string("qa_render_region_device: ") + qa_last_error());
+    qa_synchronize(ctx);
+    std::vector<float> rgb(3 * n), depth(n);
+    std::vector<uint32_t> ns(n);
+    HIP_OR_THROW(hipMemcpy(rgb.data(), denoiseFrame.rgb, n * 12, hipMemcpyDeviceToHost));
+    HIP_OR_THROW(hipMemcpy(depth.data(), denoiseFrame.depth, n * 4, hipMemcpyDeviceToHost));
+    HIP_OR_THROW(hipMemcpy(ns.data(), denoiseFrame.ns, n * 4, hipMemcpyDeviceToHost));
+    image->Deposit(0, 0, W, H, rgb.data(), depth.data(), ns.data(), (int) param.sppMax, param.useSRGB);
+  } else if (mpiSize == 1) {
     std::vector<float> rgb((size_t) 3 * W * H), depth((size_t) W * H);
     std::vector<uint32_t> ns((size_t) W * H);
     if (qa_render_region(ctx, 0, 0, W, H, (int) param.sppMin, (int) param.sppMax, Material::maxBounce, param.seed, 0,
@@ -224,6 +242,10 @@ void Renderer::Render()
 {
   ThreadRender();
   SaveImages();
+  if (denoise) {   // outside the timed span: the printed time and rate are the render's, with or without the flag
+    SaveDenoised(denoiseFrame.rgb, denoiseFrame.depth, denoiseFrame.ns);
+    denoiseFrame.Free();
+  }
 }
 
 // The batch counterpart of Renderer_GUI's progressive display (src/renderers/Renderer_GUI.cpp:37-97, which shows renderImage while
@@ -245,6 +267,7 @@ void Renderer::RenderProgressive(size_t passSpp)
     throw std::runtime_error(std::string("qa_progressive_begin: ") + qa_last_error());
   const size_t n = (size_t) W * H;
   std::vector<uint8_t> color(3 * n), count(n), zimg(n), countimg(n), mask(n);
+  if (denoise) denoiseFrame.Alloc(n);   // -denoise: the preview of each pass, filtered in place
   for (size_t spp = 0; spp < param.sppMax;) {
     spp = std::min(spp + passSpp, param.sppMax);
     const bool last = spp >= param.sppMax;
@@ -266,7 +289,13 @@ void Renderer::RenderProgressive(size_t passSpp)
     image->SaveImage((outputPrefix + "colorBuffer.png").c_str());
     image->SaveZImage((outputPrefix + "depthBuffer.png").c_str());
     image->SaveSampleCountImage((outputPrefix + "sampleBuffer.png").c_str());
+    if (denoise) {
+      if (qa_progressive_read_device(ctx, denoiseFrame.rgb, denoiseFrame.depth, denoiseFrame.ns, nullptr) != QA_OK)
+        throw std::runtime_error(std::string("qa_progressive_read_device: ") + qa_last_error());
+      SaveDenoised(denoiseFrame.rgb, denoiseFrame.depth, denoiseFrame.ns);
+    }
   }
+  denoiseFrame.Free();
   qa_progressive_end(ctx);
   qa_get_counters(ctx, &counters);
   StopTimer();
@@ -279,6 +308,43 @@ void Renderer::SaveImages()
   image->SaveImage((outputPrefix + "colorBuffer.png").c_str());
   image->SaveZImage((outputPrefix + "depthBuffer.png").c_str());
   image->SaveSampleCountImage((outputPrefix + "sampleBuffer.png").c_str());
+}
+
+void Renderer::DeviceFrame::Alloc(size_t n)
+{
+  Free();
+  HIP_OR_THROW(hipMalloc((void **) &rgb, n * 12));
+  HIP_OR_THROW(hipMalloc((void **) &depth, n * 4));
+  HIP_OR_THROW(hipMalloc((void **) &ns, n * 4));
+}
+void Renderer::DeviceFrame::Free()
+{
+  (void) hipFree(rgb); (void) hipFree(depth); (void) hipFree(ns);
+  rgb = depth = nullptr;
+  ns = nullptr;
+}
+
+// The frame in device buffers -> its filtered colour bytes (encoded as colorBuffer.png's are: qa_display_device honours -srgb) ->
+// <prefix>denoisedBuffer.png.  Everything runs on the context's stream, behind the frame
+void Renderer::SaveDenoised(float *dRgb, const float *dDepth, const uint32_t *dNs)
+{
+  if (!multi.empty() || mpiSize != 1) throw std::runtime_error("-denoise filters on one device and cannot be combined with -devices");
+  const size_t n = pixelW * pixelH;
+  qa_denoise_params dp;
+  qa_denoise_params_default(&dp);
+  if (denoiseIterations >= 0) dp.iterations = denoiseIterations;
+  struct Bytes {   // (freed on every way out)
+    uint8_t *p = nullptr;
+    ~Bytes() { if (p) (void) hipFree(p); }
+  } dColor;
+  HIP_OR_THROW(hipMalloc((void **) &dColor.p, 3 * n));
+  if (qa_denoise_device(ctx, dRgb, dDepth, dNs, (int) pixelW, (int) pixelH, &dp, dRgb, nullptr) != QA_OK ||
+      qa_display_device(ctx, dRgb, dDepth, dNs, n, (int) param.sppMax, param.useSRGB ? 1 : 0, dColor.p, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) != QA_OK)
+    throw std::runtime_error(std::string("-denoise: ") + qa_last_error());
+  qa_synchronize(ctx);
+  std::vector<uint8_t> color(3 * n);
+  HIP_OR_THROW(hipMemcpy(color.data(), dColor.p, 3 * n, hipMemcpyDeviceToHost));
+  SavePNG((outputPrefix + "denoisedBuffer.png").c_str(), color.data(), (int) pixelW, (int) pixelH, 3);
 }
 
 void Renderer::Terminate()

@@ -65,6 +65,10 @@ class Renderer {
   double LastSeconds() const { return lastSeconds; }
   const qa_counters &Counters() const { return counters; }
   std::string outputPrefix;                             // like Renderer_MPI's mpiPrefix
+  // -denoise [N]: a fourth image, <prefix>denoisedBuffer.png, the colour bytes of the frame filtered on the device
+  // (qa_denoise_device, then qa_display_device); N iterations, -1 = the library's default.  One device only
+  bool denoise = false;
+  int denoiseIterations = -1;
 
  protected:
   RendererParam &param;
@@ -78,6 +82,14 @@ class Renderer {
   std::vector<qa_ctx *> ctxs;                           // one per entry of `multi`
   void ThreadRenderMulti();
   void SaveImages();                                    // the three PNGs of the FrameBuffer
+  void SaveDenoised(float *dRgb, const float *dDepth, const uint32_t *dNs);   // the fourth; dRgb is filtered in place
+  struct DeviceFrame {                                  // -denoise: the frame's floats on the device, freed with the Renderer at the latest
+    float *rgb = nullptr, *depth = nullptr;
+    uint32_t *ns = nullptr;
+    void Alloc(size_t npix);
+    void Free();
+    ~DeviceFrame() { Free(); }
+  } denoiseFrame;
   double lastSeconds = 0, avgSeconds = 0;
   int numFrames = -1;
   qa_counters counters{};

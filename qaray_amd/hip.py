@@ -101,6 +101,28 @@ class DisplayStats(C.Structure):   # qa_display_stats
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class DenoiseParams(C.Structure):   # qa_denoise_params; DenoiseParams.default() = qa_denoise_params_default
+    _fields_ = [("iterations", C.c_int), ("sigma_color", C.c_float), ("sigma_depth", C.c_float), ("flags", C.c_uint32)]
+
+    @classmethod
+    def default(cls):
+        p = cls()
+        _check(lib().qa_denoise_params_default(C.byref(p)))
+        return p
+
+    @classmethod
+    def of(cls, params=None, iterations=None, sigma_color=None, sigma_depth=None):
+        """params (a DenoiseParams) or the library's defaults, with the keyword arguments that are given written over them."""
+        p = cls.default() if params is None else cls(params.iterations, params.sigma_color, params.sigma_depth, params.flags)
+        if iterations is not None:
+            p.iterations = int(iterations)
+        if sigma_color is not None:
+            p.sigma_color = float(sigma_color)
+        if sigma_depth is not None:
+            p.sigma_depth = float(sigma_depth)
+        return p
+
+
 # Progressive.display(): numpy arrays shaped like the region (color [h,w,3], the others [h,w], uint8) and the statistics as a dict
 Display = collections.namedtuple("Display", "color count zimg countimg mask stats")
 DISPLAY_STATS_DTYPE = np.dtype([("zmin", np.float32), ("zmax", np.float32), ("smin", np.uint32), ("smax", np.uint32)])
@@ -166,6 +188,12 @@ def lib():
         L.qa_progressive_display.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.POINTER(DisplayStats)]
         L.qa_progressive_display_device.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 7
         L.qa_test_display_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int] + [C.c_void_p] * 6
+        L.qa_denoise_params_default.argtypes = [C.POINTER(DenoiseParams)]
+        L.qa_denoise_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(DenoiseParams), C.c_void_p,
+                                        C.c_void_p]
+        L.qa_progressive_denoise.argtypes = [C.c_void_p, C.POINTER(DenoiseParams), C.c_void_p]
+        L.qa_progressive_denoise_device.argtypes = [C.c_void_p, C.POINTER(DenoiseParams), C.c_void_p, C.c_void_p]
+        L.qa_test_denoise_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(DenoiseParams), C.c_void_p]
         L.qa_scene_edit_camera.argtypes = [C.c_void_p, C.c_void_p]
         for name in ("qa_scene_edit_lights", "qa_scene_edit_materials", "qa_scene_edit_instances"):
             getattr(L, name).argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
@@ -204,6 +232,20 @@ def display_host(rgb, depth, ns, spp_max, srgb=True):
     _check(lib().qa_test_display_host(rgb.ctypes.data, depth.ctypes.data, ns.ctypes.data, n, int(spp_max), int(bool(srgb)),
                                       *(a.ctypes.data for a in out), C.addressof(st)))
     return Display(*out, st.as_dict())
+
+
+def denoise_host(rgb, depth, ns, params=None, iterations=None, sigma_color=None, sigma_depth=None):
+    """qa_test_denoise_host: the edge-avoiding filter of Context.denoise_device on the CPU, from the source the device kernels are
+    compiled from: rgb (h, w, 3), depth (h, w), ns (h, w) -> float32 (h, w, 3).  The inputs are not modified.  No GPU needed."""
+    rgb = np.ascontiguousarray(rgb, dtype=np.float32)
+    depth = np.ascontiguousarray(depth, dtype=np.float32)
+    ns = np.ascontiguousarray(ns, dtype=np.uint32)
+    assert rgb.ndim == 3 and rgb.shape[2] == 3 and depth.shape == rgb.shape[:2] and ns.shape == rgb.shape[:2]
+    h, w = depth.shape
+    out = np.zeros((h, w, 3), np.float32)
+    p = DenoiseParams.of(params, iterations, sigma_color, sigma_depth)
+    _check(lib().qa_test_denoise_host(rgb.ctypes.data, depth.ctypes.data, ns.ctypes.data, w, h, C.byref(p), out.ctypes.data))
+    return out
 
 
 def texels_host(rgb8):
@@ -440,6 +482,26 @@ class Context:
                                        *ptrs, sptr))
         return out
 
+    def denoise_device(self, rgb, depth, ns, out=None, params=None, iterations=None, sigma_color=None, sigma_depth=None, stream=None):
+        """qa_denoise_device: a filtered copy of a frame of float results in torch CUDA tensors (float32 [h,w,3], float32 [h,w],
+        int32/uint32 [h,w]) for display: an edge-avoiding a-trous filter guided by colour and depth (include/qaray_hip.h).  out:
+        the float32 [h,w,3] tensor to write (may be rgb itself; None: a new one).  params: a DenoiseParams; the keyword arguments
+        override its fields (defaults: the library's).  -> out.  Only enqueues (see render_region_device for the stream).  The
+        8-bit picture: display_device(out, depth, ns, spp_max)."""
+        import torch
+        assert rgb.is_cuda and rgb.is_contiguous() and rgb.dim() == 3 and rgb.shape[2] == 3 and rgb.dtype == torch.float32
+        h, w = rgb.shape[:2]
+        n = h * w
+        assert depth.is_cuda and depth.is_contiguous() and depth.numel() == n and depth.element_size() == 4
+        assert ns.is_cuda and ns.is_contiguous() and ns.numel() == n and ns.element_size() == 4
+        if out is None:
+            out = torch.empty_like(rgb)
+        assert out.is_cuda and out.is_contiguous() and out.shape == rgb.shape and out.dtype == torch.float32
+        p = DenoiseParams.of(params, iterations, sigma_color, sigma_depth)
+        sptr = self._stream_arg(stream, rgb)
+        _check(lib().qa_denoise_device(self._h, rgb.data_ptr(), depth.data_ptr(), ns.data_ptr(), w, h, C.byref(p), out.data_ptr(), sptr))
+        return out
+
     def render_strips_device(self, region, first_strip, strip_step, spp, rgb, depth, ns, max_bounce=5,
                              seed=DEFAULT_SEED, spp_max=None, stats=False, stream=None):
         """Render strips first_strip, first_strip+strip_step, ... (8 rows each) of `region` into PACKED
@@ -597,6 +659,29 @@ class Progressive:
             torch.cuda.current_stream(device).synchronize()
             sptr = None
         _check(lib().qa_progressive_display_device(self._ctx._h, int(bool(srgb)), *ptrs, sptr))
+        return out
+
+    def denoise(self, params=None, iterations=None, sigma_color=None, sigma_depth=None):
+        """qa_progressive_denoise: the preview read() returns, filtered on the device straight from the frame's slabs (see
+        Context.denoise_device) -> rgb[h,w,3] f32; synchronises.  The frame is not changed."""
+        x0, y0, x1, y1 = self.region
+        rgb = np.zeros((y1 - y0, x1 - x0, 3), np.float32)
+        p = DenoiseParams.of(params, iterations, sigma_color, sigma_depth)
+        _check(lib().qa_progressive_denoise(self._ctx._h, C.byref(p), rgb.ctypes.data))
+        return rgb
+
+    def denoise_device(self, out=None, params=None, iterations=None, sigma_color=None, sigma_depth=None, stream=None):
+        """qa_progressive_denoise_device: the same into a torch CUDA tensor (float32 [h,w,3]; None: a new one) on the context's
+        device -> out; only enqueues."""
+        import torch
+        device = torch.device("cuda", self._ctx.device_id)
+        x0, y0, x1, y1 = self.region
+        if out is None:
+            out = torch.empty((y1 - y0, x1 - x0, 3), dtype=torch.float32, device=device)
+        assert out.is_cuda and out.is_contiguous() and out.numel() == 3 * (x1 - x0) * (y1 - y0) and out.dtype == torch.float32
+        p = DenoiseParams.of(params, iterations, sigma_color, sigma_depth)
+        sptr = Context._stream_arg(stream, out)
+        _check(lib().qa_progressive_denoise_device(self._ctx._h, C.byref(p), out.data_ptr(), sptr))
         return out
 
     def status(self):
