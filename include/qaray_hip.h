@@ -36,6 +36,10 @@
  *                                                                       src/renderers/renderer.cpp:34-39,347-365
  *   qa_denoise_device,             (no counterpart: the reference shows its previews unfiltered; an edge-avoiding a-trous
  *   qa_progressive_denoise*        filter for the few-sample previews of an interactive session)
+ *   qa_gbuffer_region*,            (no counterpart: what the camera ray of a pixel's first sample sees - depth, normal, diffuse
+ *   qa_progressive_gbuffer_device  colour, node and material - for picking in a viewer and as guides for a preview filter)
+ *   qa_denoise_guided_device,      (no counterpart: the preview filter with those normal and albedo planes as two more
+ *   qa_progressive_denoise_guided* edge-stopping guides)
  *   qa_get_counters                (no counterpart: the reference only prints wall-clock)
  *   qa_get_kernel_time             Renderer::StartTimer/StopTimer       src/renderers/renderer.cpp:42-63
  */
@@ -297,6 +301,55 @@ int qa_denoise_device(qa_ctx *ctx, const float *d_rgb, const float *d_depth, con
 int qa_progressive_denoise(qa_ctx *ctx, const qa_denoise_params *params, float *rgb);
 int qa_progressive_denoise_device(qa_ctx *ctx, const qa_denoise_params *params, float *d_rgb, void *hip_stream);
 
+/* First-hit guide planes ("G-buffer") of pixels [x0,x1) x [y0,y1): per pixel one cast, the camera ray of the pixel's sample 0
+ * exactly as qa_render_region builds it from (seed, pixel) - Halton offset, depth-of-field draws, texture differentials - through
+ * the integrators' own closest-hit and texture code.  Region-local, row-major planes; every pointer may be NULL (not wanted), but
+ * not all of them:
+ *   depth   1 float    the hit distance, 1e30 on a miss: bit for bit the depth plane qa_render_region writes for the same seed
+ *   normal  3 floats   the world-space unit normal of the hit as the integrator shades it (geometric side: not flipped towards
+ *                      the viewer; on a mesh the normal interpolated between the face's vertex normals, which is the face's
+ *                      own where the face is planar and its vertices are not shared with a tilted neighbour); 0, 0, 0 on a miss
+ *   albedo  3 floats   the diffuse colour the integrator shades the hit with (the material's diffuse, through its texture where it
+ *                      has one); 0 for a node without material, 1 for a multi-material mesh whose face names no material; on a
+ *                      miss the background the camera ray returns (textured where the scene's background is)
+ *   ids     2 int32    the hit's node index (qa_instance) and material index (qa_material); material -1: none, -2: the white
+ *                      case above; bit 30 (QA_GBUFFER_BACKFACE) of a material word >= 0 is set when the ray hit a back
+ *                      face (QA_GBUFFER_MATERIAL(word) gives the index again; a negative word stays as it is); -1, -1 on a miss
+ * The kernel only reads the scene: no frame, progressive frame or counter (qa_get_counters) changes.  Codes as qa_render_region_device:
+ * QA_ENOSCENE, QA_EINVAL for an empty region, one outside the image or no plane at all.  Ordered as a frame is: the device variant only
+ * enqueues on hip_stream (NULL = the context's stream), behind the context's last frame and last edit, and a later edit waits for it;
+ * the host variant copies back and synchronises.
+ *   qa_progressive_gbuffer_device   the planes of the progressive frame's region and seed, computed afresh from the scene as it
+ *                                   now stands on each call: after an edit and qa_progressive_restart they show the edited scene */
+#define QA_GBUFFER_BACKFACE 0x40000000
+#define QA_GBUFFER_MATERIAL(word) ((word) < 0 ? (word) : ((word) & ~QA_GBUFFER_BACKFACE))
+int qa_gbuffer_region_device(qa_ctx *ctx, int x0, int y0, int x1, int y1, uint32_t seed, float *d_normal, float *d_albedo,
+                             float *d_depth, int32_t *d_ids, void *hip_stream);
+int qa_gbuffer_region(qa_ctx *ctx, int x0, int y0, int x1, int y1, uint32_t seed, float *normal, float *albedo, float *depth,
+                      int32_t *ids);
+int qa_progressive_gbuffer_device(qa_ctx *ctx, float *d_normal, float *d_albedo, float *d_depth, int32_t *d_ids, void *hip_stream);
+
+/* The filter above, guided by the first-hit planes as well (the GUIDED FORM section of qa_denoise_dev.h is the specification).  A
+ * pixel whose 3x3 neighbourhood agrees on the guides (normals within 11.5 degrees, albedo components within 0.3, one class) also
+ * weighs its taps by the normals' angle (1 - n_p . n_q over sigma_normal) and by the largest albedo difference (over 0.02); a pixel
+ * on an edge of the guides, which sample 0 describes from one side only, is filtered as the unguided filter does it.  Colours are
+ * never divided by the albedo.  flags names the planes given: a plane's pointer is NULL if and only if its bit is clear; with
+ * flags == 0 the result is qa_denoise_device's bit for bit.  qa_denoise_guided_params_default: iterations 5, sigma_color 4,
+ * sigma_depth 1, sigma_normal 0.1, both guides.  The progressive variants compute the frame's planes themselves
+ * (qa_progressive_gbuffer_device, from the scene as it now stands) for the bits set in flags.  Codes, streams, aliasing
+ * (d_out_rgb == d_rgb) and memory as for the unguided calls; the working planes are 72 bytes per pixel, and 96 for a progressive
+ * frame.  QA_EINVAL also for unknown flag bits, a plane that disagrees with its bit and a sigma_normal that is not finite and
+ * positive. */
+#define QA_DENOISE_GUIDE_NORMAL 1u
+#define QA_DENOISE_GUIDE_ALBEDO 2u
+typedef struct qa_denoise_guided_params { int iterations; float sigma_color, sigma_depth, sigma_normal; uint32_t flags; } qa_denoise_guided_params;
+int qa_denoise_guided_params_default(qa_denoise_guided_params *params);
+int qa_denoise_guided_device(qa_ctx *ctx, const float *d_rgb, const float *d_depth, const uint32_t *d_nsamples, const float *d_normal,
+                             const float *d_albedo, int width, int height, const qa_denoise_guided_params *params, float *d_out_rgb,
+                             void *hip_stream);
+int qa_progressive_denoise_guided(qa_ctx *ctx, const qa_denoise_guided_params *params, float *rgb);
+int qa_progressive_denoise_guided_device(qa_ctx *ctx, const qa_denoise_guided_params *params, float *d_rgb, void *hip_stream);
+
 /* Counters accumulated since the last reset (synchronises the context first). */
 int qa_get_counters(qa_ctx *ctx, qa_counters *out);
 int qa_reset_counters(qa_ctx *ctx);
@@ -399,6 +452,8 @@ int qa_test_texels_host(const uint8_t *rgb8, int w, int h, uint64_t stride, floa
  * host, pixel after pixel over host arrays (no GPU and no context needed); out_rgb == rgb is allowed. */
 int qa_test_denoise_host(const float *rgb, const float *depth, const uint32_t *nsamples, int width, int height,
                          const qa_denoise_params *params, float *out_rgb);
+int qa_test_denoise_guided_host(const float *rgb, const float *depth, const uint32_t *nsamples, const float *normal, const float *albedo,
+                                int width, int height, const qa_denoise_guided_params *params, float *out_rgb);
 
 #ifdef __cplusplus
 }

@@ -8,7 +8,8 @@
 // -denoise [N] (a fourth image, <prefix>denoisedBuffer.png: the frame filtered on the device with N iterations - default the
 // library's - and encoded as colorBuffer.png is; with -progressive rewritten after each pass; the other three images do not change.
 // N is optional: an argument made of digits alone right after -denoise is taken as N, so a scene file with such a name goes elsewhere
-// on the line or is written ./123).
+// on the line or is written ./123), -denoise-guided [N] (as -denoise, through the guided filter with the frame's first-hit normal
+// and albedo planes; the same file).
 // The reference's `-sppMax` sets sppMin by mistake (main.cpp:27-28); here it sets sppMax.
 // Flow: Init -> LoadScene -> ComputeScene -> Render -> Terminate (main.cpp:55-59).
 #include <cstdio>
@@ -28,7 +29,7 @@ int main(int argc, char **argv)
   const char *file = nullptr;
   std::string out, root;
   int device = 0, w = -1, h = -1, devices = 0, progressive = 0, denoiseIterations = -1;
-  bool denoise = false;
+  bool denoise = false, denoiseGuided = false;
   if (argc < 2) { fprintf(stderr, "Error: insufficient input\n"); return -1; }
   for (int i = 1; i < argc; ++i) {
     const std::string s(argv[i]);
@@ -52,8 +53,9 @@ int main(int argc, char **argv)
     else if (s == "-device") device = atoi(next());
     else if (s == "-devices") devices = atoi(next());
     else if (s == "-progressive") progressive = atoi(next());
-    else if (s == "-denoise") {   // the iteration count is optional: taken when the next argument is a number
+    else if (s == "-denoise" || s == "-denoise-guided") {   // the iteration count is optional: taken when the next argument is a number
       denoise = true;
+      denoiseGuided = s == "-denoise-guided";
       if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9' && std::string(argv[i + 1]).find_first_not_of("0123456789") == std::string::npos)
         denoiseIterations = atoi(argv[++i]);
     }
@@ -68,6 +70,7 @@ int main(int argc, char **argv)
     Renderer renderer(param, device);
     renderer.denoise = denoise;
     renderer.denoiseIterations = denoiseIterations;
+    renderer.denoiseGuided = denoiseGuided;
     if (devices > 0) {
       std::vector<int> ids;
       for (int d = 0; d < devices; ++d) ids.push_back(device + d);

@@ -1,5 +1,5 @@
-// qa_denoise.hip — the edge-avoiding a-trous filter of qa_denoise_dev.h on the device (qa_denoise_device, qa_progressive_denoise*)
-// and the same source on the host (qa_test_denoise_host).  A guide kernel (pass 0) fills the context's working planes - colour and
+// qa_denoise.hip — the edge-avoiding a-trous filter of qa_denoise_dev.h on the device (qa_denoise_device, qa_progressive_denoise*,
+// the guided form qa_denoise_guided_*) and the same source on the host (qa_test_denoise_host, qa_test_denoise_guided_host).  A guide kernel (pass 0) fills the context's working planes - colour and
 // variance (16 bytes per pixel, two of them: the iterations go from one to the other), depth and slope (8 bytes) - from plain
 // buffers or from the progressive frame's slabs; one kernel per iteration follows, the last of which writes the caller's rgb.
 //
@@ -123,6 +123,43 @@ __global__ __launch_bounds__(256) void qa_denoise_iterate_direct(const DenoiseCo
   if (x >= W || y >= H) return;
   const DenoiseTapGlobal tap = {color, guide, W};
   denoiseStore(denoiseIterate(tap, x, y, W, H, s, sigmaColor, sigmaDepth), (size_t) y * (size_t) W + (size_t) x, outColor, outRgb);
+}
+
+// ---- the guided form: an aux plane (normal, albedo, valid / reliable bits: 32 bytes per pixel) beside the unguided planes; one kernel
+// fills it, and the iterations load every tap directly (a tap reads 16 + 8 bytes and, where the centre is reliable, 32 more)
+static_assert(sizeof(DenoiseAux) == 32, "the aux plane is read with two 16-byte loads");
+struct DenoiseGuideSrc {
+  const float *normal, *albedo;
+  int W;
+  __device__ __forceinline__ void operator()(int x, int y, float *n, float *a) const
+  {
+    const size_t q = (size_t) y * (size_t) W + (size_t) x;
+    if (normal) { n[0] = normal[3 * q]; n[1] = normal[3 * q + 1]; n[2] = normal[3 * q + 2]; }
+    if (albedo) { a[0] = albedo[3 * q]; a[1] = albedo[3 * q + 1]; a[2] = albedo[3 * q + 2]; }
+  }
+};
+struct DenoiseAuxGlobal {
+  const DenoiseAux *aux;
+  int W;
+  __device__ __forceinline__ DenoiseAux operator()(int x, int y) const { return aux[(size_t) y * (size_t) W + (size_t) x]; }
+};
+
+__global__ __launch_bounds__(256) void qa_denoise_guided_aux(DenoiseSrc src, DenoiseGuideSrc gsrc, int W, int H, uint32_t flags, DenoiseAux *aux)
+{
+  const int x = (int) (blockIdx.x * QA_DENOISE_TILE + (threadIdx.x & 15u)), y = (int) (blockIdx.y * QA_DENOISE_TILE + (threadIdx.x >> 4));
+  if (x >= W || y >= H) return;
+  aux[(size_t) y * (size_t) W + (size_t) x] = denoiseAux(src, gsrc, x, y, W, H, flags);
+}
+
+__global__ __launch_bounds__(256) void qa_denoise_guided_iterate(const DenoiseColor *color, const DenoiseGuide *guide, const DenoiseAux *aux, int W, int H,
+                                                                 int s, float sigmaColor, float sigmaDepth, float sigmaNormal, DenoiseColor *outColor,
+                                                                 float *outRgb)
+{
+  const int x = (int) (blockIdx.x * QA_DENOISE_TILE + (threadIdx.x & 15u)), y = (int) (blockIdx.y * QA_DENOISE_TILE + (threadIdx.x >> 4));
+  if (x >= W || y >= H) return;
+  const DenoiseTapGlobal tap = {color, guide, W};
+  const DenoiseAuxGlobal at = {aux, W};
+  denoiseStore(denoiseIterateGuided(tap, at, x, y, W, H, s, sigmaColor, sigmaDepth, sigmaNormal), (size_t) y * (size_t) W + (size_t) x, outColor, outRgb);
 }
 
 }  // namespace qa
@@ -257,6 +294,159 @@ int qa_test_denoise_host(const float *rgb, const float *depth, const uint32_t *n
     std::vector<DenoiseColor> &to = plane[(i + 1) & 1];
     for (int y = 0; y < H; ++y)
       for (int x = 0; x < W; ++x) to[(size_t) y * W + x] = denoiseIterate(tap, x, y, W, H, 1 << i, p->sigma_color, p->sigma_depth);
+  }
+  const std::vector<DenoiseColor> &last = plane[p->iterations & 1];
+  for (size_t q = 0; q < n; ++q) { out_rgb[3 * q] = last[q].r; out_rgb[3 * q + 1] = last[q].g; out_rgb[3 * q + 2] = last[q].b; }
+  return QA_OK;
+}
+
+}  // extern "C"
+
+static int CheckGuidedParams(const qa_denoise_guided_params *p, int width, int height, const void *normal, const void *albedo, bool planes)
+{
+  if (!p) return Fail(QA_EINVAL, "null parameters");
+  const qa_denoise_params u = {p->iterations, p->sigma_color, p->sigma_depth, 0u};
+  if (int rc = CheckParams(&u, width, height)) return rc;
+  if (!std::isfinite(p->sigma_normal) || !(p->sigma_normal > 0.f)) return Fail(QA_EINVAL, "a sigma that is not finite and positive");
+  if (p->flags & ~(QA_DENOISE_GUIDE_NORMAL | QA_DENOISE_GUIDE_ALBEDO)) return Fail(QA_EINVAL, "unknown flags");
+  if (planes && ((normal != nullptr) != ((p->flags & QA_DENOISE_GUIDE_NORMAL) != 0u) || (albedo != nullptr) != ((p->flags & QA_DENOISE_GUIDE_ALBEDO) != 0u)))
+    return Fail(QA_EINVAL, "a guide plane that disagrees with its flag");
+  return QA_OK;
+}
+
+// The guided form on s (iterations >= 1, flags != 0).  Working planes [colour A | colour B | guide | aux | own normal | own albedo]:
+// 40 + 32 bytes per pixel, and 24 more when the planes are the context's own (a progressive frame's, computed here: prog = true).
+// Every entry is written before it is read, as in Denoise
+static int DenoiseGuided(qa_ctx *c, const DenoiseSrc &src, const float *normal, const float *albedo, bool prog, int W, int H,
+                         const qa_denoise_guided_params &p, float *out, hipStream_t s, void *hip_stream)
+{
+  const size_t n = (size_t) W * (size_t) H;
+  HIP_TRY(c->denoisePlanes.Reserve(n * (prog ? 96 : 72), true));
+  HIP_TRY(c->lastDenoise.WaitOn(s));
+  DenoiseColor *plane[2] = {static_cast<DenoiseColor *>(c->denoisePlanes.p), static_cast<DenoiseColor *>(c->denoisePlanes.p) + n};
+  DenoiseGuide *guide = reinterpret_cast<DenoiseGuide *>(plane[1] + n);
+  DenoiseAux *aux = reinterpret_cast<DenoiseAux *>(guide + n);
+  if (prog) {
+    float *own = reinterpret_cast<float *>(aux + n);
+    float *dN = (p.flags & QA_DENOISE_GUIDE_NORMAL) ? own : nullptr, *dA = (p.flags & QA_DENOISE_GUIDE_ALBEDO) ? own + 3 * n : nullptr;
+    if (int rc = qa_progressive_gbuffer_device(c, dN, dA, nullptr, nullptr, hip_stream)) return rc;
+    normal = dN; albedo = dA;
+  }
+  const dim3 grid((unsigned) ((W + QA_DENOISE_TILE - 1) / QA_DENOISE_TILE), (unsigned) ((H + QA_DENOISE_TILE - 1) / QA_DENOISE_TILE)), block(256);
+  hipLaunchKernelGGL(qa::qa_denoise_guide, grid, block, 0, s, src, W, H, plane[0], guide);
+  HIP_TRY(hipGetLastError());
+  const DenoiseGuideSrc gsrc = {normal, albedo, W};
+  hipLaunchKernelGGL(qa::qa_denoise_guided_aux, grid, block, 0, s, src, gsrc, W, H, p.flags, aux);
+  HIP_TRY(hipGetLastError());
+  for (int i = 0; i < p.iterations; ++i) {
+    float *rgb = (i == p.iterations - 1) ? out : nullptr;
+    hipLaunchKernelGGL(qa::qa_denoise_guided_iterate, grid, block, 0, s, plane[i & 1], guide, aux, W, H, 1 << i, p.sigma_color, p.sigma_depth, p.sigma_normal,
+                       plane[(i + 1) & 1], rgb);
+    HIP_TRY(hipGetLastError());
+  }
+  HIP_TRY(c->lastDenoise.Record(s));
+  return QA_OK;
+}
+
+extern "C" {
+
+int qa_denoise_guided_params_default(qa_denoise_guided_params *p)
+{
+  if (!p) return Fail(QA_EINVAL, "null parameters");
+  p->iterations = QA_DENOISE_DEFAULT_ITERATIONS;
+  p->sigma_color = QA_DENOISE_DEFAULT_SIGMA_COLOR;
+  p->sigma_depth = QA_DENOISE_DEFAULT_SIGMA_DEPTH;
+  p->sigma_normal = QA_DENOISE_DEFAULT_SIGMA_NORMAL;
+  p->flags = QA_DENOISE_GUIDE_NORMAL | QA_DENOISE_GUIDE_ALBEDO;
+  return QA_OK;
+}
+
+int qa_denoise_guided_device(qa_ctx *c, const float *d_rgb, const float *d_depth, const uint32_t *d_ns, const float *d_normal, const float *d_albedo,
+                             int width, int height, const qa_denoise_guided_params *p, float *d_out_rgb, void *hip_stream)
+{
+  if (int rc = Enter(c)) return rc;
+  if (!d_rgb || !d_depth || !d_ns || !d_out_rgb) return Fail(QA_EINVAL, "null buffer");
+  if (int rc = CheckGuidedParams(p, width, height, d_normal, d_albedo, true)) return rc;
+  const qa_denoise_params u = {p->iterations, p->sigma_color, p->sigma_depth, 0u};
+  if (p->flags == 0u || p->iterations == 0) return qa_denoise_device(c, d_rgb, d_depth, d_ns, width, height, &u, d_out_rgb, hip_stream);
+  const DenoiseSrc src = {d_rgb, d_depth, d_ns, nullptr, width};
+  return DenoiseGuided(c, src, d_normal, d_albedo, false, width, height, *p, d_out_rgb, StreamOf(c, hip_stream), hip_stream);
+}
+
+int qa_progressive_denoise_guided_device(qa_ctx *c, const qa_denoise_guided_params *p, float *d_rgb, void *hip_stream)
+{
+  int rc = ProgActive(c);
+  if (rc != QA_OK) return rc;
+  if (!d_rgb) return Fail(QA_EINVAL, "null buffer");
+  const qa_ctx::Progressive &f = c->prog;
+  const int W = f.args.x1 - f.args.x0, H = f.args.y1 - f.args.y0;
+  if ((rc = CheckGuidedParams(p, W, H, nullptr, nullptr, false)) != QA_OK) return rc;
+  const qa_denoise_params u = {p->iterations, p->sigma_color, p->sigma_depth, 0u};
+  if (p->flags == 0u || p->iterations == 0) return qa_progressive_denoise_device(c, &u, d_rgb, hip_stream);
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t s = StreamOf(c, hip_stream);
+  HIP_TRY(f.done.WaitOn(s));
+  const DenoiseSrc src = {f.args.rgb, f.args.depth, f.args.ns, f.dState, W};
+  return DenoiseGuided(c, src, nullptr, nullptr, true, W, H, *p, d_rgb, s, hip_stream);
+}
+
+int qa_progressive_denoise_guided(qa_ctx *c, const qa_denoise_guided_params *p, float *rgb)
+{
+  int rc = ProgActive(c);
+  if (rc != QA_OK) return rc;
+  if (!rgb) return Fail(QA_EINVAL, "null buffer");
+  HIP_TRY(hipSetDevice(c->device));
+  qa_ctx::Progressive &f = c->prog;
+  HIP_TRY(f.prevRgb.Reserve(f.npix * 3 * sizeof(float)));
+  if ((rc = qa_progressive_denoise_guided_device(c, p, (float *) f.prevRgb.p, nullptr)) != QA_OK) return rc;
+  HIP_TRY(hipMemcpyAsync(rgb, f.prevRgb.p, f.npix * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return QA_OK;
+}
+
+// the guided form on the CPU, pixel after pixel (no GPU, no context); normal / albedo null where the flag is clear
+int qa_test_denoise_guided_host(const float *rgb, const float *depth, const uint32_t *ns, const float *normal, const float *albedo, int width, int height,
+                                const qa_denoise_guided_params *p, float *out_rgb)
+{
+  if (!rgb || !depth || !ns || !out_rgb) return Fail(QA_EINVAL, "null buffer");
+  if (int rc = CheckGuidedParams(p, width, height, normal, albedo, true)) return rc;
+  const qa_denoise_params u = {p->iterations, p->sigma_color, p->sigma_depth, 0u};
+  if (p->flags == 0u || p->iterations == 0) return qa_test_denoise_host(rgb, depth, ns, width, height, &u, out_rgb);
+  const int W = width, H = height;
+  const size_t n = (size_t) W * (size_t) H;
+  std::vector<DenoiseColor> plane[2] = {std::vector<DenoiseColor>(n), std::vector<DenoiseColor>(n)};
+  std::vector<DenoiseGuide> guide(n);
+  std::vector<DenoiseAux> aux(n);
+  const auto src = [=](int x, int y) {
+    const size_t q = (size_t) y * (size_t) W + (size_t) x;
+    DenoisePixel px;
+    px.r = rgb[3 * q]; px.g = rgb[3 * q + 1]; px.b = rgb[3 * q + 2]; px.z = depth[q]; px.ns = ns[q];
+    return px;
+  };
+  const auto gsrc = [=](int x, int y, float *nn, float *aa) {
+    const size_t q = (size_t) y * (size_t) W + (size_t) x;
+    if (normal) { nn[0] = normal[3 * q]; nn[1] = normal[3 * q + 1]; nn[2] = normal[3 * q + 2]; }
+    if (albedo) { aa[0] = albedo[3 * q]; aa[1] = albedo[3 * q + 1]; aa[2] = albedo[3 * q + 2]; }
+  };
+  for (int y = 0; y < H; ++y)
+    for (int x = 0; x < W; ++x) {
+      denoiseGuide(src, x, y, W, H, plane[0][(size_t) y * W + x], guide[(size_t) y * W + x]);
+      aux[(size_t) y * W + x] = denoiseAux(src, gsrc, x, y, W, H, p->flags);
+    }
+  for (int i = 0; i < p->iterations; ++i) {
+    const DenoiseColor *from = plane[i & 1].data();
+    const DenoiseGuide *gd = guide.data();
+    const DenoiseAux *ad = aux.data();
+    const auto tap = [=](int x, int y, DenoiseColor &cc, DenoiseGuide &g) {
+      const size_t q = (size_t) y * (size_t) W + (size_t) x;
+      cc = from[q];
+      g = gd[q];
+    };
+    const auto at = [=](int x, int y) { return ad[(size_t) y * (size_t) W + (size_t) x]; };
+    std::vector<DenoiseColor> &to = plane[(i + 1) & 1];
+    for (int y = 0; y < H; ++y)
+      for (int x = 0; x < W; ++x)
+        to[(size_t) y * W + x] = denoiseIterateGuided(tap, at, x, y, W, H, 1 << i, p->sigma_color, p->sigma_depth, p->sigma_normal);
   }
   const std::vector<DenoiseColor> &last = plane[p->iterations & 1];
   for (size_t q = 0; q < n; ++q) { out_rgb[3 * q] = last[q].r; out_rgb[3 * q + 1] = last[q].g; out_rgb[3 * q + 2] = last[q].b; }

@@ -40,6 +40,27 @@
 //   c'_p = c_p + sc / sw   (= sum(w c_q) / sum(w), written around the centre: a constant neighbourhood stays constant exactly)
 //   var'_p = sv / (sw * sw)
 // The output is the colour after the last iteration.  sw >= 9/64: no division by zero.
+//
+// GUIDED FORM (qa_denoise_guided_*; tests/denoise_guided_util.py restates this section).  Two more inputs per pixel, each optional
+// (flags QA_DENOISE_GUIDE_NORMAL = 1, QA_DENOISE_GUIDE_ALBEDO = 2): normal[3] and albedo[3], the planes of qa_gbuffer_region*.  One more
+// parameter, sigma_normal (finite, > 0; default 0.1).  With flags == 0 it is the filter above, bit for bit.  Classes, void rules,
+// pass 0, the centre-form update and the variance recursion are unchanged; the colours are never divided or multiplied by a guide
+// (DESIGN 4g has the measurements that ruled demodulation out), so iterations == 0 is the input's bits here too.  The guides add
+// terms to the exponent e of a tap, in the one qexpf.
+//   A guide is sample 0's: on a pixel whose footprint holds an edge (of geometry, of a texture) it describes one side only, while the
+//   colour is the mean over both.  Such a pixel must not be tied to sample 0's side, so it is filtered as if it had no guides:
+//   valid_n(p): the flag is set, p is a hit pixel, the normal's components are finite and not all 0.
+//   valid_a(p): the flag is set and the albedo's components are finite.         (p not void, for both)
+//   dn(p, q) = 1 - (n_p.x * n_q.x + n_p.y * n_q.y + n_p.z * n_q.z);  da(p, q) = max(max(|a_p.r - a_q.r|, |a_p.g - a_q.g|), |a_p.b - a_q.b|)
+//   members = the pixels of the 3x3 window around p that lie in the image and are not void (p is one), of EITHER class.
+//   reliable(p): no member has the other class; every member q with valid_n(p) and valid_n(q) has dn(p, q) <= 0.02f; every member q
+//                with valid_a(p) and valid_a(q) has da(p, q) <= 0.3f.
+//   (0.02: 11.5 degrees, what a curved surface turns between neighbouring pixels at preview sizes and no crease does; 0.3: a third of
+//   the albedo range, the step of a painted edge and more than a filtered texture varies between neighbours.)
+// A tap q of pixel p that is not skipped, after the depth term, in this order:
+//   reliable(p) and valid_n(p) and valid_n(q) and dn(p, q) > 0:   e = e + dn(p, q) / sigma_normal
+//   reliable(p) and valid_a(p) and valid_a(q):                    e = e + da(p, q) / 0.02f
+// (It is the centre that is gated: an unreliable q still counts for a reliable p, at the distance its sample 0 gives it.)
 #pragma once
 #include "qa_device_math.h"
 
@@ -50,6 +71,13 @@ namespace qa {
 #define QA_DENOISE_DEFAULT_ITERATIONS 5
 #define QA_DENOISE_DEFAULT_SIGMA_COLOR 4.0f
 #define QA_DENOISE_DEFAULT_SIGMA_DEPTH 1.0f
+#define QA_DENOISE_DEFAULT_SIGMA_NORMAL 0.1f
+#define QA_DENOISE_RELIABLE_NORMAL 0.02f
+#define QA_DENOISE_RELIABLE_ALBEDO 0.3f
+#define QA_DENOISE_SIGMA_ALBEDO 0.02f
+#define QA_DENOISE_AUX_VALID_N 1u
+#define QA_DENOISE_AUX_VALID_A 2u
+#define QA_DENOISE_AUX_RELIABLE 4u
 
 struct DenoisePixel {
   float r, g, b, z;
@@ -58,6 +86,8 @@ struct DenoisePixel {
 // what the iterations work on.  Colour plane: r, g, b, variance.  Guide plane: depth and slope; slope < 0 marks a void pixel
 struct DenoiseColor { float r, g, b, var; };
 struct DenoiseGuide { float z, slope; };
+// the guided form's plane: normal, albedo and the QA_DENOISE_AUX_* bits of the pixel
+struct DenoiseAux { float nx, ny, nz; uint32_t bits; float ar, ag, ab, pad; };
 
 __host__ __device__ __forceinline__ bool denoiseFinite(float x) { return (qa_asuint(x) & 0x7f800000u) != 0x7f800000u; }
 __host__ __device__ __forceinline__ bool denoiseVoid(const DenoisePixel &p)
@@ -147,6 +177,112 @@ __host__ __device__ __forceinline__ DenoiseColor denoiseIterate(const Tap &tap, 
       if (!miss && GP.z != GQ.z) {
         const int ax = dx < 0 ? -dx : dx, ay = dy < 0 ? -dy : dy;
         e = e + qabs(GP.z - GQ.z) / (denZ * (float) (ax > ay ? ax : ay));
+      }
+      const float w = (h[dx + 2] * h[dy + 2]) * qexpf(-e);
+      sw += w;
+      sr += w * (Q.r - P.r); sg += w * (Q.g - P.g); sb += w * (Q.b - P.b);
+      sv += (w * w) * Q.var;
+    }
+  }
+  DenoiseColor o;
+  o.r = P.r + sr / sw; o.g = P.g + sg / sw; o.b = P.b + sb / sw;
+  o.var = sv / (sw * sw);
+  return o;
+}
+
+// ---- the guided form ----
+__host__ __device__ __forceinline__ float denoiseDn(const DenoiseAux &p, const DenoiseAux &q) { return 1.f - (p.nx * q.nx + p.ny * q.ny + p.nz * q.nz); }
+__host__ __device__ __forceinline__ float denoiseDa(const DenoiseAux &p, const DenoiseAux &q)
+{
+  return qmax(qmax(qabs(p.ar - q.ar), qabs(p.ag - q.ag)), qabs(p.ab - q.ab));
+}
+
+// The guides of one pixel and its valid bits.  gsrc(x, y, n, a) fetches normal and albedo (three floats each; a plane that is not
+// given is left alone), called for pixels inside the image only; px is the pixel's colour / depth / ns
+template <class GSrc>
+__host__ __device__ __forceinline__ DenoiseAux denoiseAuxLoad(const GSrc &gsrc, const DenoisePixel &px, int x, int y, uint32_t flags)
+{
+  float n[3] = {0.f, 0.f, 0.f}, a[3] = {0.f, 0.f, 0.f};
+  gsrc(x, y, n, a);
+  DenoiseAux o;
+  o.nx = n[0]; o.ny = n[1]; o.nz = n[2]; o.ar = a[0]; o.ag = a[1]; o.ab = a[2]; o.pad = 0.f;
+  o.bits = 0u;
+  if (denoiseVoid(px)) return o;
+  if ((flags & 1u) && px.z != QA_DENOISE_MISS && denoiseFinite(n[0]) && denoiseFinite(n[1]) && denoiseFinite(n[2]) &&
+      (n[0] != 0.f || n[1] != 0.f || n[2] != 0.f))
+    o.bits |= QA_DENOISE_AUX_VALID_N;
+  if ((flags & 2u) && denoiseFinite(a[0]) && denoiseFinite(a[1]) && denoiseFinite(a[2])) o.bits |= QA_DENOISE_AUX_VALID_A;
+  return o;
+}
+
+// Pass 0 of the guided form for pixel (x, y): its guides, valid bits and whether it is reliable
+template <class Src, class GSrc>
+__host__ __device__ __forceinline__ DenoiseAux denoiseAux(const Src &src, const GSrc &gsrc, int x, int y, int W, int H, uint32_t flags)
+{
+  const DenoisePixel p = src(x, y);
+  DenoiseAux P = denoiseAuxLoad(gsrc, p, x, y, flags);
+  if (denoiseVoid(p)) return P;
+  const bool miss = p.z == QA_DENOISE_MISS;
+  bool reliable = true;
+  for (int dy = -1; dy <= 1; ++dy)
+    for (int dx = -1; dx <= 1; ++dx) {
+      const int qx = x + dx, qy = y + dy;
+      if ((dx == 0 && dy == 0) || qx < 0 || qy < 0 || qx >= W || qy >= H) continue;
+      const DenoisePixel q = src(qx, qy);
+      if (denoiseVoid(q)) continue;
+      if ((q.z == QA_DENOISE_MISS) != miss) { reliable = false; continue; }
+      const DenoiseAux Q = denoiseAuxLoad(gsrc, q, qx, qy, flags);
+      if ((P.bits & Q.bits & QA_DENOISE_AUX_VALID_N) && !(denoiseDn(P, Q) <= QA_DENOISE_RELIABLE_NORMAL)) reliable = false;
+      if ((P.bits & Q.bits & QA_DENOISE_AUX_VALID_A) && !(denoiseDa(P, Q) <= QA_DENOISE_RELIABLE_ALBEDO)) reliable = false;
+    }
+  if (reliable) P.bits |= QA_DENOISE_AUX_RELIABLE;
+  return P;
+}
+
+// One iteration of the guided form.  tap as for denoiseIterate; aux(x, y) -> DenoiseAux of a pixel inside the image
+template <class Tap, class Aux>
+__host__ __device__ __forceinline__ DenoiseColor denoiseIterateGuided(const Tap &tap, const Aux &aux, int x, int y, int W, int H, int s, float sigmaColor,
+                                                                      float sigmaDepth, float sigmaNormal)
+{
+  DenoiseColor P;
+  DenoiseGuide GP;
+  tap(x, y, P, GP);
+  if (GP.slope < 0.f) return P;
+  const DenoiseAux AP = aux(x, y);
+  const uint32_t guided = (AP.bits & QA_DENOISE_AUX_RELIABLE) ? AP.bits : 0u;
+  const bool miss = GP.z == QA_DENOISE_MISS;
+  const float lp = denoiseLuma(P.r, P.g, P.b);
+  const float denL = sigmaColor * qsqrt(P.var) + 1e-4f;
+  const float denZ = sigmaDepth * GP.slope * (float) s;
+  const float h[5] = {0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f};
+  float sw = 0.f, sr = 0.f, sg = 0.f, sb = 0.f, sv = 0.f;
+#pragma unroll
+  for (int dy = -2; dy <= 2; ++dy) {
+#pragma unroll
+    for (int dx = -2; dx <= 2; ++dx) {
+      if (dx == 0 && dy == 0) {
+        const float w = 0.140625f;
+        sw += w; sv += (w * w) * P.var;
+        continue;
+      }
+      const int qx = x + s * dx, qy = y + s * dy;
+      if (qx < 0 || qy < 0 || qx >= W || qy >= H) continue;
+      DenoiseColor Q;
+      DenoiseGuide GQ;
+      tap(qx, qy, Q, GQ);
+      if (GQ.slope < 0.f || (GQ.z == QA_DENOISE_MISS) != miss) continue;
+      float e = qabs(lp - denoiseLuma(Q.r, Q.g, Q.b)) / denL;
+      if (!miss && GP.z != GQ.z) {
+        const int ax = dx < 0 ? -dx : dx, ay = dy < 0 ? -dy : dy;
+        e = e + qabs(GP.z - GQ.z) / (denZ * (float) (ax > ay ? ax : ay));
+      }
+      if (guided & (QA_DENOISE_AUX_VALID_N | QA_DENOISE_AUX_VALID_A)) {
+        const DenoiseAux AQ = aux(qx, qy);
+        if (guided & AQ.bits & QA_DENOISE_AUX_VALID_N) {
+          const float dn = denoiseDn(AP, AQ);
+          if (dn > 0.f) e = e + dn / sigmaNormal;
+        }
+        if (guided & AQ.bits & QA_DENOISE_AUX_VALID_A) e = e + denoiseDa(AP, AQ) / QA_DENOISE_SIGMA_ALBEDO;
       }
       const float w = (h[dx + 2] * h[dy + 2]) * qexpf(-e);
       sw += w;

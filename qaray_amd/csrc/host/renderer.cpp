@@ -338,7 +338,19 @@ void Renderer::SaveDenoised(float *dRgb, const float *dDepth, const uint32_t *dN
     ~Bytes() { if (p) (void) hipFree(p); }
   } dColor;
   HIP_OR_THROW(hipMalloc((void **) &dColor.p, 3 * n));
-  if (qa_denoise_device(ctx, dRgb, dDepth, dNs, (int) pixelW, (int) pixelH, &dp, dRgb, nullptr) != QA_OK ||
+  if (denoiseGuided) {   // -denoise-guided: the frame's first-hit normal and albedo planes (sample 0 of the frame's seed) guide the filter
+    Bytes dGuides;
+    HIP_OR_THROW(hipMalloc((void **) &dGuides.p, 24 * n));
+    float *dNormal = reinterpret_cast<float *>(dGuides.p), *dAlbedo = dNormal + 3 * n;
+    qa_denoise_guided_params gp;
+    qa_denoise_guided_params_default(&gp);
+    if (denoiseIterations >= 0) gp.iterations = denoiseIterations;
+    if (qa_gbuffer_region_device(ctx, 0, 0, (int) pixelW, (int) pixelH, param.seed, dNormal, dAlbedo, nullptr, nullptr, nullptr) != QA_OK ||
+        qa_denoise_guided_device(ctx, dRgb, dDepth, dNs, dNormal, dAlbedo, (int) pixelW, (int) pixelH, &gp, dRgb, nullptr) != QA_OK)
+      throw std::runtime_error(std::string("-denoise-guided: ") + qa_last_error());
+    qa_synchronize(ctx);   // (the guide planes are freed on the way out)
+  }
+  if ((!denoiseGuided && qa_denoise_device(ctx, dRgb, dDepth, dNs, (int) pixelW, (int) pixelH, &dp, dRgb, nullptr) != QA_OK) ||
       qa_display_device(ctx, dRgb, dDepth, dNs, n, (int) param.sppMax, param.useSRGB ? 1 : 0, dColor.p, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) != QA_OK)
     throw std::runtime_error(std::string("-denoise: ") + qa_last_error());
   qa_synchronize(ctx);

@@ -69,6 +69,7 @@ class Renderer {
   // (qa_denoise_device, then qa_display_device); N iterations, -1 = the library's default.  One device only
   bool denoise = false;
   int denoiseIterations = -1;
+  bool denoiseGuided = false;   // -denoise-guided [N]: the same image through qa_denoise_guided_device with the frame's normal and albedo planes
 
  protected:
   RendererParam &param;

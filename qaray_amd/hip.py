@@ -54,13 +54,14 @@ INSTANCE_DTYPE = np.dtype([("tm", np.float32, 9), ("itm", np.float32, 9), ("pos"
 TEXMAP_DTYPE = np.dtype([("itm", np.float32, 9), ("pos", np.float32, 3), ("texture", np.int32), ("pad", np.int32, 3)])
 TEXTURE_DTYPE = np.dtype([("type", np.int32), ("width", np.int32), ("height", np.int32), ("pad0", np.int32), ("color1", np.float32, 3),
                           ("color2", np.float32, 3), ("off_texels", np.uint64), ("pad1", np.uint64)])
+MTLSET_DTYPE = np.dtype([("first", np.int32), ("count", np.int32), ("multi", np.int32), ("pad", np.int32)])
 assert (CAMERA_DTYPE.itemsize, LIGHT_DTYPE.itemsize, MATERIAL_DTYPE.itemsize, INSTANCE_DTYPE.itemsize) == (76, 64, 112, 112)
 assert (TEXCOLOR_DTYPE.itemsize, TEXMAP_DTYPE.itemsize, TEXTURE_DTYPE.itemsize) == (16, 64, 56)
 QA_TEX_CHECKER, QA_TEX_FILE = 0, 1
 # qa_flat_header: byte offsets of the counts and table offsets the views below need
-_HEADER = {"camera": 16, "backdrop": 104, "instances": (136, 168), "materials": (148, 192), "lights": (152, 200), "texmaps": (156, 208),
+_HEADER = {"camera": 16, "backdrop": 104, "instances": (136, 168), "mtlsets": (144, 184), "materials": (148, 192), "lights": (152, 200), "texmaps": (156, 208),
            "textures": (160, 216)}
-_TABLE_DTYPES = {"instances": INSTANCE_DTYPE, "materials": MATERIAL_DTYPE, "lights": LIGHT_DTYPE, "texmaps": TEXMAP_DTYPE,
+_TABLE_DTYPES = {"instances": INSTANCE_DTYPE, "mtlsets": MTLSET_DTYPE, "materials": MATERIAL_DTYPE, "lights": LIGHT_DTYPE, "texmaps": TEXMAP_DTYPE,
                  "textures": TEXTURE_DTYPE}
 
 
@@ -85,7 +86,7 @@ def blob_texels(blob, i):
 
 
 def blob_table(blob, which):
-    """The 'lights' / 'materials' / 'instances' / 'texmaps' / 'textures' table of a flat scene blob (numpy uint8) as a writable
+    """The 'lights' / 'materials' / 'mtlsets' / 'instances' / 'texmaps' / 'textures' table of a flat scene blob (numpy uint8) as a writable
     structured view."""
     at_count, at_off = _HEADER[which]
     n = int(blob[at_count:at_count + 4].view(np.uint32)[0])
@@ -121,6 +122,36 @@ class DenoiseParams(C.Structure):   # qa_denoise_params; DenoiseParams.default()
         if sigma_depth is not None:
             p.sigma_depth = float(sigma_depth)
         return p
+
+
+QA_DENOISE_GUIDE_NORMAL, QA_DENOISE_GUIDE_ALBEDO = 1, 2
+
+
+class DenoiseGuidedParams(C.Structure):   # qa_denoise_guided_params; .default() = qa_denoise_guided_params_default
+    _fields_ = [("iterations", C.c_int), ("sigma_color", C.c_float), ("sigma_depth", C.c_float), ("sigma_normal", C.c_float), ("flags", C.c_uint32)]
+
+    @classmethod
+    def default(cls):
+        p = cls()
+        _check(lib().qa_denoise_guided_params_default(C.byref(p)))
+        return p
+
+    @classmethod
+    def of(cls, params=None, flags=None, iterations=None, sigma_color=None, sigma_depth=None, sigma_normal=None):
+        """params (a DenoiseGuidedParams) or the library's defaults, with the arguments that are given written over them."""
+        p = cls.default() if params is None else cls(params.iterations, params.sigma_color, params.sigma_depth, params.sigma_normal, params.flags)
+        if flags is not None:
+            p.flags = int(flags)
+        if iterations is not None:
+            p.iterations = int(iterations)
+        for name, v in (("sigma_color", sigma_color), ("sigma_depth", sigma_depth), ("sigma_normal", sigma_normal)):
+            if v is not None:
+                setattr(p, name, float(v))
+        return p
+
+
+QA_GBUFFER_BACKFACE = 0x40000000
+GBUFFER_PLANES = ("normal", "albedo", "depth", "ids")   # in the C ABI's order: float32 [h,w,3], [h,w,3], [h,w], int32 [h,w,2]
 
 
 # Progressive.display(): numpy arrays shaped like the region (color [h,w,3], the others [h,w], uint8) and the statistics as a dict
@@ -194,6 +225,14 @@ def lib():
         L.qa_progressive_denoise.argtypes = [C.c_void_p, C.POINTER(DenoiseParams), C.c_void_p]
         L.qa_progressive_denoise_device.argtypes = [C.c_void_p, C.POINTER(DenoiseParams), C.c_void_p, C.c_void_p]
         L.qa_test_denoise_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(DenoiseParams), C.c_void_p]
+        L.qa_denoise_guided_params_default.argtypes = [C.POINTER(DenoiseGuidedParams)]
+        L.qa_denoise_guided_device.argtypes = [C.c_void_p] * 6 + [C.c_int, C.c_int, C.POINTER(DenoiseGuidedParams), C.c_void_p, C.c_void_p]
+        L.qa_progressive_denoise_guided.argtypes = [C.c_void_p, C.POINTER(DenoiseGuidedParams), C.c_void_p]
+        L.qa_progressive_denoise_guided_device.argtypes = [C.c_void_p, C.POINTER(DenoiseGuidedParams), C.c_void_p, C.c_void_p]
+        L.qa_test_denoise_guided_host.argtypes = [C.c_void_p] * 5 + [C.c_int, C.c_int, C.POINTER(DenoiseGuidedParams), C.c_void_p]
+        L.qa_gbuffer_region_device.argtypes = [C.c_void_p] + [C.c_int] * 4 + [C.c_uint32] + [C.c_void_p] * 5
+        L.qa_gbuffer_region.argtypes = [C.c_void_p] + [C.c_int] * 4 + [C.c_uint32] + [C.c_void_p] * 4
+        L.qa_progressive_gbuffer_device.argtypes = [C.c_void_p] * 6
         L.qa_scene_edit_camera.argtypes = [C.c_void_p, C.c_void_p]
         for name in ("qa_scene_edit_lights", "qa_scene_edit_materials", "qa_scene_edit_instances"):
             getattr(L, name).argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
@@ -246,6 +285,46 @@ def denoise_host(rgb, depth, ns, params=None, iterations=None, sigma_color=None,
     p = DenoiseParams.of(params, iterations, sigma_color, sigma_depth)
     _check(lib().qa_test_denoise_host(rgb.ctypes.data, depth.ctypes.data, ns.ctypes.data, w, h, C.byref(p), out.ctypes.data))
     return out
+
+
+def denoise_guided_host(rgb, depth, ns, normal=None, albedo=None, params=None, iterations=None, sigma_color=None, sigma_depth=None,
+                        sigma_normal=None):
+    """qa_test_denoise_guided_host: the guided filter of Context.denoise_guided_device on the CPU, from the source the device kernels
+    are compiled from; normal / albedo (h, w, 3) or None: the flags are the guides given.  -> float32 (h, w, 3).  No GPU needed."""
+    rgb = np.ascontiguousarray(rgb, dtype=np.float32)
+    depth = np.ascontiguousarray(depth, dtype=np.float32)
+    ns = np.ascontiguousarray(ns, dtype=np.uint32)
+    assert rgb.ndim == 3 and rgb.shape[2] == 3 and depth.shape == rgb.shape[:2] and ns.shape == rgb.shape[:2]
+    guides = [None if g is None else np.ascontiguousarray(g, dtype=np.float32) for g in (normal, albedo)]
+    assert all(g is None or g.shape == rgb.shape for g in guides)
+    h, w = depth.shape
+    out = np.zeros((h, w, 3), np.float32)
+    flags = (QA_DENOISE_GUIDE_NORMAL if normal is not None else 0) | (QA_DENOISE_GUIDE_ALBEDO if albedo is not None else 0)
+    p = DenoiseGuidedParams.of(params, flags, iterations, sigma_color, sigma_depth, sigma_normal)
+    _check(lib().qa_test_denoise_guided_host(rgb.ctypes.data, depth.ctypes.data, ns.ctypes.data, *(None if g is None else g.ctypes.data for g in guides),
+                                             w, h, C.byref(p), out.ctypes.data))
+    return out
+
+
+def _gbuffer_tensors(region, device, given):
+    """The device planes of a G-buffer call: the ones given (torch tensors), or all four allocated when none is given
+    -> (dict name -> tensor, pointers in the C ABI's order)."""
+    import torch
+    x0, y0, x1, y1 = region
+    h, w = y1 - y0, x1 - x0
+    shapes = {"normal": (h, w, 3), "albedo": (h, w, 3), "depth": (h, w), "ids": (h, w, 2)}
+    out = {k: v for k, v in given.items() if v is not None}
+    if not out:
+        out = {k: torch.empty(shapes[k], dtype=torch.int32 if k == "ids" else torch.float32, device=device) for k in GBUFFER_PLANES}
+    for k, t in out.items():
+        assert t.is_cuda and t.is_contiguous() and t.element_size() == 4 and t.numel() == int(np.prod(shapes[k])), k
+    return out, [out[k].data_ptr() if k in out else None for k in GBUFFER_PLANES]
+
+
+def pick(ctx, x, y, seed=DEFAULT_SEED):
+    """What pixel (x, y) sees -> (node, material, depth) of its first hit (node -1 on a miss); a one-pixel Context.gbuffer."""
+    g = ctx.gbuffer((x, y, x + 1, y + 1), seed)
+    return int(g["ids"][0, 0, 0]), int(g["ids"][0, 0, 1]), float(g["depth"][0, 0])
 
 
 def texels_host(rgb8):
@@ -502,6 +581,49 @@ class Context:
         _check(lib().qa_denoise_device(self._h, rgb.data_ptr(), depth.data_ptr(), ns.data_ptr(), w, h, C.byref(p), out.data_ptr(), sptr))
         return out
 
+    def denoise_guided_device(self, rgb, depth, ns, normal=None, albedo=None, out=None, params=None, iterations=None, sigma_color=None,
+                              sigma_depth=None, sigma_normal=None, stream=None):
+        """qa_denoise_guided_device: denoise_device guided by the first-hit planes of gbuffer_device as well (float32 [h,w,3] CUDA
+        tensors; the flags are the guides given, and with neither the result is denoise_device's).  -> out; only enqueues."""
+        import torch
+        assert rgb.is_cuda and rgb.is_contiguous() and rgb.dim() == 3 and rgb.shape[2] == 3 and rgb.dtype == torch.float32
+        h, w = rgb.shape[:2]
+        n = h * w
+        assert depth.is_cuda and depth.is_contiguous() and depth.numel() == n and depth.element_size() == 4
+        assert ns.is_cuda and ns.is_contiguous() and ns.numel() == n and ns.element_size() == 4
+        for g in (normal, albedo):
+            assert g is None or (g.is_cuda and g.is_contiguous() and g.numel() == 3 * n and g.dtype == torch.float32)
+        if out is None:
+            out = torch.empty_like(rgb)
+        assert out.is_cuda and out.is_contiguous() and out.shape == rgb.shape and out.dtype == torch.float32
+        flags = (QA_DENOISE_GUIDE_NORMAL if normal is not None else 0) | (QA_DENOISE_GUIDE_ALBEDO if albedo is not None else 0)
+        p = DenoiseGuidedParams.of(params, flags, iterations, sigma_color, sigma_depth, sigma_normal)
+        sptr = self._stream_arg(stream, rgb)
+        _check(lib().qa_denoise_guided_device(self._h, rgb.data_ptr(), depth.data_ptr(), ns.data_ptr(), None if normal is None else normal.data_ptr(),
+                                              None if albedo is None else albedo.data_ptr(), w, h, C.byref(p), out.data_ptr(), sptr))
+        return out
+
+    def gbuffer(self, region, seed=DEFAULT_SEED):
+        """qa_gbuffer_region: the first-hit guide planes of a region -> dict of numpy arrays: normal [h,w,3] f32 (world space, 0 on a
+        miss), albedo [h,w,3] f32, depth [h,w] f32 (render_region's depth plane), ids [h,w,2] i32 (node, material; -1 on a miss;
+        QA_GBUFFER_BACKFACE of the material word: a back-face hit).  Synchronises."""
+        x0, y0, x1, y1 = region
+        h, w = y1 - y0, x1 - x0
+        out = {"normal": np.zeros((h, w, 3), np.float32), "albedo": np.zeros((h, w, 3), np.float32), "depth": np.zeros((h, w), np.float32),
+               "ids": np.zeros((h, w, 2), np.int32)}
+        _check(lib().qa_gbuffer_region(self._h, x0, y0, x1, y1, seed, *(out[k].ctypes.data for k in GBUFFER_PLANES)))
+        return out
+
+    def gbuffer_device(self, region, seed=DEFAULT_SEED, normal=None, albedo=None, depth=None, ids=None, stream=None):
+        """qa_gbuffer_region_device into torch CUDA tensors (see gbuffer for the shapes): the planes given are written; when none is
+        given all four are allocated.  -> dict name -> tensor.  Only enqueues (see render_region_device for the stream)."""
+        import torch
+        out, ptrs = _gbuffer_tensors(region, torch.device("cuda", self.device_id), dict(normal=normal, albedo=albedo, depth=depth, ids=ids))
+        sptr = self._stream_arg(stream, next(iter(out.values())))
+        x0, y0, x1, y1 = region
+        _check(lib().qa_gbuffer_region_device(self._h, x0, y0, x1, y1, seed, *ptrs, sptr))
+        return out
+
     def render_strips_device(self, region, first_strip, strip_step, spp, rgb, depth, ns, max_bounce=5,
                              seed=DEFAULT_SEED, spp_max=None, stats=False, stream=None):
         """Render strips first_strip, first_strip+strip_step, ... (8 rows each) of `region` into PACKED
@@ -682,6 +804,38 @@ class Progressive:
         p = DenoiseParams.of(params, iterations, sigma_color, sigma_depth)
         sptr = Context._stream_arg(stream, out)
         _check(lib().qa_progressive_denoise_device(self._ctx._h, C.byref(p), out.data_ptr(), sptr))
+        return out
+
+    def denoise_guided(self, params=None, flags=None, iterations=None, sigma_color=None, sigma_depth=None, sigma_normal=None):
+        """qa_progressive_denoise_guided: denoise() guided by the frame's own first-hit planes, which the call computes from the scene
+        as it now stands (flags: which guides; default both) -> rgb[h,w,3] f32; synchronises.  The frame is not changed."""
+        x0, y0, x1, y1 = self.region
+        rgb = np.zeros((y1 - y0, x1 - x0, 3), np.float32)
+        p = DenoiseGuidedParams.of(params, flags, iterations, sigma_color, sigma_depth, sigma_normal)
+        _check(lib().qa_progressive_denoise_guided(self._ctx._h, C.byref(p), rgb.ctypes.data))
+        return rgb
+
+    def denoise_guided_device(self, out=None, params=None, flags=None, iterations=None, sigma_color=None, sigma_depth=None, sigma_normal=None,
+                              stream=None):
+        """qa_progressive_denoise_guided_device: the same into a torch CUDA tensor (float32 [h,w,3]; None: a new one) -> out; only
+        enqueues."""
+        import torch
+        x0, y0, x1, y1 = self.region
+        if out is None:
+            out = torch.empty((y1 - y0, x1 - x0, 3), dtype=torch.float32, device=torch.device("cuda", self._ctx.device_id))
+        assert out.is_cuda and out.is_contiguous() and out.numel() == 3 * (x1 - x0) * (y1 - y0) and out.dtype == torch.float32
+        p = DenoiseGuidedParams.of(params, flags, iterations, sigma_color, sigma_depth, sigma_normal)
+        sptr = Context._stream_arg(stream, out)
+        _check(lib().qa_progressive_denoise_guided_device(self._ctx._h, C.byref(p), out.data_ptr(), sptr))
+        return out
+
+    def gbuffer_device(self, normal=None, albedo=None, depth=None, ids=None, stream=None):
+        """qa_progressive_gbuffer_device: the guide planes of the frame's region and seed, of the scene as it now stands (see
+        Context.gbuffer_device) -> dict name -> tensor; only enqueues."""
+        import torch
+        out, ptrs = _gbuffer_tensors(self.region, torch.device("cuda", self._ctx.device_id), dict(normal=normal, albedo=albedo, depth=depth, ids=ids))
+        sptr = Context._stream_arg(stream, next(iter(out.values())))
+        _check(lib().qa_progressive_gbuffer_device(self._ctx._h, *ptrs, sptr))
         return out
 
     def status(self):
