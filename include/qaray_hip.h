@@ -400,6 +400,9 @@ int qa_set_pipeline(qa_ctx *ctx, int mode);
  *   "chunk_spp"      -1 (default: per frame) / 0 / n: the per-lane kernels hand a tile's samples out in chunks - n samples first, then
  *   "chunk_tail"     chunks of this many (0: an eighth of the frame's spp) - so that a frame of few tiles per wave ends on small work
  *                    items; a pixel's state waits in device memory between chunks (same samples in the same order: same bits)
+ *   "tile_lists"     -1 (default: on, limit 8) / 0 / n: LDS-resident scenes without depth of field - a wave lists, once per tile,
+ *                    the leaves of every mesh's own tree its camera rays can enter, and those rays test the listed triangles
+ *                    instead of walking the tree; a mesh whose list for a tile is longer than n leaves is walked (same bits)
  *   "tile_order"     1 (default) / 0: tiles handed out centre-first
  *   "progressive_tile_limit"  tests: n > 0 = a progressive pass takes at most n tiles, then ends as if stopped; 0 (default) = none
  *   "staged_groups"  1 (default) .. 8 tile groups of the staged pipeline, each on its own stream; more than one only pays

@@ -528,6 +528,7 @@ int qa_set_option(qa_ctx *c, const char *name, long long value)
   else if (n == "walk_zero_terms") c->optWalkZeroTerms = value ? 1u : 0u;
   else if (n == "chunk_spp") c->optChunkSpp = value < 0 ? -1 : (int) (value > 65535 ? 65535 : value);
   else if (n == "chunk_tail") c->optChunkTail = value < 0 ? 0 : (int) (value > 65535 ? 65535 : value);
+  else if (n == "tile_lists") c->optTileLists = value < 0 ? -1 : (int) (value > QA_TILE_LEAF_CAP ? QA_TILE_LEAF_CAP : value);
   else if (n == "cs_pool_limit") c->optCsPool = value > 0 ? (uint32_t) std::max<long long>(64, value) : 0u;
   else if (n == "sync_samples") c->syncSamples = value < 0 ? -1 : (value > 64 ? 64 : (int) value);
   else if (n == "tile_order") c->tileOrder = value != 0;

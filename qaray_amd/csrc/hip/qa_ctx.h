@@ -173,6 +173,7 @@ struct qa_ctx {
   StreamFence lastFrame;          // the slabs (these, the area-light log, the many-light surface slab) are one per context: a frame on another stream waits
   int optChunkSpp = -1;           // "chunk_spp": -1 per frame (few tiles per wave), 0 off, n samples of a tile's first chunk
   int optChunkTail = 0;           // "chunk_tail": samples of every further chunk (0: an eighth of the frame's spp)
+  int optTileLists = -1;          // "tile_lists": -1 on with the measured limit (QA_TILE_LISTS_AUTO), 0 off, n on with a limit of n leaves per mesh and tile
   int workNext = 0;
   int *hStop = nullptr;           // mapped host memory, read by the kernel's wave leaders
   int *dStopAlias = nullptr;

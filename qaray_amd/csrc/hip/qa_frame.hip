@@ -67,7 +67,7 @@ int SelectKernel(qa_ctx *c)
   const bool lights = c->ds.num_lights > 0;
   Integrator &mega = c->integ[kMega], &cs = c->integ[kCs], &resume = c->integ[kCsResume];
   mega.fn = PickKernel(p.resident, lights, p.textured, p.area, false);
-  mega.ldsBytes = p.ldsBytes;
+  mega.ldsBytes = p.ldsBytes + p.tileListBytes;
   mega.blocksPerCU = OccupancyBlocks(mega.fn, mega.ldsBytes);
   mega.stackDepth = c->ds.stackDepth;
   c->integ[kMegaStats] = mega;
@@ -129,7 +129,9 @@ int LaunchSetup(qa_ctx *c, Launch &L, const FrameArgs &a, int ownRows, unsigned 
   rp.x0 = x0; rp.y0 = y0; rp.x1 = x1; rp.y1 = y1;
   rp.spp_min = a.sppMin; rp.spp_max = a.sppMax; rp.max_bounce = a.maxBounce;
   rp.seed = a.seed;
-  rp.tile_row0 = a.tileRow0; rp.tile_row_step = a.tileRowStep; rp.own_tile_rows = ownRows; rp.pad = 0;
+  rp.tile_row0 = a.tileRow0; rp.tile_row_step = a.tileRowStep; rp.own_tile_rows = ownRows;
+  // camera rays on per-tile leaf lists (qa_tilecull.h): where the scene's LDS plan has room for the lists (PlanScene)
+  rp.tile_lists = c->plan.tileListBytes ? (c->optTileLists < 0 ? QA_TILE_LISTS_AUTO : c->optTileLists) : 0;
   rp.sync_samples = c->syncSamples < 0 ? c->plan.syncAuto : c->syncSamples;
   rp.rgb = a.rgb; rp.depth = a.depth; rp.ns = a.ns;
   rp.work_counter = work;

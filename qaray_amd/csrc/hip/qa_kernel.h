@@ -35,6 +35,7 @@
 #include "qa_scene_dev.h"
 #include "qa_seed.h"
 #include "qa_texture_dev.h"
+#include "qa_tilecull.h"
 
 namespace qa {
 
@@ -66,7 +67,6 @@ namespace qa {
 #define QA_TACC(dst, since)
 #endif
 
-struct Ray { f3 p, d; };
 struct RayDiff { f3 dx, dy; };  // directions of the x / y differential rays (they share the origin)
 
 struct Hit {
@@ -192,14 +192,7 @@ __device__ __forceinline__ f3 toLocalFrame(f3 N, f3 sample)
 // ---------------------------------------------------------------------------------------------
 // Node transforms (src/core/node.cpp:112-139, src/core/transform.h:47-61)
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ Ray toNode(const qa_instance &in, const Ray &r)
-{
-  const f3 pos = ld3(in.pos);
-  Ray o;
-  o.p = mulMV(in.itm, r.p - pos);
-  o.d = mulMV(in.itm, (r.p + r.d) - pos) - o.p;
-  return o;
-}
+// (toNode: qa_tilecull.h)
 
 // Node::ToNodeCoords(DiffRay) (src/core/node.cpp:119-126) for the x / y rays: same origin as the
 // central ray, so only the direction needs its own transform.  `before` is the central ray before
@@ -353,12 +346,7 @@ __device__ __forceinline__ bool hitPlane(const Ray &ray, Hit &h, int k, bool clo
   return false;
 }
 
-// One axis of the slab test (src/objects/objects.cpp:360-395, src/core/box.cpp:103-123)
-__device__ __forceinline__ void slab(float d, float p0, float p1, float &t0, float &t1)
-{
-  if (qabs(d) < 1e-7f) { t0 = -QA_BIGFLOAT; t1 = QA_BIGFLOAT; }
-  else { t0 = qmin(p0, p1); t1 = qmax(p0, p1); }
-}
+// (slab, one axis of the slab test: qa_tilecull.h)
 __device__ __forceinline__ void boxEntryExit(const Ray &ray, f3 drcp, f3 bmin, f3 bmax, float &entry, float &exit_)
 {
   const f3 p0 = (-(ray.p - bmin)) * drcp;
@@ -387,24 +375,7 @@ __device__ __forceinline__ void boxEntryExitFast(const Ray &ray, f3 drcp, f3 bmi
 // Slab tests of the library's own tree: the box is widened by `pad` on every side (folded into two
 // copies of the ray origin, so the widening costs nothing per box).  Any conservative form will do
 // here - these tests only decide where the own tree is searched, never what the reference accepts.
-__device__ __forceinline__ void boxEntryExitPadFast(f3 pLo, f3 pHi, f3 drcp, f3 bmin, f3 bmax, float &entry, float &exit_)
-{
-  const f3 p0 = (bmin - pLo) * drcp;
-  const f3 p1 = (bmax - pHi) * drcp;
-  entry = __builtin_fmaxf(__builtin_fmaxf(__builtin_fminf(p0.x, p1.x), __builtin_fminf(p0.y, p1.y)), __builtin_fminf(p0.z, p1.z));
-  exit_ = __builtin_fminf(__builtin_fminf(__builtin_fmaxf(p0.x, p1.x), __builtin_fmaxf(p0.y, p1.y)), __builtin_fmaxf(p0.z, p1.z));
-}
-__device__ __forceinline__ void boxEntryExitPad(f3 pLo, f3 pHi, f3 d, f3 drcp, f3 bmin, f3 bmax, float &entry, float &exit_)
-{
-  const f3 p0 = (bmin - pLo) * drcp;
-  const f3 p1 = (bmax - pHi) * drcp;
-  f3 t0, t1;
-  slab(d.x, p0.x, p1.x, t0.x, t1.x);   // a near-zero direction component leaves the axis unbounded
-  slab(d.y, p0.y, p1.y, t0.y, t1.y);
-  slab(d.z, p0.z, p1.z, t0.z, t1.z);
-  entry = qmax(t0.x, qmax(t0.y, t0.z));
-  exit_ = qmin(t1.x, qmin(t1.y, t1.z));
-}
+// (boxEntryExitPadFast, boxEntryExitPad: qa_tilecull.h - the host check of the tile lists runs the same text)
 
 // TriObj::IntersectTriangle (src/objects/objects.cpp:212-306) on a precomputed 48-byte record
 // (three 16-byte words q0..q2, see DTri).  TriangleArea(axis, P, Q, R) =
@@ -733,10 +704,14 @@ __device__ __forceinline__ bool refReaches(const uint4 *nodes, uint32_t leaf, co
 // tests per cast on the Cornell box) and then check the answer against the reference's rules:
 // the found triangle must be reachable in the reference's tree (refReaches) and no tie may have
 // been seen; otherwise the lane repeats the query on the reference's tree.
-template <bool RES, bool STATS>
+// TL: `tileList` may point at the wave's tile lists (qa_tilecull.h; qa_integrate, section A), `listHdr` is this node's header word
+// there (0: none) and `primary` says which lanes hold a camera ray: where the node has a list, those lanes test the listed
+// leaves' triangles instead of walking the own tree.
+template <bool RES, bool STATS, bool TL = false>
 __device__ __forceinline__ bool hitMesh(const SceneMem<RES> mem, const DMesh &m, const Ray &ray, Hit &h, int k,
                                         bool closest, uint32_t *stack /* LDS, stride QA_BLOCK */, DCounters &cnt,
-                                        TriPick &pick, uint32_t stackCap = 0xFFFFu)
+                                        TriPick &pick, uint32_t stackCap = 0xFFFFu, const uint32_t *tileList = nullptr, uint32_t listHdr = 0,
+                                        bool primary = false)
 {
   const f3 drcp = F3(1.f / ray.d.x, 1.f / ray.d.y, 1.f / ray.d.z);
   // wave-uniform choice: the exact MIN/MAX/threshold form only when some lane needs it
@@ -802,9 +777,36 @@ __device__ __forceinline__ bool hitMesh(const SceneMem<RES> mem, const DMesh &m,
     // side of the mesh bounds.
     // (every point of the ray up to the far side of the bounds lies between the origin and the bounds)
     const float oMax = qmax(qmax(qabs(ray.p.x), qabs(ray.p.y)), qabs(ray.p.z));
-    const float P = qmax(m.absMax, oMax);
-    const float pad = ((QA_SLACK_SCALE * 1.2e-5f) * m.invH) * (P * P) + (QA_SLACK_SCALE * 1e-6f) * P;
-    hasHit = walkBVH<true, false>(fnodes, ftris, m.frootData, ray, drcp, fastSlab, h.z, closest, stack, cnt, bestF, tie, pad);
+    const float pad = fastWalkPad(m.invH, m.absMax, oMax);
+    bool listed = false;
+    if constexpr (TL) {
+      // Camera rays of a tile with a list for this node: the list holds every leaf a ray of the tile can enter, nearest first by a
+      // lower bound of the entry distance, so testing its leaves' triangles - the same test on the same operands - finds what the
+      // walk finds: the closest accepted distance, its triangle, and a tie where two triangles share that distance.
+      // Wave-uniform: no stack, no box tests, every record read at one address by all lanes.
+      listed = primary && (listHdr >> 31);
+      if (listed) {
+        const uint32_t n = (listHdr >> 8) & 0xFFu;
+        const uint32_t *e = tileList + QA_TILE_LIST_HDR + (listHdr & 0xFFu);
+        for (uint32_t j = 0; j < n; ++j) {
+          const uint32_t entry = __builtin_amdgcn_readfirstlane(e[j]);   // QA_TILE_ENTRY
+          const float bound = asF(entry & 0xFFFF0000u);
+          if (!__any(h.z >= bound)) break;   // no lane's held distance reaches this leaf or any later one
+          const uint32_t count = ((entry >> 12) & QA_BVH_COUNT_MASK) + 1;
+          const uint32_t first = entry & 0xFFFu;
+          for (uint32_t i = 0; i < count; ++i) {
+            const uint4 *t = ftris + 3 * (size_t) (first + i);
+            const uint4 t2 = t[2];
+            if (hitTriangleZTie<true>(t[0], t[1], t2, ray, h.z, tie)) {
+              hasHit = true;
+              bestF = t2.w >> 2;
+            }
+          }
+        }
+      }
+    }
+    if (!listed)
+      hasHit = walkBVH<true, false>(fnodes, ftris, m.frootData, ray, drcp, fastSlab, h.z, closest, stack, cnt, bestF, tie, pad);
     // Beyond the mesh bounds a triangle can only be "hit" by cancellation: at a distance D from the
     // triangle the inside test is off by ~64 eps D^2 / (L h) and would have to be off by D / L, i.e.
     // D >= h / (64 eps) ~ 2.6e5 h (all three areas then round to the same product: barycentrics 0, 0, 1).
@@ -863,9 +865,10 @@ __device__ __forceinline__ bool hitMesh(const SceneMem<RES> mem, const DMesh &m,
 // Scene::TraceNodeNormal (src/scene/scene.cpp:50-74): closest hit over every node in pre-order.
 // TEX: also maintains HitInfo::uvw / duvw / hasTexture exactly as the intersectors do (fields are
 // only overwritten by the object types that set them, so stale values survive like in the reference).
-template <bool RES, bool TEX, bool STATS>
+template <bool RES, bool TEX, bool STATS, bool TL = false>
 __device__ __forceinline__ bool traceClosest(const SceneMem<RES> mem, const DScene &sc, const Ray &world, const RayDiff &wd,
-                                             Hit &h, TexHit &th, uint32_t *stack, DCounters &cnt)
+                                             Hit &h, TexHit &th, uint32_t *stack, DCounters &cnt, const uint32_t *tileList = nullptr,
+                                             bool primary = false)
 {
   QA_TALLY(cnt.casts_normal);
   const Ray r0 = rootRay<RES>(sc, world);
@@ -873,6 +876,7 @@ __device__ __forceinline__ bool traceClosest(const SceneMem<RES> mem, const DSce
   grp.node = -1;
   grp.ray = r0;
   bool any = false;
+  uint32_t listSlot = 0;   // TL: mesh nodes with a leaf table met so far (the order buildTileLists numbers them in)
   for (int k = 1; k < sc.num_inst; ++k) {
     const int type = instAt<RES>(sc, k).obj_type;
     if (type == QA_OBJ_NONE) continue;
@@ -891,7 +895,14 @@ __device__ __forceinline__ bool traceClosest(const SceneMem<RES> mem, const DSce
       const DMesh &m = meshAt<RES>(sc, instAt<RES>(sc, k).mesh);
       TriPick pick;
       QA_T(tm0)
-      hit = hitMesh<RES, STATS>(mem, m, r, h, k, true, stack, cnt, pick, sc.stackDepth);
+      uint32_t listHdr = 0;
+      if constexpr (TL) {
+        if (tileList && m.useFast && m.numLeaves) {
+          if (listSlot < QA_TILE_LIST_HDR) listHdr = __builtin_amdgcn_readfirstlane(tileList[listSlot]);
+          ++listSlot;
+        }
+      }
+      hit = hitMesh<RES, STATS, TL>(mem, m, r, h, k, true, stack, cnt, pick, sc.stackDepth, tileList, listHdr, primary);
       QA_TACC(cnt.sl[3], tm0)
       if (TEX && hit && m.hasVT) {
         const uint4 *t = (RES ? mem.img + m.resTris : reinterpret_cast<const uint4 *>(m.tris)) + 3 * (size_t) pick.tri;
@@ -1336,6 +1347,77 @@ __device__ __forceinline__ Surface shadeSurface(const uint4 *mtlTable, const S &
 }
 
 // ---------------------------------------------------------------------------------------------
+// Tile lists (qa_tilecull.h): for the tile whose first pixel is (X0, Y0), which leaves of every mesh node's own tree can a camera
+// ray enter?  The whole wave, once per work item: lane i tests leaf i of the mesh's leaf table (global memory, behind the image),
+// a ballot gives the candidates, and they go to the wave's LDS area `tl` nearest first by the lower bound of their entry
+// distance: a header word (bit 31 | count << 8 | first entry) for each of the first QA_TILE_LIST_HDR such nodes, then the entries
+// (QA_TILE_ENTRY).  A node whose list would be longer than `limit`, or would not fit the area, gets none: its camera rays walk
+// the tree.
+// ---------------------------------------------------------------------------------------------
+template <bool RES>
+__device__ __forceinline__ void buildTileLists(const DScene &sc, uint32_t limit, float X0, float Y0, uint32_t *tl, TileCone *cone)
+{
+  static_assert(QA_TILE_LEAF_CAP <= 64 && QA_TILE_LIST_CAP <= 255, "one lane per leaf, eight bits of a header word per count");
+  static_assert(sizeof(TileCone) <= 64 * sizeof(uint32_t), "the pyramid waits in one row of the wave's traversal stacks");
+  const unsigned lane = __lane_id();
+  if (lane < QA_TILE_LIST_HDR) tl[lane] = 0u;
+  TileLens lens;
+  {
+    f3 cW[4];
+    tileWindow(ld3(sc.cam.screenA), ld3(sc.cam.screenU), ld3(sc.cam.screenV), X0, Y0, cW);
+    lens = tileLens(ld3(sc.cam.pos), cW);
+  }
+  uint32_t cursor = 0, slot = 0;
+  for (int k = 1; k < sc.num_inst && slot < QA_TILE_LIST_HDR; ++k) {
+    if (instAt<RES>(sc, k).obj_type != QA_OBJ_MESH) continue;
+    const DMesh &m = meshAt<RES>(sc, instAt<RES>(sc, k).mesh);
+    if (!m.useFast || m.numLeaves == 0) continue;
+    const uint32_t mySlot = slot++;
+    {
+      // origin and window through the node chain, as localRay takes a ray's origin; the pyramid goes to LDS (every lane writes
+      // the same words), so that none of it occupies registers while the leaves are tested
+      f3 o = ld3(sc.cam.pos), c[4];
+      tileWindow(ld3(sc.cam.screenA), ld3(sc.cam.screenU), ld3(sc.cam.screenV), X0, Y0, c);
+      // (outermost level first; the ancestor of a level is found by walking up from k: no array of nodes)
+      const int depth = instAt<RES>(sc, k).depth;
+      for (int lvl = sc.rootIdentity ? 1 : 0; lvl <= depth && lvl <= QA_MAX_NODE_DEPTH; ++lvl) {
+        int a = k;
+        for (int up = depth; up > lvl; --up) a = instAt<RES>(sc, a).parent;
+        const qa_instance &in = instAt<RES>(sc, a);
+        o = tileNodePoint(in, o);
+        for (int i = 0; i < 4; ++i) c[i] = tileNodePoint(in, c[i]);
+      }
+      __builtin_amdgcn_wave_barrier();   // (the last node's tests have read the pyramid)
+      tileCone(lens, o, c, cone);
+      asm volatile("" ::: "memory");     // read it back from LDS below: do not keep it in registers
+    }
+    const float pad = fastWalkPad(m.invH, m.absMax, cone->oAbs);
+    bool cand = false;
+    float bound = 0.f;
+    uint32_t word = 0;
+    if (lane < m.numLeaves) {
+      const uint4 *rec = sc.resident + m.resLeaves + 2 * (size_t) lane;   // DNode
+      const uint4 a = ldGlobal(rec), b = ldGlobal(rec + 1);
+      cand = tileConeMeetsBox(cone, F3(asF(a.x), asF(a.y), asF(a.z)), F3(asF(a.w), asF(b.x), asF(b.y)), pad, &bound);
+      word = b.z;
+    }
+    const unsigned long long mask = __ballot(cand);
+    const uint32_t count = (uint32_t) __popcll(mask);
+    if (count > limit || cursor + count > QA_TILE_LIST_CAP) continue;
+    uint32_t rank = 0;   // candidates that come before this lane's
+    for (unsigned long long rest = mask; rest; rest &= rest - 1) {
+      const int j = __ffsll((long long) rest) - 1;
+      const float bj = __shfl(bound, j);
+      rank += (bj < bound || (bj == bound && j < (int) lane)) ? 1u : 0u;
+    }
+    if (cand) tl[QA_TILE_LIST_HDR + cursor + rank] = QA_TILE_ENTRY(word, __float_as_uint(bound));
+    if (lane == 0) tl[mySlot] = 0x80000000u | (count << 8) | cursor;
+    cursor += count;
+  }
+  __builtin_amdgcn_wave_barrier();
+}
+
+// ---------------------------------------------------------------------------------------------
 // Per-lane path state
 // ---------------------------------------------------------------------------------------------
 struct Path {
@@ -1350,7 +1432,7 @@ struct Path {
 };
 
 // ---------------------------------------------------------------------------------------------
-// The kernel.  Dynamic LDS: [resident scene image (RES) | traversal stacks (stackDepth x 256)]
+// The kernel.  Dynamic LDS: [resident scene image (RES) | traversal stacks (stackDepth x 256) | per-lane columns | tile lists (RES, RenderParams::tile_lists)]
 // ---------------------------------------------------------------------------------------------
 // Area lights draw random numbers, and the reference evaluates a hit's lights only AFTER the whole
 // recursive subtree below it (MtlBlinn_PhotonMap.cpp:374-479 precede :484-498).  AREA variants
@@ -1398,6 +1480,15 @@ __global__ __launch_bounds__(QA_BLOCK, QA_WAVES_FOR(RES, LIGHTS)) void qa_integr
 #define QA_PUT_L(...) { const f3 v_ = (__VA_ARGS__); if (LCOLS) { acc[9 * QA_BLOCK] = v_.x; acc[10 * QA_BLOCK] = v_.y; acc[11 * QA_BLOCK] = v_.z; } else path.L = v_; }
 #define QA_GET_Q() (LCOLS ? __float_as_uint(acc[13 * QA_BLOCK]) : q)
 #define QA_GET_SIDX() (LCOLS ? __float_as_int(acc[14 * QA_BLOCK]) : sidx)
+  // Tile lists for the camera rays (qa_tilecull.h): the wave's area behind the per-lane columns, when the launch made room for it.
+  // With depth of field the camera rays of a tile share no origin.
+  // (in the variant without lights only: the lit and textured resident variants pay for the shared text in spilled registers)
+  constexpr bool TL = RES && !LIGHTS && !TEX && !AREA && !STATS && !PHOTON;
+  uint32_t *tileList = nullptr;
+  if constexpr (TL)
+    if (rp.tile_lists > 0 && !(sc.cam.dof > 0.1f))
+      tileList = reinterpret_cast<uint32_t *>(s_dyn + sc.residentVec4) + ((size_t) sc.stackDepth + QA_LANE_SLOTS_RES) * QA_BLOCK +
+                 __builtin_amdgcn_readfirstlane(threadIdx.x / 64) * QA_TILE_LIST_DWORDS;
 
   // work items walk 8x8 pixel tiles (a wave starts on a compact screen patch); ragged right /
   // bottom tiles contain padding slots that are simply skipped.
@@ -1493,6 +1584,27 @@ __global__ __launch_bounds__(QA_BLOCK, QA_WAVES_FOR(RES, LIGHTS)) void qa_integr
             __builtin_amdgcn_s_sleep(16);
           }
           __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        }
+      }
+      if constexpr (TL) {
+        if (tileList && base < total) {
+          const unsigned tile = rp.tile_order ? rp.tile_order[item] : item;
+          const unsigned otr = tile / tilesX;
+          buildTileLists<RES>(sc, (uint32_t) rp.tile_lists, (float) (rp.x0 + (int) ((tile % tilesX) * 8)),
+                              (float) (rp.y0 + (int) (((unsigned) rp.tile_row0 + otr * (unsigned) rp.tile_row_step) * 8)), tileList,
+                              reinterpret_cast<TileCone *>(stack - lane));   // row 0 of the wave's stacks: no walk is under way
+          // every lane that is alive asks for a pixel here: what it holds of its last path is dead, and saying so keeps those
+          // registers out of the way of the list build (a lane starts its next path from section B)
+          path.ray.p = F3(0, 0, 0);
+          path.ray.d = F3(0, 0, 1);
+          path.absorbMtl = -1;
+          path.bounce = 0;
+          path.fromDiffuse = false;
+          path.primary = true;
+          rng = 1;
+          sidx = 0;
+          px = py = 0;
+          q = 0;
         }
       }
       if (alive) {
@@ -1602,7 +1714,7 @@ __global__ __launch_bounds__(QA_BLOCK, QA_WAVES_FOR(RES, LIGHTS)) void qa_integr
       th.duvw0 = th.duvw1 = F3(0, 0, 0);
       th.hasTexture = false;
       QA_T(tC)
-      const bool found = traceClosest<RES, TEX, STATS>(mem, sc, path.ray, pathDiff, h, th, stack, cnt);
+      const bool found = traceClosest<RES, TEX, STATS, TL>(mem, sc, path.ray, pathDiff, h, th, stack, cnt, tileList, path.primary);
       QA_TACC(cnt.sl[2], tC)
       if (path.primary && QA_GET_SIDX() == 0) rp.depth[QA_GET_Q()] = found ? h.z : QA_BIGFLOAT;
 

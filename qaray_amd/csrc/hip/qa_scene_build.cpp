@@ -9,6 +9,7 @@
 #include "qa_device_math.h"
 #include "qa_fastbvh.h"
 #include "qa_texel_dev.h"
+#include "qa_tilecull.h"
 #include "qaray_host.h"
 
 namespace qa {
@@ -282,6 +283,11 @@ struct MeshBuild {
       t.ftris[i] = t.tris[e];
       t.ftris[i].axis = (t.tris[e].axis & 3u) | ((e & 0x7FFFu) << 2) | ((t.shade[e].pad & 0x7FFFu) << 17);
     }
+    // the leaves alone, for the per-tile lists of camera rays (qa_tilecull.h); a tree of more leaves than one ballot covers has none
+    // (every slot from 1 on is the root or a child; slot 0 and a padding slot carry no leaf bit)
+    for (size_t i = 1; i < fb.nodes.size() && m.num_faces > 0; ++i)
+      if (fb.nodes[i].data & QA_BVH_LEAF_BIT) t.leaves.push_back(fb.nodes[i]);
+    if (t.leaves.size() > QA_TILE_LEAF_CAP || m.num_faces > QA_TILE_ENTRY_FACES) t.leaves.clear();
     return fb.depth;
   }
 
@@ -598,6 +604,13 @@ void BuildImage(SceneTables &out)
     dm.numNormals = (uint32_t) (mt.normals.size() / 4);
   }
   out.ds.resMaterials = append(out.materials.data(), out.materials.size() * sizeof(DMaterial));
+  // what follows stays in global memory: the leaf tables are read once per work item (qa_integrate, section A)
+  out.imageLdsVec4 = image.size();
+  for (size_t mi = 0; mi < out.mesh.size(); ++mi) {
+    DMesh &dm = out.plan.meshes[mi];
+    dm.numLeaves = dm.useFast ? (uint32_t) out.mesh[mi].leaves.size() : 0u;
+    dm.resLeaves = dm.numLeaves ? append(out.mesh[mi].leaves.data(), out.mesh[mi].leaves.size() * sizeof(DNode)) : 0u;
+  }
 }
 
 // the DScene fields that come from the header, the stack and LDS sizes, and residency
@@ -610,15 +623,24 @@ void PlanScene(const Blob &b, const BuildKnobs &k, uint32_t stackNeedMax, SceneT
   ds.stackDepth = std::max(stackNeedMax, 8u);
   // LDS per workgroup: traversal stacks + 6 accumulator floats per lane (mean, variance); small scenes stay entirely on the CU
   const size_t stackBytes = ((size_t) ds.stackDepth + QA_LANE_SLOTS) * QA_BLOCK * sizeof(uint32_t);
-  const size_t imageBytes = out.image.size() * sizeof(uint4);
+  const size_t imageBytes = out.imageLdsVec4 * sizeof(uint4);
   if (stackBytes > kMaxLdsPerBlock) Refuse(QA_EUNSUPPORTED, "BVH too deep for the LDS traversal stack");
   // workgroups of a resident scene also keep the cold path state in LDS columns (QA_LANE_SLOTS_RES)
   const size_t stackBytesRes = ((size_t) ds.stackDepth + QA_LANE_SLOTS_RES) * QA_BLOCK * sizeof(uint32_t);
   plan.resident = imageBytes > 0 && imageBytes + stackBytesRes <= kResidentLdsBudget && h->num_instances <= QA_KARG_INST &&
                   h->num_meshes <= QA_KARG_MESH;
   plan.ldsBytes = plan.resident ? stackBytesRes + imageBytes : stackBytes;
+  // the waves' tile lists: only where some mesh has a leaf table and the workgroups per CU stay what they are.  A CU's 160 KB of
+  // LDS are handed out in units of 1280 bytes: the Cornell box's 31 520 B are 25 units, five workgroups per CU; with 960 B more
+  // (26 units) four were resident and the frame took 80 ms instead of 71 (profiles/tile_lists.txt)
+  plan.tileListBytes = 0;
+  const size_t listBytes = (QA_BLOCK / 64) * QA_TILE_LIST_DWORDS * sizeof(uint32_t), cuLds = 160 * 1024, unit = 1280;
+  auto perCU = [&](size_t bytes) { return cuLds / ((bytes + unit - 1) / unit * unit); };
+  bool anyLeaves = false;
+  for (const DMesh &dm : plan.meshes) anyLeaves = anyLeaves || dm.numLeaves > 0;
+  if (plan.resident && anyLeaves && perCU(plan.ldsBytes + listBytes) == perCU(plan.ldsBytes)) plan.tileListBytes = listBytes;
   if (plan.resident) {
-    ds.residentVec4 = (uint32_t) out.image.size();
+    ds.residentVec4 = (uint32_t) out.imageLdsVec4;
     std::copy(b.at<qa_instance>(h->off_instances), b.at<qa_instance>(h->off_instances) + h->num_instances, ds.instv);
   } else ds.resMaterials = 0;
   ds.csSlots = std::min(std::max(k.csSlots, 64u), 256u);   // an instance enters up to 64 rays at once; 8 bits of an item
@@ -754,9 +776,9 @@ int RebuildSceneSide(const unsigned char *blob, size_t nbytes, const BuildKnobs 
     PlanLightsAndRoot(b, out);
     plan.csFits = out.csFitsMeshes;
     const bool anySpecularLobes = BuildMaterials(b, out);
-    // the resident image ends with the material table (BuildImage); everything before it is mesh data
+    // the resident image's LDS part ends with the material table (BuildImage); everything before it is mesh data
     const size_t mtlVec4 = (out.materials.size() * sizeof(DMaterial) + 15) / 16;
-    if (out.image.size() >= mtlVec4 && mtlVec4) memcpy(out.image.data() + (out.image.size() - mtlVec4), out.materials.data(), out.materials.size() * sizeof(DMaterial));
+    if (out.image.size() >= out.imageLdsVec4 && out.imageLdsVec4 >= mtlVec4 && mtlVec4) memcpy(out.image.data() + (out.imageLdsVec4 - mtlVec4), out.materials.data(), out.materials.size() * sizeof(DMaterial));
     BuildCsInstances(b, out);
     plan.syncAuto = SyncAuto(plan, anySpecularLobes);
     PlanScene(b, knobs, out.ds.stackNeed, out);

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "qa_scene_dev.h"
+#include "qa_tilecull.h"
 #include "qa_widebvh.h"
 
 namespace qa {
@@ -31,6 +32,7 @@ struct MeshTables {
   std::vector<DTri> tris, ftris, wtris;  // element order, own tree's leaf order, 4-wide tree's leaf order
   std::vector<DTriShade> shade;
   std::vector<uint32_t> fmap;
+  std::vector<DNode> leaves;             // the own tree's leaves (qa_tilecull.h); empty beyond QA_TILE_LEAF_CAP
   std::vector<float> vt;                 // 6 floats per element (textured scenes)
   std::vector<float> normals;            // distinct face normals, 4 floats each (resident image)
   WideBvh wide;                          // qa_widebvh.h
@@ -46,6 +48,7 @@ struct ScenePlan {
   bool csCullOk = false;                 // the instance-culling constants are finite (otherwise every instance is visited)
   int syncAuto = 0;                      // samples of a wave start together unless the frame decides otherwise
   size_t ldsBytes = 0;                   // dynamic LDS of qa_integrate: resident image + stacks, or stacks
+  size_t tileListBytes = 0;              // + the waves' tile lists behind them (qa_tilecull.h), where they cost no workgroup per CU; else 0
 };
 // a mesh hit without texture vertices keeps the uvw of an earlier, farther hit: history only a sequential walk has
 inline bool MissesTexcoords(const ScenePlan &p, const DMesh &m) { return p.textured && m.num_faces > 0 && !m.hasVT; }
@@ -68,7 +71,8 @@ struct SceneTables {
   std::vector<uint32_t> texOff;
   std::vector<float> taps;
   std::vector<TexLayout> texLayout;      // per texture, textured or not: what no edit may change
-  std::vector<uint4> image;              // the resident image (uploaded when plan.resident)
+  std::vector<uint4> image;              // the resident image (uploaded when plan.resident): the LDS part, then the meshes' leaf tables
+  size_t imageLdsVec4 = 0;               // its LDS part: [nodes | tris | shade | own tree] per mesh, then the materials
   // what RebuildSceneSide needs of the mesh-side stages beside the tables above
   bool csFitsMeshes = false;             // plan.csFits as BuildMeshes and BuildCsTrees left it (the node transforms may still veto)
   uint32_t meshBuilds = 0;               // calls of the per-mesh builder this BuildScene made

@@ -123,7 +123,12 @@ struct DMesh {
   float nearPad;               // fp32 slack of the reference's inside test (qa_widebvh.h ComputeMeshSlack)
   float cancelDist;            // ray origins farther out than this keep the reference tree
   uint32_t csRootWord;         // root of this mesh's 4-wide tree inside the scene-wide arrays DScene::csNodes / csTris (qa_kernel_cs.h)
-  uint32_t csPad;
+  // leaf table of the own tree (qa_tilecull.h): numLeaves DNode records (a leaf's stored box and its leaf word) at
+  // DScene::resident + resLeaves, behind the part of the image that is copied into LDS; 0 = none (no own tree, or more than
+  // QA_TILE_LEAF_CAP leaves)
+  uint32_t resLeaves;
+  uint32_t numLeaves;
+  uint32_t leafPad;
 };
 
 // The widening of the own search trees' boxes and the parallelism / cancellation guards (qa_kernel.h hitMesh, qa_wf.h,
@@ -189,7 +194,7 @@ struct DScene {
   DCamera cam;
   float background[3], environment[3];
   int32_t num_inst, num_lights, halton_count, num_materials;
-  uint32_t residentVec4;       // size of the resident image in 16-byte units (0 = not resident)
+  uint32_t residentVec4;       // size of the resident image's LDS part in 16-byte units (0 = not resident); the meshes' leaf tables follow it in global memory
   uint32_t resMaterials;       // offset of the material table inside it (16-byte units)
   uint32_t stackNeed;          // max over meshes
   uint32_t rootIdentity;       // instance 0 has tm = itm = I and pos = 0 (always, for XML scenes)
@@ -255,7 +260,8 @@ struct RenderParams {
   int32_t x0, y0, x1, y1;      // region
   int32_t spp_min, spp_max, max_bounce;
   uint32_t seed;
-  int32_t tile_row0, tile_row_step, own_tile_rows, pad;  // which 8-row strips of the region
+  int32_t tile_row0, tile_row_step, own_tile_rows;  // which 8-row strips of the region
+  int32_t tile_lists;          // > 0: camera rays of a tile test a per-tile leaf list of at most this many leaves per mesh instead of walking the own tree (qa_tilecull.h); 0 = off
   int32_t sync_samples;        // 1: a wave starts its lanes' next samples together (coherent primary rays)
   float *rgb;                  // region-local outputs
   float *depth;
