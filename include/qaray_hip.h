@@ -40,6 +40,8 @@
  *   qa_progressive_gbuffer_device  colour, node and material - for picking in a viewer and as guides for a preview filter)
  *   qa_denoise_guided_device,      (no counterpart: the preview filter with those normal and albedo planes as two more
  *   qa_progressive_denoise_guided* edge-stopping guides)
+ *   qa_reproject_device,           (no counterpart: the reference renders every frame from nothing; the accumulated frame of
+ *   qa_progressive_reproject_device   an earlier camera carried into the frame of the camera as it now stands)
  *   qa_get_counters                (no counterpart: the reference only prints wall-clock)
  *   qa_get_kernel_time             Renderer::StartTimer/StopTimer       src/renderers/renderer.cpp:42-63
  */
@@ -350,6 +352,44 @@ int qa_denoise_guided_device(qa_ctx *ctx, const float *d_rgb, const float *d_dep
 int qa_progressive_denoise_guided(qa_ctx *ctx, const qa_denoise_guided_params *params, float *rgb);
 int qa_progressive_denoise_guided_device(qa_ctx *ctx, const qa_denoise_guided_params *params, float *d_rgb, void *hip_stream);
 
+/* Temporal reprojection: the accumulated frame of an EARLIER camera (the history) carried into the frame just rendered from the
+ * camera as it now stands, so that a camera move keeps the samples of the surface points both cameras see.  The header comment of
+ * qaray_amd/csrc/hip/qa_reproject_dev.h is its specification.  Both frames cover pixels [x0, x0 + width) x [y0, y0 + height) of the
+ * image, region-local and row-major.  Per pixel, from the depth of sample 0 (the depth plane of qa_render_region / qa_gbuffer_region)
+ * and the two qa_camera records, the point the pixel shows is projected into the old camera; the four history pixels around it are
+ * blended bilinearly, each counting only when it holds history (length > 0), is finite, has the pixel's class (miss / hit), lies
+ * within depth_tolerance (relative) of the depth the old camera must have seen the point at, and - when both ids planes are given -
+ * carries the pixel's node and material ids.  With history c_h of effective sample count L = min(length, max_history):
+ *   out = c_h + (c - c_h) * ns / (L + ns),  out_length = L + ns          without:  out = c (its bits),  out_length = ns
+ * A pixel with ns == 0 or a colour or depth that is not finite passes through with length 0.  Equal cameras reproject every pixel
+ * onto itself, exactly.  The caller keeps out_rgb, out_length and the current frame's depth (and ids) as the next history.
+ * Limits: no neighbourhood colour clamp, no per-pixel variance, no moving objects (the ids catch an edited node only if its id
+ * changes: reset the history after any edit that is not a camera move), a pinhole lens (the lens draw of dof > 0.1 is ignored).
+ *   qa_reproject_device               plain device buffers: the current frame (d_ids may be NULL), the history (d_hist_ids NULL if
+ *                                     and only if d_ids is) -> d_out_rgb (3 floats per pixel), d_out_length (1).  d_out_rgb ==
+ *                                     d_rgb is allowed (a pixel reads only its own current pixel); no other overlap of an output
+ *                                     with an input or the other output is, and none with a history plane.  One kernel; only enqueues on
+ *                                     hip_stream (NULL = the context's stream, as for qa_render_region_device).  No scene is needed.
+ *   qa_progressive_reproject_device   the current frame is the progressive frame's preview straight from its slabs - the floats
+ *                                     qa_progressive_read returns - with the frame's region and the resident scene's camera; with
+ *                                     d_hist_ids the current ids are computed by qa_progressive_gbuffer_device on hip_stream into a
+ *                                     plane of the context (8 bytes per pixel of the largest frame so far; the call that grows it
+ *                                     waits for the device).  Waits for the frame's last pass as qa_progressive_denoise_device
+ *                                     does.  QA_EINVAL on a stale frame (its pixels are not the resident camera's).  The frame is
+ *                                     not changed.
+ * qa_reproject_params_default: depth_tolerance 0.05, max_history 64, flags 0.  QA_EINVAL: a null camera, params or plane, width or
+ * height < 1, a negative origin or a side beyond 2^24, one ids plane without the other, a depth_tolerance that is not finite or is
+ * negative, a max_history that is not finite and positive, flags other than 0, an aliased output as above. */
+typedef struct qa_reproject_params { float depth_tolerance, max_history; uint32_t flags; } qa_reproject_params;
+int qa_reproject_params_default(qa_reproject_params *params);
+int qa_reproject_device(qa_ctx *ctx, const qa_camera *prev_cam, const qa_camera *cur_cam, int x0, int y0, int width, int height,
+                        const float *d_rgb, const float *d_depth, const uint32_t *d_nsamples, const int32_t *d_ids,
+                        const float *d_hist_rgb, const float *d_hist_depth, const float *d_hist_length, const int32_t *d_hist_ids,
+                        const qa_reproject_params *params, float *d_out_rgb, float *d_out_length, void *hip_stream);
+int qa_progressive_reproject_device(qa_ctx *ctx, const qa_camera *prev_cam, const float *d_hist_rgb, const float *d_hist_depth,
+                                    const float *d_hist_length, const int32_t *d_hist_ids, const qa_reproject_params *params,
+                                    float *d_out_rgb, float *d_out_length, void *hip_stream);
+
 /* Counters accumulated since the last reset (synchronises the context first). */
 int qa_get_counters(qa_ctx *ctx, qa_counters *out);
 int qa_reset_counters(qa_ctx *ctx);
@@ -457,6 +497,13 @@ int qa_test_denoise_host(const float *rgb, const float *depth, const uint32_t *n
                          const qa_denoise_params *params, float *out_rgb);
 int qa_test_denoise_guided_host(const float *rgb, const float *depth, const uint32_t *nsamples, const float *normal, const float *albedo,
                                 int width, int height, const qa_denoise_guided_params *params, float *out_rgb);
+
+/* Self-test hook for the reprojection (qaray_amd/csrc/hip/qa_reproject_dev.h): the source of qa_reproject_device's kernel compiled
+ * for the host, pixel after pixel over host arrays, arguments in the same order (no GPU and no context needed). */
+int qa_test_reproject_host(const qa_camera *prev_cam, const qa_camera *cur_cam, int x0, int y0, int width, int height, const float *rgb,
+                           const float *depth, const uint32_t *nsamples, const int32_t *ids, const float *hist_rgb, const float *hist_depth,
+                           const float *hist_length, const int32_t *hist_ids, const qa_reproject_params *params, float *out_rgb,
+                           float *out_length);
 
 #ifdef __cplusplus
 }

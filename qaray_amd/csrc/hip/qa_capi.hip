@@ -155,8 +155,8 @@ int qa_ctx_destroy(qa_ctx *c)
     if (p) (void) hipFree(p);
   for (void *p : {(void *) c->hEditStage, (void *) c->hStop})
     if (p) (void) hipHostFree(p);
-  for (DevBuf *b : {&c->pixState, &c->tileProgress, &c->stageRgb, &c->stageDepth, &c->stageNs, &c->stageGbuffer, &c->displayStage, &c->denoisePlanes}) b->Free();
-  for (StreamFence *f : {&c->lastFrame, &c->lastEdit, &c->lastDisplay, &c->lastDenoise, &c->texSource, &c->prog.done})
+  for (DevBuf *b : {&c->pixState, &c->tileProgress, &c->stageRgb, &c->stageDepth, &c->stageNs, &c->stageGbuffer, &c->displayStage, &c->denoisePlanes, &c->reprojectIds}) b->Free();
+  for (StreamFence *f : {&c->lastFrame, &c->lastEdit, &c->lastDisplay, &c->lastDenoise, &c->lastReproject, &c->texSource, &c->prog.done})
     if (f->ev) (void) hipEventDestroy(f->ev);
   if (c->stream) (void) hipStreamDestroy(c->stream);
   delete c;

@@ -239,6 +239,9 @@ struct qa_ctx {
   // the denoiser's working planes (qa_denoise.hip): 40 bytes per pixel of the largest frame filtered so far, made on first use
   DevBuf denoisePlanes;
   StreamFence lastDenoise;      // the planes are one per context: a filter on another stream waits
+  // qa_progressive_reproject_device's ids plane of the current frame (qa_reproject.hip): 8 bytes per pixel of the largest frame so far
+  DevBuf reprojectIds;
+  StreamFence lastReproject;    // one per context: a call on another stream waits
 };
 
 void FreePhotonMaps(qa_ctx *c);  // qa_photon.hip

@@ -1,0 +1,220 @@
+// qa_reproject.hip — temporal reprojection of qa_reproject_dev.h on the device (qa_reproject_device, qa_progressive_reproject_device)
+// and the same source on the host (qa_test_reproject_host).  One kernel, one pixel per thread on 16x16 tiles: the pixel's own 20
+// bytes (28 with ids), then a gather of up to four history taps of 20 bytes (28 with ids) around the point the old camera saw the
+// pixel's surface at; 16 bytes are written.  Neighbouring lanes project to neighbouring history pixels (the map between two views of
+// a surface is smooth), so the taps of a wave share their cache lines as a 2x2 filter's do: no LDS, no working plane but the ids of
+// a progressive frame.  tools/gpu_reproject_cost.py puts the traffic beside the measured times.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstddef>
+#include <cstdint>
+#include <cstring>
+
+#include "qa_ctx.h"
+#include "qa_reproject_dev.h"
+
+namespace qa {
+
+#define QA_REPROJECT_TILE 16
+
+// The current frame.  state = null: the plain buffers.  Else the progressive frame's slabs, resolved as qa_prog_resolve does
+// (qa_progressive.hip; qa_denoise.hip's DenoiseSrc is the same rule): the running mean and samples so far of an unfinished pixel,
+// the outputs of a finished one
+struct ReprojectSrc {
+  const float *rgb, *depth;
+  const uint32_t *ns, *state;
+  int W;
+  __device__ __forceinline__ ReprojectPixel operator()(int x, int y) const
+  {
+    const size_t q = (size_t) y * (size_t) W + (size_t) x;
+    ReprojectPixel p;
+    p.z = depth[q];
+    if (state) {
+      const uint4 a = reinterpret_cast<const uint4 *>(state)[2 * q];
+      if (!(a.y & 0x80000000u)) {
+        p.r = __uint_as_float(a.z); p.g = __uint_as_float(a.w); p.b = __uint_as_float(state[8 * q + 4]);
+        p.ns = a.y;
+        return p;
+      }
+    }
+    p.r = rgb[3 * q]; p.g = rgb[3 * q + 1]; p.b = rgb[3 * q + 2];
+    p.ns = ns[q];
+    return p;
+  }
+};
+
+// The history planes / the ids planes of both frames, on the device and on the host
+struct ReprojectHistory {
+  const float *rgb, *depth, *length;
+  int W;
+  __host__ __device__ __forceinline__ void operator()(int x, int y, ReprojectTap &t) const
+  {
+    const size_t q = (size_t) y * (size_t) W + (size_t) x;
+    t.length = length[q];
+    t.z = depth[q];
+    t.r = rgb[3 * q]; t.g = rgb[3 * q + 1]; t.b = rgb[3 * q + 2];
+  }
+};
+struct ReprojectIds {
+  const int32_t *plane[2];   // current, history
+  int W;
+  __host__ __device__ __forceinline__ void operator()(int which, int x, int y, int *out) const
+  {
+    const size_t q = (size_t) y * (size_t) W + (size_t) x;
+    out[0] = plane[which][2 * q]; out[1] = plane[which][2 * q + 1];
+  }
+};
+
+__global__ __launch_bounds__(256) void qa_reproject(ReprojectSetup S, ReprojectSrc cur, ReprojectHistory hist, ReprojectIds ids, int withIds, float *outRgb,
+                                                    float *outLength)
+{
+  const int x = (int) (blockIdx.x * QA_REPROJECT_TILE + (threadIdx.x & 15u)), y = (int) (blockIdx.y * QA_REPROJECT_TILE + (threadIdx.x >> 4));
+  if (x >= S.W || y >= S.H) return;
+  float o[3];
+  const float len = reprojectPixel(S, cur, hist, ids, withIds != 0, x, y, o);
+  const size_t q = (size_t) y * (size_t) S.W + (size_t) x;
+  outRgb[3 * q] = o[0]; outRgb[3 * q + 1] = o[1]; outRgb[3 * q + 2] = o[2];
+  outLength[q] = len;
+}
+
+}  // namespace qa
+
+static bool Overlap(const void *a, size_t na, const void *b, size_t nb)
+{
+  const uintptr_t p = (uintptr_t) a, q = (uintptr_t) b;
+  return a && b && p < q + nb && q < p + na;
+}
+
+// What every entry checks of its sizes, parameters and planes.  rgb / depth / ns / ids: the current frame's, null for a progressive
+// frame (its slabs are the library's own)
+static int CheckReproject(const qa_camera *prev, const qa_camera *cur, int x0, int y0, int W, int H, const float *rgb, const float *depth, const uint32_t *ns,
+                          const int32_t *ids, bool idsGiven, const float *hRgb, const float *hDepth, const float *hLength, const int32_t *hIds,
+                          const qa_reproject_params *p, const float *outRgb, const float *outLength)
+{
+  if (!prev || !cur) return Fail(QA_EINVAL, "null camera");
+  if (!p) return Fail(QA_EINVAL, "null parameters");
+  if (!hRgb || !hDepth || !hLength || !outRgb || !outLength) return Fail(QA_EINVAL, "null buffer");
+  // (a side of 2^24 at most: pixel coordinates are exact floats)
+  if (W < 1 || H < 1 || x0 < 0 || y0 < 0 || x0 > (1 << 24) - W || y0 > (1 << 24) - H) return Fail(QA_EINVAL, "bad frame size");
+  if ((uint64_t) W * (uint64_t) H > 0x7FFFFFFFull) return Fail(QA_EINVAL, "too many pixels");
+  if (!std::isfinite(p->depth_tolerance) || p->depth_tolerance < 0.f) return Fail(QA_EINVAL, "a depth_tolerance that is not finite or is negative");
+  if (!std::isfinite(p->max_history) || !(p->max_history > 0.f)) return Fail(QA_EINVAL, "a max_history that is not finite and positive");
+  if (p->flags != 0u) return Fail(QA_EINVAL, "unknown flags");
+  if (idsGiven != (hIds != nullptr)) return Fail(QA_EINVAL, "one ids plane without the other");
+  const size_t n = (size_t) W * (size_t) H;
+  const struct { const void *p; size_t bytes; bool history; } in[] = {{rgb, 12 * n, false}, {depth, 4 * n, false}, {ns, 4 * n, false}, {ids, 8 * n, false},
+                                                                     {hRgb, 12 * n, true}, {hDepth, 4 * n, true}, {hLength, 4 * n, true}, {hIds, 8 * n, true}};
+  if (Overlap(outRgb, 12 * n, outLength, 4 * n)) return Fail(QA_EINVAL, "the outputs overlap");
+  for (const auto &b : in) {
+    if (b.history && (Overlap(outRgb, 12 * n, b.p, b.bytes) || Overlap(outLength, 4 * n, b.p, b.bytes)))
+      return Fail(QA_EINVAL, "an output aliases a history plane");
+    // a pixel reads only its own current pixel: the colour may be written where it was read, and nothing else may overlap
+    const bool inPlace = b.p == rgb && outRgb == rgb;
+    if (!b.history && !inPlace && Overlap(outRgb, 12 * n, b.p, b.bytes))
+      return Fail(QA_EINVAL, "an output overlaps an input (only d_out_rgb == d_rgb is allowed)");
+    if (!b.history && Overlap(outLength, 4 * n, b.p, b.bytes)) return Fail(QA_EINVAL, "an output overlaps an input (only d_out_rgb == d_rgb is allowed)");
+  }
+  return QA_OK;
+}
+
+static int LaunchReproject(const ReprojectSetup &S, const ReprojectSrc &src, const float *hRgb, const float *hDepth, const float *hLength, const int32_t *ids,
+                  const int32_t *hIds, float *outRgb, float *outLength, hipStream_t s)
+{
+  const ReprojectHistory hist = {hRgb, hDepth, hLength, S.W};
+  const ReprojectIds id = {{ids, hIds}, S.W};
+  const dim3 grid((unsigned) ((S.W + QA_REPROJECT_TILE - 1) / QA_REPROJECT_TILE), (unsigned) ((S.H + QA_REPROJECT_TILE - 1) / QA_REPROJECT_TILE)), block(256);
+  hipLaunchKernelGGL(qa::qa_reproject, grid, block, 0, s, S, src, hist, id, (ids && hIds) ? 1 : 0, outRgb, outLength);
+  HIP_TRY(hipGetLastError());
+  return QA_OK;
+}
+
+extern "C" {
+
+int qa_reproject_params_default(qa_reproject_params *p)
+{
+  if (!p) return Fail(QA_EINVAL, "null parameters");
+  p->depth_tolerance = QA_REPROJECT_DEFAULT_DEPTH_TOLERANCE;
+  p->max_history = QA_REPROJECT_DEFAULT_MAX_HISTORY;
+  p->flags = 0u;
+  return QA_OK;
+}
+
+int qa_reproject_device(qa_ctx *c, const qa_camera *prev_cam, const qa_camera *cur_cam, int x0, int y0, int width, int height, const float *d_rgb,
+                        const float *d_depth, const uint32_t *d_ns, const int32_t *d_ids, const float *d_hist_rgb, const float *d_hist_depth,
+                        const float *d_hist_length, const int32_t *d_hist_ids, const qa_reproject_params *p, float *d_out_rgb, float *d_out_length,
+                        void *hip_stream)
+{
+  if (int rc = Enter(c)) return rc;
+  if (!d_rgb || !d_depth || !d_ns) return Fail(QA_EINVAL, "null buffer");
+  if (int rc = CheckReproject(prev_cam, cur_cam, x0, y0, width, height, d_rgb, d_depth, d_ns, d_ids, d_ids != nullptr, d_hist_rgb, d_hist_depth, d_hist_length,
+                              d_hist_ids, p, d_out_rgb, d_out_length))
+    return rc;
+  const ReprojectSetup S = reprojectSetup(*prev_cam, *cur_cam, x0, y0, width, height, p->depth_tolerance, p->max_history);
+  const ReprojectSrc src = {d_rgb, d_depth, d_ns, nullptr, width};
+  return LaunchReproject(S, src, d_hist_rgb, d_hist_depth, d_hist_length, d_ids, d_hist_ids, d_out_rgb, d_out_length, StreamOf(c, hip_stream));
+}
+
+int qa_progressive_reproject_device(qa_ctx *c, const qa_camera *prev_cam, const float *d_hist_rgb, const float *d_hist_depth, const float *d_hist_length,
+                                    const int32_t *d_hist_ids, const qa_reproject_params *p, float *d_out_rgb, float *d_out_length, void *hip_stream)
+{
+  int rc = ProgActive(c);
+  if (rc != QA_OK) return rc;
+  const qa_ctx::Progressive &f = c->prog;
+  if (f.stale) return Fail(QA_EINVAL, "the frame's pixels are not the resident camera's (the scene was edited): qa_progressive_restart first");
+  const int W = f.args.x1 - f.args.x0, H = f.args.y1 - f.args.y0;
+  // the camera the frame was rendered from: the header's camera block of the resident blob, as qa_scene_edit_camera leaves it
+  qa_camera cam;
+  memcpy(&cam, c->hostBlob.data() + offsetof(qa_flat_header, screenA), sizeof(qa_camera));
+  if ((rc = CheckReproject(prev_cam, &cam, f.args.x0, f.args.y0, W, H, nullptr, nullptr, nullptr, nullptr, d_hist_ids != nullptr, d_hist_rgb, d_hist_depth,
+                           d_hist_length, d_hist_ids, p, d_out_rgb, d_out_length)) != QA_OK)
+    return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t s = StreamOf(c, hip_stream);
+  HIP_TRY(f.done.WaitOn(s));
+  int32_t *ids = nullptr;
+  if (d_hist_ids) {
+    // the current ids: the context's plane (it only grows; the old one may be in use on a stream of the caller's), every entry of
+    // which the guide kernel writes on s before the reprojection reads it
+    HIP_TRY(c->reprojectIds.Reserve((size_t) W * (size_t) H * 8, true));
+    HIP_TRY(c->lastReproject.WaitOn(s));
+    ids = static_cast<int32_t *>(c->reprojectIds.p);
+    if ((rc = qa_progressive_gbuffer_device(c, nullptr, nullptr, nullptr, ids, hip_stream)) != QA_OK) return rc;
+  }
+  const ReprojectSetup S = reprojectSetup(*prev_cam, cam, f.args.x0, f.args.y0, W, H, p->depth_tolerance, p->max_history);
+  const ReprojectSrc src = {f.args.rgb, f.args.depth, f.args.ns, f.dState, W};
+  if ((rc = LaunchReproject(S, src, d_hist_rgb, d_hist_depth, d_hist_length, ids, d_hist_ids, d_out_rgb, d_out_length, s)) != QA_OK) return rc;
+  if (ids) HIP_TRY(c->lastReproject.Record(s));
+  return QA_OK;
+}
+
+// the same source on the CPU, pixel after pixel (no GPU, no context)
+int qa_test_reproject_host(const qa_camera *prev_cam, const qa_camera *cur_cam, int x0, int y0, int width, int height, const float *rgb, const float *depth,
+                           const uint32_t *ns, const int32_t *ids, const float *hist_rgb, const float *hist_depth, const float *hist_length,
+                           const int32_t *hist_ids, const qa_reproject_params *p, float *out_rgb, float *out_length)
+{
+  if (!rgb || !depth || !ns) return Fail(QA_EINVAL, "null buffer");
+  if (int rc = CheckReproject(prev_cam, cur_cam, x0, y0, width, height, rgb, depth, ns, ids, ids != nullptr, hist_rgb, hist_depth, hist_length, hist_ids, p,
+                              out_rgb, out_length))
+    return rc;
+  const int W = width, H = height;
+  const ReprojectSetup S = reprojectSetup(*prev_cam, *cur_cam, x0, y0, W, H, p->depth_tolerance, p->max_history);
+  const auto src = [=](int x, int y) {
+    const size_t q = (size_t) y * (size_t) W + (size_t) x;
+    ReprojectPixel px;
+    px.r = rgb[3 * q]; px.g = rgb[3 * q + 1]; px.b = rgb[3 * q + 2]; px.z = depth[q]; px.ns = ns[q];
+    return px;
+  };
+  const ReprojectHistory hist = {hist_rgb, hist_depth, hist_length, W};
+  const ReprojectIds id = {{ids, hist_ids}, W};
+  for (int y = 0; y < H; ++y)
+    for (int x = 0; x < W; ++x) {
+      const size_t q = (size_t) y * (size_t) W + (size_t) x;
+      float o[3];
+      out_length[q] = reprojectPixel(S, src, hist, id, ids != nullptr, x, y, o);
+      out_rgb[3 * q] = o[0]; out_rgb[3 * q + 1] = o[1]; out_rgb[3 * q + 2] = o[2];
+    }
+  return QA_OK;
+}
+
+}  // extern "C"

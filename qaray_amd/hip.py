@@ -150,6 +150,26 @@ class DenoiseGuidedParams(C.Structure):   # qa_denoise_guided_params; .default()
         return p
 
 
+class ReprojectParams(C.Structure):   # qa_reproject_params; ReprojectParams.default() = qa_reproject_params_default
+    _fields_ = [("depth_tolerance", C.c_float), ("max_history", C.c_float), ("flags", C.c_uint32)]
+
+    @classmethod
+    def default(cls):
+        p = cls()
+        _check(lib().qa_reproject_params_default(C.byref(p)))
+        return p
+
+    @classmethod
+    def of(cls, params=None, depth_tolerance=None, max_history=None):
+        """params (a ReprojectParams) or the library's defaults, with the keyword arguments that are given written over them."""
+        p = cls.default() if params is None else cls(params.depth_tolerance, params.max_history, params.flags)
+        if depth_tolerance is not None:
+            p.depth_tolerance = float(depth_tolerance)
+        if max_history is not None:
+            p.max_history = float(max_history)
+        return p
+
+
 QA_GBUFFER_BACKFACE = 0x40000000
 GBUFFER_PLANES = ("normal", "albedo", "depth", "ids")   # in the C ABI's order: float32 [h,w,3], [h,w,3], [h,w], int32 [h,w,2]
 
@@ -230,6 +250,10 @@ def lib():
         L.qa_progressive_denoise_guided.argtypes = [C.c_void_p, C.POINTER(DenoiseGuidedParams), C.c_void_p]
         L.qa_progressive_denoise_guided_device.argtypes = [C.c_void_p, C.POINTER(DenoiseGuidedParams), C.c_void_p, C.c_void_p]
         L.qa_test_denoise_guided_host.argtypes = [C.c_void_p] * 5 + [C.c_int, C.c_int, C.POINTER(DenoiseGuidedParams), C.c_void_p]
+        L.qa_reproject_params_default.argtypes = [C.POINTER(ReprojectParams)]
+        L.qa_reproject_device.argtypes = [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_void_p] * 8 + [C.POINTER(ReprojectParams)] + [C.c_void_p] * 3
+        L.qa_progressive_reproject_device.argtypes = [C.c_void_p] * 6 + [C.POINTER(ReprojectParams)] + [C.c_void_p] * 3
+        L.qa_test_reproject_host.argtypes = [C.c_void_p] * 2 + [C.c_int] * 4 + [C.c_void_p] * 8 + [C.POINTER(ReprojectParams)] + [C.c_void_p] * 2
         L.qa_gbuffer_region_device.argtypes = [C.c_void_p] + [C.c_int] * 4 + [C.c_uint32] + [C.c_void_p] * 5
         L.qa_gbuffer_region.argtypes = [C.c_void_p] + [C.c_int] * 4 + [C.c_uint32] + [C.c_void_p] * 4
         L.qa_progressive_gbuffer_device.argtypes = [C.c_void_p] * 6
@@ -304,6 +328,41 @@ def denoise_guided_host(rgb, depth, ns, normal=None, albedo=None, params=None, i
     _check(lib().qa_test_denoise_guided_host(rgb.ctypes.data, depth.ctypes.data, ns.ctypes.data, *(None if g is None else g.ctypes.data for g in guides),
                                              w, h, C.byref(p), out.ctypes.data))
     return out
+
+
+def _camera_record(cam):
+    """A camera (a record of CAMERA_DTYPE: host.HostScene.camera(), blob_camera(blob)) as a contiguous array of one record of its own."""
+    return np.array(cam, dtype=CAMERA_DTYPE).reshape(1)
+
+
+def reproject_host(cur, history, prev_cam, cur_cam, origin=(0, 0), ids=None, hist_ids=None, out=None, out_length=None, params=None,
+                   depth_tolerance=None, max_history=None):
+    """qa_test_reproject_host: the temporal reprojection of Context.reproject_device on the CPU, from the source the device kernel is
+    compiled from.  cur = (rgb (h, w, 3) f32, depth (h, w) f32, ns (h, w) u32) rendered from cur_cam; history = (rgb, depth,
+    length (h, w) f32) accumulated under prev_cam; origin: the image pixel (x0, y0) of the frames' first pixel; ids / hist_ids:
+    (h, w, 2) i32, both or neither.  out / out_length: float32 arrays to write (out may be cur's rgb itself) -> (out (h, w, 3),
+    out_length (h, w)).  The other inputs are not modified.  No GPU needed."""
+    rgb, depth, ns = cur
+    rgb = rgb if out is rgb and rgb is not None else np.ascontiguousarray(rgb, dtype=np.float32)
+    depth = np.ascontiguousarray(depth, dtype=np.float32)
+    ns = np.ascontiguousarray(ns, dtype=np.uint32)
+    assert rgb.ndim == 3 and rgb.shape[2] == 3 and depth.shape == rgb.shape[:2] and ns.shape == rgb.shape[:2]
+    h, w = depth.shape
+    hist = [np.ascontiguousarray(a, dtype=np.float32) for a in history]
+    assert hist[0].shape == (h, w, 3) and hist[1].shape == (h, w) and hist[2].shape == (h, w)
+    idp = [None if a is None else np.ascontiguousarray(a, dtype=np.int32) for a in (ids, hist_ids)]
+    assert all(a is None or a.shape == (h, w, 2) for a in idp)
+    out = np.zeros((h, w, 3), np.float32) if out is None else out
+    out_length = np.zeros((h, w), np.float32) if out_length is None else out_length
+    for a, shape in ((out, (h, w, 3)), (out_length, (h, w))):
+        assert a.dtype == np.float32 and a.flags.c_contiguous and a.shape == shape
+    p = ReprojectParams.of(params, depth_tolerance, max_history)
+    c0, c1 = _camera_record(prev_cam), _camera_record(cur_cam)
+    _check(lib().qa_test_reproject_host(c0.ctypes.data, c1.ctypes.data, int(origin[0]), int(origin[1]), w, h, rgb.ctypes.data, depth.ctypes.data,
+                                        ns.ctypes.data, None if idp[0] is None else idp[0].ctypes.data, hist[0].ctypes.data, hist[1].ctypes.data,
+                                        hist[2].ctypes.data, None if idp[1] is None else idp[1].ctypes.data, C.byref(p), out.ctypes.data,
+                                        out_length.ctypes.data))
+    return out, out_length
 
 
 def _gbuffer_tensors(region, device, given):
@@ -603,6 +662,42 @@ class Context:
                                               None if albedo is None else albedo.data_ptr(), w, h, C.byref(p), out.data_ptr(), sptr))
         return out
 
+    def reproject_device(self, cur, history, prev_cam, cur_cam, origin=(0, 0), ids=None, hist_ids=None, out=None, out_length=None, params=None,
+                         depth_tolerance=None, max_history=None, stream=None):
+        """qa_reproject_device: the accumulated frame of an earlier camera carried into the frame of the camera as it now stands
+        (include/qaray_hip.h), on torch CUDA tensors.  cur = (rgb float32 [h,w,3], depth float32 [h,w], ns int32/uint32 [h,w]) as
+        render_region_device fills them under cur_cam; history = (rgb, depth, length float32 [h,w]) accumulated under prev_cam;
+        the cameras are records of CAMERA_DTYPE; origin: the image pixel (x0, y0) of the frames' first pixel; ids / hist_ids: the
+        int32 [h,w,2] planes of gbuffer_device, both or neither.  out (may be cur's rgb itself) / out_length: the tensors to write
+        (None: new ones); neither may be a history plane.  params: a ReprojectParams; the keyword arguments override its fields.
+        -> (out, out_length), the history of the next call together with cur's depth and ids.  Only enqueues (see
+        render_region_device for the stream)."""
+        import torch
+        rgb, depth, ns = cur
+        hrgb, hdepth, hlen = history
+        assert rgb.is_cuda and rgb.is_contiguous() and rgb.dim() == 3 and rgb.shape[2] == 3 and rgb.dtype == torch.float32
+        h, w = rgb.shape[:2]
+        n = h * w
+        for t in (depth, ns, hdepth, hlen):
+            assert t.is_cuda and t.is_contiguous() and t.numel() == n and t.element_size() == 4
+        assert depth.dtype == torch.float32 and hdepth.dtype == torch.float32 and hlen.dtype == torch.float32
+        assert hrgb.is_cuda and hrgb.is_contiguous() and hrgb.numel() == 3 * n and hrgb.dtype == torch.float32
+        for t in (ids, hist_ids):
+            assert t is None or (t.is_cuda and t.is_contiguous() and t.numel() == 2 * n and t.dtype == torch.int32)
+        if out is None:
+            out = torch.empty_like(rgb)
+        if out_length is None:
+            out_length = torch.empty((h, w), dtype=torch.float32, device=rgb.device)
+        assert out.is_cuda and out.is_contiguous() and out.numel() == 3 * n and out.dtype == torch.float32
+        assert out_length.is_cuda and out_length.is_contiguous() and out_length.numel() == n and out_length.dtype == torch.float32
+        p = ReprojectParams.of(params, depth_tolerance, max_history)
+        c0, c1 = _camera_record(prev_cam), _camera_record(cur_cam)
+        sptr = self._stream_arg(stream, rgb)
+        _check(lib().qa_reproject_device(self._h, c0.ctypes.data, c1.ctypes.data, int(origin[0]), int(origin[1]), w, h, rgb.data_ptr(), depth.data_ptr(),
+                                         ns.data_ptr(), None if ids is None else ids.data_ptr(), hrgb.data_ptr(), hdepth.data_ptr(), hlen.data_ptr(),
+                                         None if hist_ids is None else hist_ids.data_ptr(), C.byref(p), out.data_ptr(), out_length.data_ptr(), sptr))
+        return out, out_length
+
     def gbuffer(self, region, seed=DEFAULT_SEED):
         """qa_gbuffer_region: the first-hit guide planes of a region -> dict of numpy arrays: normal [h,w,3] f32 (world space, 0 on a
         miss), albedo [h,w,3] f32, depth [h,w] f32 (render_region's depth plane), ids [h,w,2] i32 (node, material; -1 on a miss;
@@ -838,6 +933,35 @@ class Progressive:
         _check(lib().qa_progressive_gbuffer_device(self._ctx._h, *ptrs, sptr))
         return out
 
+    def reproject_device(self, history, prev_cam, hist_ids=None, out=None, out_length=None, params=None, depth_tolerance=None, max_history=None,
+                         stream=None):
+        """qa_progressive_reproject_device: Context.reproject_device with the frame's preview (the floats read() returns, straight
+        from its slabs), its region and the resident scene's camera as the current frame; history = (rgb, depth, length) torch CUDA
+        tensors accumulated under prev_cam.  With hist_ids (int32 [h,w,2]) the frame's own ids are computed as gbuffer_device does.
+        -> (out, out_length); only enqueues.  The frame is not changed; a stale frame (after an edit) wants restart() first."""
+        import torch
+        device = torch.device("cuda", self._ctx.device_id)
+        x0, y0, x1, y1 = self.region
+        h, w = y1 - y0, x1 - x0
+        n = h * w
+        hrgb, hdepth, hlen = history
+        for t, k in ((hrgb, 3), (hdepth, 1), (hlen, 1)):
+            assert t.is_cuda and t.is_contiguous() and t.numel() == k * n and t.dtype == torch.float32
+        assert hist_ids is None or (hist_ids.is_cuda and hist_ids.is_contiguous() and hist_ids.numel() == 2 * n and hist_ids.dtype == torch.int32)
+        if out is None:
+            out = torch.empty((h, w, 3), dtype=torch.float32, device=device)
+        if out_length is None:
+            out_length = torch.empty((h, w), dtype=torch.float32, device=device)
+        assert out.is_cuda and out.is_contiguous() and out.numel() == 3 * n and out.dtype == torch.float32
+        assert out_length.is_cuda and out_length.is_contiguous() and out_length.numel() == n and out_length.dtype == torch.float32
+        p = ReprojectParams.of(params, depth_tolerance, max_history)
+        c0 = _camera_record(prev_cam)
+        sptr = Context._stream_arg(stream, out)
+        _check(lib().qa_progressive_reproject_device(self._ctx._h, c0.ctypes.data, hrgb.data_ptr(), hdepth.data_ptr(), hlen.data_ptr(),
+                                                     None if hist_ids is None else hist_ids.data_ptr(), C.byref(p), out.data_ptr(), out_length.data_ptr(),
+                                                     sptr))
+        return out, out_length
+
     def status(self):
         """-> dict(spp_reached, pixels_finished, tiles_behind); synchronises."""
         r, f, b = C.c_int(), C.c_uint64(), C.c_uint64()
@@ -861,3 +985,74 @@ class Progressive:
     def __exit__(self, *exc):
         self.close()
         return False
+
+
+class TemporalPreview:
+    """The history of an interactive preview across camera moves: torch plumbing around Context.reproject_device.  Owns the
+    accumulated colour and length (two of each: a call reads one and writes the other), the depth and ids of the last frame and
+    the last camera.
+        tp = TemporalPreview(ctx, region)
+        per frame: ctx.edit_camera(cam); ctx.render_region_device(region, 4, rgb, depth, ns, seed=NEW SEED, stream=s)
+                   g = ctx.gbuffer_device(region, seed, ids=ids, stream=s); acc, length = tp.push(cam, rgb, depth, ns, ids, stream=s)
+    A new seed per frame matters: frames of one seed repeat their noise, and accumulating them gains nothing.  reset() after any
+    edit that is not a camera move (the reprojection knows of no other change: include/qaray_hip.h)."""
+
+    def __init__(self, ctx, region, params=None, depth_tolerance=None, max_history=None):
+        import torch
+        self._ctx = ctx
+        self.region = tuple(region)
+        x0, y0, x1, y1 = self.region
+        h, w = y1 - y0, x1 - x0
+        dev = torch.device("cuda", ctx.device_id)
+        self.params = ReprojectParams.of(params, depth_tolerance, max_history)
+        self._rgb = [torch.zeros((h, w, 3), dtype=torch.float32, device=dev) for _ in range(2)]
+        self._length = [torch.zeros((h, w), dtype=torch.float32, device=dev) for _ in range(2)]
+        self._depth = torch.zeros((h, w), dtype=torch.float32, device=dev)
+        self._ids = torch.zeros((h, w, 2), dtype=torch.int32, device=dev)
+        self._has_ids = False
+        self._cam = None
+        self._at = 0
+        torch.cuda.current_stream(dev).synchronize()
+
+    def reset(self):
+        """Forget the history: the next push returns its frame as it is."""
+        self._cam = None
+
+    def push(self, cam, rgb, depth, ns, ids=None, stream=None):
+        """The frame (rgb, depth, ns[, ids]: torch CUDA tensors as render_region_device and gbuffer_device fill them) rendered from
+        cam (a record of CAMERA_DTYPE) joins the history -> (accumulated rgb float32 [h,w,3], length float32 [h,w]); the first push,
+        and one after reset(), returns the frame itself with length = ns.  The ids are compared when this push and the last one
+        both brought them.  The two tensors are the preview's own and stay as they are until the push after the next one.  The
+        caller's tensors are free again when the call returns (depth and ids are copied).  stream: the HIP stream handle the frame
+        was rendered on: everything is enqueued there.  None: the frame was rendered on the context's own stream, and the call
+        synchronises (see render_region_device)."""
+        import torch
+        dev = self._depth.device
+        cam = _camera_record(cam)
+        if stream:
+            ts = torch.cuda.ExternalStream(stream, device=dev)
+        else:
+            self._ctx.synchronize()
+            ts = torch.cuda.current_stream(dev)
+        prev, nxt = self._at, 1 - self._at
+        fresh = self._cam is None
+        if fresh:
+            with torch.cuda.stream(ts):
+                self._length[prev].zero_()   # no history anywhere: the kernel hands the frame through
+        with_ids = ids is not None and self._has_ids and not fresh
+        x0, y0 = self.region[:2]
+        self._ctx.reproject_device((rgb, depth, ns), (self._rgb[prev], self._depth, self._length[prev]), cam if fresh else self._cam, cam, origin=(x0, y0),
+                                   ids=ids if with_ids else None, hist_ids=self._ids if with_ids else None, out=self._rgb[nxt],
+                                   out_length=self._length[nxt], params=self.params, stream=stream)
+        if not stream:
+            self._ctx.synchronize()
+        with torch.cuda.stream(ts):
+            self._depth.view(-1).copy_(depth.reshape(-1))
+            if ids is not None:
+                self._ids.view(-1).copy_(ids.reshape(-1))
+        if not stream:
+            ts.synchronize()
+        self._has_ids = ids is not None
+        self._cam = cam
+        self._at = nxt
+        return self._rgb[nxt], self._length[nxt]

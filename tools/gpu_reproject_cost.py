@@ -1,0 +1,159 @@
+#!/usr/bin/env python3
+"""What carrying a preview across a camera move costs: Context.reproject_device between two events on the caller's
+stream, on the frames of bench.py's C2 (Cornell box, 1920x1080) and C5 (trc_scene_tower.xml, 3840x2160), with and without the ids
+planes: warm-up calls, then the median of --repeats.  The two frames are rendered in the same process at 4 spp: the scene's own
+view as the history, the view one degree round what it shows as the current frame (the camera record turned about the vertical
+through the point at the median depth in front of it); the 4-spp frame is timed the same way, and every figure is also given
+as a share of it.
+
+Beside the milliseconds, the algorithmic bytes as GB/s and as a share of the HBM peak (8.0 TB/s specified).  Per pixel: the
+current frame 20 (rgb, depth, sample count), the history about 20 unique (rgb, depth, length: the four taps of a pixel are its
+neighbours' taps too, so every history pixel is needed about once), the outputs 16; the ids planes add 8 to each side: 56 without
+ids, 72 with.
+
+Each configuration runs in a child process of its own under a time limit (--limit seconds); the parent never opens the GPU, stops
+at the first child that fails and writes the table to --out.  Needs a GPU: there is no fallback."""
+import argparse
+import json
+import os
+import statistics
+import subprocess
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+CONFIGS = {"c2": ("example_project12_box.xml", 1920, 1080), "c5": ("trc_scene_tower.xml", 3840, 2160)}
+HBM_PEAK = 8.0e12
+BYTES = {False: 56, True: 72}
+
+
+def turned(cam, w, h, distance, degrees):
+    """The camera record turned by `degrees` about the image's vertical through the point `distance` in front of the image centre."""
+    v = {k: np.asarray(cam[k], np.float64) for k in ("screenA", "screenU", "screenV", "screenX", "screenY", "cam_pos")}
+    forward = v["screenA"] + v["screenU"] * (w / 2) + v["screenV"] * (h / 2) - v["cam_pos"]
+    forward /= np.linalg.norm(forward)
+    axis = -v["screenV"] / np.linalg.norm(v["screenV"])
+    pivot = v["cam_pos"] + forward * distance
+    a = np.radians(degrees)
+
+    def rot(x):   # Rodrigues
+        return x * np.cos(a) + np.cross(axis, x) * np.sin(a) + axis * (axis @ x) * (1 - np.cos(a))
+
+    out = cam.copy()
+    for k in ("screenU", "screenV", "screenX", "screenY"):
+        out[k] = rot(v[k])
+    for k in ("screenA", "cam_pos"):
+        out[k] = pivot + rot(v[k] - pivot)
+    return out
+
+
+def measure(tag, warmup, repeats):
+    import torch
+    from qaray_amd import hip
+    from qaray_amd.host import SCENES_DIR, load_scene_blob
+    if not torch.cuda.is_available():
+        raise SystemExit("gpu_reproject_cost: no GPU (nothing is measured without one)")
+    scene, w, h = CONFIGS[tag]
+    dev = torch.device("cuda", 0)
+    ctx = hip.Context(0)
+    blob = load_scene_blob(os.path.join(SCENES_DIR, scene), size=(w, h))
+    ctx.upload_scene(blob)
+    region = (0, 0, w, h)
+    s = torch.cuda.Stream(dev)
+
+    def frame(seed):
+        rgb = torch.empty((h, w, 3), dtype=torch.float32, device=dev)
+        depth = torch.empty((h, w), dtype=torch.float32, device=dev)
+        ns = torch.empty((h, w), dtype=torch.int32, device=dev)
+        ids = torch.empty((h, w, 2), dtype=torch.int32, device=dev)
+        ctx.render_region_device(region, 4, rgb, depth, ns, seed=seed, stream=s.cuda_stream)
+        ctx.gbuffer_device(region, seed, ids=ids, stream=s.cuda_stream)
+        s.synchronize()
+        return rgb, depth, ns, ids
+
+    cam0 = hip.blob_camera(blob).copy()
+    rgb0, depth0, ns0, ids0 = frame(1)
+    hits = depth0[depth0 < 1e29]
+    distance = float(hits.median()) if hits.numel() else 1.0
+    cam1 = turned(cam0, w, h, distance, 1.0)
+    ctx.edit_camera(cam1)
+    rgb1, depth1, ns1, ids1 = frame(2)
+    history = (rgb0, depth0, ns0.to(torch.float32))
+    out, out_length = torch.empty_like(rgb1), torch.empty_like(depth1)
+    torch.cuda.synchronize()
+
+    def timed(call):
+        spans = []
+        for _ in range(warmup + repeats):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            with torch.cuda.stream(s):
+                e0.record()
+                call()
+                e1.record()
+            s.synchronize()
+            spans.append(e0.elapsed_time(e1))
+        spans = spans[warmup:]
+        return statistics.median(spans), min(spans), max(spans)
+
+    def reproject(with_ids):
+        return ctx.reproject_device((rgb1, depth1, ns1), history, cam0, cam1, ids=ids1 if with_ids else None, hist_ids=ids0 if with_ids else None, out=out,
+                                    out_length=out_length, stream=s.cuda_stream)
+
+    frame_ms = timed(lambda: ctx.render_region_device(region, 4, rgb1, depth1, ns1, seed=2, stream=s.cuda_stream))[0]
+    for with_ids in (True, False):
+        ms, lo, hi = timed(lambda: reproject(with_ids))
+        s.synchronize()
+        kept = float((out_length > ns1).float().mean())
+        moved = w * h * BYTES[with_ids]
+        print(json.dumps({"config": tag, "scene": scene, "size": [w, h], "ids": with_ids, "median_ms": round(ms, 4), "min_ms": round(lo, 4),
+                          "max_ms": round(hi, 4), "frame4_ms": round(frame_ms, 4), "share_of_4spp_frame": round(ms / frame_ms, 4),
+                          "bytes_per_pixel": BYTES[with_ids], "GBps": round(moved / (ms * 1e-3) / 1e9, 1),
+                          "share_of_hbm_peak_8TBps": round(moved / (ms * 1e-3) / HBM_PEAK, 4), "pixels_with_history": round(kept, 4),
+                          "library": os.path.relpath(hip.HIP_LIB_PATH, ROOT)}), flush=True)
+    ctx.close()
+
+
+def write_table(rows, out, warmup, repeats):
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as f:
+        f.write("tools/gpu_reproject_cost.py: Context.reproject_device, view 0 -> the view one degree round the scene, 4-spp frames.\n"
+                f"One run, one MI355X; median of {repeats} after {warmup} warm-ups between two events on the caller's stream; each configuration in its own process.\n"
+                "bytes: algorithmic bytes per pixel (current 20, history about 20 unique, outputs 16; + 8 + 8 with ids); peak: 8.0 TB/s HBM.\n\n")
+        f.write(f"{'frame':<40}{'ids':<5}{'median ms (min - max)':<28}{'4-spp frame ms':<16}{'share':<8}{'B/px':<6}{'GB/s':<9}{'of peak':<9}{'with history'}\n")
+        for r in rows:
+            name = f"{r['config']} {r['scene']} {r['size'][0]}x{r['size'][1]}"
+            span = f"{r['median_ms']:.3f} ({r['min_ms']:.3f} - {r['max_ms']:.3f})"
+            f.write(f"{name:<40}{'yes' if r['ids'] else 'no':<5}{span:<28}{r['frame4_ms']:<16.3f}{r['share_of_4spp_frame']:<8.4f}{r['bytes_per_pixel']:<6}"
+                    f"{r['GBps']:<9.1f}{r['share_of_hbm_peak_8TBps']:<9.4f}{r['pixels_with_history']:.4f}\n")
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--repeats", type=int, default=7)
+    ap.add_argument("--limit", type=int, default=240, help="seconds a configuration's child process may take")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "reproject_cost.txt"))
+    ap.add_argument("--one", choices=sorted(CONFIGS), help="measure this configuration in this process")
+    a = ap.parse_args()
+    if a.one:
+        return measure(a.one, a.warmup, a.repeats)
+    rows = []
+    for tag in sorted(CONFIGS):
+        try:
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--one", tag, "--warmup", str(a.warmup), "--repeats", str(a.repeats)],
+                               timeout=a.limit, stdout=subprocess.PIPE, text=True)
+        except subprocess.TimeoutExpired:
+            raise SystemExit(f"gpu_reproject_cost: {tag} did not finish in {a.limit} s; nothing more is started")
+        sys.stdout.write(r.stdout)
+        if r.returncode != 0:
+            raise SystemExit(f"gpu_reproject_cost: {tag} ended with {r.returncode}; nothing more is started")
+        rows += [json.loads(line) for line in r.stdout.splitlines() if line.startswith("{")]
+    write_table(rows, a.out, a.warmup, a.repeats)
+    print(f"wrote {a.out}")
+
+
+if __name__ == "__main__":
+    main()
