@@ -42,6 +42,9 @@
  *   qa_progressive_denoise_guided* edge-stopping guides)
  *   qa_reproject_device,           (no counterpart: the reference renders every frame from nothing; the accumulated frame of
  *   qa_progressive_reproject_device   an earlier camera carried into the frame of the camera as it now stands)
+ *   qa_reproject_motion_device,    (no counterpart: the same with the history of a node that moved fetched from where the node
+ *   qa_progressive_reproject_motion_device,   was, and a clamp of the history to the current frame's neighbourhood)
+ *   qa_reproject_node_motion
  *   qa_get_counters                (no counterpart: the reference only prints wall-clock)
  *   qa_get_kernel_time             Renderer::StartTimer/StopTimer       src/renderers/renderer.cpp:42-63
  */
@@ -365,6 +368,7 @@ int qa_progressive_denoise_guided_device(qa_ctx *ctx, const qa_denoise_guided_pa
  * onto itself, exactly.  The caller keeps out_rgb, out_length and the current frame's depth (and ids) as the next history.
  * Limits: no neighbourhood colour clamp, no per-pixel variance, no moving objects (the ids catch an edited node only if its id
  * changes: reset the history after any edit that is not a camera move), a pinhole lens (the lens draw of dof > 0.1 is ignored).
+ * qa_reproject_motion_device and qa_progressive_reproject_motion_device (below) lift the first and the third of these.
  *   qa_reproject_device               plain device buffers: the current frame (d_ids may be NULL), the history (d_hist_ids NULL if
  *                                     and only if d_ids is) -> d_out_rgb (3 floats per pixel), d_out_length (1).  d_out_rgb ==
  *                                     d_rgb is allowed (a pixel reads only its own current pixel); no other overlap of an output
@@ -389,6 +393,58 @@ int qa_reproject_device(qa_ctx *ctx, const qa_camera *prev_cam, const qa_camera 
 int qa_progressive_reproject_device(qa_ctx *ctx, const qa_camera *prev_cam, const float *d_hist_rgb, const float *d_hist_depth,
                                     const float *d_hist_length, const int32_t *d_hist_ids, const qa_reproject_params *params,
                                     float *d_out_rgb, float *d_out_length, void *hip_stream);
+
+/* Reprojection that follows moved nodes and clamps stale history: the calls above with two additions, each behind a flag of
+ * qa_reproject_motion_params; with flags 0 they return the bits of the calls above.  The header comment of
+ * qaray_amd/csrc/hip/qa_reproject_motion_dev.h is the specification.
+ *   QA_REPROJECT_MOTION   d_motion: a table of motion_count records qa_node_motion, one per node of the scene (word 0 of an id is
+ *                         the node's index).  m is a 3x3 matrix (row-major, m[0 .. 8]) and a translation (m[9 .. 11]) taking a world
+ *                         point of the current scene to where the same point of the node lay in the scene the history was rendered
+ *                         from; moved == 0: the node and its ancestors stand where they stood (m is not read).  A hit pixel of a
+ *                         moved node is taken through m before it is projected into the old camera, also when the cameras are
+ *                         equal; the ids test then finds the object where it was, and what it uncovered gets no history.  An id
+ *                         outside [0, motion_count) is an unmoved node.  Both ids planes are required.
+ *   QA_REPROJECT_CLAMP    a pixel's history colour is clamped, per component, to mean +- clamp_gamma * standard deviation of the
+ *                         CURRENT frame's pixels within clamp_radius (1 .. 3) of it that are not void and have its class; a window
+ *                         of one such pixel clamps nothing.  History that a light, material or texture edit, a slid shadow or
+ *                         reflection has made wrong leaves within a few frames, not at 1 / max_history.  The length is not changed.
+ *                         The window reads the neighbours' current colours: d_out_rgb == d_rgb is refused with this flag.
+ * qa_reproject_node_motion builds the table on the host (no GPU, no context) from the instance tables of the previous and the
+ * current scene (`count` records each, as qa_scene_download's blob holds them or as the caller edited them): record k is
+ * Wprev(k) o Wcur(k)^-1 with W(k)(p) = W(parent(k))(tm_k p + pos_k), the inverse through the itm chain, composed in double and
+ * rounded once; moved = 0 and the exact identity where tm, itm and pos of k and of all its ancestors compare equal.  QA_EINVAL: a
+ * null table, count < 1, tables whose parent, subtree_end or depth differ, a parent that is not -1 .. k - 1.
+ *   qa_reproject_motion_device               as qa_reproject_device; d_motion is a device pointer the caller uploaded (NULL is
+ *                                            allowed when QA_REPROJECT_MOTION is clear).  One kernel; only enqueues.
+ *   qa_progressive_reproject_motion_device   as qa_progressive_reproject_device (the stale-frame refusal and the context's ids
+ *                                            plane included); QA_REPROJECT_MOTION requires d_hist_ids.
+ * qa_reproject_motion_params_default: depth_tolerance 0.05, max_history 64, clamp_radius 1, clamp_gamma 1, flags 0 (DESIGN.md 4j has
+ * the measurements behind the two clamp values).  QA_EINVAL: everything the calls above refuse; unknown flag bits;
+ * QA_REPROJECT_MOTION with a null table, motion_count < 1 or without both ids planes; QA_REPROJECT_CLAMP with a clamp_radius outside
+ * 1 .. 3, a clamp_gamma that is not finite or is negative, or d_out_rgb == d_rgb; an output overlapping the motion table. */
+#define QA_REPROJECT_MOTION 1u
+#define QA_REPROJECT_CLAMP  2u
+typedef struct qa_reproject_motion_params {
+  float    depth_tolerance, max_history, clamp_gamma;
+  int32_t  clamp_radius;
+  uint32_t flags;
+} qa_reproject_motion_params;
+typedef struct qa_node_motion {
+  float    m[12];
+  uint32_t moved;
+  uint32_t pad[3];
+} qa_node_motion;
+int qa_reproject_motion_params_default(qa_reproject_motion_params *params);
+int qa_reproject_node_motion(const qa_instance *prev, const qa_instance *cur, int count, qa_node_motion *out);
+int qa_reproject_motion_device(qa_ctx *ctx, const qa_camera *prev_cam, const qa_camera *cur_cam, int x0, int y0, int width, int height,
+                               const float *d_rgb, const float *d_depth, const uint32_t *d_nsamples, const int32_t *d_ids,
+                               const float *d_hist_rgb, const float *d_hist_depth, const float *d_hist_length, const int32_t *d_hist_ids,
+                               const qa_node_motion *d_motion, int motion_count, const qa_reproject_motion_params *params,
+                               float *d_out_rgb, float *d_out_length, void *hip_stream);
+int qa_progressive_reproject_motion_device(qa_ctx *ctx, const qa_camera *prev_cam, const float *d_hist_rgb, const float *d_hist_depth,
+                                           const float *d_hist_length, const int32_t *d_hist_ids, const qa_node_motion *d_motion,
+                                           int motion_count, const qa_reproject_motion_params *params, float *d_out_rgb,
+                                           float *d_out_length, void *hip_stream);
 
 /* Counters accumulated since the last reset (synchronises the context first). */
 int qa_get_counters(qa_ctx *ctx, qa_counters *out);
@@ -504,6 +560,11 @@ int qa_test_reproject_host(const qa_camera *prev_cam, const qa_camera *cur_cam, 
                            const float *depth, const uint32_t *nsamples, const int32_t *ids, const float *hist_rgb, const float *hist_depth,
                            const float *hist_length, const int32_t *hist_ids, const qa_reproject_params *params, float *out_rgb,
                            float *out_length);
+/* The same for qa_reproject_motion_device (qaray_amd/csrc/hip/qa_reproject_motion_dev.h), the motion table in host memory. */
+int qa_test_reproject_motion_host(const qa_camera *prev_cam, const qa_camera *cur_cam, int x0, int y0, int width, int height, const float *rgb,
+                                  const float *depth, const uint32_t *nsamples, const int32_t *ids, const float *hist_rgb,
+                                  const float *hist_depth, const float *hist_length, const int32_t *hist_ids, const qa_node_motion *motion,
+                                  int motion_count, const qa_reproject_motion_params *params, float *out_rgb, float *out_length);
 
 #ifdef __cplusplus
 }

@@ -4,15 +4,19 @@
 // pixel's surface at; 16 bytes are written.  Neighbouring lanes project to neighbouring history pixels (the map between two views of
 // a surface is smooth), so the taps of a wave share their cache lines as a 2x2 filter's do: no LDS, no working plane but the ids of
 // a progressive frame.  tools/gpu_reproject_cost.py puts the traffic beside the measured times.
+// qa_reproject_motion (qa_reproject_motion_dev.h) is the same pixel with a node's motion record ahead of the
+// projection and a colour clamp behind the taps, whose window of current colours a tile stages in LDS with a halo.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
 #include <cstring>
+#include <vector>
 
 #include "qa_ctx.h"
 #include "qa_reproject_dev.h"
+#include "qa_reproject_motion_dev.h"
 
 namespace qa {
 
@@ -78,6 +82,54 @@ __global__ __launch_bounds__(256) void qa_reproject(ReprojectSetup S, ReprojectS
   outLength[q] = len;
 }
 
+#define QA_REPROJECT_MAX_RADIUS 3
+#define QA_REPROJECT_MAX_SIDE (QA_REPROJECT_TILE + 2 * QA_REPROJECT_MAX_RADIUS)
+
+// The clamp's window out of the tile's staged pixels: (x, y) is at most `radius` outside the tile, by the caller's loops
+struct ReprojectStagedWin {
+  const float4 *tile;
+  int ox, oy, side;   // the region-local pixel of tile[0]; pixels per staged row
+  __device__ __forceinline__ ReprojectWin operator()(int x, int y) const
+  {
+    const float4 v = tile[(y - oy) * side + (x - ox)];
+    ReprojectWin q;
+    q.r = v.x; q.g = v.y; q.b = v.z; q.cls = __float_as_uint(v.w);
+    return q;
+  }
+};
+
+// One pixel per thread on 16x16 tiles, as qa_reproject.  With QA_REPROJECT_CLAMP the block first stages the current colour and
+// class of its tile and a halo of clampRadius pixels (at radius 3: 22 x 22 x 16 B = 7744 B of LDS), a pixel outside the region as
+// "does not contribute"; the window scans read LDS only.  Threads outside the region stage and wait with the others, then leave.
+__global__ __launch_bounds__(256) void qa_reproject_motion(ReprojectSetup S, ReprojectMotionSetup M, ReprojectSrc cur, ReprojectHistory hist, ReprojectIds ids,
+                                                           int withIds, float *outRgb, float *outLength)
+{
+  __shared__ float4 tile[QA_REPROJECT_MAX_SIDE * QA_REPROJECT_MAX_SIDE];
+  const int bx = (int) (blockIdx.x * QA_REPROJECT_TILE), by = (int) (blockIdx.y * QA_REPROJECT_TILE);
+  ReprojectStagedWin win = {tile, bx, by, QA_REPROJECT_TILE};
+  if (M.flags & QA_REPROJECT_CLAMP) {
+    const int r = M.clampRadius, side = QA_REPROJECT_TILE + 2 * r;   // r is 1 .. 3: side * side <= the array's size
+    win.ox = bx - r; win.oy = by - r; win.side = side;
+    for (int e = (int) threadIdx.x; e < side * side; e += 256) {
+      const int gx = win.ox + e % side, gy = win.oy + e / side;
+      float4 v = make_float4(0.f, 0.f, 0.f, __uint_as_float(0u));
+      if (gx >= 0 && gy >= 0 && gx < S.W && gy < S.H) {
+        const ReprojectWin q = reprojectWinOf(cur(gx, gy));
+        v = make_float4(q.r, q.g, q.b, __uint_as_float(q.cls));
+      }
+      tile[e] = v;
+    }
+    __syncthreads();
+  }
+  const int x = bx + (int) (threadIdx.x & 15u), y = by + (int) (threadIdx.x >> 4);
+  if (x >= S.W || y >= S.H) return;
+  float o[3];
+  const float len = reprojectMotionPixel(S, M, cur, hist, ids, win, withIds != 0, x, y, o);
+  const size_t q = (size_t) y * (size_t) S.W + (size_t) x;
+  outRgb[3 * q] = o[0]; outRgb[3 * q + 1] = o[1]; outRgb[3 * q + 2] = o[2];
+  outLength[q] = len;
+}
+
 }  // namespace qa
 
 static bool Overlap(const void *a, size_t na, const void *b, size_t nb)
@@ -127,6 +179,64 @@ static int LaunchReproject(const ReprojectSetup &S, const ReprojectSrc &src, con
   hipLaunchKernelGGL(qa::qa_reproject, grid, block, 0, s, S, src, hist, id, (ids && hIds) ? 1 : 0, outRgb, outLength);
   HIP_TRY(hipGetLastError());
   return QA_OK;
+}
+
+// What the motion entries check beyond CheckReproject.  inPlace: the output is the current colour plane
+static int CheckReprojectMotion(const qa_camera *prev, const qa_camera *cur, int x0, int y0, int W, int H, const float *rgb, const float *depth,
+                                const uint32_t *ns, const int32_t *ids, bool idsGiven, const float *hRgb, const float *hDepth, const float *hLength,
+                                const int32_t *hIds, const qa_node_motion *motion, int count, const qa_reproject_motion_params *p, const float *outRgb,
+                                const float *outLength)
+{
+  if (!p) return Fail(QA_EINVAL, "null parameters");
+  const qa_reproject_params base = {p->depth_tolerance, p->max_history, 0u};
+  if (int rc = CheckReproject(prev, cur, x0, y0, W, H, rgb, depth, ns, ids, idsGiven, hRgb, hDepth, hLength, hIds, &base, outRgb, outLength)) return rc;
+  if (p->flags & ~(QA_REPROJECT_MOTION | QA_REPROJECT_CLAMP)) return Fail(QA_EINVAL, "unknown flags");
+  const size_t n = (size_t) W * (size_t) H;
+  if (p->flags & QA_REPROJECT_MOTION) {
+    if (!motion) return Fail(QA_EINVAL, "QA_REPROJECT_MOTION without a motion table");
+    if (count < 1) return Fail(QA_EINVAL, "QA_REPROJECT_MOTION with a motion_count below 1");
+    if ((uintptr_t) motion % alignof(qa_node_motion)) return Fail(QA_EINVAL, "a misaligned motion table");
+    if (!idsGiven || !hIds) return Fail(QA_EINVAL, "QA_REPROJECT_MOTION needs both ids planes");
+    const size_t bytes = (size_t) count * sizeof(qa_node_motion);
+    if (Overlap(outRgb, 12 * n, motion, bytes) || Overlap(outLength, 4 * n, motion, bytes)) return Fail(QA_EINVAL, "an output overlaps the motion table");
+  }
+  if (p->flags & QA_REPROJECT_CLAMP) {
+    if (p->clamp_radius < 1 || p->clamp_radius > QA_REPROJECT_MAX_RADIUS) return Fail(QA_EINVAL, "a clamp_radius outside 1 .. 3");
+    if (!std::isfinite(p->clamp_gamma) || p->clamp_gamma < 0.f) return Fail(QA_EINVAL, "a clamp_gamma that is not finite or is negative");
+    if (rgb && outRgb == rgb) return Fail(QA_EINVAL, "QA_REPROJECT_CLAMP reads the neighbours' current colours: d_out_rgb == d_rgb is not allowed with it");
+  }
+  return QA_OK;
+}
+
+static qa::ReprojectMotionSetup MotionSetup(const qa_node_motion *motion, int count, const qa_reproject_motion_params *p)
+{
+  const bool on = (p->flags & QA_REPROJECT_MOTION) != 0u;
+  return {on ? motion : nullptr, on ? count : 0, p->flags, (p->flags & QA_REPROJECT_CLAMP) ? p->clamp_radius : 0, p->clamp_gamma};
+}
+
+static int LaunchReprojectMotion(const ReprojectSetup &S, const ReprojectMotionSetup &M, const ReprojectSrc &src, const float *hRgb, const float *hDepth,
+                                 const float *hLength, const int32_t *ids, const int32_t *hIds, float *outRgb, float *outLength, hipStream_t s)
+{
+  const ReprojectHistory hist = {hRgb, hDepth, hLength, S.W};
+  const ReprojectIds id = {{ids, hIds}, S.W};
+  const dim3 grid((unsigned) ((S.W + QA_REPROJECT_TILE - 1) / QA_REPROJECT_TILE), (unsigned) ((S.H + QA_REPROJECT_TILE - 1) / QA_REPROJECT_TILE)), block(256);
+  hipLaunchKernelGGL(qa::qa_reproject_motion, grid, block, 0, s, S, M, src, hist, id, (ids && hIds) ? 1 : 0, outRgb, outLength);
+  HIP_TRY(hipGetLastError());
+  return QA_OK;
+}
+
+// A 3x4 affine map in double: x -> a x + t (a row-major)
+struct Affine {
+  double a[9], t[3];
+};
+static Affine Compose(const Affine &f, const Affine &g)   // f o g
+{
+  Affine r;
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j) r.a[3 * i + j] = f.a[3 * i] * g.a[j] + f.a[3 * i + 1] * g.a[3 + j] + f.a[3 * i + 2] * g.a[6 + j];
+    r.t[i] = f.a[3 * i] * g.t[0] + f.a[3 * i + 1] * g.t[1] + f.a[3 * i + 2] * g.t[2] + f.t[i];
+  }
+  return r;
 }
 
 extern "C" {
@@ -212,6 +322,148 @@ int qa_test_reproject_host(const qa_camera *prev_cam, const qa_camera *cur_cam, 
       const size_t q = (size_t) y * (size_t) W + (size_t) x;
       float o[3];
       out_length[q] = reprojectPixel(S, src, hist, id, ids != nullptr, x, y, o);
+      out_rgb[3 * q] = o[0]; out_rgb[3 * q + 1] = o[1]; out_rgb[3 * q + 2] = o[2];
+    }
+  return QA_OK;
+}
+
+int qa_reproject_motion_params_default(qa_reproject_motion_params *p)
+{
+  if (!p) return Fail(QA_EINVAL, "null parameters");
+  p->depth_tolerance = QA_REPROJECT_DEFAULT_DEPTH_TOLERANCE;
+  p->max_history = QA_REPROJECT_DEFAULT_MAX_HISTORY;
+  p->clamp_gamma = QA_REPROJECT_DEFAULT_CLAMP_GAMMA;
+  p->clamp_radius = QA_REPROJECT_DEFAULT_CLAMP_RADIUS;
+  p->flags = 0u;
+  return QA_OK;
+}
+
+int qa_reproject_node_motion(const qa_instance *prev, const qa_instance *cur, int count, qa_node_motion *out)
+{
+  if (!prev || !cur || !out) return Fail(QA_EINVAL, "null table");
+  if (count < 1) return Fail(QA_EINVAL, "count below 1");
+  for (int k = 0; k < count; ++k) {
+    if (prev[k].parent != cur[k].parent || prev[k].subtree_end != cur[k].subtree_end || prev[k].depth != cur[k].depth)
+      return Fail(QA_EINVAL, "the tables differ in parent, subtree_end or depth: not two states of one scene graph");
+    if (cur[k].parent < -1 || cur[k].parent >= k) return Fail(QA_EINVAL, "a parent that does not precede its node (the table is in depth-first pre-order)");
+  }
+  // per node: Wprev(k), Wcur(k)^-1 and whether k or an ancestor differs
+  std::vector<Affine> wPrev((size_t) count), wInv((size_t) count);
+  std::vector<uint8_t> moved((size_t) count);
+  for (int k = 0; k < count; ++k) {
+    const qa_instance &a = prev[k], &b = cur[k];
+    Affine lPrev, lInv;   // L_k of the previous table: tm p + pos;  L_k^-1 of the current one: itm (q - pos) = itm q - itm pos
+    for (int i = 0; i < 3; ++i) {
+      for (int j = 0; j < 3; ++j) {
+        lPrev.a[3 * i + j] = (double) a.tm[3 * j + i];   // (tm and itm are column-major)
+        lInv.a[3 * i + j] = (double) b.itm[3 * j + i];
+      }
+      lPrev.t[i] = (double) a.pos[i];
+    }
+    for (int i = 0; i < 3; ++i)
+      lInv.t[i] = -(lInv.a[3 * i] * (double) b.pos[0] + lInv.a[3 * i + 1] * (double) b.pos[1] + lInv.a[3 * i + 2] * (double) b.pos[2]);
+    bool differs = false;
+    for (int i = 0; i < 9; ++i) differs = differs || !(a.tm[i] == b.tm[i]) || !(a.itm[i] == b.itm[i]);
+    for (int i = 0; i < 3; ++i) differs = differs || !(a.pos[i] == b.pos[i]);
+    const int parent = b.parent;
+    wPrev[k] = parent < 0 ? lPrev : Compose(wPrev[parent], lPrev);
+    wInv[k] = parent < 0 ? lInv : Compose(lInv, wInv[parent]);
+    moved[k] = (uint8_t) (differs || (parent >= 0 && moved[parent]));
+    qa_node_motion &o = out[k];
+    memset(&o, 0, sizeof o);
+    o.m[0] = o.m[4] = o.m[8] = 1.f;
+    if (moved[k]) {
+      const Affine m = Compose(wPrev[k], wInv[k]);
+      for (int i = 0; i < 9; ++i) o.m[i] = (float) m.a[i];
+      for (int i = 0; i < 3; ++i) o.m[9 + i] = (float) m.t[i];
+      o.moved = 1u;
+    }
+  }
+  return QA_OK;
+}
+
+int qa_reproject_motion_device(qa_ctx *c, const qa_camera *prev_cam, const qa_camera *cur_cam, int x0, int y0, int width, int height, const float *d_rgb,
+                               const float *d_depth, const uint32_t *d_ns, const int32_t *d_ids, const float *d_hist_rgb, const float *d_hist_depth,
+                               const float *d_hist_length, const int32_t *d_hist_ids, const qa_node_motion *d_motion, int motion_count,
+                               const qa_reproject_motion_params *p, float *d_out_rgb, float *d_out_length, void *hip_stream)
+{
+  if (int rc = Enter(c)) return rc;
+  if (!d_rgb || !d_depth || !d_ns) return Fail(QA_EINVAL, "null buffer");
+  if (int rc = CheckReprojectMotion(prev_cam, cur_cam, x0, y0, width, height, d_rgb, d_depth, d_ns, d_ids, d_ids != nullptr, d_hist_rgb, d_hist_depth,
+                                    d_hist_length, d_hist_ids, d_motion, motion_count, p, d_out_rgb, d_out_length))
+    return rc;
+  const ReprojectSetup S = reprojectSetup(*prev_cam, *cur_cam, x0, y0, width, height, p->depth_tolerance, p->max_history);
+  const ReprojectSrc src = {d_rgb, d_depth, d_ns, nullptr, width};
+  return LaunchReprojectMotion(S, MotionSetup(d_motion, motion_count, p), src, d_hist_rgb, d_hist_depth, d_hist_length, d_ids, d_hist_ids, d_out_rgb,
+                               d_out_length, StreamOf(c, hip_stream));
+}
+
+int qa_progressive_reproject_motion_device(qa_ctx *c, const qa_camera *prev_cam, const float *d_hist_rgb, const float *d_hist_depth, const float *d_hist_length,
+                                           const int32_t *d_hist_ids, const qa_node_motion *d_motion, int motion_count, const qa_reproject_motion_params *p,
+                                           float *d_out_rgb, float *d_out_length, void *hip_stream)
+{
+  int rc = ProgActive(c);
+  if (rc != QA_OK) return rc;
+  const qa_ctx::Progressive &f = c->prog;
+  if (f.stale) return Fail(QA_EINVAL, "the frame's pixels are not the resident camera's (the scene was edited): qa_progressive_restart first");
+  const int W = f.args.x1 - f.args.x0, H = f.args.y1 - f.args.y0;
+  qa_camera cam;   // the camera the frame was rendered from, as in qa_progressive_reproject_device
+  memcpy(&cam, c->hostBlob.data() + offsetof(qa_flat_header, screenA), sizeof(qa_camera));
+  if ((rc = CheckReprojectMotion(prev_cam, &cam, f.args.x0, f.args.y0, W, H, nullptr, nullptr, nullptr, nullptr, d_hist_ids != nullptr, d_hist_rgb,
+                                 d_hist_depth, d_hist_length, d_hist_ids, d_motion, motion_count, p, d_out_rgb, d_out_length)) != QA_OK)
+    return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t s = StreamOf(c, hip_stream);
+  HIP_TRY(f.done.WaitOn(s));
+  int32_t *ids = nullptr;
+  if (d_hist_ids) {   // the context's ids plane, under the rules of qa_progressive_reproject_device
+    HIP_TRY(c->reprojectIds.Reserve((size_t) W * (size_t) H * 8, true));
+    HIP_TRY(c->lastReproject.WaitOn(s));
+    ids = static_cast<int32_t *>(c->reprojectIds.p);
+    if ((rc = qa_progressive_gbuffer_device(c, nullptr, nullptr, nullptr, ids, hip_stream)) != QA_OK) return rc;
+  }
+  const ReprojectSetup S = reprojectSetup(*prev_cam, cam, f.args.x0, f.args.y0, W, H, p->depth_tolerance, p->max_history);
+  const ReprojectSrc src = {f.args.rgb, f.args.depth, f.args.ns, f.dState, W};
+  if ((rc = LaunchReprojectMotion(S, MotionSetup(d_motion, motion_count, p), src, d_hist_rgb, d_hist_depth, d_hist_length, ids, d_hist_ids, d_out_rgb,
+                                  d_out_length, s)) != QA_OK)
+    return rc;
+  if (ids) HIP_TRY(c->lastReproject.Record(s));
+  return QA_OK;
+}
+
+// the same source on the CPU, pixel after pixel (no GPU, no context)
+int qa_test_reproject_motion_host(const qa_camera *prev_cam, const qa_camera *cur_cam, int x0, int y0, int width, int height, const float *rgb,
+                                  const float *depth, const uint32_t *ns, const int32_t *ids, const float *hist_rgb, const float *hist_depth,
+                                  const float *hist_length, const int32_t *hist_ids, const qa_node_motion *motion, int motion_count,
+                                  const qa_reproject_motion_params *p, float *out_rgb, float *out_length)
+{
+  if (!rgb || !depth || !ns) return Fail(QA_EINVAL, "null buffer");
+  if (int rc = CheckReprojectMotion(prev_cam, cur_cam, x0, y0, width, height, rgb, depth, ns, ids, ids != nullptr, hist_rgb, hist_depth, hist_length,
+                                    hist_ids, motion, motion_count, p, out_rgb, out_length))
+    return rc;
+  const int W = width, H = height;
+  const ReprojectSetup S = reprojectSetup(*prev_cam, *cur_cam, x0, y0, W, H, p->depth_tolerance, p->max_history);
+  const ReprojectMotionSetup M = MotionSetup(motion, motion_count, p);
+  const auto src = [=](int x, int y) {
+    const size_t q = (size_t) y * (size_t) W + (size_t) x;
+    ReprojectPixel px;
+    px.r = rgb[3 * q]; px.g = rgb[3 * q + 1]; px.b = rgb[3 * q + 2]; px.z = depth[q]; px.ns = ns[q];
+    return px;
+  };
+  const auto win = [=](int x, int y) {
+    if (x < 0 || y < 0 || x >= W || y >= H) {
+      const ReprojectWin none = {0.f, 0.f, 0.f, 0u};
+      return none;
+    }
+    return reprojectWinOf(src(x, y));
+  };
+  const ReprojectHistory hist = {hist_rgb, hist_depth, hist_length, W};
+  const ReprojectIds id = {{ids, hist_ids}, W};
+  for (int y = 0; y < H; ++y)
+    for (int x = 0; x < W; ++x) {
+      const size_t q = (size_t) y * (size_t) W + (size_t) x;
+      float o[3];
+      out_length[q] = reprojectMotionPixel(S, M, src, hist, id, win, ids != nullptr, x, y, o);
       out_rgb[3 * q] = o[0]; out_rgb[3 * q + 1] = o[1]; out_rgb[3 * q + 2] = o[2];
     }
   return QA_OK;

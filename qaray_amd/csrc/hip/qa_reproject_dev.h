@@ -102,6 +102,78 @@ inline ReprojectSetup reprojectSetup(const qa_camera &c0, const qa_camera &c1, i
   return s;
 }
 
+// Step 3 for a pixel's w: -> false for NO HISTORY, else the region-local (ul, vl) and, for a hit, z'
+__host__ __device__ __forceinline__ bool reprojectProject(const ReprojectSetup &S, f3 w, bool miss, float &ul, float &vl, float &zh)
+{
+  const float wn = dot(w, S.nrm);
+  if (wn == 0.f) return false;
+  const float s = S.an / wn;
+  if (!(s > 0.f)) return false;
+  const f3 r = w * s - S.a;
+  const float u = dot(r, S.vn) / S.du, v = dot(r, S.nu) / S.dv;
+  ul = u - (float) S.x0; vl = v - (float) S.y0;
+  if (!reprojectFinite(ul) || !reprojectFinite(vl)) return false;
+  if (!(ul >= -1.f && ul < (float) S.W && vl >= -1.f && vl < (float) S.H)) return false;
+  zh = 0.f;
+  if (!miss) {
+    zh = length(w);
+    if (!reprojectFinite(zh)) return false;
+  }
+  return true;
+}
+
+// Step 5 around (ul, vl) for a centre of class `miss` and ids cid: -> sw, and the sums sc[3] and sl over the counting taps
+template <class Tap, class Ids>
+__host__ __device__ __forceinline__ float reprojectTaps(const ReprojectSetup &S, const Tap &tap, const Ids &ids, bool withIds, const int *cid, bool miss,
+                                                        float ul, float vl, float zh, float *sc, float &sl)
+{
+  const float fi = __builtin_floorf(ul), fj = __builtin_floorf(vl);
+  const float fx = ul - fi, fy = vl - fj;
+  const int i0 = (int) fi, j0 = (int) fj;   // -1 .. W - 1, -1 .. H - 1
+  const float tol = S.depthTolerance * zh;
+  float sw = 0.f, sr = 0.f, sg = 0.f, sb = 0.f;
+  sl = 0.f;
+#pragma unroll
+  for (int dj = 0; dj < 2; ++dj) {
+#pragma unroll
+    for (int di = 0; di < 2; ++di) {
+      const float wt = (di ? fx : 1.f - fx) * (dj ? fy : 1.f - fy);
+      const int i = i0 + di, j = j0 + dj;
+      if (wt == 0.f || i < 0 || j < 0 || i >= S.W || j >= S.H) continue;
+      ReprojectTap t;
+      tap(i, j, t);
+      if (!(t.length > 0.f) || !reprojectFinite(t.r) || !reprojectFinite(t.g) || !reprojectFinite(t.b) || !reprojectFinite(t.z)) continue;
+      if ((t.z == QA_REPROJECT_MISS) != miss) continue;
+      if (!miss && !(qabs(t.z - zh) <= tol)) continue;
+      if (withIds) {
+        int hid[2];
+        ids(1, i, j, hid);
+        if (hid[0] != cid[0] || hid[1] != cid[1]) continue;
+      }
+      sw += wt;
+      sr += wt * t.r; sg += wt * t.g; sb += wt * t.b;
+      sl += wt * t.length;
+    }
+  }
+  sc[0] = sr; sc[1] = sg; sc[2] = sb;
+  return sw;
+}
+
+// Step 6 with the history colour ch[3] and the sums of step 5: -> out[3] and the new length
+__host__ __device__ __forceinline__ float reprojectAccumulate(const ReprojectSetup &S, const ReprojectPixel &p, float n, const float *ch, float sw, float sl,
+                                                              float *out)
+{
+  const float L = qmin(sl / sw, S.maxHistory);
+  const float k = n / (L + n);
+  const float c[3] = {p.r, p.g, p.b};
+#pragma unroll
+  for (int e = 0; e < 3; ++e) {
+    const float diff = c[e] - ch[e];
+    out[e] = diff == 0.f ? c[e] : ch[e] + diff * k;
+  }
+  return L + n;
+}
+
 // Pixel (tx, ty) of the region.  cur(tx, ty) -> ReprojectPixel; tap(i, j, t) fetches a history pixel, and ids(which, i, j, out)
 // the two id words of the current (which = 0) or the history (1) frame, all called for pixels inside the region only; withIds:
 // both ids planes are given.  -> out[3] and the new length
@@ -126,61 +198,15 @@ __host__ __device__ __forceinline__ float reprojectPixel(const ReprojectSetup &S
       const f3 P = S.pos1 + d * p.z;
       w = P - S.pos0;
     }
-    const float wn = dot(w, S.nrm);
-    if (wn == 0.f) return n;
-    const float s = S.an / wn;
-    if (!(s > 0.f)) return n;
-    const f3 r = w * s - S.a;
-    const float u = dot(r, S.vn) / S.du, v = dot(r, S.nu) / S.dv;
-    ul = u - (float) S.x0; vl = v - (float) S.y0;
-    if (!reprojectFinite(ul) || !reprojectFinite(vl)) return n;
-    if (!(ul >= -1.f && ul < (float) S.W && vl >= -1.f && vl < (float) S.H)) return n;
-    zh = 0.f;
-    if (!miss) {
-      zh = length(w);
-      if (!reprojectFinite(zh)) return n;
-    }
+    if (!reprojectProject(S, w, miss, ul, vl, zh)) return n;
   }
-  const float fi = __builtin_floorf(ul), fj = __builtin_floorf(vl);
-  const float fx = ul - fi, fy = vl - fj;
-  const int i0 = (int) fi, j0 = (int) fj;   // -1 .. W - 1, -1 .. H - 1
   int cid[2] = {0, 0};
   if (withIds) ids(0, tx, ty, cid);
-  const float tol = S.depthTolerance * zh;
-  float sw = 0.f, sr = 0.f, sg = 0.f, sb = 0.f, sl = 0.f;
-#pragma unroll
-  for (int dj = 0; dj < 2; ++dj) {
-#pragma unroll
-    for (int di = 0; di < 2; ++di) {
-      const float wt = (di ? fx : 1.f - fx) * (dj ? fy : 1.f - fy);
-      const int i = i0 + di, j = j0 + dj;
-      if (wt == 0.f || i < 0 || j < 0 || i >= S.W || j >= S.H) continue;
-      ReprojectTap t;
-      tap(i, j, t);
-      if (!(t.length > 0.f) || !reprojectFinite(t.r) || !reprojectFinite(t.g) || !reprojectFinite(t.b) || !reprojectFinite(t.z)) continue;
-      if ((t.z == QA_REPROJECT_MISS) != miss) continue;
-      if (!miss && !(qabs(t.z - zh) <= tol)) continue;
-      if (withIds) {
-        int hid[2];
-        ids(1, i, j, hid);
-        if (hid[0] != cid[0] || hid[1] != cid[1]) continue;
-      }
-      sw += wt;
-      sr += wt * t.r; sg += wt * t.g; sb += wt * t.b;
-      sl += wt * t.length;
-    }
-  }
+  float sc[3], sl;
+  const float sw = reprojectTaps(S, tap, ids, withIds, cid, miss, ul, vl, zh, sc, sl);
   if (sw < QA_REPROJECT_MIN_WEIGHT) return n;
-  const float L = qmin(sl / sw, S.maxHistory);
-  const float k = n / (L + n);
-  const float ch[3] = {sr / sw, sg / sw, sb / sw};
-  const float c[3] = {p.r, p.g, p.b};
-#pragma unroll
-  for (int e = 0; e < 3; ++e) {
-    const float diff = c[e] - ch[e];
-    out[e] = diff == 0.f ? c[e] : ch[e] + diff * k;
-  }
-  return L + n;
+  const float ch[3] = {sc[0] / sw, sc[1] / sw, sc[2] / sw};
+  return reprojectAccumulate(S, p, n, ch, sw, sl, out);
 }
 
 }  // namespace qa

@@ -170,6 +170,37 @@ class ReprojectParams(C.Structure):   # qa_reproject_params; ReprojectParams.def
         return p
 
 
+QA_REPROJECT_MOTION, QA_REPROJECT_CLAMP = 1, 2
+# qa_node_motion: m = a row-major 3x3 matrix and a translation, current world point -> where it lay in the previous scene
+NODE_MOTION_DTYPE = np.dtype([("m", np.float32, 12), ("moved", np.uint32), ("pad", np.uint32, 3)])
+assert NODE_MOTION_DTYPE.itemsize == 64
+
+
+class ReprojectMotionParams(C.Structure):   # qa_reproject_motion_params; .default() = qa_reproject_motion_params_default
+    _fields_ = [("depth_tolerance", C.c_float), ("max_history", C.c_float), ("clamp_gamma", C.c_float), ("clamp_radius", C.c_int32), ("flags", C.c_uint32)]
+
+    @classmethod
+    def default(cls):
+        p = cls()
+        _check(lib().qa_reproject_motion_params_default(C.byref(p)))
+        return p
+
+    @classmethod
+    def of(cls, params=None, depth_tolerance=None, max_history=None, motion=None, clamp=None, clamp_radius=None, clamp_gamma=None):
+        """params (a ReprojectMotionParams) or the library's defaults, with the keyword arguments that are given written over them;
+        motion / clamp (bool) set or clear QA_REPROJECT_MOTION / QA_REPROJECT_CLAMP of the flags."""
+        p = cls.default() if params is None else cls(params.depth_tolerance, params.max_history, params.clamp_gamma, params.clamp_radius, params.flags)
+        for name, v in (("depth_tolerance", depth_tolerance), ("max_history", max_history), ("clamp_gamma", clamp_gamma)):
+            if v is not None:
+                setattr(p, name, float(v))
+        if clamp_radius is not None:
+            p.clamp_radius = int(clamp_radius)
+        for bit, v in ((QA_REPROJECT_MOTION, motion), (QA_REPROJECT_CLAMP, clamp)):
+            if v is not None:
+                p.flags = (p.flags | bit) if v else (p.flags & ~bit)
+        return p
+
+
 QA_GBUFFER_BACKFACE = 0x40000000
 GBUFFER_PLANES = ("normal", "albedo", "depth", "ids")   # in the C ABI's order: float32 [h,w,3], [h,w,3], [h,w], int32 [h,w,2]
 
@@ -254,6 +285,13 @@ def lib():
         L.qa_reproject_device.argtypes = [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_void_p] * 8 + [C.POINTER(ReprojectParams)] + [C.c_void_p] * 3
         L.qa_progressive_reproject_device.argtypes = [C.c_void_p] * 6 + [C.POINTER(ReprojectParams)] + [C.c_void_p] * 3
         L.qa_test_reproject_host.argtypes = [C.c_void_p] * 2 + [C.c_int] * 4 + [C.c_void_p] * 8 + [C.POINTER(ReprojectParams)] + [C.c_void_p] * 2
+        L.qa_reproject_motion_params_default.argtypes = [C.POINTER(ReprojectMotionParams)]
+        L.qa_reproject_node_motion.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.qa_reproject_motion_device.argtypes = ([C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_void_p] * 9 + [C.c_int, C.POINTER(ReprojectMotionParams)]
+                                                 + [C.c_void_p] * 3)
+        L.qa_progressive_reproject_motion_device.argtypes = [C.c_void_p] * 7 + [C.c_int, C.POINTER(ReprojectMotionParams)] + [C.c_void_p] * 3
+        L.qa_test_reproject_motion_host.argtypes = ([C.c_void_p] * 2 + [C.c_int] * 4 + [C.c_void_p] * 9 + [C.c_int, C.POINTER(ReprojectMotionParams)]
+                                                    + [C.c_void_p] * 2)
         L.qa_gbuffer_region_device.argtypes = [C.c_void_p] + [C.c_int] * 4 + [C.c_uint32] + [C.c_void_p] * 5
         L.qa_gbuffer_region.argtypes = [C.c_void_p] + [C.c_int] * 4 + [C.c_uint32] + [C.c_void_p] * 4
         L.qa_progressive_gbuffer_device.argtypes = [C.c_void_p] * 6
@@ -363,6 +401,67 @@ def reproject_host(cur, history, prev_cam, cur_cam, origin=(0, 0), ids=None, his
                                         hist[2].ctypes.data, None if idp[1] is None else idp[1].ctypes.data, C.byref(p), out.ctypes.data,
                                         out_length.ctypes.data))
     return out, out_length
+
+
+def node_motion(prev_instances, cur_instances):
+    """qa_reproject_node_motion: the motion table (NODE_MOTION_DTYPE, one record per node) between two states of one scene graph,
+    each the whole INSTANCE_DTYPE table (blob_table(blob, "instances"), or an edited copy of it): record k takes a world point of
+    the current scene to where the same point of node k lay in the previous one; moved = 0 and the exact identity where the node
+    and all its ancestors stand as they stood.  No GPU needed."""
+    prev = np.ascontiguousarray(prev_instances, dtype=INSTANCE_DTYPE).reshape(-1)
+    cur = np.ascontiguousarray(cur_instances, dtype=INSTANCE_DTYPE).reshape(-1)
+    assert prev.shape == cur.shape, "two tables of one scene"
+    out = np.zeros(len(cur), NODE_MOTION_DTYPE)
+    _check(lib().qa_reproject_node_motion(prev.ctypes.data, cur.ctypes.data, len(cur), out.ctypes.data))
+    return out
+
+
+def reproject_motion_host(cur, history, prev_cam, cur_cam, origin=(0, 0), ids=None, hist_ids=None, motion=None, out=None, out_length=None,
+                          params=None, depth_tolerance=None, max_history=None, clamp=None, clamp_radius=None, clamp_gamma=None):
+    """qa_test_reproject_motion_host: Context.reproject_motion_device on the CPU, from the source the device kernel is compiled
+    from; the arguments of reproject_host, and motion: a table of NODE_MOTION_DTYPE (node_motion()) - given, it sets
+    QA_REPROJECT_MOTION; clamp (bool) sets or clears QA_REPROJECT_CLAMP, clamp_radius / clamp_gamma override params' values.
+    -> (out (h, w, 3), out_length (h, w)).  No GPU needed."""
+    rgb, depth, ns = cur
+    rgb = rgb if out is rgb and rgb is not None else np.ascontiguousarray(rgb, dtype=np.float32)
+    depth = np.ascontiguousarray(depth, dtype=np.float32)
+    ns = np.ascontiguousarray(ns, dtype=np.uint32)
+    assert rgb.ndim == 3 and rgb.shape[2] == 3 and depth.shape == rgb.shape[:2] and ns.shape == rgb.shape[:2]
+    h, w = depth.shape
+    hist = [np.ascontiguousarray(a, dtype=np.float32) for a in history]
+    assert hist[0].shape == (h, w, 3) and hist[1].shape == (h, w) and hist[2].shape == (h, w)
+    idp = [None if a is None else np.ascontiguousarray(a, dtype=np.int32) for a in (ids, hist_ids)]
+    assert all(a is None or a.shape == (h, w, 2) for a in idp)
+    out = np.zeros((h, w, 3), np.float32) if out is None else out
+    out_length = np.zeros((h, w), np.float32) if out_length is None else out_length
+    for a, shape in ((out, (h, w, 3)), (out_length, (h, w))):
+        assert a.dtype == np.float32 and a.flags.c_contiguous and a.shape == shape
+    table = None if motion is None else np.ascontiguousarray(motion, dtype=NODE_MOTION_DTYPE).reshape(-1)
+    p = ReprojectMotionParams.of(params, depth_tolerance, max_history, True if table is not None else None, clamp, clamp_radius, clamp_gamma)
+    c0, c1 = _camera_record(prev_cam), _camera_record(cur_cam)
+    _check(lib().qa_test_reproject_motion_host(c0.ctypes.data, c1.ctypes.data, int(origin[0]), int(origin[1]), w, h, rgb.ctypes.data, depth.ctypes.data,
+                                               ns.ctypes.data, None if idp[0] is None else idp[0].ctypes.data, hist[0].ctypes.data, hist[1].ctypes.data,
+                                               hist[2].ctypes.data, None if idp[1] is None else idp[1].ctypes.data,
+                                               None if table is None else table.ctypes.data, 0 if table is None else len(table), C.byref(p),
+                                               out.ctypes.data, out_length.ctypes.data))
+    return out, out_length
+
+
+def _motion_tensor(motion, device, stream):
+    """A motion table for a device call: a CUDA tensor of 64-byte records as it is, a numpy table of NODE_MOTION_DTYPE uploaded on
+    the call's stream (None: torch's current one, which the call waits for) -> (tensor or None, records)."""
+    import torch
+    if motion is None:
+        return None, 0
+    if isinstance(motion, torch.Tensor):
+        nbytes = motion.numel() * motion.element_size()
+        assert motion.is_cuda and motion.is_contiguous() and nbytes and nbytes % 64 == 0
+        return motion, nbytes // 64
+    table = np.ascontiguousarray(motion, dtype=NODE_MOTION_DTYPE).reshape(-1)
+    ts = torch.cuda.ExternalStream(stream, device=device) if stream else torch.cuda.current_stream(device)
+    with torch.cuda.stream(ts):
+        t = torch.from_numpy(table.view(np.uint8)).to(device)
+    return t, len(table)
 
 
 def _gbuffer_tensors(region, device, given):
@@ -698,6 +797,43 @@ class Context:
                                          None if hist_ids is None else hist_ids.data_ptr(), C.byref(p), out.data_ptr(), out_length.data_ptr(), sptr))
         return out, out_length
 
+    def reproject_motion_device(self, cur, history, prev_cam, cur_cam, origin=(0, 0), ids=None, hist_ids=None, motion=None, out=None, out_length=None,
+                                params=None, depth_tolerance=None, max_history=None, clamp=None, clamp_radius=None, clamp_gamma=None, stream=None):
+        """qa_reproject_motion_device: reproject_device that follows moved nodes and clamps stale history (include/qaray_hip.h).
+        The arguments of reproject_device, and motion: the table of node_motion() as a numpy array (uploaded on the call's stream)
+        or a CUDA tensor of its 64-byte records - given, it sets QA_REPROJECT_MOTION and wants both ids planes; clamp (bool) sets
+        or clears QA_REPROJECT_CLAMP (out may then not be cur's rgb), clamp_radius / clamp_gamma override params' values (a
+        ReprojectMotionParams).  With neither, the result is reproject_device's.  -> (out, out_length); only enqueues."""
+        import torch
+        rgb, depth, ns = cur
+        hrgb, hdepth, hlen = history
+        assert rgb.is_cuda and rgb.is_contiguous() and rgb.dim() == 3 and rgb.shape[2] == 3 and rgb.dtype == torch.float32
+        h, w = rgb.shape[:2]
+        n = h * w
+        for t in (depth, ns, hdepth, hlen):
+            assert t.is_cuda and t.is_contiguous() and t.numel() == n and t.element_size() == 4
+        assert depth.dtype == torch.float32 and hdepth.dtype == torch.float32 and hlen.dtype == torch.float32
+        assert hrgb.is_cuda and hrgb.is_contiguous() and hrgb.numel() == 3 * n and hrgb.dtype == torch.float32
+        for t in (ids, hist_ids):
+            assert t is None or (t.is_cuda and t.is_contiguous() and t.numel() == 2 * n and t.dtype == torch.int32)
+        if out is None:
+            out = torch.empty_like(rgb)
+        if out_length is None:
+            out_length = torch.empty((h, w), dtype=torch.float32, device=rgb.device)
+        assert out.is_cuda and out.is_contiguous() and out.numel() == 3 * n and out.dtype == torch.float32
+        assert out_length.is_cuda and out_length.is_contiguous() and out_length.numel() == n and out_length.dtype == torch.float32
+        # (kept until the next call: without a stream of the caller's the kernel is not ordered against torch's allocator)
+        self._motion_upload, count = _motion_tensor(motion, rgb.device, stream)
+        p = ReprojectMotionParams.of(params, depth_tolerance, max_history, True if motion is not None else None, clamp, clamp_radius, clamp_gamma)
+        c0, c1 = _camera_record(prev_cam), _camera_record(cur_cam)
+        sptr = self._stream_arg(stream, rgb)
+        _check(lib().qa_reproject_motion_device(self._h, c0.ctypes.data, c1.ctypes.data, int(origin[0]), int(origin[1]), w, h, rgb.data_ptr(),
+                                                depth.data_ptr(), ns.data_ptr(), None if ids is None else ids.data_ptr(), hrgb.data_ptr(),
+                                                hdepth.data_ptr(), hlen.data_ptr(), None if hist_ids is None else hist_ids.data_ptr(),
+                                                None if motion is None else self._motion_upload.data_ptr(), count, C.byref(p), out.data_ptr(),
+                                                out_length.data_ptr(), sptr))
+        return out, out_length
+
     def gbuffer(self, region, seed=DEFAULT_SEED):
         """qa_gbuffer_region: the first-hit guide planes of a region -> dict of numpy arrays: normal [h,w,3] f32 (world space, 0 on a
         miss), albedo [h,w,3] f32, depth [h,w] f32 (render_region's depth plane), ids [h,w,2] i32 (node, material; -1 on a miss;
@@ -962,6 +1098,36 @@ class Progressive:
                                                      sptr))
         return out, out_length
 
+    def reproject_motion_device(self, history, prev_cam, hist_ids=None, motion=None, out=None, out_length=None, params=None, depth_tolerance=None,
+                                max_history=None, clamp=None, clamp_radius=None, clamp_gamma=None, stream=None):
+        """qa_progressive_reproject_motion_device: reproject_device of this frame with Context.reproject_motion_device's additions
+        (motion: a numpy table or a CUDA tensor, wants hist_ids; clamp, clamp_radius, clamp_gamma).  -> (out, out_length); only
+        enqueues.  The frame is not changed; a stale frame wants restart() first."""
+        import torch
+        device = torch.device("cuda", self._ctx.device_id)
+        x0, y0, x1, y1 = self.region
+        h, w = y1 - y0, x1 - x0
+        n = h * w
+        hrgb, hdepth, hlen = history
+        for t, k in ((hrgb, 3), (hdepth, 1), (hlen, 1)):
+            assert t.is_cuda and t.is_contiguous() and t.numel() == k * n and t.dtype == torch.float32
+        assert hist_ids is None or (hist_ids.is_cuda and hist_ids.is_contiguous() and hist_ids.numel() == 2 * n and hist_ids.dtype == torch.int32)
+        if out is None:
+            out = torch.empty((h, w, 3), dtype=torch.float32, device=device)
+        if out_length is None:
+            out_length = torch.empty((h, w), dtype=torch.float32, device=device)
+        assert out.is_cuda and out.is_contiguous() and out.numel() == 3 * n and out.dtype == torch.float32
+        assert out_length.is_cuda and out_length.is_contiguous() and out_length.numel() == n and out_length.dtype == torch.float32
+        self._ctx._motion_upload, count = _motion_tensor(motion, device, stream)
+        p = ReprojectMotionParams.of(params, depth_tolerance, max_history, True if motion is not None else None, clamp, clamp_radius, clamp_gamma)
+        c0 = _camera_record(prev_cam)
+        sptr = Context._stream_arg(stream, out)
+        _check(lib().qa_progressive_reproject_motion_device(self._ctx._h, c0.ctypes.data, hrgb.data_ptr(), hdepth.data_ptr(), hlen.data_ptr(),
+                                                            None if hist_ids is None else hist_ids.data_ptr(),
+                                                            None if motion is None else self._ctx._motion_upload.data_ptr(), count, C.byref(p),
+                                                            out.data_ptr(), out_length.data_ptr(), sptr))
+        return out, out_length
+
     def status(self):
         """-> dict(spp_reached, pixels_finished, tiles_behind); synchronises."""
         r, f, b = C.c_int(), C.c_uint64(), C.c_uint64()
@@ -988,16 +1154,21 @@ class Progressive:
 
 
 class TemporalPreview:
-    """The history of an interactive preview across camera moves: torch plumbing around Context.reproject_device.  Owns the
-    accumulated colour and length (two of each: a call reads one and writes the other), the depth and ids of the last frame and
-    the last camera.
-        tp = TemporalPreview(ctx, region)
-        per frame: ctx.edit_camera(cam); ctx.render_region_device(region, 4, rgb, depth, ns, seed=NEW SEED, stream=s)
-                   g = ctx.gbuffer_device(region, seed, ids=ids, stream=s); acc, length = tp.push(cam, rgb, depth, ns, ids, stream=s)
-    A new seed per frame matters: frames of one seed repeat their noise, and accumulating them gains nothing.  reset() after any
-    edit that is not a camera move (the reprojection knows of no other change: include/qaray_hip.h)."""
+    """The history of an interactive preview across camera moves, node moves and scene edits: torch plumbing around
+    Context.reproject_device and Context.reproject_motion_device.  Owns the accumulated colour and length (two of each: a call reads
+    one and writes the other), the depth and ids of the last frame, the last camera and the last instance table.
+        tp = TemporalPreview(ctx, region, clamp=True)
+        per frame: ctx.edit_camera(cam) / ctx.edit_instances(first, records) / ctx.edit_lights(...)
+                   ctx.render_region_device(region, 4, rgb, depth, ns, seed=NEW SEED, stream=s)
+                   g = ctx.gbuffer_device(region, seed, ids=ids, stream=s)
+                   acc, length = tp.push(cam, rgb, depth, ns, ids, instances=TABLE AS IT NOW STANDS, stream=s)
+    A new seed per frame matters: frames of one seed repeat their noise, and accumulating them gains nothing.
+    With instances= (and ids) on every push, node moves (edit_instances) need no reset: the history follows the node.  With
+    clamp=True, light, material and texture edits need no reset: the history is clamped to the current frame's neighbourhood and
+    leaves within a few frames.  reset() is still needed after an edit that changes ids or topology (a new scene upload), and after
+    any edit that is not a camera move when neither of the two is in use (include/qaray_hip.h)."""
 
-    def __init__(self, ctx, region, params=None, depth_tolerance=None, max_history=None):
+    def __init__(self, ctx, region, params=None, depth_tolerance=None, max_history=None, clamp=False, clamp_radius=None, clamp_gamma=None):
         import torch
         self._ctx = ctx
         self.region = tuple(region)
@@ -1005,30 +1176,39 @@ class TemporalPreview:
         h, w = y1 - y0, x1 - x0
         dev = torch.device("cuda", ctx.device_id)
         self.params = ReprojectParams.of(params, depth_tolerance, max_history)
+        self.motion_params = ReprojectMotionParams.of(None, self.params.depth_tolerance, self.params.max_history, None, bool(clamp), clamp_radius,
+                                                      clamp_gamma)
         self._rgb = [torch.zeros((h, w, 3), dtype=torch.float32, device=dev) for _ in range(2)]
         self._length = [torch.zeros((h, w), dtype=torch.float32, device=dev) for _ in range(2)]
         self._depth = torch.zeros((h, w), dtype=torch.float32, device=dev)
         self._ids = torch.zeros((h, w, 2), dtype=torch.int32, device=dev)
         self._has_ids = False
         self._cam = None
+        self._instances = None
         self._at = 0
         torch.cuda.current_stream(dev).synchronize()
 
     def reset(self):
         """Forget the history: the next push returns its frame as it is."""
         self._cam = None
+        self._instances = None
 
-    def push(self, cam, rgb, depth, ns, ids=None, stream=None):
+    def push(self, cam, rgb, depth, ns, ids=None, instances=None, stream=None):
         """The frame (rgb, depth, ns[, ids]: torch CUDA tensors as render_region_device and gbuffer_device fill them) rendered from
         cam (a record of CAMERA_DTYPE) joins the history -> (accumulated rgb float32 [h,w,3], length float32 [h,w]); the first push,
         and one after reset(), returns the frame itself with length = ns.  The ids are compared when this push and the last one
-        both brought them.  The two tensors are the preview's own and stay as they are until the push after the next one.  The
-        caller's tensors are free again when the call returns (depth and ids are copied).  stream: the HIP stream handle the frame
-        was rendered on: everything is enqueued there.  None: the frame was rendered on the context's own stream, and the call
-        synchronises (see render_region_device)."""
+        both brought them.  instances: the scene's whole INSTANCE_DTYPE table as it stands for this frame
+        (blob_table(ctx.download_scene(), "instances"), or the caller's own edited copy; it is copied); when this push and the last
+        one both brought instances and ids, the history of a node that moved in between is fetched from where the node was
+        (node_motion).  The two tensors returned are the preview's own and stay as they are until the push after the next one.
+        The caller's tensors are free again when the call returns (depth and ids are copied).  stream: the HIP stream handle the
+        frame was rendered on: everything is enqueued there.  None: the frame was rendered on the context's own stream, and the
+        call synchronises (see render_region_device)."""
         import torch
         dev = self._depth.device
         cam = _camera_record(cam)
+        if instances is not None:
+            instances = np.array(instances, dtype=INSTANCE_DTYPE).reshape(-1)
         if stream:
             ts = torch.cuda.ExternalStream(stream, device=dev)
         else:
@@ -1040,10 +1220,17 @@ class TemporalPreview:
             with torch.cuda.stream(ts):
                 self._length[prev].zero_()   # no history anywhere: the kernel hands the frame through
         with_ids = ids is not None and self._has_ids and not fresh
+        motion = None
+        if with_ids and instances is not None and self._instances is not None:
+            motion = node_motion(self._instances, instances)
         x0, y0 = self.region[:2]
-        self._ctx.reproject_device((rgb, depth, ns), (self._rgb[prev], self._depth, self._length[prev]), cam if fresh else self._cam, cam, origin=(x0, y0),
-                                   ids=ids if with_ids else None, hist_ids=self._ids if with_ids else None, out=self._rgb[nxt],
-                                   out_length=self._length[nxt], params=self.params, stream=stream)
+        frame, history = (rgb, depth, ns), (self._rgb[prev], self._depth, self._length[prev])
+        kw = dict(origin=(x0, y0), ids=ids if with_ids else None, hist_ids=self._ids if with_ids else None, out=self._rgb[nxt],
+                  out_length=self._length[nxt], stream=stream)
+        if motion is None and not self.motion_params.flags:
+            self._ctx.reproject_device(frame, history, cam if fresh else self._cam, cam, params=self.params, **kw)
+        else:
+            self._ctx.reproject_motion_device(frame, history, cam if fresh else self._cam, cam, motion=motion, params=self.motion_params, **kw)
         if not stream:
             self._ctx.synchronize()
         with torch.cuda.stream(ts):
@@ -1053,6 +1240,7 @@ class TemporalPreview:
         if not stream:
             ts.synchronize()
         self._has_ids = ids is not None
+        self._instances = instances
         self._cam = cam
         self._at = nxt
         return self._rgb[nxt], self._length[nxt]
