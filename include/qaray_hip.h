@@ -40,11 +40,14 @@
  *   qa_progressive_gbuffer_device  colour, node and material - for picking in a viewer and as guides for a preview filter)
  *   qa_denoise_guided_device,      (no counterpart: the preview filter with those normal and albedo planes as two more
  *   qa_progressive_denoise_guided* edge-stopping guides)
+ *   qa_denoise_variance_device     (no counterpart: that filter with a per-pixel variance of the caller's in place of its spatial guess)
  *   qa_reproject_device,           (no counterpart: the reference renders every frame from nothing; the accumulated frame of
  *   qa_progressive_reproject_device   an earlier camera carried into the frame of the camera as it now stands)
  *   qa_reproject_motion_device,    (no counterpart: the same with the history of a node that moved fetched from where the node
  *   qa_progressive_reproject_motion_device,   was, and a clamp of the history to the current frame's neighbourhood)
  *   qa_reproject_node_motion
+ *   qa_reproject_moments_device,   (no counterpart: the same carrying the first two luma moments of every pixel, for a per-pixel
+ *   qa_progressive_reproject_moments_device   variance of the accumulated colour, and shortening the history the clamp moved)
  *   qa_get_counters                (no counterpart: the reference only prints wall-clock)
  *   qa_get_kernel_time             Renderer::StartTimer/StopTimer       src/renderers/renderer.cpp:42-63
  */
@@ -355,6 +358,28 @@ int qa_denoise_guided_device(qa_ctx *ctx, const float *d_rgb, const float *d_dep
 int qa_progressive_denoise_guided(qa_ctx *ctx, const qa_denoise_guided_params *params, float *rgb);
 int qa_progressive_denoise_guided_device(qa_ctx *ctx, const qa_denoise_guided_params *params, float *d_rgb, void *hip_stream);
 
+/* The guided filter above with a variance plane of the caller's (the VARIANCE FORM section of qa_denoise_dev.h is the
+ * specification): d_variance, 1 float per pixel, an estimate of the variance of the pixel's luma from the frames behind it - the
+ * d_out_variance plane of qa_reproject_moments_device (below).  Pass 0 of the filter estimates a pixel's variance from the 3x3 luma
+ * window of the one frame it is given, which cannot tell texture on a converged surface from noise; with QA_DENOISE_GUIDE_VARIANCE
+ * = 4 a pixel whose plane value is finite and >= 0 takes variance_scale x the (1, 2, 1) x (1, 2, 1) mean of such values among the
+ * pixels of its class in its 3x3 window instead, and every other pixel (the plane says -1, "none") keeps the spatial estimate.  Only
+ * pass 0 changes: one more kernel in place of the old pass 0, the iterations run as they are.  With the flag clear, or a plane of -1
+ * everywhere, the result is qa_denoise_guided_device's bit for bit.  qa_denoise_variance_params_default: the guided defaults,
+ * variance_scale 4 (DESIGN.md 4k has the sweep), all three flags.  QA_EINVAL: everything qa_denoise_guided_device refuses, a
+ * variance_scale that is not finite and positive, a variance plane that disagrees with its flag.  The variance is of the luma only;
+ * there are no progressive variants (a viewer filters the accumulated buffers of the reprojection). */
+#define QA_DENOISE_GUIDE_VARIANCE 4u
+typedef struct qa_denoise_variance_params {
+  int      iterations;
+  float    sigma_color, sigma_depth, sigma_normal, variance_scale;
+  uint32_t flags;
+} qa_denoise_variance_params;
+int qa_denoise_variance_params_default(qa_denoise_variance_params *params);
+int qa_denoise_variance_device(qa_ctx *ctx, const float *d_rgb, const float *d_depth, const uint32_t *d_nsamples, const float *d_normal,
+                               const float *d_albedo, const float *d_variance, int width, int height,
+                               const qa_denoise_variance_params *params, float *d_out_rgb, void *hip_stream);
+
 /* Temporal reprojection: the accumulated frame of an EARLIER camera (the history) carried into the frame just rendered from the
  * camera as it now stands, so that a camera move keeps the samples of the surface points both cameras see.  The header comment of
  * qaray_amd/csrc/hip/qa_reproject_dev.h is its specification.  Both frames cover pixels [x0, x0 + width) x [y0, y0 + height) of the
@@ -445,6 +470,47 @@ int qa_progressive_reproject_motion_device(qa_ctx *ctx, const qa_camera *prev_ca
                                            const float *d_hist_length, const int32_t *d_hist_ids, const qa_node_motion *d_motion,
                                            int motion_count, const qa_reproject_motion_params *params, float *d_out_rgb,
                                            float *d_out_length, void *hip_stream);
+
+/* Reprojection that carries luminance moments and shortens clamped history: the motion calls above with two more flags of
+ * qa_reproject_moments_params; with neither they return the bits of the motion calls.  The header comment of
+ * qaray_amd/csrc/hip/qa_reproject_moments_dev.h is the specification.
+ *   QA_REPROJECT_MOMENTS  d_hist_moments (2 floats per pixel, 8-byte aligned; NULL: nobody has moment history) holds the accumulated
+ *                         first and second moment of the luma (0.2126, 0.7152, 0.0722).  They are fetched with the colour taps and
+ *                         blended with the frame's luma l and l * l at the colour's rate k = ns / (L + ns) into d_out_moments (the
+ *                         next call's d_hist_moments).  d_out_variance (1 float) is max(o2 - o1 * o1, 0) * k, the variance of the
+ *                         accumulated colour's luma, for a pixel that has moment history and out_length >= min_frames * ns; else
+ *                         -1, "none", as it is on the first frame, after a disocclusion and on a void pixel.  It is a plane for
+ *                         qa_denoise_variance_device.  Exact for frames of equal weight; once max_history caps the length it
+ *                         overstates by up to 2x; it does not see the clamp (the moments are not clamped); the threshold counts
+ *                         samples, not frames.  With the flag clear the two outputs are not written and may be NULL.
+ *   QA_REPROJECT_SHORTEN  only with QA_REPROJECT_CLAMP.  Where the clamp moved the history colour by d (largest component) against a
+ *                         box of half-width s = clamp_gamma * sigma (largest component), the history's length enters the
+ *                         accumulation as L / (1 + shorten_rate * d / (s + 1e-4)): wrong history stops weighing on the frames
+ *                         that follow.  A history inside the box keeps its length, bit for bit.
+ * qa_reproject_moments_params_default: the motion call's defaults, min_frames 4, shorten_rate 4, flags 0 (DESIGN.md 4k has the
+ * sweep behind shorten_rate).  QA_EINVAL: everything the motion calls refuse; unknown flag bits; QA_REPROJECT_SHORTEN without
+ * QA_REPROJECT_CLAMP or with a shorten_rate that is not finite or is negative; QA_REPROJECT_MOMENTS with a min_frames that is not
+ * finite or is below 1, without both output planes, with d_out_moments == d_hist_moments, with a moments plane that is not 8-byte
+ * aligned, or with one of the two outputs overlapping any other plane of the call.  Not in the CLI, distributed.py or bench.py. */
+#define QA_REPROJECT_MOMENTS 4u
+#define QA_REPROJECT_SHORTEN 8u
+typedef struct qa_reproject_moments_params {
+  float    depth_tolerance, max_history, clamp_gamma, min_frames, shorten_rate;
+  int32_t  clamp_radius;
+  uint32_t flags;
+} qa_reproject_moments_params;
+int qa_reproject_moments_params_default(qa_reproject_moments_params *params);
+int qa_reproject_moments_device(qa_ctx *ctx, const qa_camera *prev_cam, const qa_camera *cur_cam, int x0, int y0, int width, int height,
+                                const float *d_rgb, const float *d_depth, const uint32_t *d_nsamples, const int32_t *d_ids,
+                                const float *d_hist_rgb, const float *d_hist_depth, const float *d_hist_length, const int32_t *d_hist_ids,
+                                const float *d_hist_moments, const qa_node_motion *d_motion, int motion_count,
+                                const qa_reproject_moments_params *params, float *d_out_rgb, float *d_out_length, float *d_out_moments,
+                                float *d_out_variance, void *hip_stream);
+int qa_progressive_reproject_moments_device(qa_ctx *ctx, const qa_camera *prev_cam, const float *d_hist_rgb, const float *d_hist_depth,
+                                            const float *d_hist_length, const int32_t *d_hist_ids, const float *d_hist_moments,
+                                            const qa_node_motion *d_motion, int motion_count, const qa_reproject_moments_params *params,
+                                            float *d_out_rgb, float *d_out_length, float *d_out_moments, float *d_out_variance,
+                                            void *hip_stream);
 
 /* Counters accumulated since the last reset (synchronises the context first). */
 int qa_get_counters(qa_ctx *ctx, qa_counters *out);
@@ -554,6 +620,9 @@ int qa_test_denoise_host(const float *rgb, const float *depth, const uint32_t *n
 int qa_test_denoise_guided_host(const float *rgb, const float *depth, const uint32_t *nsamples, const float *normal, const float *albedo,
                                 int width, int height, const qa_denoise_guided_params *params, float *out_rgb);
 
+int qa_test_denoise_variance_host(const float *rgb, const float *depth, const uint32_t *nsamples, const float *normal, const float *albedo,
+                                  const float *variance, int width, int height, const qa_denoise_variance_params *params, float *out_rgb);
+
 /* Self-test hook for the reprojection (qaray_amd/csrc/hip/qa_reproject_dev.h): the source of qa_reproject_device's kernel compiled
  * for the host, pixel after pixel over host arrays, arguments in the same order (no GPU and no context needed). */
 int qa_test_reproject_host(const qa_camera *prev_cam, const qa_camera *cur_cam, int x0, int y0, int width, int height, const float *rgb,
@@ -565,6 +634,12 @@ int qa_test_reproject_motion_host(const qa_camera *prev_cam, const qa_camera *cu
                                   const float *depth, const uint32_t *nsamples, const int32_t *ids, const float *hist_rgb,
                                   const float *hist_depth, const float *hist_length, const int32_t *hist_ids, const qa_node_motion *motion,
                                   int motion_count, const qa_reproject_motion_params *params, float *out_rgb, float *out_length);
+/* The same for qa_reproject_moments_device (qaray_amd/csrc/hip/qa_reproject_moments_dev.h). */
+int qa_test_reproject_moments_host(const qa_camera *prev_cam, const qa_camera *cur_cam, int x0, int y0, int width, int height, const float *rgb,
+                                   const float *depth, const uint32_t *nsamples, const int32_t *ids, const float *hist_rgb, const float *hist_depth,
+                                   const float *hist_length, const int32_t *hist_ids, const float *hist_moments, const qa_node_motion *motion,
+                                   int motion_count, const qa_reproject_moments_params *params, float *out_rgb, float *out_length,
+                                   float *out_moments, float *out_variance);
 
 #ifdef __cplusplus
 }

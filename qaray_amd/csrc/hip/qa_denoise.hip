@@ -1,5 +1,5 @@
 // qa_denoise.hip — the edge-avoiding a-trous filter of qa_denoise_dev.h on the device (qa_denoise_device, qa_progressive_denoise*,
-// the guided form qa_denoise_guided_*) and the same source on the host (qa_test_denoise_host, qa_test_denoise_guided_host).  A guide kernel (pass 0) fills the context's working planes - colour and
+// the guided form qa_denoise_guided_*, the variance form qa_denoise_variance_device) and the same source on the host (qa_test_denoise_host, qa_test_denoise_guided_host, qa_test_denoise_variance_host).  A guide kernel (pass 0) fills the context's working planes - colour and
 // variance (16 bytes per pixel, two of them: the iterations go from one to the other), depth and slope (8 bytes) - from plain
 // buffers or from the progressive frame's slabs; one kernel per iteration follows, the last of which writes the caller's rgb.
 //
@@ -55,6 +55,26 @@ __global__ __launch_bounds__(256) void qa_denoise_guide(DenoiseSrc src, int W, i
   DenoiseColor c;
   DenoiseGuide g;
   denoiseGuide(src, x, y, W, H, c, g);
+  const size_t q = (size_t) y * (size_t) W + (size_t) x;
+  color[q] = c;
+  guide[q] = g;
+}
+
+// Pass 0 of the variance form: qa_denoise_guide with the caller's variance plane, 4 more bytes per window pixel
+struct DenoiseVarianceSrc {
+  const float *variance;
+  int W;
+  __host__ __device__ __forceinline__ float operator()(int x, int y) const { return variance[(size_t) y * (size_t) W + (size_t) x]; }
+};
+
+__global__ __launch_bounds__(256) void qa_denoise_guide_variance(DenoiseSrc src, DenoiseVarianceSrc vsrc, float varianceScale, int W, int H,
+                                                                 DenoiseColor *color, DenoiseGuide *guide)
+{
+  const int x = (int) (blockIdx.x * QA_DENOISE_TILE + (threadIdx.x & 15u)), y = (int) (blockIdx.y * QA_DENOISE_TILE + (threadIdx.x >> 4));
+  if (x >= W || y >= H) return;
+  DenoiseColor c;
+  DenoiseGuide g;
+  denoiseGuideVariance(src, vsrc, varianceScale, x, y, W, H, c, g);
   const size_t q = (size_t) y * (size_t) W + (size_t) x;
   color[q] = c;
   guide[q] = g;
@@ -176,9 +196,24 @@ static int CheckParams(const qa_denoise_params *p, int width, int height)
   return QA_OK;
 }
 
+// Pass 0 on s: the variance form's kernel when the caller brought a variance plane, else qa_denoise_guide
+static int LaunchPass0(const DenoiseSrc &src, const float *variance, float varianceScale, int W, int H, DenoiseColor *color, DenoiseGuide *guide, dim3 grid,
+                       hipStream_t s)
+{
+  if (variance) {
+    const DenoiseVarianceSrc vsrc = {variance, W};
+    hipLaunchKernelGGL(qa::qa_denoise_guide_variance, grid, dim3(256), 0, s, src, vsrc, varianceScale, W, H, color, guide);
+  } else {
+    hipLaunchKernelGGL(qa::qa_denoise_guide, grid, dim3(256), 0, s, src, W, H, color, guide);
+  }
+  HIP_TRY(hipGetLastError());
+  return QA_OK;
+}
+
 // The guide kernel and the iterations on s.  The working planes (40 bytes per pixel: [colour A | colour B | guide]) are one per
 // context and only grow; a call on another stream than the last one waits for it
-static int Denoise(qa_ctx *c, const DenoiseSrc &src, int W, int H, const qa_denoise_params &p, float *out, hipStream_t s)
+static int Denoise(qa_ctx *c, const DenoiseSrc &src, int W, int H, const qa_denoise_params &p, float *out, hipStream_t s, const float *variance = nullptr,
+                   float varianceScale = 1.f)
 {
   const size_t n = (size_t) W * (size_t) H;
   if (p.iterations == 0) {   // the input's bits (a progressive frame still has to be resolved: its callers never get here)
@@ -190,8 +225,7 @@ static int Denoise(qa_ctx *c, const DenoiseSrc &src, int W, int H, const qa_deno
   DenoiseColor *plane[2] = {static_cast<DenoiseColor *>(c->denoisePlanes.p), static_cast<DenoiseColor *>(c->denoisePlanes.p) + n};
   DenoiseGuide *guide = reinterpret_cast<DenoiseGuide *>(plane[1] + n);
   const dim3 grid((unsigned) ((W + QA_DENOISE_TILE - 1) / QA_DENOISE_TILE), (unsigned) ((H + QA_DENOISE_TILE - 1) / QA_DENOISE_TILE)), block(256);
-  hipLaunchKernelGGL(qa::qa_denoise_guide, grid, block, 0, s, src, W, H, plane[0], guide);
-  HIP_TRY(hipGetLastError());
+  if (int rc = LaunchPass0(src, variance, varianceScale, W, H, plane[0], guide, grid, s)) return rc;
   for (int i = 0; i < p.iterations; ++i) {
     const DenoiseColor *from = plane[i & 1];
     DenoiseColor *to = plane[(i + 1) & 1];
@@ -202,6 +236,60 @@ static int Denoise(qa_ctx *c, const DenoiseSrc &src, int W, int H, const qa_deno
     HIP_TRY(hipGetLastError());
   }
   HIP_TRY(c->lastDenoise.Record(s));
+  return QA_OK;
+}
+
+// Every form on the CPU, pixel after pixel, after the entry's checks: pass 0 (the variance form's with a variance plane), the aux
+// plane when p.flags names a guide, and the iterations of the form that p.flags selects
+static int DenoiseOnHost(const float *rgb, const float *depth, const uint32_t *ns, const float *normal, const float *albedo, const float *variance,
+                         float varianceScale, int W, int H, const qa_denoise_guided_params &p, float *out_rgb)
+{
+  const size_t n = (size_t) W * (size_t) H;
+  if (p.iterations == 0) {
+    if (out_rgb != rgb) memcpy(out_rgb, rgb, n * 3 * sizeof(float));
+    return QA_OK;
+  }
+  const bool guided = (p.flags & (QA_DENOISE_GUIDE_NORMAL | QA_DENOISE_GUIDE_ALBEDO)) != 0u;
+  std::vector<DenoiseColor> plane[2] = {std::vector<DenoiseColor>(n), std::vector<DenoiseColor>(n)};
+  std::vector<DenoiseGuide> guide(n);
+  std::vector<DenoiseAux> aux(guided ? n : 0);
+  const auto src = [=](int x, int y) {
+    const size_t q = (size_t) y * (size_t) W + (size_t) x;
+    DenoisePixel px;
+    px.r = rgb[3 * q]; px.g = rgb[3 * q + 1]; px.b = rgb[3 * q + 2]; px.z = depth[q]; px.ns = ns[q];
+    return px;
+  };
+  const auto gsrc = [=](int x, int y, float *nn, float *aa) {
+    const size_t q = (size_t) y * (size_t) W + (size_t) x;
+    if (normal) { nn[0] = normal[3 * q]; nn[1] = normal[3 * q + 1]; nn[2] = normal[3 * q + 2]; }
+    if (albedo) { aa[0] = albedo[3 * q]; aa[1] = albedo[3 * q + 1]; aa[2] = albedo[3 * q + 2]; }
+  };
+  const DenoiseVarianceSrc vsrc = {variance, W};
+  for (int y = 0; y < H; ++y)
+    for (int x = 0; x < W; ++x) {
+      const size_t q = (size_t) y * W + x;
+      if (variance) denoiseGuideVariance(src, vsrc, varianceScale, x, y, W, H, plane[0][q], guide[q]);
+      else denoiseGuide(src, x, y, W, H, plane[0][q], guide[q]);
+      if (guided) aux[q] = denoiseAux(src, gsrc, x, y, W, H, p.flags);
+    }
+  for (int i = 0; i < p.iterations; ++i) {
+    const DenoiseColor *from = plane[i & 1].data();
+    const DenoiseGuide *gd = guide.data();
+    const DenoiseAux *ad = aux.data();
+    const auto tap = [=](int x, int y, DenoiseColor &cc, DenoiseGuide &g) {
+      const size_t q = (size_t) y * (size_t) W + (size_t) x;
+      cc = from[q];
+      g = gd[q];
+    };
+    const auto at = [=](int x, int y) { return ad[(size_t) y * (size_t) W + (size_t) x]; };
+    std::vector<DenoiseColor> &to = plane[(i + 1) & 1];
+    for (int y = 0; y < H; ++y)
+      for (int x = 0; x < W; ++x)
+        to[(size_t) y * W + x] = guided ? denoiseIterateGuided(tap, at, x, y, W, H, 1 << i, p.sigma_color, p.sigma_depth, p.sigma_normal)
+                                        : denoiseIterate(tap, x, y, W, H, 1 << i, p.sigma_color, p.sigma_depth);
+  }
+  const std::vector<DenoiseColor> &last = plane[p.iterations & 1];
+  for (size_t q = 0; q < n; ++q) { out_rgb[3 * q] = last[q].r; out_rgb[3 * q + 1] = last[q].g; out_rgb[3 * q + 2] = last[q].b; }
   return QA_OK;
 }
 
@@ -267,37 +355,8 @@ int qa_test_denoise_host(const float *rgb, const float *depth, const uint32_t *n
 {
   if (!rgb || !depth || !ns || !out_rgb) return Fail(QA_EINVAL, "null buffer");
   if (int rc = CheckParams(p, width, height)) return rc;
-  const int W = width, H = height;
-  const size_t n = (size_t) W * (size_t) H;
-  if (p->iterations == 0) {
-    if (out_rgb != rgb) memcpy(out_rgb, rgb, n * 3 * sizeof(float));
-    return QA_OK;
-  }
-  std::vector<DenoiseColor> plane[2] = {std::vector<DenoiseColor>(n), std::vector<DenoiseColor>(n)};
-  std::vector<DenoiseGuide> guide(n);
-  const auto src = [=](int x, int y) {
-    const size_t q = (size_t) y * (size_t) W + (size_t) x;
-    DenoisePixel px;
-    px.r = rgb[3 * q]; px.g = rgb[3 * q + 1]; px.b = rgb[3 * q + 2]; px.z = depth[q]; px.ns = ns[q];
-    return px;
-  };
-  for (int y = 0; y < H; ++y)
-    for (int x = 0; x < W; ++x) denoiseGuide(src, x, y, W, H, plane[0][(size_t) y * W + x], guide[(size_t) y * W + x]);
-  for (int i = 0; i < p->iterations; ++i) {
-    const DenoiseColor *from = plane[i & 1].data();
-    const DenoiseGuide *gd = guide.data();
-    const auto tap = [=](int x, int y, DenoiseColor &c, DenoiseGuide &g) {
-      const size_t q = (size_t) y * (size_t) W + (size_t) x;
-      c = from[q];
-      g = gd[q];
-    };
-    std::vector<DenoiseColor> &to = plane[(i + 1) & 1];
-    for (int y = 0; y < H; ++y)
-      for (int x = 0; x < W; ++x) to[(size_t) y * W + x] = denoiseIterate(tap, x, y, W, H, 1 << i, p->sigma_color, p->sigma_depth);
-  }
-  const std::vector<DenoiseColor> &last = plane[p->iterations & 1];
-  for (size_t q = 0; q < n; ++q) { out_rgb[3 * q] = last[q].r; out_rgb[3 * q + 1] = last[q].g; out_rgb[3 * q + 2] = last[q].b; }
-  return QA_OK;
+  const qa_denoise_guided_params g = {p->iterations, p->sigma_color, p->sigma_depth, QA_DENOISE_DEFAULT_SIGMA_NORMAL, 0u};
+  return DenoiseOnHost(rgb, depth, ns, nullptr, nullptr, nullptr, 1.f, width, height, g, out_rgb);
 }
 
 }  // extern "C"
@@ -318,7 +377,8 @@ static int CheckGuidedParams(const qa_denoise_guided_params *p, int width, int h
 // 40 + 32 bytes per pixel, and 24 more when the planes are the context's own (a progressive frame's, computed here: prog = true).
 // Every entry is written before it is read, as in Denoise
 static int DenoiseGuided(qa_ctx *c, const DenoiseSrc &src, const float *normal, const float *albedo, bool prog, int W, int H,
-                         const qa_denoise_guided_params &p, float *out, hipStream_t s, void *hip_stream)
+                         const qa_denoise_guided_params &p, float *out, hipStream_t s, void *hip_stream, const float *variance = nullptr,
+                         float varianceScale = 1.f)
 {
   const size_t n = (size_t) W * (size_t) H;
   HIP_TRY(c->denoisePlanes.Reserve(n * (prog ? 96 : 72), true));
@@ -333,8 +393,7 @@ static int DenoiseGuided(qa_ctx *c, const DenoiseSrc &src, const float *normal, 
     normal = dN; albedo = dA;
   }
   const dim3 grid((unsigned) ((W + QA_DENOISE_TILE - 1) / QA_DENOISE_TILE), (unsigned) ((H + QA_DENOISE_TILE - 1) / QA_DENOISE_TILE)), block(256);
-  hipLaunchKernelGGL(qa::qa_denoise_guide, grid, block, 0, s, src, W, H, plane[0], guide);
-  HIP_TRY(hipGetLastError());
+  if (int rc = LaunchPass0(src, variance, varianceScale, W, H, plane[0], guide, grid, s)) return rc;
   const DenoiseGuideSrc gsrc = {normal, albedo, W};
   hipLaunchKernelGGL(qa::qa_denoise_guided_aux, grid, block, 0, s, src, gsrc, W, H, p.flags, aux);
   HIP_TRY(hipGetLastError());
@@ -410,47 +469,59 @@ int qa_test_denoise_guided_host(const float *rgb, const float *depth, const uint
 {
   if (!rgb || !depth || !ns || !out_rgb) return Fail(QA_EINVAL, "null buffer");
   if (int rc = CheckGuidedParams(p, width, height, normal, albedo, true)) return rc;
-  const qa_denoise_params u = {p->iterations, p->sigma_color, p->sigma_depth, 0u};
-  if (p->flags == 0u || p->iterations == 0) return qa_test_denoise_host(rgb, depth, ns, width, height, &u, out_rgb);
-  const int W = width, H = height;
-  const size_t n = (size_t) W * (size_t) H;
-  std::vector<DenoiseColor> plane[2] = {std::vector<DenoiseColor>(n), std::vector<DenoiseColor>(n)};
-  std::vector<DenoiseGuide> guide(n);
-  std::vector<DenoiseAux> aux(n);
-  const auto src = [=](int x, int y) {
-    const size_t q = (size_t) y * (size_t) W + (size_t) x;
-    DenoisePixel px;
-    px.r = rgb[3 * q]; px.g = rgb[3 * q + 1]; px.b = rgb[3 * q + 2]; px.z = depth[q]; px.ns = ns[q];
-    return px;
-  };
-  const auto gsrc = [=](int x, int y, float *nn, float *aa) {
-    const size_t q = (size_t) y * (size_t) W + (size_t) x;
-    if (normal) { nn[0] = normal[3 * q]; nn[1] = normal[3 * q + 1]; nn[2] = normal[3 * q + 2]; }
-    if (albedo) { aa[0] = albedo[3 * q]; aa[1] = albedo[3 * q + 1]; aa[2] = albedo[3 * q + 2]; }
-  };
-  for (int y = 0; y < H; ++y)
-    for (int x = 0; x < W; ++x) {
-      denoiseGuide(src, x, y, W, H, plane[0][(size_t) y * W + x], guide[(size_t) y * W + x]);
-      aux[(size_t) y * W + x] = denoiseAux(src, gsrc, x, y, W, H, p->flags);
-    }
-  for (int i = 0; i < p->iterations; ++i) {
-    const DenoiseColor *from = plane[i & 1].data();
-    const DenoiseGuide *gd = guide.data();
-    const DenoiseAux *ad = aux.data();
-    const auto tap = [=](int x, int y, DenoiseColor &cc, DenoiseGuide &g) {
-      const size_t q = (size_t) y * (size_t) W + (size_t) x;
-      cc = from[q];
-      g = gd[q];
-    };
-    const auto at = [=](int x, int y) { return ad[(size_t) y * (size_t) W + (size_t) x]; };
-    std::vector<DenoiseColor> &to = plane[(i + 1) & 1];
-    for (int y = 0; y < H; ++y)
-      for (int x = 0; x < W; ++x)
-        to[(size_t) y * W + x] = denoiseIterateGuided(tap, at, x, y, W, H, 1 << i, p->sigma_color, p->sigma_depth, p->sigma_normal);
-  }
-  const std::vector<DenoiseColor> &last = plane[p->iterations & 1];
-  for (size_t q = 0; q < n; ++q) { out_rgb[3 * q] = last[q].r; out_rgb[3 * q + 1] = last[q].g; out_rgb[3 * q + 2] = last[q].b; }
+  return DenoiseOnHost(rgb, depth, ns, normal, albedo, nullptr, 1.f, width, height, *p, out_rgb);
+}
+
+// ---- the variance form: pass 0 takes the caller's variance plane; everything after it is the form that the guide flags select
+
+static int CheckVarianceParams(const qa_denoise_variance_params *p, int width, int height, const void *normal, const void *albedo, const void *variance,
+                               qa_denoise_guided_params *guided)
+{
+  if (!p) return Fail(QA_EINVAL, "null parameters");
+  if (p->flags & ~(QA_DENOISE_GUIDE_NORMAL | QA_DENOISE_GUIDE_ALBEDO | QA_DENOISE_GUIDE_VARIANCE)) return Fail(QA_EINVAL, "unknown flags");
+  *guided = {p->iterations, p->sigma_color, p->sigma_depth, p->sigma_normal, p->flags & (QA_DENOISE_GUIDE_NORMAL | QA_DENOISE_GUIDE_ALBEDO)};
+  if (int rc = CheckGuidedParams(guided, width, height, normal, albedo, true)) return rc;
+  if (!std::isfinite(p->variance_scale) || !(p->variance_scale > 0.f)) return Fail(QA_EINVAL, "a variance_scale that is not finite and positive");
+  if ((variance != nullptr) != ((p->flags & QA_DENOISE_GUIDE_VARIANCE) != 0u)) return Fail(QA_EINVAL, "a variance plane that disagrees with its flag");
   return QA_OK;
+}
+
+int qa_denoise_variance_params_default(qa_denoise_variance_params *p)
+{
+  if (!p) return Fail(QA_EINVAL, "null parameters");
+  p->iterations = QA_DENOISE_DEFAULT_ITERATIONS;
+  p->sigma_color = QA_DENOISE_DEFAULT_SIGMA_COLOR;
+  p->sigma_depth = QA_DENOISE_DEFAULT_SIGMA_DEPTH;
+  p->sigma_normal = QA_DENOISE_DEFAULT_SIGMA_NORMAL;
+  p->variance_scale = QA_DENOISE_DEFAULT_VARIANCE_SCALE;
+  p->flags = QA_DENOISE_GUIDE_NORMAL | QA_DENOISE_GUIDE_ALBEDO | QA_DENOISE_GUIDE_VARIANCE;
+  return QA_OK;
+}
+
+int qa_denoise_variance_device(qa_ctx *c, const float *d_rgb, const float *d_depth, const uint32_t *d_ns, const float *d_normal, const float *d_albedo,
+                               const float *d_variance, int width, int height, const qa_denoise_variance_params *p, float *d_out_rgb, void *hip_stream)
+{
+  if (int rc = Enter(c)) return rc;
+  if (!d_rgb || !d_depth || !d_ns || !d_out_rgb) return Fail(QA_EINVAL, "null buffer");
+  qa_denoise_guided_params g;
+  if (int rc = CheckVarianceParams(p, width, height, d_normal, d_albedo, d_variance, &g)) return rc;
+  if (!d_variance || p->iterations == 0) return qa_denoise_guided_device(c, d_rgb, d_depth, d_ns, d_normal, d_albedo, width, height, &g, d_out_rgb, hip_stream);
+  const DenoiseSrc src = {d_rgb, d_depth, d_ns, nullptr, width};
+  if (g.flags == 0u) {
+    const qa_denoise_params u = {p->iterations, p->sigma_color, p->sigma_depth, 0u};
+    return Denoise(c, src, width, height, u, d_out_rgb, StreamOf(c, hip_stream), d_variance, p->variance_scale);
+  }
+  return DenoiseGuided(c, src, d_normal, d_albedo, false, width, height, g, d_out_rgb, StreamOf(c, hip_stream), hip_stream, d_variance, p->variance_scale);
+}
+
+// the variance form on the CPU, pixel after pixel (no GPU, no context); a plane is null where its flag is clear
+int qa_test_denoise_variance_host(const float *rgb, const float *depth, const uint32_t *ns, const float *normal, const float *albedo, const float *variance,
+                                  int width, int height, const qa_denoise_variance_params *p, float *out_rgb)
+{
+  if (!rgb || !depth || !ns || !out_rgb) return Fail(QA_EINVAL, "null buffer");
+  qa_denoise_guided_params g;
+  if (int rc = CheckVarianceParams(p, width, height, normal, albedo, variance, &g)) return rc;
+  return DenoiseOnHost(rgb, depth, ns, normal, albedo, variance, p->variance_scale, width, height, g, out_rgb);
 }
 
 }  // extern "C"

@@ -61,6 +61,24 @@
 //   reliable(p) and valid_n(p) and valid_n(q) and dn(p, q) > 0:   e = e + dn(p, q) / sigma_normal
 //   reliable(p) and valid_a(p) and valid_a(q):                    e = e + da(p, q) / 0.02f
 // (It is the centre that is gated: an unreliable q still counts for a reliable p, at the distance its sample 0 gives it.)
+//
+// VARIANCE FORM (qa_denoise_variance_*; tests/denoise_variance_util.py restates this section).  One more input per pixel, optional
+// (flag QA_DENOISE_GUIDE_VARIANCE = 4, beside the two guide flags): variance[1], an estimate of the variance of the pixel's luma
+// that the caller brings - the out_variance plane of qa_reproject_moments_dev.h, which knows from the frames behind a pixel what no
+// window of one frame can tell: texture detail on a converged surface from Monte-Carlo noise.  One more parameter, variance_scale
+// (finite, > 0; default 4: DESIGN 4k has the sweep), which reconciles that estimate's scale with the sigma_color tuned on the spatial
+// one.  With the flag clear it is the guided form, bit for bit, and so it is with a plane that holds -1 everywhere.  Only pass 0
+// changes; the iterations, the variance recursion, the classes, the void rules and the guides' gating are unchanged.
+//   trusted(q): q is not void and its variance t_q is finite and >= 0.    (A negative value, one that is not a number and an
+//               infinite one all say "none".)
+//   Pass 0 computes var_p as above.  For a trusted p it is then replaced:
+//     members = the pixels of the 3x3 window around p that lie in the image, are not void, have p's class and are trusted (p is
+//               one), visited row-major; w = (1, 2, 1) x (1, 2, 1): 4 for p, 2 for its edge neighbours, 1 for the corners.
+//     sw += w;  st += w * t_q     (both from 0);          var_p = variance_scale * (st / sw)
+//   (The 3x3 prefilter that SVGF applies to its variance: an estimate from a handful of 4-spp frames is itself noisy.  A trusted p
+//   alone in its window takes variance_scale * t_p exactly.)  Every other pixel keeps the spatial estimate.
+// What it does not do: the plane is of the luma only; it is read by pass 0 and never updated by anything but the recursion; the
+// progressive variants have no such form (a viewer filters the accumulated plain buffers of hip.TemporalPreview).
 #pragma once
 #include "qa_device_math.h"
 
@@ -72,6 +90,7 @@ namespace qa {
 #define QA_DENOISE_DEFAULT_SIGMA_COLOR 4.0f
 #define QA_DENOISE_DEFAULT_SIGMA_DEPTH 1.0f
 #define QA_DENOISE_DEFAULT_SIGMA_NORMAL 0.1f
+#define QA_DENOISE_DEFAULT_VARIANCE_SCALE 4.0f
 #define QA_DENOISE_RELIABLE_NORMAL 0.02f
 #define QA_DENOISE_RELIABLE_ALBEDO 0.3f
 #define QA_DENOISE_SIGMA_ALBEDO 0.02f
@@ -142,6 +161,32 @@ __host__ __device__ __forceinline__ void denoiseGuide(const Src &src, int x, int
     slope = qmax(slope, d);
   }
   g.slope = qmax(slope, 1e-3f * qabs(p.z));
+}
+
+// Pass 0 of the variance form for pixel (x, y): denoiseGuide, then the prefiltered estimate of the caller's plane in var's place where
+// the pixel is trusted.  vsrc(x, y) -> the plane's value, called for pixels inside the image only
+__host__ __device__ __forceinline__ bool denoiseTrusted(float t) { return denoiseFinite(t) && t >= 0.f; }
+template <class Src, class VSrc>
+__host__ __device__ __forceinline__ void denoiseGuideVariance(const Src &src, const VSrc &vsrc, float varianceScale, int x, int y, int W, int H,
+                                                              DenoiseColor &c, DenoiseGuide &g)
+{
+  denoiseGuide(src, x, y, W, H, c, g);
+  if (g.slope < 0.f || !denoiseTrusted(vsrc(x, y))) return;
+  const bool miss = g.z == QA_DENOISE_MISS;
+  float sw = 0.f, st = 0.f;
+  for (int dy = -1; dy <= 1; ++dy)
+    for (int dx = -1; dx <= 1; ++dx) {
+      const int qx = x + dx, qy = y + dy;
+      if (qx < 0 || qy < 0 || qx >= W || qy >= H) continue;
+      const DenoisePixel q = src(qx, qy);
+      if (denoiseVoid(q) || (q.z == QA_DENOISE_MISS) != miss) continue;
+      const float t = vsrc(qx, qy);
+      if (!denoiseTrusted(t)) continue;
+      const float w = (dx == 0 ? 2.f : 1.f) * (dy == 0 ? 2.f : 1.f);
+      sw += w;
+      st += w * t;
+    }
+  c.var = varianceScale * (st / sw);
 }
 
 // One iteration of pixel (x, y) at step s.  tap(x, y, c, g) fetches a pixel's planes, called for pixels inside the image only

@@ -17,6 +17,7 @@
 #include "qa_ctx.h"
 #include "qa_reproject_dev.h"
 #include "qa_reproject_motion_dev.h"
+#include "qa_reproject_moments_dev.h"
 
 namespace qa {
 
@@ -60,6 +61,15 @@ struct ReprojectHistory {
     t.r = rgb[3 * q]; t.g = rgb[3 * q + 1]; t.b = rgb[3 * q + 2];
   }
 };
+struct ReprojectMomentPlane {
+  const float2 *moments;   // 8-byte aligned: one vector load per tap
+  int W;
+  __host__ __device__ __forceinline__ void operator()(int x, int y, float *h) const
+  {
+    const float2 v = moments[(size_t) y * (size_t) W + (size_t) x];
+    h[0] = v.x; h[1] = v.y;
+  }
+};
 struct ReprojectIds {
   const int32_t *plane[2];   // current, history
   int W;
@@ -98,14 +108,11 @@ struct ReprojectStagedWin {
   }
 };
 
-// One pixel per thread on 16x16 tiles, as qa_reproject.  With QA_REPROJECT_CLAMP the block first stages the current colour and
-// class of its tile and a halo of clampRadius pixels (at radius 3: 22 x 22 x 16 B = 7744 B of LDS), a pixel outside the region as
-// "does not contribute"; the window scans read LDS only.  Threads outside the region stage and wait with the others, then leave.
-__global__ __launch_bounds__(256) void qa_reproject_motion(ReprojectSetup S, ReprojectMotionSetup M, ReprojectSrc cur, ReprojectHistory hist, ReprojectIds ids,
-                                                           int withIds, float *outRgb, float *outLength)
+// The clamp's staging for the tile at (bx, by), by all 256 threads of the block: with QA_REPROJECT_CLAMP the tile and its halo of
+// clampRadius pixels go to `tile` (QA_REPROJECT_MAX_SIDE squared entries), and the block meets at a barrier
+__device__ __forceinline__ ReprojectStagedWin reprojectStage(float4 *tile, const ReprojectSetup &S, const ReprojectMotionSetup &M, const ReprojectSrc &cur, int bx,
+                                                             int by)
 {
-  __shared__ float4 tile[QA_REPROJECT_MAX_SIDE * QA_REPROJECT_MAX_SIDE];
-  const int bx = (int) (blockIdx.x * QA_REPROJECT_TILE), by = (int) (blockIdx.y * QA_REPROJECT_TILE);
   ReprojectStagedWin win = {tile, bx, by, QA_REPROJECT_TILE};
   if (M.flags & QA_REPROJECT_CLAMP) {
     const int r = M.clampRadius, side = QA_REPROJECT_TILE + 2 * r;   // r is 1 .. 3: side * side <= the array's size
@@ -121,6 +128,18 @@ __global__ __launch_bounds__(256) void qa_reproject_motion(ReprojectSetup S, Rep
     }
     __syncthreads();
   }
+  return win;
+}
+
+// One pixel per thread on 16x16 tiles, as qa_reproject.  With QA_REPROJECT_CLAMP the block first stages the current colour and
+// class of its tile and a halo of clampRadius pixels (at radius 3: 22 x 22 x 16 B = 7744 B of LDS), a pixel outside the region as
+// "does not contribute"; the window scans read LDS only.  Threads outside the region stage and wait with the others, then leave.
+__global__ __launch_bounds__(256) void qa_reproject_motion(ReprojectSetup S, ReprojectMotionSetup M, ReprojectSrc cur, ReprojectHistory hist, ReprojectIds ids,
+                                                           int withIds, float *outRgb, float *outLength)
+{
+  __shared__ float4 tile[QA_REPROJECT_MAX_SIDE * QA_REPROJECT_MAX_SIDE];
+  const int bx = (int) (blockIdx.x * QA_REPROJECT_TILE), by = (int) (blockIdx.y * QA_REPROJECT_TILE);
+  const ReprojectStagedWin win = reprojectStage(tile, S, M, cur, bx, by);
   const int x = bx + (int) (threadIdx.x & 15u), y = by + (int) (threadIdx.x >> 4);
   if (x >= S.W || y >= S.H) return;
   float o[3];
@@ -128,6 +147,28 @@ __global__ __launch_bounds__(256) void qa_reproject_motion(ReprojectSetup S, Rep
   const size_t q = (size_t) y * (size_t) S.W + (size_t) x;
   outRgb[3 * q] = o[0]; outRgb[3 * q + 1] = o[1]; outRgb[3 * q + 2] = o[2];
   outLength[q] = len;
+}
+
+// qa_reproject_motion with the moments: the staging, the tile and the pixel per thread are the same.  withMoments: QA_REPROJECT_MOMENTS
+// is set and the history has a moments plane; outMoments / outVariance are written with QA_REPROJECT_MOMENTS only (else they may be null)
+__global__ __launch_bounds__(256) void qa_reproject_moments(ReprojectSetup S, ReprojectMotionSetup M, ReprojectMomentsSetup X, ReprojectSrc cur,
+                                                            ReprojectHistory hist, ReprojectMomentPlane mom, ReprojectIds ids, int withIds, int withMoments,
+                                                            float *outRgb, float *outLength, float2 *outMoments, float *outVariance)
+{
+  __shared__ float4 tile[QA_REPROJECT_MAX_SIDE * QA_REPROJECT_MAX_SIDE];
+  const int bx = (int) (blockIdx.x * QA_REPROJECT_TILE), by = (int) (blockIdx.y * QA_REPROJECT_TILE);
+  const ReprojectStagedWin win = reprojectStage(tile, S, M, cur, bx, by);
+  const int x = bx + (int) (threadIdx.x & 15u), y = by + (int) (threadIdx.x >> 4);
+  if (x >= S.W || y >= S.H) return;
+  float o[3], om[2], var;
+  const float len = reprojectMomentsPixel(S, M, X, cur, hist, mom, ids, win, withIds != 0, withMoments != 0, x, y, o, om, var);
+  const size_t q = (size_t) y * (size_t) S.W + (size_t) x;
+  outRgb[3 * q] = o[0]; outRgb[3 * q + 1] = o[1]; outRgb[3 * q + 2] = o[2];
+  outLength[q] = len;
+  if (M.flags & QA_REPROJECT_MOMENTS) {
+    outMoments[q] = make_float2(om[0], om[1]);
+    outVariance[q] = var;
+  }
 }
 
 }  // namespace qa
@@ -221,6 +262,64 @@ static int LaunchReprojectMotion(const ReprojectSetup &S, const ReprojectMotionS
   const ReprojectIds id = {{ids, hIds}, S.W};
   const dim3 grid((unsigned) ((S.W + QA_REPROJECT_TILE - 1) / QA_REPROJECT_TILE), (unsigned) ((S.H + QA_REPROJECT_TILE - 1) / QA_REPROJECT_TILE)), block(256);
   hipLaunchKernelGGL(qa::qa_reproject_motion, grid, block, 0, s, S, M, src, hist, id, (ids && hIds) ? 1 : 0, outRgb, outLength);
+  HIP_TRY(hipGetLastError());
+  return QA_OK;
+}
+
+// What the moments entries check beyond CheckReprojectMotion
+static int CheckReprojectMoments(const qa_camera *prev, const qa_camera *cur, int x0, int y0, int W, int H, const float *rgb, const float *depth,
+                                 const uint32_t *ns, const int32_t *ids, bool idsGiven, const float *hRgb, const float *hDepth, const float *hLength,
+                                 const int32_t *hIds, const float *hMoments, const qa_node_motion *motion, int count, const qa_reproject_moments_params *p,
+                                 const float *outRgb, const float *outLength, const float *outMoments, const float *outVariance)
+{
+  if (!p) return Fail(QA_EINVAL, "null parameters");
+  if (p->flags & ~(QA_REPROJECT_MOTION | QA_REPROJECT_CLAMP | QA_REPROJECT_MOMENTS | QA_REPROJECT_SHORTEN)) return Fail(QA_EINVAL, "unknown flags");
+  const qa_reproject_motion_params base = {p->depth_tolerance, p->max_history, p->clamp_gamma, p->clamp_radius,
+                                           p->flags & (QA_REPROJECT_MOTION | QA_REPROJECT_CLAMP)};
+  if (int rc = CheckReprojectMotion(prev, cur, x0, y0, W, H, rgb, depth, ns, ids, idsGiven, hRgb, hDepth, hLength, hIds, motion, count, &base, outRgb,
+                                    outLength))
+    return rc;
+  if (p->flags & QA_REPROJECT_SHORTEN) {
+    if (!(p->flags & QA_REPROJECT_CLAMP)) return Fail(QA_EINVAL, "QA_REPROJECT_SHORTEN without QA_REPROJECT_CLAMP");
+    if (!std::isfinite(p->shorten_rate) || p->shorten_rate < 0.f) return Fail(QA_EINVAL, "a shorten_rate that is not finite or is negative");
+  }
+  if (!(p->flags & QA_REPROJECT_MOMENTS)) return QA_OK;
+  if (!std::isfinite(p->min_frames) || !(p->min_frames >= 1.f)) return Fail(QA_EINVAL, "a min_frames that is not finite or is below 1");
+  if (!outMoments || !outVariance) return Fail(QA_EINVAL, "QA_REPROJECT_MOMENTS without both d_out_moments and d_out_variance");
+  if (hMoments && outMoments == hMoments) return Fail(QA_EINVAL, "d_out_moments is the history's moments plane");
+  if ((uintptr_t) hMoments % 8 || (uintptr_t) outMoments % 8) return Fail(QA_EINVAL, "a moments plane that is not 8-byte aligned");
+  const size_t n = (size_t) W * (size_t) H;
+  const bool motionOn = (p->flags & QA_REPROJECT_MOTION) != 0u;
+  // the two new outputs overlap nothing: no input, no history plane, no other output, not the motion table
+  const struct { const void *p; size_t bytes; } other[] = {{rgb, 12 * n}, {depth, 4 * n}, {ns, 4 * n}, {ids, 8 * n}, {hRgb, 12 * n}, {hDepth, 4 * n},
+                                                          {hLength, 4 * n}, {hIds, 8 * n}, {hMoments, 8 * n}, {outRgb, 12 * n}, {outLength, 4 * n},
+                                                          {motionOn ? motion : nullptr, motionOn ? (size_t) count * sizeof(qa_node_motion) : 0}};
+  if (Overlap(outMoments, 8 * n, outVariance, 4 * n)) return Fail(QA_EINVAL, "the outputs overlap");
+  for (const auto &b : other)
+    if (Overlap(outMoments, 8 * n, b.p, b.bytes) || Overlap(outVariance, 4 * n, b.p, b.bytes))
+      return Fail(QA_EINVAL, "d_out_moments or d_out_variance overlaps another plane of the call");
+  // and the old outputs stay clear of the history's moments
+  if (Overlap(outRgb, 12 * n, hMoments, 8 * n) || Overlap(outLength, 4 * n, hMoments, 8 * n)) return Fail(QA_EINVAL, "an output aliases a history plane");
+  return QA_OK;
+}
+
+static qa::ReprojectMotionSetup MomentsMotionSetup(const qa_node_motion *motion, int count, const qa_reproject_moments_params *p)
+{
+  const bool on = (p->flags & QA_REPROJECT_MOTION) != 0u;
+  return {on ? motion : nullptr, on ? count : 0, p->flags, (p->flags & QA_REPROJECT_CLAMP) ? p->clamp_radius : 0, p->clamp_gamma};
+}
+
+static int LaunchReprojectMoments(const ReprojectSetup &S, const ReprojectMotionSetup &M, const ReprojectMomentsSetup &X, const ReprojectSrc &src,
+                                  const float *hRgb, const float *hDepth, const float *hLength, const float *hMoments, const int32_t *ids, const int32_t *hIds,
+                                  float *outRgb, float *outLength, float *outMoments, float *outVariance, hipStream_t s)
+{
+  const ReprojectHistory hist = {hRgb, hDepth, hLength, S.W};
+  const ReprojectMomentPlane mom = {reinterpret_cast<const float2 *>(hMoments), S.W};
+  const ReprojectIds id = {{ids, hIds}, S.W};
+  const int withMoments = ((M.flags & QA_REPROJECT_MOMENTS) && hMoments) ? 1 : 0;
+  const dim3 grid((unsigned) ((S.W + QA_REPROJECT_TILE - 1) / QA_REPROJECT_TILE), (unsigned) ((S.H + QA_REPROJECT_TILE - 1) / QA_REPROJECT_TILE)), block(256);
+  hipLaunchKernelGGL(qa::qa_reproject_moments, grid, block, 0, s, S, M, X, src, hist, mom, id, (ids && hIds) ? 1 : 0, withMoments, outRgb, outLength,
+                     reinterpret_cast<float2 *>(outMoments), outVariance);
   HIP_TRY(hipGetLastError());
   return QA_OK;
 }
@@ -465,6 +564,120 @@ int qa_test_reproject_motion_host(const qa_camera *prev_cam, const qa_camera *cu
       float o[3];
       out_length[q] = reprojectMotionPixel(S, M, src, hist, id, win, ids != nullptr, x, y, o);
       out_rgb[3 * q] = o[0]; out_rgb[3 * q + 1] = o[1]; out_rgb[3 * q + 2] = o[2];
+    }
+  return QA_OK;
+}
+
+int qa_reproject_moments_params_default(qa_reproject_moments_params *p)
+{
+  if (!p) return Fail(QA_EINVAL, "null parameters");
+  p->depth_tolerance = QA_REPROJECT_DEFAULT_DEPTH_TOLERANCE;
+  p->max_history = QA_REPROJECT_DEFAULT_MAX_HISTORY;
+  p->clamp_gamma = QA_REPROJECT_DEFAULT_CLAMP_GAMMA;
+  p->min_frames = QA_REPROJECT_DEFAULT_MIN_FRAMES;
+  p->shorten_rate = QA_REPROJECT_DEFAULT_SHORTEN_RATE;
+  p->clamp_radius = QA_REPROJECT_DEFAULT_CLAMP_RADIUS;
+  p->flags = 0u;
+  return QA_OK;
+}
+
+int qa_reproject_moments_device(qa_ctx *c, const qa_camera *prev_cam, const qa_camera *cur_cam, int x0, int y0, int width, int height, const float *d_rgb,
+                                const float *d_depth, const uint32_t *d_ns, const int32_t *d_ids, const float *d_hist_rgb, const float *d_hist_depth,
+                                const float *d_hist_length, const int32_t *d_hist_ids, const float *d_hist_moments, const qa_node_motion *d_motion,
+                                int motion_count, const qa_reproject_moments_params *p, float *d_out_rgb, float *d_out_length, float *d_out_moments,
+                                float *d_out_variance, void *hip_stream)
+{
+  if (int rc = Enter(c)) return rc;
+  if (!d_rgb || !d_depth || !d_ns) return Fail(QA_EINVAL, "null buffer");
+  if (int rc = CheckReprojectMoments(prev_cam, cur_cam, x0, y0, width, height, d_rgb, d_depth, d_ns, d_ids, d_ids != nullptr, d_hist_rgb, d_hist_depth,
+                                     d_hist_length, d_hist_ids, d_hist_moments, d_motion, motion_count, p, d_out_rgb, d_out_length, d_out_moments,
+                                     d_out_variance))
+    return rc;
+  const ReprojectSetup S = reprojectSetup(*prev_cam, *cur_cam, x0, y0, width, height, p->depth_tolerance, p->max_history);
+  const ReprojectSrc src = {d_rgb, d_depth, d_ns, nullptr, width};
+  const ReprojectMomentsSetup X = {p->min_frames, p->shorten_rate};
+  return LaunchReprojectMoments(S, MomentsMotionSetup(d_motion, motion_count, p), X, src, d_hist_rgb, d_hist_depth, d_hist_length, d_hist_moments, d_ids,
+                                d_hist_ids, d_out_rgb, d_out_length, d_out_moments, d_out_variance, StreamOf(c, hip_stream));
+}
+
+int qa_progressive_reproject_moments_device(qa_ctx *c, const qa_camera *prev_cam, const float *d_hist_rgb, const float *d_hist_depth,
+                                            const float *d_hist_length, const int32_t *d_hist_ids, const float *d_hist_moments,
+                                            const qa_node_motion *d_motion, int motion_count, const qa_reproject_moments_params *p, float *d_out_rgb,
+                                            float *d_out_length, float *d_out_moments, float *d_out_variance, void *hip_stream)
+{
+  int rc = ProgActive(c);
+  if (rc != QA_OK) return rc;
+  const qa_ctx::Progressive &f = c->prog;
+  if (f.stale) return Fail(QA_EINVAL, "the frame's pixels are not the resident camera's (the scene was edited): qa_progressive_restart first");
+  const int W = f.args.x1 - f.args.x0, H = f.args.y1 - f.args.y0;
+  qa_camera cam;   // the camera the frame was rendered from, as in qa_progressive_reproject_device
+  memcpy(&cam, c->hostBlob.data() + offsetof(qa_flat_header, screenA), sizeof(qa_camera));
+  if ((rc = CheckReprojectMoments(prev_cam, &cam, f.args.x0, f.args.y0, W, H, nullptr, nullptr, nullptr, nullptr, d_hist_ids != nullptr, d_hist_rgb,
+                                  d_hist_depth, d_hist_length, d_hist_ids, d_hist_moments, d_motion, motion_count, p, d_out_rgb, d_out_length,
+                                  d_out_moments, d_out_variance)) != QA_OK)
+    return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t s = StreamOf(c, hip_stream);
+  HIP_TRY(f.done.WaitOn(s));
+  int32_t *ids = nullptr;
+  if (d_hist_ids) {   // the context's ids plane, under the rules of qa_progressive_reproject_device
+    HIP_TRY(c->reprojectIds.Reserve((size_t) W * (size_t) H * 8, true));
+    HIP_TRY(c->lastReproject.WaitOn(s));
+    ids = static_cast<int32_t *>(c->reprojectIds.p);
+    if ((rc = qa_progressive_gbuffer_device(c, nullptr, nullptr, nullptr, ids, hip_stream)) != QA_OK) return rc;
+  }
+  const ReprojectSetup S = reprojectSetup(*prev_cam, cam, f.args.x0, f.args.y0, W, H, p->depth_tolerance, p->max_history);
+  const ReprojectSrc src = {f.args.rgb, f.args.depth, f.args.ns, f.dState, W};
+  const ReprojectMomentsSetup X = {p->min_frames, p->shorten_rate};
+  if ((rc = LaunchReprojectMoments(S, MomentsMotionSetup(d_motion, motion_count, p), X, src, d_hist_rgb, d_hist_depth, d_hist_length, d_hist_moments, ids,
+                                   d_hist_ids, d_out_rgb, d_out_length, d_out_moments, d_out_variance, s)) != QA_OK)
+    return rc;
+  if (ids) HIP_TRY(c->lastReproject.Record(s));
+  return QA_OK;
+}
+
+// the same source on the CPU, pixel after pixel (no GPU, no context)
+int qa_test_reproject_moments_host(const qa_camera *prev_cam, const qa_camera *cur_cam, int x0, int y0, int width, int height, const float *rgb,
+                                   const float *depth, const uint32_t *ns, const int32_t *ids, const float *hist_rgb, const float *hist_depth,
+                                   const float *hist_length, const int32_t *hist_ids, const float *hist_moments, const qa_node_motion *motion,
+                                   int motion_count, const qa_reproject_moments_params *p, float *out_rgb, float *out_length, float *out_moments,
+                                   float *out_variance)
+{
+  if (!rgb || !depth || !ns) return Fail(QA_EINVAL, "null buffer");
+  if (int rc = CheckReprojectMoments(prev_cam, cur_cam, x0, y0, width, height, rgb, depth, ns, ids, ids != nullptr, hist_rgb, hist_depth, hist_length,
+                                     hist_ids, hist_moments, motion, motion_count, p, out_rgb, out_length, out_moments, out_variance))
+    return rc;
+  const int W = width, H = height;
+  const ReprojectSetup S = reprojectSetup(*prev_cam, *cur_cam, x0, y0, W, H, p->depth_tolerance, p->max_history);
+  const ReprojectMotionSetup M = MomentsMotionSetup(motion, motion_count, p);
+  const ReprojectMomentsSetup X = {p->min_frames, p->shorten_rate};
+  const auto src = [=](int x, int y) {
+    const size_t q = (size_t) y * (size_t) W + (size_t) x;
+    ReprojectPixel px;
+    px.r = rgb[3 * q]; px.g = rgb[3 * q + 1]; px.b = rgb[3 * q + 2]; px.z = depth[q]; px.ns = ns[q];
+    return px;
+  };
+  const auto win = [=](int x, int y) {
+    if (x < 0 || y < 0 || x >= W || y >= H) {
+      const ReprojectWin none = {0.f, 0.f, 0.f, 0u};
+      return none;
+    }
+    return reprojectWinOf(src(x, y));
+  };
+  const ReprojectHistory hist = {hist_rgb, hist_depth, hist_length, W};
+  const ReprojectMomentPlane mom = {reinterpret_cast<const float2 *>(hist_moments), W};
+  const ReprojectIds id = {{ids, hist_ids}, W};
+  const bool withMoments = (p->flags & QA_REPROJECT_MOMENTS) && hist_moments;
+  for (int y = 0; y < H; ++y)
+    for (int x = 0; x < W; ++x) {
+      const size_t q = (size_t) y * (size_t) W + (size_t) x;
+      float o[3], om[2], var;
+      out_length[q] = reprojectMomentsPixel(S, M, X, src, hist, mom, id, win, ids != nullptr, withMoments, x, y, o, om, var);
+      out_rgb[3 * q] = o[0]; out_rgb[3 * q + 1] = o[1]; out_rgb[3 * q + 2] = o[2];
+      if (p->flags & QA_REPROJECT_MOMENTS) {
+        out_moments[2 * q] = om[0]; out_moments[2 * q + 1] = om[1];
+        out_variance[q] = var;
+      }
     }
   return QA_OK;
 }

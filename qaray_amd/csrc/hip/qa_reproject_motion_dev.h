@@ -80,10 +80,12 @@ __host__ __device__ __forceinline__ ReprojectWin reprojectWinOf(const ReprojectP
   return q;
 }
 
-// Step 5': c_h[3] clamped to the window around (tx, ty).  win(x, y) -> ReprojectWin for x in tx - r .. tx + r, y in ty - r .. ty + r
-// (cls 0 outside the region)
+// The box of step 5' around (tx, ty): -> false when the window clamps nothing (k < 2, or a bound that is not finite), else lo[3],
+// hi[3] and g[3] = clamp_gamma * sigma.  win(x, y) -> ReprojectWin for x in tx - r .. tx + r, y in ty - r .. ty + r (cls 0 outside
+// the region)
 template <class Win>
-__host__ __device__ __forceinline__ void reprojectClamp(const ReprojectMotionSetup &M, const Win &win, uint32_t cls, int tx, int ty, float *ch)
+__host__ __device__ __forceinline__ bool reprojectClampBox(const ReprojectMotionSetup &M, const Win &win, uint32_t cls, int tx, int ty, float *lo, float *hi,
+                                                           float *g)
 {
   const int r = M.clampRadius;
   int k = 0;
@@ -95,7 +97,7 @@ __host__ __device__ __forceinline__ void reprojectClamp(const ReprojectMotionSet
       ++k;
       s[0] += q.r; s[1] += q.g; s[2] += q.b;
     }
-  if (k < 2) return;
+  if (k < 2) return false;
   const float kf = (float) k;
   const float m[3] = {s[0] / kf, s[1] / kf, s[2] / kf};
   float v[3] = {0.f, 0.f, 0.f};
@@ -106,18 +108,52 @@ __host__ __device__ __forceinline__ void reprojectClamp(const ReprojectMotionSet
       const float e0 = q.r - m[0], e1 = q.g - m[1], e2 = q.b - m[2];
       v[0] += e0 * e0; v[1] += e1 * e1; v[2] += e2 * e2;
     }
-  float lo[3], hi[3];
   bool finite = true;
 #pragma unroll
   for (int e = 0; e < 3; ++e) {
     const float sigma = qsqrt(v[e] / kf);
-    const float g = M.clampGamma * sigma;
-    lo[e] = m[e] - g; hi[e] = m[e] + g;
+    g[e] = M.clampGamma * sigma;
+    lo[e] = m[e] - g[e]; hi[e] = m[e] + g[e];
     finite = finite && reprojectFinite(lo[e]) && reprojectFinite(hi[e]);
   }
-  if (!finite) return;
+  return finite;
+}
+
+// Step 5': c_h[3] clamped to the window around (tx, ty); win as for reprojectClampBox
+template <class Win>
+__host__ __device__ __forceinline__ void reprojectClamp(const ReprojectMotionSetup &M, const Win &win, uint32_t cls, int tx, int ty, float *ch)
+{
+  float lo[3], hi[3], g[3];
+  if (!reprojectClampBox(M, win, cls, tx, ty, lo, hi, g)) return;
 #pragma unroll
   for (int e = 0; e < 3; ++e) ch[e] = ch[e] < lo[e] ? lo[e] : (ch[e] > hi[e] ? hi[e] : ch[e]);
+}
+
+// Steps 2, 2', 3 and 4' for the non-void pixel p at (tx, ty) with ids cid: -> false for NO HISTORY, else where its taps lie
+__host__ __device__ __forceinline__ bool reprojectMotionWhere(const ReprojectSetup &S, const ReprojectMotionSetup &M, const ReprojectPixel &p, bool miss,
+                                                              const int *cid, int tx, int ty, float &ul, float &vl, float &zh)
+{
+  // the node's record: addressed only with an id inside the table, read only when the node moved
+  const qa_node_motion *rec = nullptr;
+  if ((M.flags & QA_REPROJECT_MOTION) && !miss && cid[0] >= 0 && cid[0] < M.count && M.motion[cid[0]].moved != 0u) rec = M.motion + cid[0];
+  if (S.still && !rec) {
+    ul = (float) tx; vl = (float) ty; zh = p.z;
+    return true;
+  }
+  const float fpx = (float) (S.x0 + tx), fpy = (float) (S.y0 + ty);
+  const f3 cpt = (S.A1 + S.U1 * fpx) + S.V1 * fpy;
+  const f3 d = normalize(cpt - S.pos1);
+  f3 w = d;
+  if (!miss) {
+    f3 P = S.pos1 + d * p.z;
+    if (rec) {
+      const float *m = rec->m;
+      P = F3(((m[0] * P.x + m[1] * P.y) + m[2] * P.z) + m[9], ((m[3] * P.x + m[4] * P.y) + m[5] * P.z) + m[10],
+             ((m[6] * P.x + m[7] * P.y) + m[8] * P.z) + m[11]);
+    }
+    w = P - S.pos0;
+  }
+  return reprojectProject(S, w, miss, ul, vl, zh);
 }
 
 // reprojectPixel of qa_reproject_dev.h with steps 2', 4' and 5'.  cur, tap and ids as there; win as for reprojectClamp (called
@@ -133,28 +169,8 @@ __host__ __device__ __forceinline__ float reprojectMotionPixel(const ReprojectSe
   const bool miss = p.z == QA_REPROJECT_MISS;
   int cid[2] = {0, 0};
   if (withIds) ids(0, tx, ty, cid);
-  // the node's record: addressed only with an id inside the table, read only when the node moved
-  const qa_node_motion *rec = nullptr;
-  if ((M.flags & QA_REPROJECT_MOTION) && !miss && cid[0] >= 0 && cid[0] < M.count && M.motion[cid[0]].moved != 0u) rec = M.motion + cid[0];
   float ul, vl, zh;
-  if (S.still && !rec) {
-    ul = (float) tx; vl = (float) ty; zh = p.z;
-  } else {
-    const float fpx = (float) (S.x0 + tx), fpy = (float) (S.y0 + ty);
-    const f3 cpt = (S.A1 + S.U1 * fpx) + S.V1 * fpy;
-    const f3 d = normalize(cpt - S.pos1);
-    f3 w = d;
-    if (!miss) {
-      f3 P = S.pos1 + d * p.z;
-      if (rec) {
-        const float *m = rec->m;
-        P = F3(((m[0] * P.x + m[1] * P.y) + m[2] * P.z) + m[9], ((m[3] * P.x + m[4] * P.y) + m[5] * P.z) + m[10],
-               ((m[6] * P.x + m[7] * P.y) + m[8] * P.z) + m[11]);
-      }
-      w = P - S.pos0;
-    }
-    if (!reprojectProject(S, w, miss, ul, vl, zh)) return n;
-  }
+  if (!reprojectMotionWhere(S, M, p, miss, cid, tx, ty, ul, vl, zh)) return n;
   float sc[3], sl;
   const float sw = reprojectTaps(S, tap, ids, withIds, cid, miss, ul, vl, zh, sc, sl);
   if (sw < QA_REPROJECT_MIN_WEIGHT) return n;

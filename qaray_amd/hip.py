@@ -150,6 +150,33 @@ class DenoiseGuidedParams(C.Structure):   # qa_denoise_guided_params; .default()
         return p
 
 
+QA_DENOISE_GUIDE_VARIANCE = 4
+
+
+class DenoiseVarianceParams(C.Structure):   # qa_denoise_variance_params; .default() = qa_denoise_variance_params_default
+    _fields_ = [("iterations", C.c_int), ("sigma_color", C.c_float), ("sigma_depth", C.c_float), ("sigma_normal", C.c_float),
+                ("variance_scale", C.c_float), ("flags", C.c_uint32)]
+
+    @classmethod
+    def default(cls):
+        p = cls()
+        _check(lib().qa_denoise_variance_params_default(C.byref(p)))
+        return p
+
+    @classmethod
+    def of(cls, params=None, flags=None, iterations=None, sigma_color=None, sigma_depth=None, sigma_normal=None, variance_scale=None):
+        """params (a DenoiseVarianceParams) or the library's defaults, with the arguments that are given written over them."""
+        p = cls.default() if params is None else cls(*(getattr(params, name) for name, _ in cls._fields_))
+        if flags is not None:
+            p.flags = int(flags)
+        if iterations is not None:
+            p.iterations = int(iterations)
+        for name, v in (("sigma_color", sigma_color), ("sigma_depth", sigma_depth), ("sigma_normal", sigma_normal), ("variance_scale", variance_scale)):
+            if v is not None:
+                setattr(p, name, float(v))
+        return p
+
+
 class ReprojectParams(C.Structure):   # qa_reproject_params; ReprojectParams.default() = qa_reproject_params_default
     _fields_ = [("depth_tolerance", C.c_float), ("max_history", C.c_float), ("flags", C.c_uint32)]
 
@@ -196,6 +223,37 @@ class ReprojectMotionParams(C.Structure):   # qa_reproject_motion_params; .defau
         if clamp_radius is not None:
             p.clamp_radius = int(clamp_radius)
         for bit, v in ((QA_REPROJECT_MOTION, motion), (QA_REPROJECT_CLAMP, clamp)):
+            if v is not None:
+                p.flags = (p.flags | bit) if v else (p.flags & ~bit)
+        return p
+
+
+QA_REPROJECT_MOMENTS, QA_REPROJECT_SHORTEN = 4, 8
+
+
+class ReprojectMomentsParams(C.Structure):   # qa_reproject_moments_params; .default() = qa_reproject_moments_params_default
+    _fields_ = [("depth_tolerance", C.c_float), ("max_history", C.c_float), ("clamp_gamma", C.c_float), ("min_frames", C.c_float),
+                ("shorten_rate", C.c_float), ("clamp_radius", C.c_int32), ("flags", C.c_uint32)]
+
+    @classmethod
+    def default(cls):
+        p = cls()
+        _check(lib().qa_reproject_moments_params_default(C.byref(p)))
+        return p
+
+    @classmethod
+    def of(cls, params=None, depth_tolerance=None, max_history=None, motion=None, clamp=None, clamp_radius=None, clamp_gamma=None, moments=None,
+           shorten=None, min_frames=None, shorten_rate=None):
+        """params (a ReprojectMomentsParams) or the library's defaults, with the keyword arguments that are given written over them;
+        motion / clamp / moments / shorten (bool) set or clear the four flags."""
+        p = cls.default() if params is None else cls(*(getattr(params, name) for name, _ in cls._fields_))
+        for name, v in (("depth_tolerance", depth_tolerance), ("max_history", max_history), ("clamp_gamma", clamp_gamma), ("min_frames", min_frames),
+                        ("shorten_rate", shorten_rate)):
+            if v is not None:
+                setattr(p, name, float(v))
+        if clamp_radius is not None:
+            p.clamp_radius = int(clamp_radius)
+        for bit, v in ((QA_REPROJECT_MOTION, motion), (QA_REPROJECT_CLAMP, clamp), (QA_REPROJECT_MOMENTS, moments), (QA_REPROJECT_SHORTEN, shorten)):
             if v is not None:
                 p.flags = (p.flags | bit) if v else (p.flags & ~bit)
         return p
@@ -281,6 +339,9 @@ def lib():
         L.qa_progressive_denoise_guided.argtypes = [C.c_void_p, C.POINTER(DenoiseGuidedParams), C.c_void_p]
         L.qa_progressive_denoise_guided_device.argtypes = [C.c_void_p, C.POINTER(DenoiseGuidedParams), C.c_void_p, C.c_void_p]
         L.qa_test_denoise_guided_host.argtypes = [C.c_void_p] * 5 + [C.c_int, C.c_int, C.POINTER(DenoiseGuidedParams), C.c_void_p]
+        L.qa_denoise_variance_params_default.argtypes = [C.POINTER(DenoiseVarianceParams)]
+        L.qa_denoise_variance_device.argtypes = [C.c_void_p] * 7 + [C.c_int, C.c_int, C.POINTER(DenoiseVarianceParams), C.c_void_p, C.c_void_p]
+        L.qa_test_denoise_variance_host.argtypes = [C.c_void_p] * 6 + [C.c_int, C.c_int, C.POINTER(DenoiseVarianceParams), C.c_void_p]
         L.qa_reproject_params_default.argtypes = [C.POINTER(ReprojectParams)]
         L.qa_reproject_device.argtypes = [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_void_p] * 8 + [C.POINTER(ReprojectParams)] + [C.c_void_p] * 3
         L.qa_progressive_reproject_device.argtypes = [C.c_void_p] * 6 + [C.POINTER(ReprojectParams)] + [C.c_void_p] * 3
@@ -292,6 +353,12 @@ def lib():
         L.qa_progressive_reproject_motion_device.argtypes = [C.c_void_p] * 7 + [C.c_int, C.POINTER(ReprojectMotionParams)] + [C.c_void_p] * 3
         L.qa_test_reproject_motion_host.argtypes = ([C.c_void_p] * 2 + [C.c_int] * 4 + [C.c_void_p] * 9 + [C.c_int, C.POINTER(ReprojectMotionParams)]
                                                     + [C.c_void_p] * 2)
+        L.qa_reproject_moments_params_default.argtypes = [C.POINTER(ReprojectMomentsParams)]
+        L.qa_reproject_moments_device.argtypes = ([C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_void_p] * 10 + [C.c_int, C.POINTER(ReprojectMomentsParams)]
+                                                  + [C.c_void_p] * 5)
+        L.qa_progressive_reproject_moments_device.argtypes = [C.c_void_p] * 8 + [C.c_int, C.POINTER(ReprojectMomentsParams)] + [C.c_void_p] * 5
+        L.qa_test_reproject_moments_host.argtypes = ([C.c_void_p] * 2 + [C.c_int] * 4 + [C.c_void_p] * 10 + [C.c_int, C.POINTER(ReprojectMomentsParams)]
+                                                     + [C.c_void_p] * 4)
         L.qa_gbuffer_region_device.argtypes = [C.c_void_p] + [C.c_int] * 4 + [C.c_uint32] + [C.c_void_p] * 5
         L.qa_gbuffer_region.argtypes = [C.c_void_p] + [C.c_int] * 4 + [C.c_uint32] + [C.c_void_p] * 4
         L.qa_progressive_gbuffer_device.argtypes = [C.c_void_p] * 6
@@ -365,6 +432,26 @@ def denoise_guided_host(rgb, depth, ns, normal=None, albedo=None, params=None, i
     p = DenoiseGuidedParams.of(params, flags, iterations, sigma_color, sigma_depth, sigma_normal)
     _check(lib().qa_test_denoise_guided_host(rgb.ctypes.data, depth.ctypes.data, ns.ctypes.data, *(None if g is None else g.ctypes.data for g in guides),
                                              w, h, C.byref(p), out.ctypes.data))
+    return out
+
+
+def denoise_variance_host(rgb, depth, ns, normal=None, albedo=None, variance=None, params=None, iterations=None, sigma_color=None,
+                          sigma_depth=None, sigma_normal=None, variance_scale=None):
+    """qa_test_denoise_variance_host: Context.denoise_variance_device on the CPU, from the source the device kernels are compiled
+    from; normal / albedo (h, w, 3) and variance (h, w) or None: the flags are the planes given.  -> float32 (h, w, 3).  No GPU needed."""
+    rgb = np.ascontiguousarray(rgb, dtype=np.float32)
+    depth = np.ascontiguousarray(depth, dtype=np.float32)
+    ns = np.ascontiguousarray(ns, dtype=np.uint32)
+    assert rgb.ndim == 3 and rgb.shape[2] == 3 and depth.shape == rgb.shape[:2] and ns.shape == rgb.shape[:2]
+    guides = [None if g is None else np.ascontiguousarray(g, dtype=np.float32) for g in (normal, albedo, variance)]
+    assert all(g is None or g.shape == rgb.shape for g in guides[:2]) and (guides[2] is None or guides[2].shape == depth.shape)
+    h, w = depth.shape
+    out = np.zeros((h, w, 3), np.float32)
+    flags = ((QA_DENOISE_GUIDE_NORMAL if normal is not None else 0) | (QA_DENOISE_GUIDE_ALBEDO if albedo is not None else 0)
+             | (QA_DENOISE_GUIDE_VARIANCE if variance is not None else 0))
+    p = DenoiseVarianceParams.of(params, flags, iterations, sigma_color, sigma_depth, sigma_normal, variance_scale)
+    _check(lib().qa_test_denoise_variance_host(rgb.ctypes.data, depth.ctypes.data, ns.ctypes.data, *(None if g is None else g.ctypes.data for g in guides),
+                                               w, h, C.byref(p), out.ctypes.data))
     return out
 
 
@@ -445,6 +532,59 @@ def reproject_motion_host(cur, history, prev_cam, cur_cam, origin=(0, 0), ids=No
                                                None if table is None else table.ctypes.data, 0 if table is None else len(table), C.byref(p),
                                                out.ctypes.data, out_length.ctypes.data))
     return out, out_length
+
+
+def reproject_moments_host(cur, history, prev_cam, cur_cam, origin=(0, 0), ids=None, hist_ids=None, hist_moments=None, motion=None, out=None,
+                           out_length=None, out_moments=None, out_variance=None, params=None, depth_tolerance=None, max_history=None, clamp=None,
+                           clamp_radius=None, clamp_gamma=None, moments=None, shorten=None, min_frames=None, shorten_rate=None):
+    """qa_test_reproject_moments_host: Context.reproject_moments_device on the CPU, from the source the device kernel is compiled
+    from; the arguments of reproject_motion_host, and hist_moments: (h, w, 2) f32 or None (nobody has moment history); moments /
+    shorten (bool) set or clear QA_REPROJECT_MOMENTS / QA_REPROJECT_SHORTEN, min_frames / shorten_rate override params' values (a
+    ReprojectMomentsParams).  -> (out (h, w, 3), out_length (h, w), out_moments (h, w, 2), out_variance (h, w)); the last two are
+    None when QA_REPROJECT_MOMENTS is clear and they were not given.  No GPU needed."""
+    rgb, depth, ns = cur
+    rgb = rgb if out is rgb and rgb is not None else np.ascontiguousarray(rgb, dtype=np.float32)
+    depth = np.ascontiguousarray(depth, dtype=np.float32)
+    ns = np.ascontiguousarray(ns, dtype=np.uint32)
+    assert rgb.ndim == 3 and rgb.shape[2] == 3 and depth.shape == rgb.shape[:2] and ns.shape == rgb.shape[:2]
+    h, w = depth.shape
+    hist = [np.ascontiguousarray(a, dtype=np.float32) for a in history]
+    assert hist[0].shape == (h, w, 3) and hist[1].shape == (h, w) and hist[2].shape == (h, w)
+    idp = [None if a is None else np.ascontiguousarray(a, dtype=np.int32) for a in (ids, hist_ids)]
+    assert all(a is None or a.shape == (h, w, 2) for a in idp)
+    hmom = None if hist_moments is None else np.ascontiguousarray(hist_moments, dtype=np.float32)
+    assert hmom is None or hmom.shape == (h, w, 2)
+    table = None if motion is None else np.ascontiguousarray(motion, dtype=NODE_MOTION_DTYPE).reshape(-1)
+    p = ReprojectMomentsParams.of(params, depth_tolerance, max_history, True if table is not None else None, clamp, clamp_radius, clamp_gamma, moments,
+                                  shorten, min_frames, shorten_rate)
+    out = np.zeros((h, w, 3), np.float32) if out is None else out
+    out_length = np.zeros((h, w), np.float32) if out_length is None else out_length
+    if p.flags & QA_REPROJECT_MOMENTS:
+        out_moments = np.zeros((h, w, 2), np.float32) if out_moments is None else out_moments
+        out_variance = np.zeros((h, w), np.float32) if out_variance is None else out_variance
+    for a, shape in ((out, (h, w, 3)), (out_length, (h, w)), (out_moments, (h, w, 2)), (out_variance, (h, w))):
+        assert a is None or (a.dtype == np.float32 and a.flags.c_contiguous and a.shape == shape)
+    c0, c1 = _camera_record(prev_cam), _camera_record(cur_cam)
+    ptr = lambda a: None if a is None else a.ctypes.data   # noqa: E731
+    _check(lib().qa_test_reproject_moments_host(c0.ctypes.data, c1.ctypes.data, int(origin[0]), int(origin[1]), w, h, rgb.ctypes.data, depth.ctypes.data,
+                                                ns.ctypes.data, ptr(idp[0]), hist[0].ctypes.data, hist[1].ctypes.data, hist[2].ctypes.data, ptr(idp[1]),
+                                                ptr(hmom), ptr(table), 0 if table is None else len(table), C.byref(p), out.ctypes.data,
+                                                out_length.ctypes.data, ptr(out_moments), ptr(out_variance)))
+    return out, out_length, out_moments, out_variance
+
+
+def _moments_tensors(p, h, w, device, hist_moments, out_moments, out_variance):
+    """The moment planes of a device call checked, and with QA_REPROJECT_MOMENTS the two outputs allocated where they are not given."""
+    import torch
+    n = h * w
+    if p.flags & QA_REPROJECT_MOMENTS:
+        if out_moments is None:
+            out_moments = torch.empty((h, w, 2), dtype=torch.float32, device=device)
+        if out_variance is None:
+            out_variance = torch.empty((h, w), dtype=torch.float32, device=device)
+    for t, k in ((hist_moments, 2), (out_moments, 2), (out_variance, 1)):
+        assert t is None or (t.is_cuda and t.is_contiguous() and t.numel() == k * n and t.dtype == torch.float32)
+    return out_moments, out_variance
 
 
 def _motion_tensor(motion, device, stream):
@@ -761,6 +901,33 @@ class Context:
                                               None if albedo is None else albedo.data_ptr(), w, h, C.byref(p), out.data_ptr(), sptr))
         return out
 
+    def denoise_variance_device(self, rgb, depth, ns, normal=None, albedo=None, variance=None, out=None, params=None, iterations=None,
+                                sigma_color=None, sigma_depth=None, sigma_normal=None, variance_scale=None, stream=None):
+        """qa_denoise_variance_device: denoise_guided_device with a per-pixel variance of the luma in place of pass 0's spatial guess
+        (include/qaray_hip.h): variance, a float32 [h,w] CUDA tensor, -1 where there is none - TemporalPreview(moments=True).variance
+        or the out_variance of reproject_moments_device.  The flags are the planes given; without variance the result is
+        denoise_guided_device's.  -> out; only enqueues."""
+        import torch
+        assert rgb.is_cuda and rgb.is_contiguous() and rgb.dim() == 3 and rgb.shape[2] == 3 and rgb.dtype == torch.float32
+        h, w = rgb.shape[:2]
+        n = h * w
+        assert depth.is_cuda and depth.is_contiguous() and depth.numel() == n and depth.element_size() == 4
+        assert ns.is_cuda and ns.is_contiguous() and ns.numel() == n and ns.element_size() == 4
+        for g in (normal, albedo):
+            assert g is None or (g.is_cuda and g.is_contiguous() and g.numel() == 3 * n and g.dtype == torch.float32)
+        assert variance is None or (variance.is_cuda and variance.is_contiguous() and variance.numel() == n and variance.dtype == torch.float32)
+        if out is None:
+            out = torch.empty_like(rgb)
+        assert out.is_cuda and out.is_contiguous() and out.shape == rgb.shape and out.dtype == torch.float32
+        flags = ((QA_DENOISE_GUIDE_NORMAL if normal is not None else 0) | (QA_DENOISE_GUIDE_ALBEDO if albedo is not None else 0)
+                 | (QA_DENOISE_GUIDE_VARIANCE if variance is not None else 0))
+        p = DenoiseVarianceParams.of(params, flags, iterations, sigma_color, sigma_depth, sigma_normal, variance_scale)
+        sptr = self._stream_arg(stream, rgb)
+        ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731
+        _check(lib().qa_denoise_variance_device(self._h, rgb.data_ptr(), depth.data_ptr(), ns.data_ptr(), ptr(normal), ptr(albedo), ptr(variance), w, h,
+                                                C.byref(p), out.data_ptr(), sptr))
+        return out
+
     def reproject_device(self, cur, history, prev_cam, cur_cam, origin=(0, 0), ids=None, hist_ids=None, out=None, out_length=None, params=None,
                          depth_tolerance=None, max_history=None, stream=None):
         """qa_reproject_device: the accumulated frame of an earlier camera carried into the frame of the camera as it now stands
@@ -833,6 +1000,49 @@ class Context:
                                                 None if motion is None else self._motion_upload.data_ptr(), count, C.byref(p), out.data_ptr(),
                                                 out_length.data_ptr(), sptr))
         return out, out_length
+
+    def reproject_moments_device(self, cur, history, prev_cam, cur_cam, origin=(0, 0), ids=None, hist_ids=None, hist_moments=None, motion=None, out=None,
+                                 out_length=None, out_moments=None, out_variance=None, params=None, depth_tolerance=None, max_history=None, clamp=None,
+                                 clamp_radius=None, clamp_gamma=None, moments=None, shorten=None, min_frames=None, shorten_rate=None, stream=None):
+        """qa_reproject_moments_device: reproject_motion_device that carries the luma's first two moments and shortens the history
+        the clamp moved (include/qaray_hip.h).  The arguments of reproject_motion_device, and hist_moments: float32 [h,w,2], the
+        out_moments of the call before (None: nobody has moment history); moments (bool) sets or clears QA_REPROJECT_MOMENTS, which
+        writes out_moments [h,w,2] and out_variance [h,w] (None: new ones) - the variance of the accumulated colour's luma, -1 where
+        there is none; shorten (bool) sets or clears QA_REPROJECT_SHORTEN (wants clamp); min_frames / shorten_rate override params'
+        values (a ReprojectMomentsParams).  With neither flag the result is reproject_motion_device's.
+        -> (out, out_length, out_moments, out_variance), the last two None when the flag is clear and they were not given; only
+        enqueues."""
+        import torch
+        rgb, depth, ns = cur
+        hrgb, hdepth, hlen = history
+        assert rgb.is_cuda and rgb.is_contiguous() and rgb.dim() == 3 and rgb.shape[2] == 3 and rgb.dtype == torch.float32
+        h, w = rgb.shape[:2]
+        n = h * w
+        for t in (depth, ns, hdepth, hlen):
+            assert t.is_cuda and t.is_contiguous() and t.numel() == n and t.element_size() == 4
+        assert depth.dtype == torch.float32 and hdepth.dtype == torch.float32 and hlen.dtype == torch.float32
+        assert hrgb.is_cuda and hrgb.is_contiguous() and hrgb.numel() == 3 * n and hrgb.dtype == torch.float32
+        for t in (ids, hist_ids):
+            assert t is None or (t.is_cuda and t.is_contiguous() and t.numel() == 2 * n and t.dtype == torch.int32)
+        if out is None:
+            out = torch.empty_like(rgb)
+        if out_length is None:
+            out_length = torch.empty((h, w), dtype=torch.float32, device=rgb.device)
+        assert out.is_cuda and out.is_contiguous() and out.numel() == 3 * n and out.dtype == torch.float32
+        assert out_length.is_cuda and out_length.is_contiguous() and out_length.numel() == n and out_length.dtype == torch.float32
+        p = ReprojectMomentsParams.of(params, depth_tolerance, max_history, True if motion is not None else None, clamp, clamp_radius, clamp_gamma,
+                                      moments, shorten, min_frames, shorten_rate)
+        out_moments, out_variance = _moments_tensors(p, h, w, rgb.device, hist_moments, out_moments, out_variance)
+        # (kept until the next call: without a stream of the caller's the kernel is not ordered against torch's allocator)
+        self._motion_upload, count = _motion_tensor(motion, rgb.device, stream)
+        c0, c1 = _camera_record(prev_cam), _camera_record(cur_cam)
+        sptr = self._stream_arg(stream, rgb)
+        ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731
+        _check(lib().qa_reproject_moments_device(self._h, c0.ctypes.data, c1.ctypes.data, int(origin[0]), int(origin[1]), w, h, rgb.data_ptr(),
+                                                 depth.data_ptr(), ns.data_ptr(), ptr(ids), hrgb.data_ptr(), hdepth.data_ptr(), hlen.data_ptr(),
+                                                 ptr(hist_ids), ptr(hist_moments), None if motion is None else self._motion_upload.data_ptr(), count,
+                                                 C.byref(p), out.data_ptr(), out_length.data_ptr(), ptr(out_moments), ptr(out_variance), sptr))
+        return out, out_length, out_moments, out_variance
 
     def gbuffer(self, region, seed=DEFAULT_SEED):
         """qa_gbuffer_region: the first-hit guide planes of a region -> dict of numpy arrays: normal [h,w,3] f32 (world space, 0 on a
@@ -1128,6 +1338,40 @@ class Progressive:
                                                             out.data_ptr(), out_length.data_ptr(), sptr))
         return out, out_length
 
+    def reproject_moments_device(self, history, prev_cam, hist_ids=None, hist_moments=None, motion=None, out=None, out_length=None, out_moments=None,
+                                 out_variance=None, params=None, depth_tolerance=None, max_history=None, clamp=None, clamp_radius=None, clamp_gamma=None,
+                                 moments=None, shorten=None, min_frames=None, shorten_rate=None, stream=None):
+        """qa_progressive_reproject_moments_device: reproject_motion_device of this frame with Context.reproject_moments_device's
+        additions (hist_moments, moments, shorten, min_frames, shorten_rate).  -> (out, out_length, out_moments, out_variance); only
+        enqueues.  The frame is not changed; a stale frame wants restart() first."""
+        import torch
+        device = torch.device("cuda", self._ctx.device_id)
+        x0, y0, x1, y1 = self.region
+        h, w = y1 - y0, x1 - x0
+        n = h * w
+        hrgb, hdepth, hlen = history
+        for t, k in ((hrgb, 3), (hdepth, 1), (hlen, 1)):
+            assert t.is_cuda and t.is_contiguous() and t.numel() == k * n and t.dtype == torch.float32
+        assert hist_ids is None or (hist_ids.is_cuda and hist_ids.is_contiguous() and hist_ids.numel() == 2 * n and hist_ids.dtype == torch.int32)
+        if out is None:
+            out = torch.empty((h, w, 3), dtype=torch.float32, device=device)
+        if out_length is None:
+            out_length = torch.empty((h, w), dtype=torch.float32, device=device)
+        assert out.is_cuda and out.is_contiguous() and out.numel() == 3 * n and out.dtype == torch.float32
+        assert out_length.is_cuda and out_length.is_contiguous() and out_length.numel() == n and out_length.dtype == torch.float32
+        p = ReprojectMomentsParams.of(params, depth_tolerance, max_history, True if motion is not None else None, clamp, clamp_radius, clamp_gamma,
+                                      moments, shorten, min_frames, shorten_rate)
+        out_moments, out_variance = _moments_tensors(p, h, w, device, hist_moments, out_moments, out_variance)
+        self._ctx._motion_upload, count = _motion_tensor(motion, device, stream)
+        c0 = _camera_record(prev_cam)
+        sptr = Context._stream_arg(stream, out)
+        ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731
+        _check(lib().qa_progressive_reproject_moments_device(self._ctx._h, c0.ctypes.data, hrgb.data_ptr(), hdepth.data_ptr(), hlen.data_ptr(),
+                                                             ptr(hist_ids), ptr(hist_moments),
+                                                             None if motion is None else self._ctx._motion_upload.data_ptr(), count, C.byref(p),
+                                                             out.data_ptr(), out_length.data_ptr(), ptr(out_moments), ptr(out_variance), sptr))
+        return out, out_length, out_moments, out_variance
+
     def status(self):
         """-> dict(spp_reached, pixels_finished, tiles_behind); synchronises."""
         r, f, b = C.c_int(), C.c_uint64(), C.c_uint64()
@@ -1166,9 +1410,14 @@ class TemporalPreview:
     With instances= (and ids) on every push, node moves (edit_instances) need no reset: the history follows the node.  With
     clamp=True, light, material and texture edits need no reset: the history is clamped to the current frame's neighbourhood and
     leaves within a few frames.  reset() is still needed after an edit that changes ids or topology (a new scene upload), and after
-    any edit that is not a camera move when neither of the two is in use (include/qaray_hip.h)."""
+    any edit that is not a camera move when neither of the two is in use (include/qaray_hip.h).
+    With shorten=True (wants clamp=True) a history the clamp moved also loses its length, so the frames after an edit stop weighing
+    it.  With moments=True the preview also carries the luma's moments: tp.variance is then the plane of the last push (float32
+    [h,w], the variance of the accumulated colour's luma, -1 where there is none - everywhere after the first push and after
+    reset()), and None before the first push or without moments.  With both off a push makes the calls it made before."""
 
-    def __init__(self, ctx, region, params=None, depth_tolerance=None, max_history=None, clamp=False, clamp_radius=None, clamp_gamma=None):
+    def __init__(self, ctx, region, params=None, depth_tolerance=None, max_history=None, clamp=False, clamp_radius=None, clamp_gamma=None,
+                 moments=False, shorten=False, min_frames=None, shorten_rate=None):
         import torch
         self._ctx = ctx
         self.region = tuple(region)
@@ -1186,6 +1435,16 @@ class TemporalPreview:
         self._cam = None
         self._instances = None
         self._at = 0
+        # moments / shorten: every push goes through reproject_moments_device, which owns two moment planes and a variance plane
+        self.moments_params = None
+        self.variance = None
+        if moments or shorten:
+            self.moments_params = ReprojectMomentsParams.of(None, self.params.depth_tolerance, self.params.max_history, None, bool(clamp),
+                                                            self.motion_params.clamp_radius, self.motion_params.clamp_gamma, bool(moments), bool(shorten),
+                                                            min_frames, shorten_rate)
+        if moments:
+            self._moments = [torch.zeros((h, w, 2), dtype=torch.float32, device=dev) for _ in range(2)]
+            self._variance = torch.full((h, w), -1.0, dtype=torch.float32, device=dev)
         torch.cuda.current_stream(dev).synchronize()
 
     def reset(self):
@@ -1227,7 +1486,14 @@ class TemporalPreview:
         frame, history = (rgb, depth, ns), (self._rgb[prev], self._depth, self._length[prev])
         kw = dict(origin=(x0, y0), ids=ids if with_ids else None, hist_ids=self._ids if with_ids else None, out=self._rgb[nxt],
                   out_length=self._length[nxt], stream=stream)
-        if motion is None and not self.motion_params.flags:
+        if self.moments_params is not None:
+            with_moments = bool(self.moments_params.flags & QA_REPROJECT_MOMENTS)
+            if with_moments:   # (a fresh history has length 0 everywhere: no tap counts, and the stale moments are not read)
+                kw.update(hist_moments=self._moments[prev], out_moments=self._moments[nxt], out_variance=self._variance)
+            self._ctx.reproject_moments_device(frame, history, cam if fresh else self._cam, cam, motion=motion, params=self.moments_params, **kw)
+            if with_moments:
+                self.variance = self._variance
+        elif motion is None and not self.motion_params.flags:
             self._ctx.reproject_device(frame, history, cam if fresh else self._cam, cam, params=self.params, **kw)
         else:
             self._ctx.reproject_motion_device(frame, history, cam if fresh else self._cam, cam, motion=motion, params=self.motion_params, **kw)
