@@ -494,6 +494,14 @@ __device__ __forceinline__ void triangleDetails(const uint4 q0, const uint4 q1, 
   h.front = (dz <= 0);
 }
 
+// A/B switches of the cast's two shortcuts (profiles/cast_cost.txt): make hip EXTRA="-DQA_FMA_SLAB=0" etc.
+#ifndef QA_FMA_SLAB
+#define QA_FMA_SLAB 1         /* 0: the own tree's fast slab step subtracts and multiplies in every variant (boxEntryExitPadFast) */
+#endif
+#ifndef QA_REACH_AT_FOUND
+#define QA_REACH_AT_FOUND 1   /* 0: refReaches tests entry < t for closest-hit queries too */
+#endif
+
 // TriObj::IntersectRay + TraceBVHNode (src/objects/objects.cpp:310-420).  The traversal stack
 // holds node DATA words (leaf flag + range, or child index) instead of ids: the word arrives with
 // the node's box when the parent tests its two children, so an inner visit is a single 64-byte
@@ -507,12 +515,16 @@ struct TriPick { uint32_t tri; float a, b; };  // accepted triangle (element ord
 // the distance already held.  Returns whether a triangle was accepted; best = its element index in
 // the walked tree's order.  closest = false stops at the first accepted triangle.
 // STRIDE: distance between a lane's stack entries (QA_BLOCK: the per-lane columns of the LDS stacks; 1: a private array).
-template <bool FAST, bool STATS, bool GMEM = false, int STRIDE = QA_BLOCK>
+// FMA (FAST only): the fast slab step in its one-fma-per-plane form (boxEntryExitPadFma, qa_tilecull.h).  A flag, because the shared
+// text costs the lit and textured resident variants 7 - 50 spilled registers (profiles/cast_cost.txt): theirs is the old form.
+template <bool FAST, bool STATS, bool GMEM = false, int STRIDE = QA_BLOCK, bool FMA = false>
 __device__ __forceinline__ bool walkBVH(const uint4 *nodes, const uint4 *tris, uint32_t rootData, const Ray &ray, f3 drcp,
                                         bool fastSlab, float &hz, bool closest, uint32_t *stack, DCounters &cnt,
                                         uint32_t &best, bool &tie, float pad = 0.f)
 {
-  const f3 pLo = ray.p + F3(pad, pad, pad), pHi = ray.p - F3(pad, pad, pad);   // FAST only
+  // FAST only: the origin moved by the pad; in the fast form the ray's share of a plane distance instead (slabRayTerm, qa_tilecull.h)
+  f3 pLo = ray.p + F3(pad, pad, pad), pHi = ray.p - F3(pad, pad, pad);
+  if (FAST && FMA && fastSlab) { pLo = slabRayTerm(pLo, drcp); pHi = slabRayTerm(pHi, drcp); }
   bool hasHit = false;
   int sp = 0;
   uint32_t cur = rootData;
@@ -527,8 +539,13 @@ __device__ __forceinline__ bool walkBVH(const uint4 *nodes, const uint4 *tris, u
       const f3 min1 = F3(asF(b0.x), asF(b0.y), asF(b0.z)), max1 = F3(asF(b0.w), asF(b1.x), asF(b1.y));
       if constexpr (FAST) {
         if (fastSlab) {
-          boxEntryExitPadFast(pLo, pHi, drcp, min0, max0, entry0, exit0);
-          boxEntryExitPadFast(pLo, pHi, drcp, min1, max1, entry1, exit1);
+          if constexpr (FMA) {
+            boxEntryExitPadFma(pLo, pHi, drcp, min0, max0, entry0, exit0);
+            boxEntryExitPadFma(pLo, pHi, drcp, min1, max1, entry1, exit1);
+          } else {
+            boxEntryExitPadFast(pLo, pHi, drcp, min0, max0, entry0, exit0);
+            boxEntryExitPadFast(pLo, pHi, drcp, min1, max1, entry1, exit1);
+          }
         } else {
           boxEntryExitPad(pLo, pHi, ray.d, drcp, min0, max0, entry0, exit0);
           boxEntryExitPad(pLo, pHi, ray.d, drcp, min1, max1, entry1, exit1);
@@ -678,11 +695,26 @@ __device__ __forceinline__ bool insideCancelReach(const M &m, f3 o)
 // strict box test passes against the distance held at that moment.  Every inner box of the tree is
 // the union of its children's boxes (min / max of the same floats), and the slab arithmetic is
 // monotone in the box bounds, so an ancestor's [entry, exit] interval contains the leaf's: if the
-// LEAF's box passes the strict test against `limit`, every node above it does.  `limit` is the final
-// hit distance for a closest-hit query (the distance held earlier can only be larger: sufficient),
-// the fixed t_max for an any-hit query (exact).  DTriShade::pad holds an element's leaf id.
+// LEAF's box passes the strict test against `limit`, every node above it does.  `limit` is the
+// fixed t_max for an any-hit query (exact).  DTriShade::pad holds an element's leaf id.
+// atFound (closest-hit queries in which no tie was seen): `limit` is the distance t just found, and
+// the leaf passes with entry <= t (refLeafReached, qa_tilecull.h), because the reference held more
+// than t when it tested that box:
+//   * let X be the closest accepted triangle, at t.  The own search tests every triangle whose padded
+//     leaf the ray enters at entry <= the distance held (the tile lists by their h.z >= bound rule),
+//     X's and that of any other triangle the inside test accepts at t among them: a second triangle
+//     accepted at exactly t would have raised `tie`, whichever of the two came first;
+//   * the reference's running t_max starts above t (X was accepted against it) and falls only to
+//     distances of accepted triangles: none is below t (X is the closest), none equals t (no tie).
+//     So until the reference accepts X itself, its t_max is strictly larger than t;
+//   * the reference tests a child's box when it visits the parent and never again when it pops the
+//     child, and it visits X's leaf before it accepts X: the leaf's box, with entry == t, met
+//     entry < t_max.  The ancestors' entries are not larger and their exits not smaller, and they
+//     were tested earlier, against a t_max at least as large: they pass as well.
+// An entry that exceeds t (by the rounding of the slab products: the triangle's plane is a face of a
+// flat leaf box) still fails, and the lane repeats the query.
 template <bool GMEM = false>
-__device__ __forceinline__ bool refReaches(const uint4 *nodes, uint32_t leaf, const Ray &ray, f3 drcp, bool fastSlab, float limit)
+__device__ __forceinline__ bool refReaches(const uint4 *nodes, uint32_t leaf, const Ray &ray, f3 drcp, bool fastSlab, float limit, bool atFound = false)
 {
   if (leaf <= 1) return true;   // the root is entered unconditionally (the mesh bounds were tested by the caller)
   const uint4 n0 = ld16<GMEM>(nodes + 2 * (size_t) leaf), n1 = ld16<GMEM>(nodes + 2 * (size_t) leaf + 1);
@@ -690,7 +722,7 @@ __device__ __forceinline__ bool refReaches(const uint4 *nodes, uint32_t leaf, co
   const f3 bmin = F3(asF(n0.x), asF(n0.y), asF(n0.z)), bmax = F3(asF(n0.w), asF(n1.x), asF(n1.y));
   if (fastSlab) boxEntryExitFast(ray, drcp, bmin, bmax, entry, exit_);
   else boxEntryExit(ray, drcp, bmin, bmax, entry, exit_);
-  return entry < limit && entry < exit_;
+  return refLeafReached(entry, exit_, limit, QA_REACH_AT_FOUND && atFound);
 }
 
 // TriObj::IntersectRay + TraceBVHNode (src/objects/objects.cpp:310-420).
@@ -753,7 +785,7 @@ __device__ __forceinline__ bool hitMesh(const SceneMem<RES> mem, const DMesh &m,
       redo = tie;
       if (hasHit && !redo) {
         const uint32_t leaf = ldGlobal(shade + 3 * (size_t) bestTri + 2).w;   // DTriShade::pad
-        redo = !refReaches<true>(nodes, leaf, ray, drcp, fastSlab, closest ? h.z : hz0);
+        redo = !refReaches<true>(nodes, leaf, ray, drcp, fastSlab, closest ? h.z : hz0, closest);   // (no tie: redo was `tie`)
       }
     }
     if (redo) {
@@ -806,7 +838,7 @@ __device__ __forceinline__ bool hitMesh(const SceneMem<RES> mem, const DMesh &m,
       }
     }
     if (!listed)
-      hasHit = walkBVH<true, false>(fnodes, ftris, m.frootData, ray, drcp, fastSlab, h.z, closest, stack, cnt, bestF, tie, pad);
+      hasHit = walkBVH<true, false, false, QA_BLOCK, TL && QA_FMA_SLAB>(fnodes, ftris, m.frootData, ray, drcp, fastSlab, h.z, closest, stack, cnt, bestF, tie, pad);
     // Beyond the mesh bounds a triangle can only be "hit" by cancellation: at a distance D from the
     // triangle the inside test is off by ~64 eps D^2 / (L h) and would have to be off by D / L, i.e.
     // D >= h / (64 eps) ~ 2.6e5 h (all three areas then round to the same product: barycentrics 0, 0, 1).
@@ -832,7 +864,9 @@ __device__ __forceinline__ bool hitMesh(const SceneMem<RES> mem, const DMesh &m,
       const uint32_t leaf = bestF >> 15;          // its leaf in the reference tree (the record's word, see DMesh::ftris)
       // closest: the distance just found; any-hit: the fixed t_max (h.z is untouched by walkBVH then... it is
       // set to the accepted distance, so take the saved one)
-      redo = redo || !refReaches(nodes, leaf, ray, drcp, fastSlab, closest ? h.z : hz0);
+      // (at the found distance in the variant without lights only: the shared text costs the lit resident variants four spilled
+      // registers and 1 % of their frames, profiles/cast_cost.txt)
+      redo = redo || !refReaches(nodes, leaf, ray, drcp, fastSlab, closest ? h.z : hz0, TL && closest && !tie);
     }
     if (redo) {
       h.z = hz0;

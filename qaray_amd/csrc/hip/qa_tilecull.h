@@ -76,6 +76,40 @@ __host__ __device__ __forceinline__ void boxEntryExitPad(f3 pLo, f3 pHi, f3 d, f
   exit_ = qmin(t1.x, qmin(t1.y, t1.z));
 }
 
+// The fast form with the ray's share of a plane distance formed once per ray and mesh: (b - q) * drcp = b * drcp + c with
+// c = -(q * drcp), one fma per plane (walkBVH<true> carries cLo / cHi where the other forms carry pLo / pHi).  Only for rays
+// whose every |d| component is >= 1e-7, as boxEntryExitPadFast: then every drcp is finite.
+// Rounding (u = 2^-24, T = the exact plane distance (b - q) * drcp):
+//   old form   fl(fl(b - q) * drcp):   |error| <= u |b - q| |drcp| + u |T|            = 2 u |b - q| |drcp|
+//   this form  fma(b, drcp, fl(-q drcp)): |error| <= u |q| |drcp| + u |T|             = u (|q| + |b - q|) |drcp|
+// (second order terms dropped).  An error e of a plane distance is the error of a plane moved by e / |drcp|: at most 2 u |b - q|
+// before, u (|q| + |b - q|) now.  With P = max(|o|, |b|) the largest coordinate involved and pad << P: |q| <= P + pad and
+// |b - q| <= 2 P + pad, so the old form moves a plane by up to 4 u P and this one by up to 3 u P ~ 1.8e-7 P - its worst case is the
+// smaller one, although it is the larger one where b ~ q (an origin on a box face: the difference is exact, the product q drcp
+// is not; there this form is off by u |q| <= 6e-8 P).  drcp itself is 1 / d rounded: another u / 2 of |b - q| in both forms, 4 u P ~
+// 2.4e-7 P in all for this one.  Either way it is a quarter of the 1e-6 P term of fastWalkPad, which was sized
+// for the slab arithmetic of the old form and the error of the ray's own point together: the pad stays as it is.  The tile
+// lists' margin (TileCone::rel >= 3e-5 = 500 u of the same coordinates) covers this form as it covers the old one
+// (tests/cpp/slab_form_check.cpp asks both questions ray by ray).
+__host__ __device__ __forceinline__ f3 slabRayTerm(f3 q, f3 drcp) { return -(q * drcp); }
+__host__ __device__ __forceinline__ void boxEntryExitPadFma(f3 cLo, f3 cHi, f3 drcp, f3 bmin, f3 bmax, float &entry, float &exit_)
+{
+  const float p0x = __builtin_fmaf(bmin.x, drcp.x, cLo.x), p0y = __builtin_fmaf(bmin.y, drcp.y, cLo.y), p0z = __builtin_fmaf(bmin.z, drcp.z, cLo.z);
+  const float p1x = __builtin_fmaf(bmax.x, drcp.x, cHi.x), p1y = __builtin_fmaf(bmax.y, drcp.y, cHi.y), p1z = __builtin_fmaf(bmax.z, drcp.z, cHi.z);
+  entry = __builtin_fmaxf(__builtin_fmaxf(__builtin_fminf(p0x, p1x), __builtin_fminf(p0y, p1y)), __builtin_fminf(p0z, p1z));
+  exit_ = __builtin_fminf(__builtin_fminf(__builtin_fmaxf(p0x, p1x), __builtin_fmaxf(p0y, p1y)), __builtin_fmaxf(p0z, p1z));
+}
+
+// The leaf test of refReaches (qa_kernel.h) on the reference's own slab interval of the accepted triangle's leaf.
+// atFound = false: `limit` is a distance the reference held when it tested the box (an any-hit query's fixed t_max), or one not
+// larger than that: its strict test.  atFound = true: `limit` is the distance t the search just found for a closest-hit query and
+// no tie was seen - the reference then held MORE than t when it tested this box (refReaches has the argument), so entry == t passes
+// its strict test too.
+__host__ __device__ __forceinline__ bool refLeafReached(float entry, float exit_, float limit, bool atFound)
+{
+  return (atFound ? entry <= limit : entry < limit) && entry < exit_;
+}
+
 // The widening of the own tree's boxes for a ray whose origin's largest |coordinate| is oMax (hitMesh explains the constants);
 // invH, absMax: DMesh.  Camera rays without depth of field share their origin: one pad per tile and mesh.
 __host__ __device__ __forceinline__ float fastWalkPad(float invH, float absMax, float oMax)
