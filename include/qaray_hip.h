@@ -594,6 +594,10 @@ int qa_set_pipeline(qa_ctx *ctx, int mode);
  *   "walk_zero_terms" tests: 1 = the shadow ray of a light whose term is zero in every component whatever the ray finds (the surface
  *                    faces away from the light) is walked all the same, as the reference does; 0 (default) = counted, not walked
  *                    (same bits, same counters)
+ *   "last_cast"      -1 (default) / 1: LDS-resident scenes without lights, reflective or refractive lobes and absorption whose only
+ *                    emitters are planes and spheres - a path's last ray asks which emitter it meets (an any-hit sweep in place of the
+ *                    closest-hit search, no hit details, no shading); 0: the same kernel runs the closest-hit sweep (same bits, same
+ *                    counters; tests and A/B runs)
  *   "cs_pool_limit"  n > 0: upper bound for the pool of the cooperative walks (tests: forces the overflow path); 0 = none
  *   "sync_samples"   -1 (default: per scene) / 0 / 1: a wave starts the next samples of its 64 pixels together; n >= 2 (cooperative
  *                    kernel; elsewhere like 1): finished paths wait until n of the wave's have gathered

@@ -29,6 +29,8 @@ int EnsureHalton(qa_ctx *c, int count)
 // on: C3, 9 nodes, + 4 %), the untextured ones on scenes of more than 12 nodes (their register budget: see the kernel's comment).
 // Both read the live plan: they agree with the kernels SelectKernel picked because every edit that changes the plan runs it again
 static bool CsManyVariant(const qa_ctx *c) { return c->plan.shadowLights.size() > QA_CS_LIGHT_BATCH && !c->plan.area; }
+// The resident variant whose bounce rays ask which emitter they meet (qa_kernel.h lastCastQuery)
+static bool LastCastVariant(const qa_ctx *c) { return c->plan.resident && c->plan.lastCastQuery && c->ds.num_lights == 0; }
 static bool CsCullVariant(const qa_ctx *c) { return c->plan.csCullOk && (CsManyVariant(c) || c->plan.area || c->plan.textured || c->ds.num_inst > 12); }
 
 // The name of a slot's integrator for the uploaded scene (qa_get_kernel_name)
@@ -40,7 +42,8 @@ static std::string IntegratorName(const qa_ctx *c, Slot s)
   if (s == kCs || s == kCsResume)
     snprintf(name, sizeof(name), "qa_integrate_cs%s<LIGHTS=%d,TEX=%d,CULL=%d%s%s>", s == kCsResume ? "_resume" : "", lights, (int) p.textured, (int) CsCullVariant(c),
              CsManyVariant(c) ? ",MANY=1" : "", p.area ? ",AREA=1" : "");
-  else snprintf(name, sizeof(name), "qa_integrate<RES=%d,LIGHTS=%d,TEX=%d,AREA=%d>", (int) p.resident, lights, (int) p.textured, (int) p.area);
+  else snprintf(name, sizeof(name), "qa_integrate<RES=%d,LIGHTS=%d,TEX=%d,AREA=%d%s>", (int) p.resident, lights, (int) p.textured, (int) p.area,
+                s == kMega && LastCastVariant(c) ? ",LASTCAST=1" : "");
   std::string out = name;
   if (s == kPm || s == kPmStats) out += " + photon-map gathers (PHOTON=1)";
   if (s == kMegaStats || s == kPmStats) out += " counting variant (STATS=1, reference tree)";
@@ -66,7 +69,7 @@ int SelectKernel(qa_ctx *c)
   const ScenePlan &p = c->plan;
   const bool lights = c->ds.num_lights > 0;
   Integrator &mega = c->integ[kMega], &cs = c->integ[kCs], &resume = c->integ[kCsResume];
-  mega.fn = PickKernel(p.resident, lights, p.textured, p.area, false);
+  mega.fn = LastCastVariant(c) ? PickLastCastKernel() : PickKernel(p.resident, lights, p.textured, p.area, false);
   mega.ldsBytes = p.ldsBytes + p.tileListBytes;
   mega.blocksPerCU = OccupancyBlocks(mega.fn, mega.ldsBytes);
   mega.stackDepth = c->ds.stackDepth;
@@ -194,6 +197,8 @@ int LaunchSetup(qa_ctx *c, Launch &L, const FrameArgs &a, int ownRows, unsigned 
   ds.csCullOn = (c->optCsCull && c->plan.csCullOk) ? 1u : 0u;
   ds.csForceExact = c->optCsForceExact;
   ds.walkZeroTerms = c->optWalkZeroTerms;
+  ds.lastCast = (LastCastVariant(c) && c->optLastCast != 0) ? 1u : 0u;
+  ds.lastCastGlow = c->plan.lastCastGlow;
   ds.csPoolLimit = DevEnv("QA_CS_POOL") ? (uint32_t) std::max(64, atoi(DevEnv("QA_CS_POOL"))) : c->optCsPool;
 
   L.tiles = (unsigned) ((x1 - x0 + 7) / 8) * (unsigned) ownRows;

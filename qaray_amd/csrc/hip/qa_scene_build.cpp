@@ -613,7 +613,8 @@ void BuildImage(SceneTables &out)
   }
 }
 
-// the DScene fields that come from the header, the stack and LDS sizes, and residency
+void PlanLastCast(const Blob &b, SceneTables &out);
+// the DScene fields that come from the header, the stack and LDS sizes, and residency; the last-cast predicate
 void PlanScene(const Blob &b, const BuildKnobs &k, uint32_t stackNeedMax, SceneTables &out)
 {
   const qa_flat_header *h = b.h;
@@ -661,6 +662,7 @@ void PlanScene(const Blob &b, const BuildKnobs &k, uint32_t stackNeedMax, SceneT
   ds.num_inst = (int) h->num_instances;
   ds.num_lights = (int) h->num_lights;
   ds.num_materials = (int) h->num_materials;
+  PlanLastCast(b, out);
 }
 
 // what follows from the lights and the root node alone
@@ -687,6 +689,62 @@ void KeepTexLayout(const Blob &b, SceneTables &out)
   out.texLayout.resize(b.h->num_textures);
   for (uint32_t i = 0; i < b.h->num_textures; ++i)
     out.texLayout[i] = TexLayout{textures[i].type, textures[i].width, textures[i].height, 0, textures[i].off_texels};
+}
+
+// May the bounce rays of this scene be asked "which emitter do you meet" instead of "what do you hit" (qa_kernel.h lastCastQuery)?
+// Without lights, textures and reflective / refractive lobes a path is camera ray, diffuse hit, one bounce ray, and the bounce ray's
+// hit adds its material's emission, draws RandomSelectMtl's one number and spawns nothing (shadeSurface: !fromDiffuse fails).  Then
+// the hit itself is not needed where
+//   * no material absorbs (Beer's factor of a back-face hit is exp(-0 * z) = 1 exactly),
+//   * every node with an object has a material, a plane or sphere a single one (a MultiMtl on them is indexed by the mtlID an earlier
+//     mesh hit left behind), and a mesh under a MultiMtl no face id outside it (that hit adds white and draws nothing),
+//   * the emitting materials belong to planes and spheres only ("glow nodes", at most 32 nodes: one mask word): a mesh hit adds
+//     T * 0 whichever triangle it is.  A scene with an emitting mesh material keeps the closest-hit kernel.
+// Every edit that can change any of this ends in PlanScene (RebuildSceneSide).
+void PlanLastCast(const Blob &b, SceneTables &out)
+{
+  const qa_flat_header *h = b.h;
+  ScenePlan &plan = out.plan;
+  plan.lastCastQuery = false;
+  plan.lastCastGlow = 0;
+  if (h->num_lights != 0 || plan.textured || plan.area || h->num_instances > 32) return;
+  const qa_material *mats = b.at<qa_material>(h->off_materials);
+  const qa_mtlset *sets = b.at<qa_mtlset>(h->off_mtlsets);
+  const qa_instance *inst = b.at<qa_instance>(h->off_instances);
+  const qa_mesh *meshes = b.at<qa_mesh>(h->off_meshes);
+  auto emits = [&](int32_t mi) { const float *e = mats[mi].emission.color; return !(e[0] == 0.f && e[1] == 0.f && e[2] == 0.f); };
+  for (uint32_t i = 0; i < h->num_materials; ++i) {
+    const qa_material &m = mats[i];
+    for (int k = 0; k < 3; ++k)
+      if (m.reflection.color[k] != 0.f || m.refraction.color[k] != 0.f || !(m.absorption[k] == 0.f)) return;
+  }
+  uint32_t glow = 0;
+  for (uint32_t k = 0; k < h->num_instances; ++k) {
+    const qa_instance &in = inst[k];
+    if (in.obj_type == QA_OBJ_NONE) continue;
+    if (k == 0) continue;   // (the sweeps start at node 1: an object on the root is never traced)
+    if (in.mtlset < 0 || (uint32_t) in.mtlset >= h->num_mtlsets) return;
+    const qa_mtlset &ms = sets[in.mtlset];
+    const int32_t count = ms.multi ? ms.count : 1;
+    if (ms.first < 0 || count < 1 || (uint64_t) ms.first + (uint64_t) count > h->num_materials) return;
+    bool glows = false;
+    for (int32_t i = 0; i < count; ++i) glows = glows || emits(ms.first + i);
+    if (in.obj_type == QA_OBJ_MESH) {
+      if (glows) return;
+      if (in.mesh < 0 || (uint32_t) in.mesh >= h->num_meshes) return;
+      if (ms.multi) {
+        const qa_mesh &m = meshes[in.mesh];
+        const qa_face *faces = b.at<qa_face>(m.off_faces);
+        for (uint32_t f = 0; f < m.num_faces; ++f)
+          if (faces[f].mtl < 0 || faces[f].mtl >= ms.count) return;
+      }
+    } else {
+      if (ms.multi) return;
+      if (glows) glow |= 1u << k;
+    }
+  }
+  plan.lastCastQuery = true;
+  plan.lastCastGlow = glow;
 }
 
 // Without reflective / refractive lobes a path is at most camera ray + one diffuse bounce: starting

@@ -49,6 +49,10 @@ struct ScenePlan {
   int syncAuto = 0;                      // samples of a wave start together unless the frame decides otherwise
   size_t ldsBytes = 0;                   // dynamic LDS of qa_integrate: resident image + stacks, or stacks
   size_t tileListBytes = 0;              // + the waves' tile lists behind them (qa_tilecull.h), where they cost no workgroup per CU; else 0
+  // Unlit scenes whose bounce rays need nothing of their hit but which emitter it is (PlanLastCast, qa_scene_build.cpp): the
+  // resident ones run qa_integrate_lastcast (qa_kernel.h lastCastQuery).  lastCastGlow: bit k = node k is a glow node
+  bool lastCastQuery = false;
+  uint32_t lastCastGlow = 0;
 };
 // a mesh hit without texture vertices keeps the uvw of an earlier, farther hit: history only a sequential walk has
 inline bool MissesTexcoords(const ScenePlan &p, const DMesh &m) { return p.textured && m.num_faces > 0 && !m.hasVT; }

@@ -221,6 +221,10 @@ struct DScene {
   // resident scenes only: the tables themselves, in the kernel-argument segment
   qa_instance instv[QA_KARG_INST];
   DMesh meshv[QA_KARG_MESH];
+  // qa_integrate_lastcast (qa_kernel.h lastCastQuery; ScenePlan::lastCastQuery), behind the tables so that no other field moves:
+  // lastCast = 1: a bounce ray asks only which emitter it meets (option "last_cast"; 0: the closest-hit sweep and shading of every
+  // other variant); lastCastGlow: bit k = node k is a plane or sphere with an emitting material (the only emitters of such a scene)
+  uint32_t lastCast, lastCastGlow;
 };
 
 struct DCounters {
@@ -230,9 +234,12 @@ struct DCounters {
   // over waves, printed by qa_get_counters: 0 kernel, 1 fetch + sample start, 2 closest-hit queries, 3 of which mesh walks,
   // 4 shadeSurface, 5 direct light, 6 of which shadow mesh walks, 7 sample end, 8 loop iterations, 9 waves, 10 miss branch,
   // 11 hit before shading, 12 spawn.
+  // The resident variant without lights also: 19 the part of 3 in waves that hold no camera ray (the bounce rays' walks), 20 what follows
+  // the sweep in those waves (miss branch, hit before shading, shadeSurface, spawn), 21 last-cast queries (lastCastQuery), 22 of which mesh walks,
+  // 23 lanes whose query answered "ask again" (a count).
   // qa_integrate_cs also: 13 closest-hit sweep without the rounds, 14 details of the winners, 15 lanes sent to the exact closest-hit
   // walk, 16 (lane, light) pairs sent to the exact shadow walk, 17 shadow sweeps without the rounds, 18 light terms
-#define QA_NSTAMPS 20
+#define QA_NSTAMPS 24
   unsigned long long stamp[QA_NSTAMPS];
   unsigned long long *sl;   // device side: the wave's accumulators in LDS (one elected lane adds: a section entered by part of the wave counts in full)
 #endif

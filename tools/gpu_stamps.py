@@ -1,5 +1,6 @@
 """Section shares of the megakernel's wave time (diagnostic build: make hip LIBDIR=../lib_stamp OBJDIR=../lib_stamp/obj EXTRA=-DQA_STAMPS).
-   QA_HIP_LIB=qaray_amd/lib_stamp/libqaray_hip.so python tools/gpu_stamps.py [spp]"""
+   QA_HIP_LIB=qaray_amd/lib_stamp/libqaray_hip.so python tools/gpu_stamps.py [spp]
+   QA_LAST_CAST=0: option "last_cast" off (the bounce rays of qa_integrate_lastcast run the closest-hit sweep and shading)"""
 import os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -12,6 +13,7 @@ spp = int(sys.argv[1]) if len(sys.argv) > 1 else 32
 CASES = [("c2", "example_project12_box.xml", (1920, 1080), 4 * spp), ("c3", "example_project7_object.xml", (1920, 1080), spp),
          ("c4", "example_project12_caustics_glossy.xml", (3840, 2160), spp), ("c5", "trc_scene_tower.xml", (3840, 2160), spp)]
 ctx = hip.Context(0)
+if "QA_LAST_CAST" in os.environ: ctx.set_option("last_cast", int(os.environ["QA_LAST_CAST"]))
 for tag, scene, size, n in CASES:
     if tag not in only: continue
     ctx.upload_scene(load_scene_blob(scene, size=size))
