@@ -50,6 +50,9 @@
  *   qa_reproject_node_motion
  *   qa_reproject_moments_device,   (no counterpart: the same carrying the first two luma moments of every pixel, for a per-pixel
  *   qa_progressive_reproject_moments_device   variance of the accumulated colour, and shortening the history the clamp moved)
+ *   qa_radiance_rays*,             (no counterpart: PixelRender's path - Scene::TraceNodeNormal, Material::Shade, the lights - started
+ *   qa_camera_sample_rays_device   from rays of the caller's instead of the camera ray, and the camera rays of every sample handed
+ *                                  out)                                 src/renderers/renderer.cpp:312-341
  *   qa_get_counters                (no counterpart: the reference only prints wall-clock)
  *   qa_get_kernel_time             Renderer::StartTimer/StopTimer       src/renderers/renderer.cpp:42-63
  */
@@ -682,6 +685,56 @@ int qa_test_reproject_moments_host(const qa_camera *prev_cam, const qa_camera *c
                                    const float *hist_length, const int32_t *hist_ids, const float *hist_moments, const qa_node_motion *motion,
                                    int motion_count, const qa_reproject_moments_params *params, float *out_rgb, float *out_length,
                                    float *out_moments, float *out_variance);
+
+/* Radiance queries: n rays of the caller's path-traced on the resident scene by the integrator of qa_render_region, started from
+ * the rays instead of the camera (qa_integrate_rays: qa_kernel_body.h sections A and B under RAYS; the opening comment of
+ * qaray_amd/csrc/hip/qa_radiance.hip is the specification).  Ray arrays as for the ray queries above: [records][3] floats, world
+ * space, contiguous; the direction is used as given and NOT normalised (shading assumes unit length, as for a camera ray).
+ *   qa_radiance_params          spp >= 1 samples per ray (fixed: no adaptive stop), max_bounce >= 0 as qa_render_region's, seed, flags:
+ *     QA_RADIANCE_PER_SAMPLE      every ray array holds n * spp records, sample s of ray q starts from record q * spp + s; without it
+ *                                 n records, every sample of ray q starts from record q
+ *     QA_RADIANCE_MISS_ENVIRONMENT a first ray that misses takes the environment by direction, as a bounce ray does; without it
+ *                                 the background, as a frame's camera ray does
+ *   qa_radiance_params_default  spp 1, max_bounce 5, seed 0x51A7A7, flags 0.  Needs no context.
+ *   qa_radiance_rays_device     d_dx, d_dy: the ray's differential directions for the texture filter, both or neither (NULL: a ray
+ *                               of no width, the first hit's textures are looked up unfiltered); d_screen: [records][2] the position
+ *                               in pixels at which a missed first ray looks a background texmap up (NULL: required only when the
+ *                               background has a texmap and QA_RADIANCE_MISS_ENVIRONMENT is not set); d_stream: [n] uint32, ray q
+ *                               draws from the random-number stream of pixel index d_stream[q] (NULL: q).  Outputs by ray: d_rgb
+ *                               [n][3] the mean of the spp samples; d_t [n] (may be NULL) the parameter of sample 0's first hit,
+ *                               QA_RAY_MISS on a miss; d_nsamples [n] uint32 (may be NULL): zeroed first, spp for a finished ray,
+ *                               0 for one that qa_request_stop left unfinished.  A void ray (a component that is not finite, or
+ *                               direction (0, 0, 0)) is not walked and draws no random number: its sample is black, and counts.
+ *                               Only enqueues on hip_stream (NULL = the context's stream).
+ *   qa_radiance_rays            the same from and to host memory through a staging buffer of the call's own that only grows (24 bytes
+ *                               per ray and 56 per record of the largest batch so far, freed with the context); synchronises.
+ *   qa_camera_sample_rays_device  samples [first, first + count) of the camera rays of every pixel of [x0,x1) x [y0,y1) exactly as
+ *                               qa_render_region builds them (qa_kernel_body.h section B): record (pixel, k) at pixel * count + k,
+ *                               pixels region-local and row-major; d_stream [pixels] = y * width + x.  Each output may be NULL, not
+ *                               all.  Handed to qa_radiance_rays_device with QA_RADIANCE_PER_SAMPLE (first 0, count spp) they give
+ *                               qa_render_region's rgb, depth and nsamples bit for bit.  Sample 0's origins and directions are
+ *                               qa_camera_rays_device's.  QA_EUNSUPPORTED for a camera with dof > 0.1: its lens draws come from
+ *                               the pixel's stream in the middle of a path sequence, and no ray array can carry them.
+ * Ordered as a frame: behind the context's last frame and last edit, one at a time per context; qa_get_counters and
+ * qa_get_kernel_time move as for a frame of n * spp samples; qa_get_kernel_name, progressive frames and frames rendered before and
+ * after are untouched.  Codes: QA_ENOSCENE without a scene; n == 0 is QA_OK and launches nothing; QA_EINVAL for n > 2^31 - 1 (and
+ * for (n + 63) / 64 * 64 >= 0xF0000000: the work counter is 32 bits), a NULL ray array, rgb or params, spp < 1, max_bounce < 0,
+ * unknown flag bits, one of d_dx / d_dy without the other, a textured background without d_screen and without
+ * QA_RADIANCE_MISS_ENVIRONMENT; QA_EUNSUPPORTED for area lights with max_bounce > 7 (as qa_render_region) and while photon maps
+ * are built (no gathering instance is compiled).  A refused call writes nothing.  Every mesh is walked per lane, rays are taken
+ * in the caller's order. */
+#define QA_RADIANCE_PER_SAMPLE       1u
+#define QA_RADIANCE_MISS_ENVIRONMENT 2u
+typedef struct qa_radiance_params { int spp, max_bounce; uint32_t seed, flags; } qa_radiance_params;
+int qa_radiance_params_default(qa_radiance_params *params);
+int qa_radiance_rays_device(qa_ctx *ctx, uint64_t n, const float *d_origins, const float *d_dirs, const float *d_dx, const float *d_dy,
+                            const float *d_screen, const uint32_t *d_stream, const qa_radiance_params *params, float *d_rgb, float *d_t,
+                            uint32_t *d_nsamples, void *hip_stream);
+int qa_radiance_rays(qa_ctx *ctx, uint64_t n, const float *origins, const float *dirs, const float *dx, const float *dy,
+                     const float *screen, const uint32_t *stream, const qa_radiance_params *params, float *rgb, float *t,
+                     uint32_t *nsamples);
+int qa_camera_sample_rays_device(qa_ctx *ctx, int x0, int y0, int x1, int y1, int first, int count, float *d_origins, float *d_dirs,
+                                 float *d_dx, float *d_dy, float *d_screen, uint32_t *d_stream, void *hip_stream);
 
 #ifdef __cplusplus
 }

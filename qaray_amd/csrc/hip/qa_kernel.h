@@ -1669,7 +1669,8 @@ struct Path {
 template <bool RES, bool LIGHTS, bool TEX, bool AREA, bool STATS, bool PHOTON = false>
 __global__ __launch_bounds__(QA_BLOCK, QA_WAVES_FOR(RES, LIGHTS)) void qa_integrate(const DScene sc, const RenderParams rp)
 {
-  constexpr bool LASTQ = false;
+  constexpr bool LASTQ = false, RAYS = false;
+  const RayBatch rb = {};
 #include "qa_kernel_body.h"
 }
 
@@ -1680,6 +1681,19 @@ __global__ __launch_bounds__(QA_BLOCK, QA_WAVES_FOR(RES, false)) void qa_integra
 {
   constexpr bool LIGHTS = false, TEX = false, AREA = false, STATS = false, PHOTON = false;
   constexpr bool LASTQ = true;   // its bounce rays go through lastCastQuery
+  constexpr bool RAYS = false;
+  const RayBatch rb = {};
+#include "qa_kernel_body.h"
+}
+
+// qa_integrate<RES, LIGHTS, TEX, AREA> whose paths start from rays of the caller's (qa_radiance_rays*; the opening comment of
+// qa_radiance.hip is the specification): the third entry point over the body.  The ray arrays are a third kernel argument, so that
+// RenderParams and the kernel arguments of every shipped kernel stay as they are.  Instances: qa_radiance.hip.
+template <bool RES, bool LIGHTS, bool TEX, bool AREA>
+__global__ __launch_bounds__(QA_BLOCK, QA_WAVES_FOR(RES, LIGHTS)) void qa_integrate_rays(const DScene sc, const RenderParams rp, const RayBatch rb)
+{
+  constexpr bool STATS = false, PHOTON = false, LASTQ = false;
+  constexpr bool RAYS = true;
 #include "qa_kernel_body.h"
 }
 

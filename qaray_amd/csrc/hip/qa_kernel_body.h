@@ -1,8 +1,12 @@
-// qa_kernel_body.h - the body of the per-lane megakernel (qa_kernel.h), included by its two entry points: qa_integrate and
-// qa_integrate_lastcast.  Not a header of its own: it is the text of a function whose parameters are `sc` and `rp`, with the template
-// parameters RES, LIGHTS, TEX, AREA, STATS, PHOTON and the constant LASTQ in scope.  (A text include rather than an inline function,
-// as qa_kernel_cs_body.h: the shipped instances keep exactly the code they had - through a function the kernel arguments are copied
-// to scratch and the AREA variants spill a thousand registers.)
+// qa_kernel_body.h - the body of the per-lane megakernel (qa_kernel.h), included by its three entry points: qa_integrate,
+// qa_integrate_lastcast and qa_integrate_rays.  Not a header of its own: it is the text of a function whose parameters are `sc` and
+// `rp`, with the template parameters RES, LIGHTS, TEX, AREA, STATS, PHOTON, the constants LASTQ and RAYS and the ray batch `rb`
+// (RayBatch; empty unless RAYS) in scope.  (A text include rather than an inline function, as qa_kernel_cs_body.h: the shipped
+// instances keep exactly the code they had - through a function the kernel arguments are copied to scratch and the AREA variants
+// spill a thousand registers.)
+// RAYS (qa_integrate_rays; the opening comment of qa_radiance.hip is the specification): the paths start from the rays of `rb` and
+// not from the camera.  Only the work items (section A), the start of a sample (B), the first ray's miss (C) and the output sites
+// differ, each under `if constexpr (RAYS)`: with RAYS false the text below is the text the shipped kernels were compiled from.
   extern __shared__ uint4 s_dyn[];
   SceneMem<RES> mem;
   mem.img = s_dyn;
@@ -29,7 +33,7 @@
   // Tile lists for the camera rays (qa_tilecull.h): the wave's area behind the per-lane columns, when the launch made room for it.
   // With depth of field the camera rays of a tile share no origin.
   // (in the variant without lights only: the lit and textured resident variants pay for the shared text in spilled registers)
-  constexpr bool TL = RES && !LIGHTS && !TEX && !AREA && !STATS && !PHOTON;
+  constexpr bool TL = RES && !LIGHTS && !TEX && !AREA && !STATS && !PHOTON && !RAYS;   // (rays of a batch share no tile)
   static_assert(!LASTQ || TL, "the last-cast query belongs to the resident variant without lights");
   uint32_t *tileList = nullptr;
   if constexpr (TL)
@@ -51,7 +55,8 @@
   // publishes the tile's progress (agent-scope release), and whoever fetches (chunk + 1, tile) - a whole pass of the frame later -
   // reads the state back behind an acquire.  Same samples in the same order for every pixel: same bits.
   const unsigned numTiles = tilesX * (unsigned) rp.own_tile_rows;
-  const unsigned total = numTiles * (rp.chunk_spp ? rp.num_chunks : 1u) * 64u;
+  // (RAYS: a work item is 64 consecutive rays, lane = ray)
+  const unsigned total = RAYS ? (rb.n + 63u) / 64u * 64u : numTiles * (rp.chunk_spp ? rp.num_chunks : 1u) * 64u;
   const unsigned lane = __lane_id();
   unsigned curTile = 0xFFFFFFFFu, curChunk = 0;   // (wave-uniform) the work item in hand
   int chunkEnd = 0x7FFFFFFF;                      // samples a pixel has when its chunk is complete
@@ -158,6 +163,19 @@
         const unsigned w = base + lane;
         if (base >= total) {
           alive = false;
+        } else if constexpr (RAYS) {
+          if (w < rb.n) {   // (else: padding lane of the last item - this lane sits it out)
+            q = w;
+            rng = qa_pixel_seed(rp.seed, rb.stream ? rb.stream[q] : (uint32_t) q);
+            sidx = 0;
+            for (int i = 0; i < 6; ++i) acc[i * QA_BLOCK] = 0.f;
+            needSample = true;
+            needPixel = false;
+            if (LCOLS) {
+              acc[13 * QA_BLOCK] = __uint_as_float(q);
+              acc[14 * QA_BLOCK] = __int_as_float(sidx);
+            }
+          }
         } else {
           const unsigned in = w % 64;
           const unsigned tile = rp.tile_order ? rp.tile_order[item] : item;
@@ -208,6 +226,22 @@
     const bool goSample = !rp.sync_samples || (__ballot(needSample) == __ballot(alive && !needPixel));
     if (alive && needSample && goSample) {
       const int si = QA_GET_SIDX();
+      if constexpr (RAYS) {
+        // sample si of ray q: the caller's ray, used as given (no Halton term, no camera, no lens draws)
+        const size_t ri = (rb.flags & QA_RAYS_PER_SAMPLE) ? (size_t) QA_GET_Q() * (size_t) rp.spp_max + (size_t) si : (size_t) QA_GET_Q();
+        path.ray.p = F3(rb.o[3 * ri], rb.o[3 * ri + 1], rb.o[3 * ri + 2]);
+        path.ray.d = F3(rb.d[3 * ri], rb.d[3 * ri + 1], rb.d[3 * ri + 2]);
+        if (TEX) {
+          // without differentials a ray of no width: DiffRay(pos, dir), x = y = c - the filter takes its unfiltered branch
+          pathDiff.dx = pathDiff.dy = path.ray.d;
+          if (rb.dx) {
+            pathDiff.dx = F3(rb.dx[3 * ri], rb.dx[3 * ri + 1], rb.dx[3 * ri + 2]);
+            pathDiff.dy = F3(rb.dy[3 * ri], rb.dy[3 * ri + 1], rb.dy[3 * ri + 2]);
+          }
+          texpos = F3(0, 0, 0);   // where a missed first ray looks the background texmap up (pixels)
+          if (rb.screen) texpos = F3(rb.screen[2 * ri], rb.screen[2 * ri + 1], 0.f);
+        }
+      } else {
       const float hx = sc.halton[2 * si], hy = sc.halton[2 * si + 1];
       if (LCOLS) {
         const unsigned pxy = __float_as_uint(acc[12 * QA_BLOCK]);
@@ -233,6 +267,7 @@
         const f3 ypt = (A + U * texpos.x) + V * (texpos.y + QA_DX);
         pathDiff.dx = normalize(xpt - campos);
         pathDiff.dy = normalize(ypt - campos);
+      }
       }
       QA_PUT_T(F3(1, 1, 1))
       QA_PUT_L(F3(0, 0, 0))
@@ -297,16 +332,43 @@
 #endif
         }
       }
+      if constexpr (RAYS) {
+        // a void first ray (a component that is not finite, or direction 0) is not walked and draws nothing from the stream: the
+        // sample is black, and it counts
+        const Ray &r0 = path.ray;
+        const bool finite = isfinite(r0.p.x) && isfinite(r0.p.y) && isfinite(r0.p.z) && isfinite(r0.d.x) && isfinite(r0.d.y) && isfinite(r0.d.z);
+        if (path.primary && !(finite && !(r0.d.x == 0.f && r0.d.y == 0.f && r0.d.z == 0.f))) {
+          if (QA_GET_SIDX() == 0 && rp.depth) rp.depth[QA_GET_Q()] = QA_BIGFLOAT;
+          done = true;
+          sweep = false;
+        }
+      }
       if (sweep) {
       QA_T(tC)
       const bool found = traceClosest<RES, TEX, STATS, TL>(mem, sc, path.ray, pathDiff, h, th, stack, cnt, tileList, path.primary);
       QA_TACC(cnt.sl[2], tC)
+      if constexpr (RAYS) {
+        if (path.primary && QA_GET_SIDX() == 0 && rp.depth) rp.depth[QA_GET_Q()] = found ? h.z : QA_BIGFLOAT;   // (t is optional)
+      } else {
       if (path.primary && QA_GET_SIDX() == 0) rp.depth[QA_GET_Q()] = found ? h.z : QA_BIGFLOAT;
+      }
 
       QA_T(tM)
       if (!found) {
         // background for camera rays (renderer.cpp:337-341), environment otherwise
         // (MtlBlinn_PhotonMap.cpp:249-251); textured versions: TEX kernel variants
+        if constexpr (RAYS) {
+          // QA_RADIANCE_MISS_ENVIRONMENT sends a missed first ray to the environment by direction, as a bounce ray
+          const bool asCamera = path.primary && !(rb.flags & QA_RAYS_MISS_ENVIRONMENT);
+          f3 c = asCamera ? ld3(sc.background) : ld3(sc.environment);
+          if (TEX) {
+            if (asCamera)
+              c = texColorSample(tt, c, sc.bgTexmap, F3(texpos.x / (float) sc.cam.width, texpos.y / (float) sc.cam.height, 0.f));
+            else
+              c = sampleEnvironment(tt, c, sc.envTexmap, path.ray.d);
+          }
+          QA_PUT_L(QA_GET_L() + QA_GET_T() * c)
+        } else {
         f3 c = path.primary ? ld3(sc.background) : ld3(sc.environment);
         if (TEX) {
           if (path.primary)
@@ -315,6 +377,7 @@
             c = sampleEnvironment(tt, c, sc.envTexmap, path.ray.d);
         }
         QA_PUT_L(QA_GET_L() + QA_GET_T() * c)
+        }
         done = true;
         QA_TACC(cnt.sl[10], tM)
       } else {
@@ -457,7 +520,11 @@
         rp.rgb[3 * qo + 0] = mean.x;
         rp.rgb[3 * qo + 1] = mean.y;
         rp.rgb[3 * qo + 2] = mean.z;
+        if constexpr (RAYS) {
+          if (rp.ns) rp.ns[qo] = (uint32_t) sidx;   // (optional)
+        } else {
         rp.ns[qo] = (uint32_t) sidx;
+        }
         if (rp.chunk_spp)   // (later chunks of the tile skip this pixel)
           __hip_atomic_store(reinterpret_cast<unsigned long long *>(rp.pix_state) + 4 * (size_t) qo, 0x80000000ull << 32, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         QA_TALLY(cnt.pixels);

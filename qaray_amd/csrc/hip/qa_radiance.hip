@@ -1,0 +1,293 @@
+// qa_radiance.hip — radiance along rays of the caller's (qa_radiance_rays*): the per-lane integrator of qa_kernel.h started from a
+// ray batch instead of the camera, its ten instances and their picker; and the renderer's own camera rays of every sample handed
+// out (qa_camera_sample_rays_device).  A unit of its own, as qa_lastcast.hip: the kernels are compiled side by side with the
+// shipped integrators, which keep their names, resources and code.  No reference counterpart (the reference path-traces only the
+// rays of its own camera); what ties it to the reference is that the renderer's own camera rays, handed back in, give the frame.
+//
+// SEMANTICS
+// A ray is an origin o and a direction d, both world space, fp32.  d is used as given and is NOT normalised (shading assumes unit
+// length, as for a camera ray): the renderer's own rays pass through bit for bit.  Ray q of a batch of n is the first segment of
+// spp paths; what follows the first segment is the integrator's, unchanged (qa_kernel_body.h sections C - E: the closest-hit sweep,
+// shading, direct light, the bounces, the running mean with its correctly rounded divisions).  The result of a ray depends on the
+// ray (with its differentials and screen position), its stream id, the seed, spp and max_bounce alone: not on n, on the ray's place
+// in the batch or on what else the batch holds.
+//   Rays per sample: by default sample s of ray q starts from record q of every ray array; with QA_RADIANCE_PER_SAMPLE from record
+//     q * spp + s (arrays of n * spp records): jittered or lens-sampled rays of the caller's own making.
+//   Random numbers: ray q draws from the stream qa_pixel_seed(seed, stream[q]), or qa_pixel_seed(seed, q) without stream ids; the
+//     samples of a ray continue one stream, as the samples of a pixel do.  The first segment draws nothing (no lens, no jitter).
+//   Differentials (textured scenes): dx / dy are the directions of the ray through the neighbouring pixel samples, DiffRay's x and
+//     y; both or neither.  Without them dx = dy = d, a ray of no width, the DiffRay(pos, dir) of a bounce ray: at the first hit
+//     the texture filter then takes its unfiltered branch (textureSampleFiltered, `filtered == false`: one unfiltered lookup), so a
+//     textured surface seen through such rays differs from the frame's filtered lookup.
+//   A first ray that misses takes the background colour, as a frame's camera ray does; a background texmap is looked up at the
+//     ray's screen position (screen[2 r], screen[2 r + 1], in pixels: divided by the image's width and height).  A scene whose
+//     background has a texmap is refused with QA_EINVAL when neither screen positions nor QA_RADIANCE_MISS_ENVIRONMENT are given:
+//     nothing is approximated silently.  With QA_RADIANCE_MISS_ENVIRONMENT it takes the environment by direction
+//     (sampleEnvironment), as every bounce ray does.
+//   Void rays: a (ray, sample) record is void if any component of o or d is not finite, or if d == (0, 0, 0) (as qa_ray_query.hip).
+//     It is not walked and draws nothing from the stream; the sample is black and counts as a sample.
+//   Outputs, indexed by ray: rgb [n][3] the mean over the spp samples; t [n] (optional) the parameter of sample 0's first hit, 1e30
+//     on a miss and for a void ray; ns [n] uint32 (optional) the samples taken: zeroed first, spp once the ray is finished - a ray
+//     that a stop request left unfinished reads 0, and its rgb is not written.
+//   spp is fixed: no adaptive stop (the running variance of a batch ray stops nothing).
+//   The camera is not read.  Area lights: max_bounce <= 7, as for a frame.  Photon maps: a context whose maps are built is refused
+//     (QA_EUNSUPPORTED): no gathering instance is compiled.
+//   State: the call is ordered as a frame is (behind the context's last frame and last edit, one at a time per context), adds to
+//     qa_get_counters (samples += n * spp, the casts of its paths) and to qa_get_kernel_time (one launch) as a frame does, and
+//     leaves qa_get_kernel_name, progressive frames and the frames' slabs alone.
+//
+// qa_camera_sample_rays_device: samples [first, first + count) of the camera rays of the pixels of a region, exactly as
+// qa_kernel_body.h section B builds them: texpos = (halton[2 s], halton[2 s + 1]) + (px, py), the point (A + U x) + V y of the
+// image plane, d = normalize(point - position), and for the differentials the same point with x + QA_DX and with y + QA_DX.  Record
+// (pixel, k) is at pixel * count + k, pixels region-local and row-major; stream ids are one per pixel, py * width + px.
+// Handed to qa_radiance_rays_device with QA_RADIANCE_PER_SAMPLE (first = 0, count = spp) they give qa_render_region's rgb, depth
+// and ns bit for bit.  A camera with dof > 0.1 is refused (QA_EUNSUPPORTED): its two lens draws come from the pixel's stream
+// between a sample's paths, in the middle of the stream - no ray array can carry them, and a frame of such a camera cannot be
+// reproduced from outside.
+//
+// Shape: a work item is 64 consecutive rays, lane = ray, handed out by the frame's work counter (a stop request ends the batch
+// between items).  No tiles: no tile order, no strips, no tile lists, no sample chunks; the last-cast query of
+// qa_integrate_lastcast is not carried over.  Every mesh is walked per lane (no cooperative walks), rays are taken in the caller's
+// order (not sorted).
+#include <algorithm>
+#include <cstring>
+#include <mutex>
+#include <unordered_map>
+
+#include "qa_kernel.h"
+#include "qa_ctx.h"
+#include "qa_radiance.h"
+
+static_assert(QA_RAYS_PER_SAMPLE == QA_RADIANCE_PER_SAMPLE && QA_RAYS_MISS_ENVIRONMENT == QA_RADIANCE_MISS_ENVIRONMENT, "RayBatch::flags are the C ABI's");
+
+namespace qa {
+
+struct CamSampleParams {
+  int32_t x0, y0, x1, y1;
+  int32_t first, count;
+  float *o, *d, *dx, *dy;   // [pixels * count][3] each; any may be null
+  float *screen;            // [pixels * count][2]
+  uint32_t *stream;         // [pixels]
+};
+
+// One thread per (pixel, sample); reads the camera record and the Halton table only
+__global__ __launch_bounds__(QA_BLOCK) void qa_camera_sample_rays(const DCamera cam, const float *halton, const CamSampleParams cs)
+{
+  const uint64_t rw = (uint64_t) (cs.x1 - cs.x0), nrec = rw * (uint64_t) (cs.y1 - cs.y0) * (uint64_t) cs.count;
+  const uint64_t i = (uint64_t) blockIdx.x * QA_BLOCK + threadIdx.x;
+  if (i >= nrec) return;
+  const uint64_t q = i / (uint64_t) cs.count;
+  const int k = (int) (i % (uint64_t) cs.count), si = cs.first + k;
+  const int px = cs.x0 + (int) (q % rw), py = cs.y0 + (int) (q / rw);
+
+  // ---- the camera ray of sample si: qa_kernel_body.h section B, the same operations in the same order (pinhole: dof <= 0.1)
+  const float hx = halton[2 * si], hy = halton[2 * si + 1];
+  const f3 texpos = F3(hx, hy, 0.f) + F3((float) px, (float) py, 0.f);
+  const f3 A = ld3(cam.screenA), U = ld3(cam.screenU), V = ld3(cam.screenV);
+  const f3 cpt = (A + U * texpos.x) + V * texpos.y;
+  const f3 campos = ld3(cam.pos);
+  const f3 dir = normalize(cpt - campos);
+  if (cs.o) { cs.o[3 * i] = campos.x; cs.o[3 * i + 1] = campos.y; cs.o[3 * i + 2] = campos.z; }
+  if (cs.d) { cs.d[3 * i] = dir.x; cs.d[3 * i + 1] = dir.y; cs.d[3 * i + 2] = dir.z; }
+  if (cs.dx) {
+    const f3 xpt = (A + U * (texpos.x + QA_DX)) + V * texpos.y;
+    const f3 v = normalize(xpt - campos);
+    cs.dx[3 * i] = v.x; cs.dx[3 * i + 1] = v.y; cs.dx[3 * i + 2] = v.z;
+  }
+  if (cs.dy) {
+    const f3 ypt = (A + U * texpos.x) + V * (texpos.y + QA_DX);
+    const f3 v = normalize(ypt - campos);
+    cs.dy[3 * i] = v.x; cs.dy[3 * i + 1] = v.y; cs.dy[3 * i + 2] = v.z;
+  }
+  if (cs.screen) { cs.screen[2 * i] = texpos.x; cs.screen[2 * i + 1] = texpos.y; }
+  if (cs.stream && k == 0) cs.stream[q] = (uint32_t) py * (uint32_t) cam.width + (uint32_t) px;
+}
+
+}  // namespace qa
+
+// ---- the ten instances: the five shadings PickShading lists (qa_mega.hip), for scenes in LDS and in global memory
+typedef void (*RaysFn)(const DScene, const RenderParams, const RayBatch);
+template <bool RES>
+static RaysFn PickRaysShading(bool lights, bool tex, bool area)
+{
+  if (area) return tex ? (RaysFn) qa_integrate_rays<RES, true, true, true> : (RaysFn) qa_integrate_rays<RES, true, false, true>;
+  if (tex) return (RaysFn) qa_integrate_rays<RES, true, true, false>;
+  if (lights) return (RaysFn) qa_integrate_rays<RES, true, false, false>;
+  return (RaysFn) qa_integrate_rays<RES, false, false, false>;
+}
+// by the predicates SelectKernel hands to PickKernel: plan.resident, num_lights > 0, plan.textured, plan.area
+static RaysFn PickRays(const qa_ctx *c)
+{
+  const ScenePlan &p = c->plan;
+  const bool lights = c->ds.num_lights > 0;
+  return p.resident ? PickRaysShading<true>(lights, p.textured, p.area) : PickRaysShading<false>(lights, p.textured, p.area);
+}
+
+// The host forms' staging: one device buffer per context that only grows and is only used synchronously, kept here as
+// qa_ray_query.hip keeps its own (qa_ctx.h is part of the integrator units).  qa_ctx_destroy frees it (FreeRadianceStage)
+static std::mutex g_stageLock;
+static std::unordered_map<const qa_ctx *, DevBuf> g_stage;
+static DevBuf &StageOf(const qa_ctx *c)
+{
+  std::lock_guard<std::mutex> hold(g_stageLock);
+  return g_stage[c];
+}
+void FreeRadianceStage(qa_ctx *c)
+{
+  std::lock_guard<std::mutex> hold(g_stageLock);
+  auto it = g_stage.find(c);
+  if (it == g_stage.end()) return;
+  it->second.Free();
+  g_stage.erase(it);
+}
+
+#define QA_MAX_RAYS 0x7FFFFFFFull
+#define QA_RADIANCE_FLAGS (QA_RADIANCE_PER_SAMPLE | QA_RADIANCE_MISS_ENVIRONMENT)
+
+// What the device and the host form refuse alike, before anything is sized by n.  QA_OK with n == 0: nothing to do
+static int RadianceChecks(qa_ctx *c, uint64_t n, bool rays, bool dx, bool dy, bool screen, const qa_radiance_params *p, bool rgb)
+{
+  if (!c->haveScene) return Fail(QA_ENOSCENE, "no scene uploaded");
+  if (n == 0) return QA_OK;
+  if (n > QA_MAX_RAYS) return Fail(QA_EINVAL, "more than 2^31 - 1 rays");
+  if ((n + 63) / 64 * 64 >= 0xF0000000ull) return Fail(QA_EINVAL, "too many rays for the 32-bit work counter");   // (every exiting wave adds 64 more)
+  if (!rays) return Fail(QA_EINVAL, "null ray array");
+  if (!rgb) return Fail(QA_EINVAL, "null rgb output");
+  if (!p) return Fail(QA_EINVAL, "null params");
+  if (p->spp < 1 || p->max_bounce < 0) return Fail(QA_EINVAL, "bad spp / bounce");
+  if (p->flags & ~QA_RADIANCE_FLAGS) return Fail(QA_EINVAL, "unknown flag bits");
+  if (dx != dy) return Fail(QA_EINVAL, "one differential array without the other");
+  if (c->plan.area && p->max_bounce + 1 > kMaxPath) return Fail(QA_EUNSUPPORTED, "area lights: maxBounce must be <= " + std::to_string(kMaxPath - 1));
+  if (c->photonReady) return Fail(QA_EUNSUPPORTED, "photon maps are built: no gathering instance of qa_integrate_rays is compiled (qa_photon_maps_clear first)");
+  if (c->plan.textured && c->ds.bgTexmap >= 0 && !screen && !(p->flags & QA_RADIANCE_MISS_ENVIRONMENT))
+    return Fail(QA_EINVAL, "the background has a texmap: give screen positions or QA_RADIANCE_MISS_ENVIRONMENT");
+  return QA_OK;
+}
+
+// One batch: the launch of a frame (qa_frame.hip LaunchSetup / LaunchFrame) without tiles, chunks, tile lists and photon maps
+static int Radiance(qa_ctx *c, uint64_t n, const RayBatch &rb, const qa_radiance_params &p, float *rgb, float *t, uint32_t *ns, hipStream_t s)
+{
+  HIP_TRY(c->lastFrame.WaitOn(s));
+  HIP_TRY(c->lastEdit.WaitOn(s));
+  if (ns) HIP_TRY(hipMemsetAsync(ns, 0, n * sizeof(uint32_t), s));   // rays skipped by a stop request read as "not finished"
+  unsigned int *work = c->dWork + c->workNext;
+  c->workNext = (c->workNext + 1) % qa_ctx::kCounterRing;
+  HIP_TRY(hipMemsetAsync(work, 0, sizeof(unsigned int), s));
+
+  RenderParams rp;
+  memset(&rp, 0, sizeof(rp));
+  rp.spp_min = rp.spp_max = p.spp;
+  rp.max_bounce = p.max_bounce;
+  rp.seed = p.seed;
+  rp.tile_row_step = 1;
+  rp.sync_samples = c->syncSamples < 0 ? c->plan.syncAuto : c->syncSamples;
+  rp.rgb = rgb; rp.depth = t; rp.ns = ns;
+  rp.work_counter = work;
+  rp.stop_flag = c->dStopAlias;
+  rp.counters = c->dCounters;
+  rp.num_chunks = 1;
+
+  const Integrator &mega = c->integ[kMega];   // the frames' LDS layout and stack depth (the tile lists' room stays unused)
+  DScene ds = c->ds;
+  ds.stackDepth = mega.stackDepth;
+  ds.walkZeroTerms = c->optWalkZeroTerms;
+  ds.lastCast = 0;
+  ds.lastCastGlow = c->plan.lastCastGlow;
+
+  const RaysFn fn = PickRays(c);
+  // persistent grid of what is resident at once, at most 8 workgroups per CU: the area-light log is sized for that (EnsurePlanSlab)
+  const long long needBlocks = (long long) ((n + QA_BLOCK - 1) / QA_BLOCK);
+  const long long blocks = std::max<long long>(1, std::min<long long>(needBlocks, (long long) c->numCUs * OccupancyBlocks((KernelFn) fn, mega.ldsBytes)));
+
+  EventPair ev;
+  if (!c->freeEvents.empty()) { ev = c->freeEvents.back(); c->freeEvents.pop_back(); }
+  else { HIP_TRY(hipEventCreate(&ev.a)); HIP_TRY(hipEventCreate(&ev.b)); }
+  HIP_TRY(hipEventRecord(ev.a, s));
+  hipLaunchKernelGGL(fn, dim3((unsigned) blocks), dim3(QA_BLOCK), (unsigned) mega.ldsBytes, s, ds, rp, rb);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(c->lastFrame.Record(s));
+  HIP_TRY(hipEventRecord(ev.b, s));
+  c->pending.push_back(ev);
+  c->launches++;
+  if (c->pending.size() > 256) return DrainEvents(c);
+  return QA_OK;
+}
+
+extern "C" {
+
+int qa_radiance_params_default(qa_radiance_params *params)
+{
+  if (!params) return Fail(QA_EINVAL, "null argument");
+  params->spp = 1;
+  params->max_bounce = 5;
+  params->seed = 0x51A7A7u;
+  params->flags = 0;
+  return QA_OK;
+}
+
+int qa_radiance_rays_device(qa_ctx *c, uint64_t n, const float *d_origins, const float *d_dirs, const float *d_dx, const float *d_dy,
+                            const float *d_screen, const uint32_t *d_stream, const qa_radiance_params *params, float *d_rgb, float *d_t,
+                            uint32_t *d_ns, void *hip_stream)
+{
+  if (int rc = Enter(c)) return rc;
+  if (int rc = RadianceChecks(c, n, d_origins && d_dirs, d_dx != nullptr, d_dy != nullptr, d_screen != nullptr, params, d_rgb != nullptr)) return rc;
+  if (n == 0) return QA_OK;
+  const RayBatch rb = {d_origins, d_dirs, d_dx, d_dy, d_screen, d_stream, (uint32_t) n, params->flags};
+  return Radiance(c, n, rb, *params, d_rgb, d_t, d_ns, StreamOf(c, hip_stream));
+}
+
+int qa_radiance_rays(qa_ctx *c, uint64_t n, const float *origins, const float *dirs, const float *dx, const float *dy, const float *screen,
+                     const uint32_t *stream, const qa_radiance_params *params, float *rgb, float *t, uint32_t *ns)
+{
+  if (int rc = Enter(c)) return rc;
+  if (int rc = RadianceChecks(c, n, origins && dirs, dx != nullptr, dy != nullptr, screen != nullptr, params, rgb != nullptr)) return rc;
+  if (n == 0) return QA_OK;
+  // staging, in floats per ray: [rgb 3 | t 1 | ns 1 | stream 1] then per record [origins 3 | dirs 3 | dx 3 | dy 3 | screen 2]
+  const uint64_t r = n * ((params->flags & QA_RADIANCE_PER_SAMPLE) ? (uint64_t) params->spp : 1ull);
+  DevBuf &stage = StageOf(c);
+  HIP_TRY(stage.Reserve((size_t) (n * 6 + r * 14) * sizeof(float)));
+  float *dRgb = (float *) stage.p, *dT = dRgb + 3 * n;
+  uint32_t *dNs = (uint32_t *) (dT + n), *dStream = dNs + n;
+  float *dO = (float *) (dStream + n), *dD = dO + 3 * r, *dDx = dD + 3 * r, *dDy = dDx + 3 * r, *dScreen = dDy + 3 * r;
+  HIP_TRY(hipMemcpyAsync(dO, origins, r * 12, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(dD, dirs, r * 12, hipMemcpyHostToDevice, c->stream));
+  if (dx) {
+    HIP_TRY(hipMemcpyAsync(dDx, dx, r * 12, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(dDy, dy, r * 12, hipMemcpyHostToDevice, c->stream));
+  }
+  if (screen) HIP_TRY(hipMemcpyAsync(dScreen, screen, r * 8, hipMemcpyHostToDevice, c->stream));
+  if (stream) HIP_TRY(hipMemcpyAsync(dStream, stream, n * 4, hipMemcpyHostToDevice, c->stream));
+  const RayBatch rb = {dO, dD, dx ? dDx : nullptr, dx ? dDy : nullptr, screen ? dScreen : nullptr, stream ? dStream : nullptr, (uint32_t) n, params->flags};
+  if (int rc = Radiance(c, n, rb, *params, dRgb, t ? dT : nullptr, ns ? dNs : nullptr, c->stream)) return rc;
+  HIP_TRY(hipMemcpyAsync(rgb, dRgb, n * 12, hipMemcpyDeviceToHost, c->stream));
+  if (t) HIP_TRY(hipMemcpyAsync(t, dT, n * 4, hipMemcpyDeviceToHost, c->stream));
+  if (ns) HIP_TRY(hipMemcpyAsync(ns, dNs, n * 4, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return DrainEvents(c);   // the batch is complete: fold its event pair into the kernel time
+}
+
+int qa_camera_sample_rays_device(qa_ctx *c, int x0, int y0, int x1, int y1, int first, int count, float *d_origins, float *d_dirs, float *d_dx,
+                                 float *d_dy, float *d_screen, uint32_t *d_stream, void *hip_stream)
+{
+  if (int rc = Enter(c)) return rc;
+  FrameArgs a;   // the region is checked as a frame's is
+  a.x0 = x0; a.y0 = y0; a.x1 = x1; a.y1 = y1;
+  if (int rc = CheckFrame(c, a)) return rc;
+  if (first < 0 || count < 1 || (long long) first + count > 0x7FFFFFFFll) return Fail(QA_EINVAL, "bad sample range");
+  if (!d_origins && !d_dirs && !d_dx && !d_dy && !d_screen && !d_stream) return Fail(QA_EINVAL, "no output");
+  if (c->ds.cam.dof > 0.1f)
+    return Fail(QA_EUNSUPPORTED, "depth of field: the lens draws come from the pixel's stream between a sample's paths; no ray array can carry them");
+  const uint64_t nrec = (uint64_t) (x1 - x0) * (uint64_t) (y1 - y0) * (uint64_t) count;
+  if (nrec > QA_MAX_RAYS) return Fail(QA_EINVAL, "more than 2^31 - 1 rays");
+  if (int rc = EnsureHalton(c, first + count)) return rc;
+  const hipStream_t s = StreamOf(c, hip_stream);
+  HIP_TRY(c->lastFrame.WaitOn(s));
+  HIP_TRY(c->lastEdit.WaitOn(s));
+  const CamSampleParams cs = {x0, y0, x1, y1, first, count, d_origins, d_dirs, d_dx, d_dy, d_screen, d_stream};
+  hipLaunchKernelGGL(qa_camera_sample_rays, dim3((unsigned) ((nrec + QA_BLOCK - 1) / QA_BLOCK)), dim3(QA_BLOCK), 0, s, c->ds.cam, c->ds.halton, cs);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(c->lastFrame.Record(s));
+  return QA_OK;
+}
+
+}  // extern "C"

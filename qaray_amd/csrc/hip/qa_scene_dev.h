@@ -289,4 +289,17 @@ struct RenderParams {
   uint2 *heap;
 };
 
+// qa_integrate_rays (qa_kernel.h; the opening comment of qa_radiance.hip is the specification): the rays a batch's paths start from,
+// a kernel argument of its own behind RenderParams.  rgb, t and ns of the batch are RenderParams::rgb, depth and ns, indexed by ray.
+// Arrays marked [r] hold one record per ray, or per (ray, sample) at ray * spp + sample with QA_RAYS_PER_SAMPLE
+#define QA_RAYS_PER_SAMPLE 1u         /* = QA_RADIANCE_PER_SAMPLE */
+#define QA_RAYS_MISS_ENVIRONMENT 2u   /* = QA_RADIANCE_MISS_ENVIRONMENT */
+struct RayBatch {
+  const float *o, *d;         // [r][3] origins and directions (used as given)
+  const float *dx, *dy;       // [r][3] differential directions: both or neither (TEX variants)
+  const float *screen;        // [r][2] where a missed first ray looks the background texmap up, in pixels; optional
+  const uint32_t *stream;     // [n] random-number stream of each ray (qa_pixel_seed's index); optional: the ray's index
+  uint32_t n, flags;
+};
+
 }  // namespace qa

@@ -125,6 +125,30 @@ class DenoiseParams(C.Structure):   # qa_denoise_params; DenoiseParams.default()
 
 
 QA_DENOISE_GUIDE_NORMAL, QA_DENOISE_GUIDE_ALBEDO = 1, 2
+QA_RADIANCE_PER_SAMPLE, QA_RADIANCE_MISS_ENVIRONMENT = 1, 2
+
+
+class RadianceParams(C.Structure):   # qa_radiance_params; RadianceParams.default() = qa_radiance_params_default
+    _fields_ = [("spp", C.c_int), ("max_bounce", C.c_int), ("seed", C.c_uint32), ("flags", C.c_uint32)]
+
+    @classmethod
+    def default(cls):
+        p = cls()
+        _check(lib().qa_radiance_params_default(C.byref(p)))
+        return p
+
+    @classmethod
+    def of(cls, spp=None, max_bounce=None, seed=None, per_sample=False, miss_environment=False):
+        """The library's defaults with the arguments that are given written over them."""
+        p = cls.default()
+        if spp is not None:
+            p.spp = int(spp)
+        if max_bounce is not None:
+            p.max_bounce = int(max_bounce)
+        if seed is not None:
+            p.seed = int(seed) & 0xFFFFFFFF
+        p.flags = (QA_RADIANCE_PER_SAMPLE if per_sample else 0) | (QA_RADIANCE_MISS_ENVIRONMENT if miss_environment else 0)
+        return p
 
 
 class DenoiseGuidedParams(C.Structure):   # qa_denoise_guided_params; .default() = qa_denoise_guided_params_default
@@ -370,6 +394,10 @@ def lib():
         L.qa_occluded_device.argtypes = [C.c_void_p, C.c_uint64] + [C.c_void_p] * 5
         L.qa_occluded.argtypes = [C.c_void_p, C.c_uint64] + [C.c_void_p] * 4
         L.qa_camera_rays_device.argtypes = [C.c_void_p] + [C.c_int] * 4 + [C.c_uint32] + [C.c_void_p] * 3
+        L.qa_radiance_params_default.argtypes = [C.POINTER(RadianceParams)]
+        L.qa_radiance_rays_device.argtypes = [C.c_void_p, C.c_uint64] + [C.c_void_p] * 6 + [C.POINTER(RadianceParams)] + [C.c_void_p] * 4
+        L.qa_radiance_rays.argtypes = [C.c_void_p, C.c_uint64] + [C.c_void_p] * 6 + [C.POINTER(RadianceParams)] + [C.c_void_p] * 3
+        L.qa_camera_sample_rays_device.argtypes = [C.c_void_p] + [C.c_int] * 6 + [C.c_void_p] * 7
         L.qa_scene_edit_camera.argtypes = [C.c_void_p, C.c_void_p]
         for name in ("qa_scene_edit_lights", "qa_scene_edit_materials", "qa_scene_edit_instances"):
             getattr(L, name).argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
@@ -660,6 +688,22 @@ def _ray_arrays(origins, dirs):
     if d.shape != o.shape:
         raise ValueError(f"dirs: shape {o.shape} is expected, not {d.shape}")
     return o, d, n
+
+
+def _radiance_shape(name, t, spp):
+    """(n, per_sample) of the origins of a radiance call: [n, 3], or [n, spp, 3] for rays per sample (torch or numpy)"""
+    if t.ndim == 3 and t.shape[1] == spp and t.shape[2] == 3:
+        n, per_sample = int(t.shape[0]), True
+    elif t.ndim == 2 and t.shape[1] == 3:
+        n, per_sample = int(t.shape[0]), False
+    else:
+        raise ValueError(f"{name}: shape (n, 3) or (n, {spp}, 3) is expected, not {tuple(t.shape)}")
+    if n > QA_MAX_RAYS:
+        raise ValueError(f"{name}: more than 2^31 - 1 rays")
+    return n, per_sample
+
+
+CAMERA_SAMPLE_OUTPUTS = ("origins", "dirs", "dx", "dy", "screen", "stream_ids")   # in the C ABI's order
 
 
 def pick(ctx, x, y, seed=DEFAULT_SEED):
@@ -1200,6 +1244,117 @@ class Context:
         o, d = self.camera_rays_device(region, seed)
         self.synchronize()
         return o.cpu().numpy(), d.cpu().numpy()
+
+    # -- radiance queries (qa_radiance.hip) --------------------------------------------------------
+    def radiance_rays_device(self, origins, dirs, spp=1, max_bounce=5, seed=DEFAULT_SEED, dx=None, dy=None, screen=None, stream_ids=None,
+                             miss_environment=False, rgb=None, t=None, ns=None, stream=None):
+        """qa_radiance_rays_device: n rays of the caller's path-traced by the renderer's integrator, spp samples each.  origins, dirs:
+        float32 contiguous CUDA tensors, [n,3] (every sample of ray q starts from ray q) or [n,spp,3] (rays per sample:
+        QA_RADIANCE_PER_SAMPLE); dirs are used as given (unit length is assumed).  Optional, shaped as origins: dx, dy the
+        differential directions (both or neither; without them textures at the first hit are looked up unfiltered), screen
+        [...,2] where a missed first ray looks a background image up (pixels).  stream_ids: int32 or uint32 [n], the random-number
+        stream of each ray (None: the ray's index).  miss_environment: a missed first ray takes the environment by direction
+        and not the background.  Outputs (given, or allocated): rgb float32 [n,3], t float32 [n] (QA_RAY_MISS on a miss), ns
+        int32 [n] (spp for a finished ray) -> (rgb, t, ns).  Only enqueues (see render_region_device for the stream)."""
+        import torch
+        dev = torch.device("cuda", self.device_id)
+        if not isinstance(origins, torch.Tensor):
+            raise TypeError(f"origins: a torch tensor is expected, not {type(origins).__name__}")
+        spp = int(spp)
+        n, per_sample = _radiance_shape("origins", origins, spp)
+        rec = (n, spp) if per_sample else (n,)
+        _ray_tensor("origins", origins, rec + (3,), torch.float32, dev)
+        _ray_tensor("dirs", dirs, rec + (3,), torch.float32, dev)
+        if (dx is None) != (dy is None):
+            raise ValueError("dx and dy: both or neither")
+        for name, a, last in (("dx", dx, 3), ("dy", dy, 3), ("screen", screen, 2)):
+            if a is not None:
+                _ray_tensor(name, a, rec + (last,), torch.float32, dev)
+        if stream_ids is not None:
+            if isinstance(stream_ids, torch.Tensor) and stream_ids.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)):
+                raise TypeError(f"stream_ids: dtype torch.int32 or torch.uint32 is expected, not {stream_ids.dtype}")
+            _ray_tensor("stream_ids", stream_ids, (n,), getattr(stream_ids, "dtype", None), dev)
+        rgb = torch.empty((n, 3), dtype=torch.float32, device=dev) if rgb is None else rgb
+        t = torch.empty((n,), dtype=torch.float32, device=dev) if t is None else t
+        ns = torch.empty((n,), dtype=torch.int32, device=dev) if ns is None else ns
+        _ray_tensor("rgb", rgb, (n, 3), torch.float32, dev)
+        _ray_tensor("t", t, (n,), torch.float32, dev)
+        _ray_tensor("ns", ns, (n,), torch.int32, dev)
+        p = RadianceParams.of(spp, max_bounce, seed, per_sample, miss_environment)
+        sptr = self._stream_arg(stream, origins)
+        ptr = lambda a: None if a is None else (a.data_ptr() or None)   # noqa: E731
+        _check(lib().qa_radiance_rays_device(self._h, n, ptr(origins), ptr(dirs), ptr(dx), ptr(dy), ptr(screen), ptr(stream_ids), C.byref(p),
+                                             ptr(rgb), ptr(t), ptr(ns), sptr))
+        return rgb, t, ns
+
+    def radiance_rays(self, origins, dirs, spp=1, max_bounce=5, seed=DEFAULT_SEED, dx=None, dy=None, screen=None, stream_ids=None,
+                      miss_environment=False):
+        """qa_radiance_rays: radiance_rays_device from and to host memory.  Arrays as there, converted to float32 (stream_ids to
+        uint32) -> (rgb [n,3] f32, t [n] f32, ns [n] u32) numpy arrays.  Synchronises."""
+        spp = int(spp)
+        o = np.ascontiguousarray(origins, dtype=np.float32)
+        n, per_sample = _radiance_shape("origins", o, spp)
+        rec = (n, spp) if per_sample else (n,)
+        if (dx is None) != (dy is None):
+            raise ValueError("dx and dy: both or neither")
+        arrs = {}
+        for name, a, last in (("dirs", dirs, 3), ("dx", dx, 3), ("dy", dy, 3), ("screen", screen, 2)):
+            if a is None:
+                arrs[name] = None
+                continue
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            if a.shape != rec + (last,):
+                raise ValueError(f"{name}: shape {rec + (last,)} is expected, not {a.shape}")
+            arrs[name] = a
+        if arrs["dirs"] is None:
+            raise TypeError("dirs: an array is expected")
+        sid = None
+        if stream_ids is not None:
+            sid = np.ascontiguousarray(stream_ids, dtype=np.uint32)
+            if sid.shape != (n,):
+                raise ValueError(f"stream_ids: shape ({n},) is expected, not {sid.shape}")
+        rgb, t, ns = np.zeros((n, 3), np.float32), np.zeros(n, np.float32), np.zeros(n, np.uint32)
+        p = RadianceParams.of(spp, max_bounce, seed, per_sample, miss_environment)
+        ptr = lambda a: None if a is None else a.ctypes.data   # noqa: E731
+        _check(lib().qa_radiance_rays(self._h, n, ptr(o), ptr(arrs["dirs"]), ptr(arrs["dx"]), ptr(arrs["dy"]), ptr(arrs["screen"]), ptr(sid),
+                                      C.byref(p), ptr(rgb), ptr(t), ptr(ns)))
+        return rgb, t, ns
+
+    def camera_sample_rays_device(self, region, first=0, count=1, outputs=CAMERA_SAMPLE_OUTPUTS, stream=None, **given):
+        """qa_camera_sample_rays_device: samples [first, first + count) of the camera rays of the pixels of a region, exactly as a
+        frame builds them -> dict name -> CUDA tensor for the names in `outputs` (or the tensors passed by name): origins, dirs, dx,
+        dy float32 [h*w,count,3], screen float32 [h*w,count,2] (the sample's position in pixels), stream_ids int32 [h*w] (y * width + x).
+        radiance_rays_device(**them, spp=count) with first = 0 is render_region_device's frame bit for bit.  A camera with depth of
+        field is refused (HipError, QA_EUNSUPPORTED).  Only enqueues."""
+        import torch
+        dev = torch.device("cuda", self.device_id)
+        x0, y0, x1, y1 = (int(v) for v in region)
+        first, count = int(first), int(count)
+        n = max(x1 - x0, 0) * max(y1 - y0, 0)
+        k = max(count, 0)
+        shapes = {"origins": (n, k, 3), "dirs": (n, k, 3), "dx": (n, k, 3), "dy": (n, k, 3), "screen": (n, k, 2), "stream_ids": (n,)}
+        for name in list(outputs) + list(given):
+            if name not in shapes:
+                raise ValueError(f"unknown output {name!r}: one of {CAMERA_SAMPLE_OUTPUTS}")
+        out = {}
+        for name in CAMERA_SAMPLE_OUTPUTS:
+            dtype = torch.int32 if name == "stream_ids" else torch.float32
+            if given.get(name) is not None:
+                out[name] = _ray_tensor(name, given[name], shapes[name], dtype, dev)
+            elif name in outputs and name not in given:
+                out[name] = torch.empty(shapes[name], dtype=dtype, device=dev)
+        if not out:
+            raise ValueError("no output asked for")
+        sptr = self._stream_arg(stream, next(iter(out.values())))
+        _check(lib().qa_camera_sample_rays_device(self._h, x0, y0, x1, y1, first, count,
+                                                  *((out[name].data_ptr() or None) if name in out else None for name in CAMERA_SAMPLE_OUTPUTS), sptr))
+        return out
+
+    def camera_sample_rays(self, region, first=0, count=1, outputs=CAMERA_SAMPLE_OUTPUTS):
+        """camera_sample_rays_device to host memory -> dict name -> numpy array.  Synchronises."""
+        out = self.camera_sample_rays_device(region, first, count, outputs)
+        self.synchronize()
+        return {k: v.cpu().numpy() for k, v in out.items()}
 
     def render_strips_device(self, region, first_strip, strip_step, spp, rgb, depth, ns, max_bounce=5,
                              seed=DEFAULT_SEED, spp_max=None, stats=False, stream=None):
