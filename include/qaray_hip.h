@@ -601,6 +601,9 @@ int qa_set_pipeline(qa_ctx *ctx, int mode);
  *                    emitters are planes and spheres - a path's last ray asks which emitter it meets (an any-hit sweep in place of the
  *                    closest-hit search, no hit details, no shading); 0: the same kernel runs the closest-hit sweep (same bits, same
  *                    counters; tests and A/B runs)
+ *   "leaf_sweep"     -1 (default) / 1: where "last_cast" applies, the any-hit query of a mesh with a leaf table (an own tree of 2 - 64
+ *                    leaves) tests every leaf box once, all lanes at the same leaf, and then each lane the triangles of its own
+ *                    candidates, instead of walking the tree; 0: it walks the tree (same bits, same counters; tests and A/B runs)
  *   "cs_pool_limit"  n > 0: upper bound for the pool of the cooperative walks (tests: forces the overflow path); 0 = none
  *   "sync_samples"   -1 (default: per scene) / 0 / 1: a wave starts the next samples of its 64 pixels together; n >= 2 (cooperative
  *                    kernel; elsewhere like 1): finished paths wait until n of the wave's have gathered

@@ -534,6 +534,7 @@ int qa_set_option(qa_ctx *c, const char *name, long long value)
   else if (n == "cs_force_exact") c->optCsForceExact = (uint32_t) (value & 3);
   else if (n == "walk_zero_terms") c->optWalkZeroTerms = value ? 1u : 0u;
   else if (n == "last_cast") c->optLastCast = value < 0 ? -1 : (value ? 1 : 0);
+  else if (n == "leaf_sweep") c->optLeafSweep = value < 0 ? -1 : (value ? 1 : 0);
   else if (n == "chunk_spp") c->optChunkSpp = value < 0 ? -1 : (int) (value > 65535 ? 65535 : value);
   else if (n == "chunk_tail") c->optChunkTail = value < 0 ? 0 : (int) (value > 65535 ? 65535 : value);
   else if (n == "tile_lists") c->optTileLists = value < 0 ? -1 : (int) (value > QA_TILE_LEAF_CAP ? QA_TILE_LEAF_CAP : value);

@@ -210,6 +210,7 @@ struct qa_ctx {
   bool optCoop = true;          // "coop": cooperative mesh walks (qa_kernel_cs.h) where the scene allows them
   bool optCsCull = true;        // "cs_cull": instance culling in the cooperative kernel's sweeps (0: every instance is visited; A/B tests)
   int optLastCast = -1;           // "last_cast": -1 / 1 the bounce rays of qa_integrate_lastcast ask which emitter they meet, 0 they run the closest-hit sweep (same kernel, same frame)
+  int optLeafSweep = -1;          // "leaf_sweep": -1 / 1 those queries sweep a mesh's leaf table where it has one (DScene::lastCast = 2; qa_kernel.h sweepLeaves), 0 they walk its own tree (same frame)
   uint32_t optWalkZeroTerms = 0; // "walk_zero_terms": tests - also walk the shadow rays of lights whose term is zero whatever they find
   uint32_t optCsForceExact = 0; // "cs_force_exact": tests of the exact walks (bit 0 closest-hit, bit 1 shadow queries)
   uint32_t optCsPool = 0;       // "cs_pool_limit": upper bound for the walks' pool capacity (tests force the overflow path)

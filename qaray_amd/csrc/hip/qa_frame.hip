@@ -197,7 +197,7 @@ int LaunchSetup(qa_ctx *c, Launch &L, const FrameArgs &a, int ownRows, unsigned 
   ds.csCullOn = (c->optCsCull && c->plan.csCullOk) ? 1u : 0u;
   ds.csForceExact = c->optCsForceExact;
   ds.walkZeroTerms = c->optWalkZeroTerms;
-  ds.lastCast = (LastCastVariant(c) && c->optLastCast != 0) ? 1u : 0u;
+  ds.lastCast = (LastCastVariant(c) && c->optLastCast != 0) ? (c->optLeafSweep != 0 ? 2u : 1u) : 0u;   // (2: with the leaf sweep; inert where the query is off)
   ds.lastCastGlow = c->plan.lastCastGlow;
   ds.csPoolLimit = DevEnv("QA_CS_POOL") ? (uint32_t) std::max(64, atoi(DevEnv("QA_CS_POOL"))) : c->optCsPool;
 

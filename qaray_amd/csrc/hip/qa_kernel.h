@@ -1021,10 +1021,81 @@ __device__ __forceinline__ float shadow(const SceneMem<RES> mem, const DScene &s
 // A lane whose found triangle's leaf fails the strict test at the limit, which saw a triangle at exactly the limit or whose mesh has
 // no own tree answers "ask again": it repeats the ray as the closest-hit sweep and shading of every other variant.
 // ---------------------------------------------------------------------------------------------
+// A/B switch (profiles/leaf_sweep_cost.txt): make hip EXTRA="-DQA_LEAF_SWEEP=0"
+#ifndef QA_LEAF_SWEEP
+#define QA_LEAF_SWEEP 1   /* 0: the bounce rays' any-hit query walks the own tree whatever DScene::lastCast says */
+#endif
+#ifndef QA_LEAF_SWEEP_SORTED
+#define QA_LEAF_SWEEP_SORTED 1   /* 0: a lane takes its candidates in the leaf table's order, not largest box first (the copy behind the table) */
+#endif
+
+// Box phase of sweepLeaves: leaves j0 .. j1 - 1 (at most 32) of a leaf table -> bit j - j0 = this lane's ray passes the test that
+// walkBVH<true> applies to a child's box when it visits the parent (the same operands, the same form), against `limit`.  `rec`: the
+// table through the constant address space (no kernel writes it) at a wave-uniform index: scalar loads, the boxes arrive in SGPRs.
+typedef const __attribute__((address_space(4))) uint32_t *QaLeafPtr;
+__device__ __forceinline__ uint32_t sweepLeafBoxes(QaLeafPtr rec, uint32_t j0, uint32_t j1, const Ray &ray, f3 pLo, f3 pHi, f3 drcp, bool fastSlab, float limit)
+{
+  uint32_t mask = 0;
+#pragma unroll 4   // (several records per wait)
+  for (uint32_t j = j0; j < j1; ++j) {
+    QaLeafPtr r = rec + 8 * (size_t) j;   // DNode
+    const f3 bmin = F3(asF(r[0]), asF(r[1]), asF(r[2])), bmax = F3(asF(r[3]), asF(r[4]), asF(r[5]));
+    float entry, exit_;
+    if (fastSlab) {
+#if QA_FMA_SLAB
+      boxEntryExitPadFma(pLo, pHi, drcp, bmin, bmax, entry, exit_);
+#else
+      boxEntryExitPadFast(pLo, pHi, drcp, bmin, bmax, entry, exit_);
+#endif
+    } else boxEntryExitPad(pLo, pHi, ray.d, drcp, bmin, bmax, entry, exit_);
+    mask |= (entry <= limit && entry <= exit_) ? (1u << (j - j0)) : 0u;
+  }
+  return mask;
+}
+
+// The any-hit query of walkBVH<true, ..., FMA>(closest = false) on a mesh whose own tree has a leaf table (DMesh::resLeaves; 2 ..
+// QA_TILE_LEAF_CAP leaves), without the tree: every leaf's box is tested once, all lanes at the same leaf (no stack, no near / far
+// choice - an any-hit query at a fixed limit gains nothing from the nearer box first), then each lane tests the triangles of its
+// own candidates, in the table's order, until one is accepted (the host hands in the copy of the table that is sorted largest box
+// first: an any-hit query wants the likeliest blocker first, and it is the walls that block most rays).  The walk reaches a leaf only after this test on this box has
+// passed, so its leaves are among the candidates; what an extra candidate can add is a triangle the reference's own test accepts
+// below the limit, and the caller asks refReaches about the found triangle as it does for the walk's.
+// `table`: global memory, wave-uniform; `ftris`: DMesh::ftris in LDS.  hz: the limit, the accepted distance on return.
+__device__ __forceinline__ bool sweepLeaves(const uint4 *table, uint32_t numLeaves, const uint4 *ftris, const Ray &ray, f3 drcp, bool fastSlab,
+                                            float &hz, uint32_t &best, bool &tie, float pad)
+{
+  f3 pLo = ray.p + F3(pad, pad, pad), pHi = ray.p - F3(pad, pad, pad);
+  if (QA_FMA_SLAB && fastSlab) { pLo = slabRayTerm(pLo, drcp); pHi = slabRayTerm(pHi, drcp); }
+  QaLeafPtr rec = (QaLeafPtr) table;
+  const uint32_t n0 = numLeaves < 32u ? numLeaves : 32u;
+  uint32_t lo = sweepLeafBoxes(rec, 0, n0, ray, pLo, pHi, drcp, fastSlab, hz), hi = 0;
+  if (numLeaves > 32u) hi = sweepLeafBoxes(rec, 32, numLeaves, ray, pLo, pHi, drcp, fastSlab, hz);
+  typedef const __attribute__((address_space(1))) uint32_t *WordPtr;
+  WordPtr words = (WordPtr) table;
+  while (lo | hi) {
+    uint32_t j;
+    if (lo) { j = (uint32_t) __ffs((int) lo) - 1u; lo &= lo - 1u; }
+    else { j = 31u + (uint32_t) __ffs((int) hi); hi &= hi - 1u; }
+    const uint32_t word = words[8 * (size_t) j + 6];   // DNode::data of the lane's own leaf
+    const uint32_t count = ((word >> QA_BVH_COUNT_SHIFT) & QA_BVH_COUNT_MASK) + 1;
+    const uint32_t first = word & QA_BVH_OFFSET_MASK;
+    for (uint32_t i = 0; i < count; ++i) {
+      const uint4 *t = ftris + 3 * (size_t) (first + i);
+      const uint4 t2 = t[2];
+      if (hitTriangleZTie<true>(t[0], t[1], t2, ray, hz, tie)) {
+        best = t2.w >> 2;   // element | reference leaf << 15 (DMesh::ftris)
+        return true;
+      }
+    }
+  }
+  return false;
+}
+
 // One mesh: is there a triangle nearer than `limit`?  `again`: the answer is not known to be the reference's.
+// leafTable: where the mesh has a leaf table, sweep it instead of walking the own tree (DScene::lastCast = 2; null: walk)
 template <bool RES>
 __device__ __forceinline__ bool blocksMesh(const SceneMem<RES> mem, const DMesh &m, const Ray &ray, float limit, uint32_t *stack,
-                                           DCounters &cnt, bool &again)
+                                           DCounters &cnt, bool &again, const uint4 *leafTable = nullptr)
 {
   const f3 drcp = F3(1.f / ray.d.x, 1.f / ray.d.y, 1.f / ray.d.z);
   const bool fastSlab = !__any(qabs(ray.d.x) < 1e-7f || qabs(ray.d.y) < 1e-7f || qabs(ray.d.z) < 1e-7f);
@@ -1051,7 +1122,16 @@ __device__ __forceinline__ bool blocksMesh(const SceneMem<RES> mem, const DMesh 
   float hz = limit;
   uint32_t bestF = 0;
   bool tie = false;
-  const bool hit = walkBVH<true, false, false, QA_BLOCK, QA_FMA_SLAB != 0>(fnodes, ftris, m.frootData, ray, drcp, fastSlab, hz, false, stack, cnt, bestF, tie, pad);
+  bool hit;
+#if QA_LEAF_SWEEP
+  // (a tree that is a single leaf is walked without a box test; numLeaves is 0 for a mesh without a table, and wave-uniform)
+  const uint32_t numLeaves = __builtin_amdgcn_readfirstlane(m.numLeaves);
+  if (leafTable && numLeaves >= 2 && numLeaves <= QA_TILE_LEAF_CAP)
+    hit = sweepLeaves(leafTable + __builtin_amdgcn_readfirstlane(m.resLeaves) + (QA_LEAF_SWEEP_SORTED ? 2 * (size_t) numLeaves : 0), numLeaves, ftris, ray,
+                      drcp, fastSlab, hz, bestF, tie, pad);
+  else
+#endif
+  hit = walkBVH<true, false, false, QA_BLOCK, QA_FMA_SLAB != 0>(fnodes, ftris, m.frootData, ray, drcp, fastSlab, hz, false, stack, cnt, bestF, tie, pad);
   if (tie) {
     again = true;
     return false;
@@ -1161,7 +1241,7 @@ __device__ __forceinline__ bool lastCastQuery(const SceneMem<RES> mem, const DSc
       else if (type == QA_OBJ_PLANE) blocked = hitPlane(r, b, k, false);
       else {
         QA_T(tm0)
-        blocked = blocksMesh<RES>(mem, meshAt<RES>(sc, instAt<RES>(sc, k).mesh), r, limit, stack, cnt, again);
+        blocked = blocksMesh<RES>(mem, meshAt<RES>(sc, instAt<RES>(sc, k).mesh), r, limit, stack, cnt, again, sc.lastCast == 2u ? sc.resident : nullptr);
         QA_TACC(cnt.sl[22], tm0)
       }
     }

@@ -288,6 +288,15 @@ struct MeshBuild {
     for (size_t i = 1; i < fb.nodes.size() && m.num_faces > 0; ++i)
       if (fb.nodes[i].data & QA_BVH_LEAF_BIT) t.leaves.push_back(fb.nodes[i]);
     if (t.leaves.size() > QA_TILE_LEAF_CAP || m.num_faces > QA_TILE_ENTRY_FACES) t.leaves.clear();
+    // ... and once more by descending half-area of the box (the table's order among equals), for the any-hit queries of bounce rays
+    // that sweep the table (qa_kernel.h sweepLeaves): such a query wants the likeliest blocker first, and large walls block most rays
+    // (profiles/leaf_sweep_cost.txt).  A table of its own: the list builder's order, and with it the tile lists, stay what they are
+    t.sweepLeaves = t.leaves;
+    auto halfArea = [](const DNode &n) {
+      const float dx = n.box[3] - n.box[0], dy = n.box[4] - n.box[1], dz = n.box[5] - n.box[2];
+      return (dx * dy + dy * dz) + dz * dx;
+    };
+    std::stable_sort(t.sweepLeaves.begin(), t.sweepLeaves.end(), [&](const DNode &a, const DNode &b) { return halfArea(a) > halfArea(b); });
     return fb.depth;
   }
 
@@ -604,12 +613,14 @@ void BuildImage(SceneTables &out)
     dm.numNormals = (uint32_t) (mt.normals.size() / 4);
   }
   out.ds.resMaterials = append(out.materials.data(), out.materials.size() * sizeof(DMaterial));
-  // what follows stays in global memory: the leaf tables are read once per work item (qa_integrate, section A)
+  // what follows stays in global memory: the leaf tables are read once per work item (qa_integrate, section A), their sorted copies by
+  // scalar loads, once per bounce ray's query of the mesh (qa_kernel.h sweepLeaves)
   out.imageLdsVec4 = image.size();
   for (size_t mi = 0; mi < out.mesh.size(); ++mi) {
     DMesh &dm = out.plan.meshes[mi];
     dm.numLeaves = dm.useFast ? (uint32_t) out.mesh[mi].leaves.size() : 0u;
     dm.resLeaves = dm.numLeaves ? append(out.mesh[mi].leaves.data(), out.mesh[mi].leaves.size() * sizeof(DNode)) : 0u;
+    if (dm.numLeaves) append(out.mesh[mi].sweepLeaves.data(), out.mesh[mi].sweepLeaves.size() * sizeof(DNode));   // at resLeaves + 2 * numLeaves
   }
 }
 

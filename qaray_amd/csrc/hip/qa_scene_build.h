@@ -33,6 +33,7 @@ struct MeshTables {
   std::vector<DTriShade> shade;
   std::vector<uint32_t> fmap;
   std::vector<DNode> leaves;             // the own tree's leaves (qa_tilecull.h); empty beyond QA_TILE_LEAF_CAP
+  std::vector<DNode> sweepLeaves;        // the same records, largest box first: the order in which a last-cast query takes its candidates (qa_kernel.h sweepLeaves)
   std::vector<float> vt;                 // 6 floats per element (textured scenes)
   std::vector<float> normals;            // distinct face normals, 4 floats each (resident image)
   WideBvh wide;                          // qa_widebvh.h

@@ -125,7 +125,7 @@ struct DMesh {
   uint32_t csRootWord;         // root of this mesh's 4-wide tree inside the scene-wide arrays DScene::csNodes / csTris (qa_kernel_cs.h)
   // leaf table of the own tree (qa_tilecull.h): numLeaves DNode records (a leaf's stored box and its leaf word) at
   // DScene::resident + resLeaves, behind the part of the image that is copied into LDS; 0 = none (no own tree, or more than
-  // QA_TILE_LEAF_CAP leaves)
+  // QA_TILE_LEAF_CAP leaves); behind it, at resLeaves + 2 * numLeaves, the same records once more, largest box first (qa_kernel.h sweepLeaves)
   uint32_t resLeaves;
   uint32_t numLeaves;
   uint32_t leafPad;
@@ -223,7 +223,8 @@ struct DScene {
   DMesh meshv[QA_KARG_MESH];
   // qa_integrate_lastcast (qa_kernel.h lastCastQuery; ScenePlan::lastCastQuery), behind the tables so that no other field moves:
   // lastCast = 1: a bounce ray asks only which emitter it meets (option "last_cast"; 0: the closest-hit sweep and shading of every
-  // other variant); lastCastGlow: bit k = node k is a plane or sphere with an emitting material (the only emitters of such a scene)
+  // other variant), 2: and where a mesh has a leaf table its query sweeps the table instead of walking the own tree (option "leaf_sweep";
+  // qa_kernel.h sweepLeaves); lastCastGlow: bit k = node k is a plane or sphere with an emitting material (the only emitters of such a scene)
   uint32_t lastCast, lastCastGlow;
 };
 
