@@ -606,7 +606,8 @@ int qa_set_pipeline(qa_ctx *ctx, int mode);
  *                    candidates, instead of walking the tree; 0: it walks the tree (same bits, same counters; tests and A/B runs)
  *   "cs_pool_limit"  n > 0: upper bound for the pool of the cooperative walks (tests: forces the overflow path); 0 = none
  *   "sync_samples"   -1 (default: per scene) / 0 / 1: a wave starts the next samples of its 64 pixels together; n >= 2 (cooperative
- *                    kernel; elsewhere like 1): finished paths wait until n of the wave's have gathered
+ *                    kernel; elsewhere like 1): finished paths wait until n of the wave's have gathered.  Taken without effect where
+ *                    "last_cast" applies: that kernel runs one whole sample of every lane per turn of its loop
  *   "chunk_spp"      -1 (default: per frame) / 0 / n: the per-lane kernels hand a tile's samples out in chunks - n samples first, then
  *   "chunk_tail"     chunks of this many (0: an eighth of the frame's spp) - so that a frame of few tiles per wave ends on small work
  *                    items; a pixel's state waits in device memory between chunks (same samples in the same order: same bits)

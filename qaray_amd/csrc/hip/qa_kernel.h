@@ -1513,7 +1513,8 @@ __device__ __forceinline__ Surface shadeSurfaceTexFirst(const uint4 *mtlTable, c
 }
 
 // (S: anything with the material -> texmap table `mtlTex`: DScene, or the few words an out-of-line caller hands over)
-template <bool TEX, class S = DScene>
+// (LOBES = false: the caller knows that no material has QA_MTL_SPECULAR_LOBES - PlanLastCast - and the Fresnel and lobe code goes)
+template <bool TEX, class S = DScene, bool LOBES = true>
 __device__ __forceinline__ Surface shadeSurface(const uint4 *mtlTable, const S &sc, const TexTables &tt, int mi, f3 N,
                                                 f3 V, bool front, const TexHit &th, int bounceLeft, bool fromDiffuse,
                                                 uint32_t &rng)
@@ -1542,7 +1543,7 @@ __device__ __forceinline__ Surface shadeSurface(const uint4 *mtlTable, const S &
     f3 sampleTransmission = F3(0, 0, 0), sampleReflection = F3(0, 0, 0);
     f3 tDir = F3(0, 0, 0), rDir = F3(0, 0, 0);
     float glossRefl = 0.f, glossRefr = 0.f;
-    if (mflags & QA_MTL_SPECULAR_LOBES) {
+    if (LOBES && (mflags & QA_MTL_SPECULAR_LOBES)) {
       const uint4 m3 = mr[3], m4 = mr[4];
       f3 rK = F3(asF(m3.x), asF(m3.y), asF(m3.z)), tK = F3(asF(m4.x), asF(m4.y), asF(m4.z));
       if (TEX) {
@@ -1745,6 +1746,15 @@ struct Path {
 #define QA_C2_EXTRA_WAVE 1   /* 0: four waves per SIMD for that variant too - spill-free and 6 % slower (profiles/round02/c2_register_variants.txt) */
 #endif
 #define QA_WAVES_FOR(RES, LIGHTS) (((RES) && !(LIGHTS)) ? QA_MIN_WAVES + QA_C2_EXTRA_WAVE : QA_MIN_WAVES)
+// qa_integrate_lastcast has a macro of its own: four against five waves per SIMD were measured again on its straight-line body
+// (profiles/lastcast_straight_cost.txt); -DQA_LASTCAST_WAVES=4 for the A/B
+#ifndef QA_LASTCAST_WAVES
+#define QA_LASTCAST_WAVES (QA_MIN_WAVES + QA_C2_EXTRA_WAVE)
+#endif
+// A/B switch: make hip EXTRA="-DQA_LASTCAST_STRAIGHT=0" compiles qa_integrate_lastcast from qa_kernel_body.h, as before
+#ifndef QA_LASTCAST_STRAIGHT
+#define QA_LASTCAST_STRAIGHT 1
+#endif
 
 template <bool RES, bool LIGHTS, bool TEX, bool AREA, bool STATS, bool PHOTON = false>
 __global__ __launch_bounds__(QA_BLOCK, QA_WAVES_FOR(RES, LIGHTS)) void qa_integrate(const DScene sc, const RenderParams rp)
@@ -1756,14 +1766,19 @@ __global__ __launch_bounds__(QA_BLOCK, QA_WAVES_FOR(RES, LIGHTS)) void qa_integr
 
 // qa_integrate<RES, LIGHTS=0, TEX=0, AREA=0> for scenes whose plan has lastCastQuery (qa_frame.hip SelectKernel; kernel_name():
 // "qa_integrate<RES=1,LIGHTS=0,TEX=0,AREA=0,LASTCAST=1>").  A kernel of its own name, so that every qa_integrate instance keeps its own.
+// Its paths are camera ray, diffuse hit, one bounce ray: one turn of the loop per sample (qa_kernel_lastcast_body.h).
 template <bool RES>
-__global__ __launch_bounds__(QA_BLOCK, QA_WAVES_FOR(RES, false)) void qa_integrate_lastcast(const DScene sc, const RenderParams rp)
+__global__ __launch_bounds__(QA_BLOCK, QA_LASTCAST_WAVES) void qa_integrate_lastcast(const DScene sc, const RenderParams rp)
 {
+#if QA_LASTCAST_STRAIGHT
+#include "qa_kernel_lastcast_body.h"
+#else
   constexpr bool LIGHTS = false, TEX = false, AREA = false, STATS = false, PHOTON = false;
   constexpr bool LASTQ = true;   // its bounce rays go through lastCastQuery
   constexpr bool RAYS = false;
   const RayBatch rb = {};
 #include "qa_kernel_body.h"
+#endif
 }
 
 // qa_integrate<RES, LIGHTS, TEX, AREA> whose paths start from rays of the caller's (qa_radiance_rays*; the opening comment of
