@@ -2,7 +2,8 @@
 // rendered from the camera as it now stands, so that a camera move keeps the samples of every surface point both cameras see.  No
 // reference counterpart: the reference renders every frame from nothing.  Every function here is compiled for the host too:
 // qa_test_reproject_host and the kernel of qa_reproject.hip run the same source (tests/test_gpu_reproject.py: equal bit for bit);
-// tests/reproject_util.py restates THIS COMMENT in float64 numpy.
+// tests/reproject_util.py restates THIS COMMENT in float64 numpy.  The steps below are this header's functions; the pixel that
+// runs them, for this form and the two that extend it, is reprojectPixel<FORM> of qa_reproject_moments_dev.h (this form: FORM 0).
 //
 // SPECIFICATION.  All arithmetic is fp32 in the order written, without contraction; / and sqrtf are correctly rounded.  Vector
 // operations are those of qa_device_math.h: dot(a, b) = a.x*b.x + a.y*b.y + a.z*b.z summed left to right, cross as glm's,
@@ -172,41 +173,6 @@ __host__ __device__ __forceinline__ float reprojectAccumulate(const ReprojectSet
     out[e] = diff == 0.f ? c[e] : ch[e] + diff * k;
   }
   return L + n;
-}
-
-// Pixel (tx, ty) of the region.  cur(tx, ty) -> ReprojectPixel; tap(i, j, t) fetches a history pixel, and ids(which, i, j, out)
-// the two id words of the current (which = 0) or the history (1) frame, all called for pixels inside the region only; withIds:
-// both ids planes are given.  -> out[3] and the new length
-template <class Cur, class Tap, class Ids>
-__host__ __device__ __forceinline__ float reprojectPixel(const ReprojectSetup &S, const Cur &cur, const Tap &tap, const Ids &ids, bool withIds, int tx, int ty,
-                                                         float *out)
-{
-  const ReprojectPixel p = cur(tx, ty);
-  out[0] = p.r; out[1] = p.g; out[2] = p.b;
-  if (p.ns == 0u || !reprojectFinite(p.r) || !reprojectFinite(p.g) || !reprojectFinite(p.b) || !reprojectFinite(p.z)) return 0.f;
-  const float n = (float) p.ns;
-  const bool miss = p.z == QA_REPROJECT_MISS;
-  float ul, vl, zh;
-  if (S.still) {
-    ul = (float) tx; vl = (float) ty; zh = p.z;
-  } else {
-    const float fpx = (float) (S.x0 + tx), fpy = (float) (S.y0 + ty);
-    const f3 cpt = (S.A1 + S.U1 * fpx) + S.V1 * fpy;
-    const f3 d = normalize(cpt - S.pos1);
-    f3 w = d;
-    if (!miss) {
-      const f3 P = S.pos1 + d * p.z;
-      w = P - S.pos0;
-    }
-    if (!reprojectProject(S, w, miss, ul, vl, zh)) return n;
-  }
-  int cid[2] = {0, 0};
-  if (withIds) ids(0, tx, ty, cid);
-  float sc[3], sl;
-  const float sw = reprojectTaps(S, tap, ids, withIds, cid, miss, ul, vl, zh, sc, sl);
-  if (sw < QA_REPROJECT_MIN_WEIGHT) return n;
-  const float ch[3] = {sc[0] / sw, sc[1] / sw, sc[2] / sw};
-  return reprojectAccumulate(S, p, n, ch, sw, sl, out);
 }
 
 }  // namespace qa

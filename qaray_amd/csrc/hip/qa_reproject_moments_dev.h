@@ -1,6 +1,6 @@
 // qa_reproject_moments_dev.h — temporal reprojection that carries luminance moments and shortens clamped history: the form of
 // qa_reproject_motion_dev.h with two more additions, each behind a flag.  No reference counterpart.  Every function here is compiled
-// for the host too: qa_test_reproject_moments_host and the kernel qa_reproject_moments of qa_reproject.hip run the same source
+// for the host too: qa_test_reproject_moments_host and the kernel qa_reproject_k<2> of qa_reproject.hip run the same source
 // (tests/test_gpu_reproject_moments.py: equal bit for bit); tests/reproject_moments_util.py restates THIS COMMENT in float64 numpy.
 //
 // SPECIFICATION.  Steps 1 - 6, 2', 4' and 5', the arithmetic rules (fp32 in the order written, no contraction, correctly rounded /
@@ -82,73 +82,98 @@ struct ReprojectMomentTap {
   }
 };
 
-// reprojectMotionPixel of qa_reproject_motion_dev.h with steps 5'', 6', 5m and 6m.  cur, tap, ids and win as there; mom(x, y, h)
-// fetches a history pixel's two moments, called only with withMoments: QA_REPROJECT_MOMENTS is set and the plane is given.  -> out[3],
-// om[2], var (which the caller stores with QA_REPROJECT_MOMENTS only) and the new length
-template <class Cur, class Tap, class Mom, class Ids, class Win>
-__host__ __device__ __forceinline__ float reprojectMomentsPixel(const ReprojectSetup &S, const ReprojectMotionSetup &M, const ReprojectMomentsSetup &X,
-                                                                const Cur &cur, const Tap &tap, const Mom &mom, const Ids &ids, const Win &win, bool withIds,
-                                                                bool withMoments, int tx, int ty, float *out, float *om, float &var)
+// Steps 5' and 5'' on c_h[3]: the clamp of reprojectClamp, and -> b of what it moved (0 where it moved nothing)
+template <class Win>
+__host__ __device__ __forceinline__ float reprojectClampShorten(const ReprojectMotionSetup &M, const ReprojectMomentsSetup &X, const Win &win, uint32_t cls,
+                                                                int tx, int ty, float *ch)
+{
+  float lo[3], hi[3], g[3];
+  if (!reprojectClampBox(M, win, cls, tx, ty, lo, hi, g)) return 0.f;
+  float d = 0.f, s = 0.f;
+#pragma unroll
+  for (int e = 0; e < 3; ++e) {
+    const float before = ch[e];
+    ch[e] = before < lo[e] ? lo[e] : (before > hi[e] ? hi[e] : before);
+    const float x = qabs(before - ch[e]);
+    if (x > d) d = x;
+    if (g[e] > s) s = g[e];
+  }
+  const float b = X.shortenRate * d / (s + QA_REPROJECT_SHORTEN_FLOOR);
+  return b > 0.f ? b : 0.f;
+}
+
+// THE PIXEL OF ALL THREE FORMS.  FORM is the rank of the form the caller's entry belongs to, a compile-time fact: 0 the plain form of
+// qa_reproject_dev.h, 1 with steps 2', 4' and 5' of qa_reproject_motion_dev.h, 2 with steps 5'', 6', 5m and 6m of this header.  What
+// a lower rank does not have is not compiled into it: it reads neither M, X, mom, win, om nor var (rank 0), or neither X, mom, om
+// nor var (rank 1), whatever their types, and a flag of a higher rank in M.flags means nothing to it.
+// Pixel (tx, ty) of the region.  cur(tx, ty) -> ReprojectPixel; tap(i, j, t) fetches a history pixel, and ids(which, i, j, out)
+// the two id words of the current (which = 0) or the history (1) frame, all called for pixels inside the region only; withIds:
+// both ids planes are given.  win(x, y) -> ReprojectWin as for reprojectClamp (called with QA_REPROJECT_CLAMP only); mom(x, y, h)
+// fetches a history pixel's two moments, called only with withMoments: QA_REPROJECT_MOMENTS is set and the plane is given.
+// -> out[3] and the new length; in rank 2 also om[2] and var, which the caller stores with QA_REPROJECT_MOMENTS only
+template <int FORM, class Cur, class Tap, class Mom, class Ids, class Win>
+__host__ __device__ __forceinline__ float reprojectPixel(const ReprojectSetup &S, const ReprojectMotionSetup &M, const ReprojectMomentsSetup &X, const Cur &cur,
+                                                         const Tap &tap, const Mom &mom, const Ids &ids, const Win &win, bool withIds, bool withMoments, int tx,
+                                                         int ty, float *out, float *om, float &var)
 {
   const ReprojectPixel p = cur(tx, ty);
   out[0] = p.r; out[1] = p.g; out[2] = p.b;
-  om[0] = 0.f; om[1] = 0.f; var = -1.f;
+  if constexpr (FORM >= 2) {
+    om[0] = 0.f; om[1] = 0.f; var = -1.f;
+  }
   if (p.ns == 0u || !reprojectFinite(p.r) || !reprojectFinite(p.g) || !reprojectFinite(p.b) || !reprojectFinite(p.z)) return 0.f;
   const float n = (float) p.ns;
   const bool miss = p.z == QA_REPROJECT_MISS;
-  const float l = denoiseLuma(p.r, p.g, p.b);
-  om[0] = l; om[1] = l * l;
+  float l = 0.f;
+  if constexpr (FORM >= 2) {
+    l = denoiseLuma(p.r, p.g, p.b);
+    om[0] = l; om[1] = l * l;
+  }
   int cid[2] = {0, 0};
   if (withIds) ids(0, tx, ty, cid);
+  // steps 2 - 4: those of rank 1 with no node's record to find, which is all rank 0 knows
+  const ReprojectMotionSetup unmoved = {nullptr, 0, 0u, 0, 0.f};
   float ul, vl, zh;
-  if (!reprojectMotionWhere(S, M, p, miss, cid, tx, ty, ul, vl, zh)) return n;
+  if (!reprojectMotionWhere(S, FORM >= 1 ? M : unmoved, p, miss, cid, tx, ty, ul, vl, zh)) return n;
   float sc[3], sl;
   const float sw = reprojectTaps(S, tap, ids, withIds, cid, miss, ul, vl, zh, sc, sl);
   if (sw < QA_REPROJECT_MIN_WEIGHT) return n;
   float ch[3] = {sc[0] / sw, sc[1] / sw, sc[2] / sw};
   float b = 0.f;
-  if (M.flags & QA_REPROJECT_CLAMP) {
-    if (M.flags & QA_REPROJECT_SHORTEN) {
-      float lo[3], hi[3], g[3];
-      if (reprojectClampBox(M, win, miss ? 1u : 2u, tx, ty, lo, hi, g)) {
-        float d = 0.f, s = 0.f;
-#pragma unroll
-        for (int e = 0; e < 3; ++e) {
-          const float before = ch[e];
-          ch[e] = before < lo[e] ? lo[e] : (before > hi[e] ? hi[e] : before);
-          const float x = qabs(before - ch[e]);
-          if (x > d) d = x;
-          if (g[e] > s) s = g[e];
-        }
-        b = X.shortenRate * d / (s + QA_REPROJECT_SHORTEN_FLOOR);
-        if (!(b > 0.f)) b = 0.f;
-      }
-    } else {
-      reprojectClamp(M, win, miss ? 1u : 2u, tx, ty, ch);
+  if constexpr (FORM >= 1) {
+    if (M.flags & QA_REPROJECT_CLAMP) {
+      if (FORM >= 2 && (M.flags & QA_REPROJECT_SHORTEN))
+        b = reprojectClampShorten(M, X, win, miss ? 1u : 2u, tx, ty, ch);
+      else
+        reprojectClamp(M, win, miss ? 1u : 2u, tx, ty, ch);
     }
   }
-  float len;
-  float k;
-  if (M.flags & QA_REPROJECT_SHORTEN) {
-    // step 6 on L' : min(L' / 1, max_history) is L', since L' <= L <= max_history
-    const float L = qmin(sl / sw, S.maxHistory) / (1.f + b);
-    len = reprojectAccumulate(S, p, n, ch, 1.f, L, out);
-    k = n / (L + n);
+  if constexpr (FORM < 2) {
+    return reprojectAccumulate(S, p, n, ch, sw, sl, out);
   } else {
-    len = reprojectAccumulate(S, p, n, ch, sw, sl, out);
-    k = n / (qmin(sl / sw, S.maxHistory) + n);
+    float len;
+    float k;
+    if (M.flags & QA_REPROJECT_SHORTEN) {
+      // step 6 on L' : min(L' / 1, max_history) is L', since L' <= L <= max_history
+      const float L = qmin(sl / sw, S.maxHistory) / (1.f + b);
+      len = reprojectAccumulate(S, p, n, ch, 1.f, L, out);
+      k = n / (L + n);
+    } else {
+      len = reprojectAccumulate(S, p, n, ch, sw, sl, out);
+      k = n / (qmin(sl / sw, S.maxHistory) + n);
+    }
+    if (!withMoments) return len;
+    const ReprojectMomentTap<Tap, Mom> mtap = {tap, mom};
+    float sm[3], sl2;
+    const float sw2 = reprojectTaps(S, mtap, ids, withIds, cid, miss, ul, vl, zh, sm, sl2);   // the same taps count: sw2 has sw's bits
+    if (sm[2] > 0.f || !(sw2 >= QA_REPROJECT_MIN_WEIGHT)) return len;
+    const float h1 = sm[0] / sw2, h2 = sm[1] / sw2;
+    const float o1 = h1 + (l - h1) * k, o2 = h2 + (l * l - h2) * k;
+    om[0] = o1; om[1] = o2;
+    const float v = o2 - o1 * o1;
+    if (len >= X.minFrames * n && reprojectFinite(v)) var = qmax(v, 0.f) * k;
+    return len;
   }
-  if (!withMoments) return len;
-  const ReprojectMomentTap<Tap, Mom> mtap = {tap, mom};
-  float sm[3], sl2;
-  const float sw2 = reprojectTaps(S, mtap, ids, withIds, cid, miss, ul, vl, zh, sm, sl2);   // the same taps count: sw2 has sw's bits
-  if (sm[2] > 0.f || !(sw2 >= QA_REPROJECT_MIN_WEIGHT)) return len;
-  const float h1 = sm[0] / sw2, h2 = sm[1] / sw2;
-  const float o1 = h1 + (l - h1) * k, o2 = h2 + (l * l - h2) * k;
-  om[0] = o1; om[1] = o2;
-  const float v = o2 - o1 * o1;
-  if (len >= X.minFrames * n && reprojectFinite(v)) var = qmax(v, 0.f) * k;
-  return len;
 }
 
 }  // namespace qa

@@ -1,7 +1,8 @@
 // qa_reproject_motion_dev.h — temporal reprojection that follows moved nodes and clamps stale history: the form of
 // qa_reproject_dev.h with two additions, each behind a flag.  No reference counterpart.  Every function here is compiled for the host
-// too: qa_test_reproject_motion_host and the kernel qa_reproject_motion of qa_reproject.hip run the same source
+// too: qa_test_reproject_motion_host and the kernel qa_reproject_k<1> of qa_reproject.hip run the same source
 // (tests/test_gpu_reproject_motion.py: equal bit for bit); tests/reproject_motion_util.py restates THIS COMMENT in float64 numpy.
+// The pixel that runs these steps is reprojectPixel<FORM> of qa_reproject_moments_dev.h (this form: FORM 1).
 //
 // SPECIFICATION.  Steps 1 - 6, the arithmetic rules (fp32 in the order written, no contraction, correctly rounded / and sqrtf), the
 // frames, the classes and the outputs are those of qa_reproject_dev.h; with flags 0 every output has that form's bits.
@@ -154,29 +155,6 @@ __host__ __device__ __forceinline__ bool reprojectMotionWhere(const ReprojectSet
     w = P - S.pos0;
   }
   return reprojectProject(S, w, miss, ul, vl, zh);
-}
-
-// reprojectPixel of qa_reproject_dev.h with steps 2', 4' and 5'.  cur, tap and ids as there; win as for reprojectClamp (called
-// with QA_REPROJECT_CLAMP only).  -> out[3] and the new length
-template <class Cur, class Tap, class Ids, class Win>
-__host__ __device__ __forceinline__ float reprojectMotionPixel(const ReprojectSetup &S, const ReprojectMotionSetup &M, const Cur &cur, const Tap &tap,
-                                                               const Ids &ids, const Win &win, bool withIds, int tx, int ty, float *out)
-{
-  const ReprojectPixel p = cur(tx, ty);
-  out[0] = p.r; out[1] = p.g; out[2] = p.b;
-  if (p.ns == 0u || !reprojectFinite(p.r) || !reprojectFinite(p.g) || !reprojectFinite(p.b) || !reprojectFinite(p.z)) return 0.f;
-  const float n = (float) p.ns;
-  const bool miss = p.z == QA_REPROJECT_MISS;
-  int cid[2] = {0, 0};
-  if (withIds) ids(0, tx, ty, cid);
-  float ul, vl, zh;
-  if (!reprojectMotionWhere(S, M, p, miss, cid, tx, ty, ul, vl, zh)) return n;
-  float sc[3], sl;
-  const float sw = reprojectTaps(S, tap, ids, withIds, cid, miss, ul, vl, zh, sc, sl);
-  if (sw < QA_REPROJECT_MIN_WEIGHT) return n;
-  float ch[3] = {sc[0] / sw, sc[1] / sw, sc[2] / sw};
-  if (M.flags & QA_REPROJECT_CLAMP) reprojectClamp(M, win, miss ? 1u : 2u, tx, ty, ch);
-  return reprojectAccumulate(S, p, n, ch, sw, sl, out);
 }
 
 }  // namespace qa

@@ -201,6 +201,21 @@ class DenoiseVarianceParams(C.Structure):   # qa_denoise_variance_params; .defau
         return p
 
 
+def _reproject_params_of(cls, params, floats, clamp_radius=None, bits=()):
+    """The override logic of the three Reproject*Params.of: a copy of params (or cls.default()) with the floats that are not None
+    written over its fields, clamp_radius likewise, and every (flag bit, bool or None) of bits set, cleared or left."""
+    p = cls.default() if params is None else cls(*(getattr(params, name) for name, _ in cls._fields_))
+    for name, v in floats.items():
+        if v is not None:
+            setattr(p, name, float(v))
+    if clamp_radius is not None:
+        p.clamp_radius = int(clamp_radius)
+    for bit, v in bits:
+        if v is not None:
+            p.flags = (p.flags | bit) if v else (p.flags & ~bit)
+    return p
+
+
 class ReprojectParams(C.Structure):   # qa_reproject_params; ReprojectParams.default() = qa_reproject_params_default
     _fields_ = [("depth_tolerance", C.c_float), ("max_history", C.c_float), ("flags", C.c_uint32)]
 
@@ -213,12 +228,7 @@ class ReprojectParams(C.Structure):   # qa_reproject_params; ReprojectParams.def
     @classmethod
     def of(cls, params=None, depth_tolerance=None, max_history=None):
         """params (a ReprojectParams) or the library's defaults, with the keyword arguments that are given written over them."""
-        p = cls.default() if params is None else cls(params.depth_tolerance, params.max_history, params.flags)
-        if depth_tolerance is not None:
-            p.depth_tolerance = float(depth_tolerance)
-        if max_history is not None:
-            p.max_history = float(max_history)
-        return p
+        return _reproject_params_of(cls, params, dict(depth_tolerance=depth_tolerance, max_history=max_history))
 
 
 QA_REPROJECT_MOTION, QA_REPROJECT_CLAMP = 1, 2
@@ -240,16 +250,8 @@ class ReprojectMotionParams(C.Structure):   # qa_reproject_motion_params; .defau
     def of(cls, params=None, depth_tolerance=None, max_history=None, motion=None, clamp=None, clamp_radius=None, clamp_gamma=None):
         """params (a ReprojectMotionParams) or the library's defaults, with the keyword arguments that are given written over them;
         motion / clamp (bool) set or clear QA_REPROJECT_MOTION / QA_REPROJECT_CLAMP of the flags."""
-        p = cls.default() if params is None else cls(params.depth_tolerance, params.max_history, params.clamp_gamma, params.clamp_radius, params.flags)
-        for name, v in (("depth_tolerance", depth_tolerance), ("max_history", max_history), ("clamp_gamma", clamp_gamma)):
-            if v is not None:
-                setattr(p, name, float(v))
-        if clamp_radius is not None:
-            p.clamp_radius = int(clamp_radius)
-        for bit, v in ((QA_REPROJECT_MOTION, motion), (QA_REPROJECT_CLAMP, clamp)):
-            if v is not None:
-                p.flags = (p.flags | bit) if v else (p.flags & ~bit)
-        return p
+        return _reproject_params_of(cls, params, dict(depth_tolerance=depth_tolerance, max_history=max_history, clamp_gamma=clamp_gamma), clamp_radius,
+                                    ((QA_REPROJECT_MOTION, motion), (QA_REPROJECT_CLAMP, clamp)))
 
 
 QA_REPROJECT_MOMENTS, QA_REPROJECT_SHORTEN = 4, 8
@@ -270,17 +272,10 @@ class ReprojectMomentsParams(C.Structure):   # qa_reproject_moments_params; .def
            shorten=None, min_frames=None, shorten_rate=None):
         """params (a ReprojectMomentsParams) or the library's defaults, with the keyword arguments that are given written over them;
         motion / clamp / moments / shorten (bool) set or clear the four flags."""
-        p = cls.default() if params is None else cls(*(getattr(params, name) for name, _ in cls._fields_))
-        for name, v in (("depth_tolerance", depth_tolerance), ("max_history", max_history), ("clamp_gamma", clamp_gamma), ("min_frames", min_frames),
-                        ("shorten_rate", shorten_rate)):
-            if v is not None:
-                setattr(p, name, float(v))
-        if clamp_radius is not None:
-            p.clamp_radius = int(clamp_radius)
-        for bit, v in ((QA_REPROJECT_MOTION, motion), (QA_REPROJECT_CLAMP, clamp), (QA_REPROJECT_MOMENTS, moments), (QA_REPROJECT_SHORTEN, shorten)):
-            if v is not None:
-                p.flags = (p.flags | bit) if v else (p.flags & ~bit)
-        return p
+        return _reproject_params_of(cls, params, dict(depth_tolerance=depth_tolerance, max_history=max_history, clamp_gamma=clamp_gamma,
+                                                      min_frames=min_frames, shorten_rate=shorten_rate), clamp_radius,
+                                    ((QA_REPROJECT_MOTION, motion), (QA_REPROJECT_CLAMP, clamp), (QA_REPROJECT_MOMENTS, moments),
+                                     (QA_REPROJECT_SHORTEN, shorten)))
 
 
 QA_GBUFFER_BACKFACE = 0x40000000
@@ -496,13 +491,15 @@ def _camera_record(cam):
     return np.array(cam, dtype=CAMERA_DTYPE).reshape(1)
 
 
-def reproject_host(cur, history, prev_cam, cur_cam, origin=(0, 0), ids=None, hist_ids=None, out=None, out_length=None, params=None,
-                   depth_tolerance=None, max_history=None):
-    """qa_test_reproject_host: the temporal reprojection of Context.reproject_device on the CPU, from the source the device kernel is
-    compiled from.  cur = (rgb (h, w, 3) f32, depth (h, w) f32, ns (h, w) u32) rendered from cur_cam; history = (rgb, depth,
-    length (h, w) f32) accumulated under prev_cam; origin: the image pixel (x0, y0) of the frames' first pixel; ids / hist_ids:
-    (h, w, 2) i32, both or neither.  out / out_length: float32 arrays to write (out may be cur's rgb itself) -> (out (h, w, 3),
-    out_length (h, w)).  The other inputs are not modified.  No GPU needed."""
+def _ptr(a):
+    """The address of a numpy array or a torch tensor for a ctypes call; None stays None."""
+    return None if a is None else a.ctypes.data if isinstance(a, np.ndarray) else a.data_ptr()
+
+
+def _reproject_host_planes(cur, history, prev_cam, cur_cam, origin, ids, hist_ids, out, out_length):
+    """What the three reproject*_host calls share: the planes as contiguous arrays of their types and shapes, out / out_length
+    allocated where they are not given -> ((h, w), head, keep, out, out_length): head, the C call's arguments from prev_cam to
+    hist_ids; keep, the arrays behind its pointers, for the caller to hold until the call has returned."""
     rgb, depth, ns = cur
     rgb = rgb if out is rgb and rgb is not None else np.ascontiguousarray(rgb, dtype=np.float32)
     depth = np.ascontiguousarray(depth, dtype=np.float32)
@@ -517,12 +514,70 @@ def reproject_host(cur, history, prev_cam, cur_cam, origin=(0, 0), ids=None, his
     out_length = np.zeros((h, w), np.float32) if out_length is None else out_length
     for a, shape in ((out, (h, w, 3)), (out_length, (h, w))):
         assert a.dtype == np.float32 and a.flags.c_contiguous and a.shape == shape
+    keep = [_camera_record(prev_cam), _camera_record(cur_cam), rgb, depth, ns, idp[0], *hist, idp[1]]
+    head = [_ptr(keep[0]), _ptr(keep[1]), int(origin[0]), int(origin[1]), w, h, *(_ptr(a) for a in keep[2:])]
+    return (h, w), head, keep, out, out_length
+
+
+def _reproject_history_tensors(h, w, device, history, hist_ids, out, out_length):
+    """The history and the outputs of a device reprojection, checked: float32 CUDA tensors [h,w,3], [h,w], [h,w], hist_ids int32
+    [h,w,2] or None; out / out_length allocated where they are not given -> (the four history pointers, out, out_length)."""
+    import torch
+    n = h * w
+    hrgb, hdepth, hlen = history
+    for t, k in ((hrgb, 3), (hdepth, 1), (hlen, 1)):
+        assert t.is_cuda and t.is_contiguous() and t.numel() == k * n and t.dtype == torch.float32
+    assert hist_ids is None or (hist_ids.is_cuda and hist_ids.is_contiguous() and hist_ids.numel() == 2 * n and hist_ids.dtype == torch.int32)
+    if out is None:
+        out = torch.empty((h, w, 3), dtype=torch.float32, device=device)
+    if out_length is None:
+        out_length = torch.empty((h, w), dtype=torch.float32, device=device)
+    assert out.is_cuda and out.is_contiguous() and out.numel() == 3 * n and out.dtype == torch.float32
+    assert out_length.is_cuda and out_length.is_contiguous() and out_length.numel() == n and out_length.dtype == torch.float32
+    return [_ptr(hrgb), _ptr(hdepth), _ptr(hlen), _ptr(hist_ids)], out, out_length
+
+
+def _reproject_device_planes(cur, history, prev_cam, cur_cam, origin, ids, hist_ids, out, out_length):
+    """What the three Context.reproject*_device calls share: the torch planes checked, out / out_length allocated where they are
+    not given -> ((h, w), head, keep, out, out_length): head, the C call's arguments from prev_cam to hist_ids; keep, the camera
+    records behind its first two pointers."""
+    import torch
+    rgb, depth, ns = cur
+    assert rgb.is_cuda and rgb.is_contiguous() and rgb.dim() == 3 and rgb.shape[2] == 3 and rgb.dtype == torch.float32
+    h, w = rgb.shape[:2]
+    for t in (depth, ns):
+        assert t.is_cuda and t.is_contiguous() and t.numel() == h * w and t.element_size() == 4
+    assert depth.dtype == torch.float32
+    assert ids is None or (ids.is_cuda and ids.is_contiguous() and ids.numel() == 2 * h * w and ids.dtype == torch.int32)
+    hist, out, out_length = _reproject_history_tensors(h, w, rgb.device, history, hist_ids, out, out_length)
+    keep = [_camera_record(prev_cam), _camera_record(cur_cam)]
+    head = [_ptr(keep[0]), _ptr(keep[1]), int(origin[0]), int(origin[1]), w, h, _ptr(rgb), _ptr(depth), _ptr(ns), _ptr(ids), *hist]
+    return (h, w), head, keep, out, out_length
+
+
+def _reproject_progressive_planes(frame, history, prev_cam, hist_ids, out, out_length):
+    """What the three Progressive.reproject*_device calls share (the current planes and the region are the frame's own)
+    -> ((h, w), device, head, keep, out, out_length): head, the C call's arguments from the context to hist_ids; keep, the camera
+    record behind its pointer."""
+    import torch
+    device = torch.device("cuda", frame._ctx.device_id)
+    x0, y0, x1, y1 = frame.region
+    h, w = y1 - y0, x1 - x0
+    hist, out, out_length = _reproject_history_tensors(h, w, device, history, hist_ids, out, out_length)
+    keep = _camera_record(prev_cam)
+    return (h, w), device, [frame._ctx._h, _ptr(keep), *hist], keep, out, out_length
+
+
+def reproject_host(cur, history, prev_cam, cur_cam, origin=(0, 0), ids=None, hist_ids=None, out=None, out_length=None, params=None,
+                   depth_tolerance=None, max_history=None):
+    """qa_test_reproject_host: the temporal reprojection of Context.reproject_device on the CPU, from the source the device kernel is
+    compiled from.  cur = (rgb (h, w, 3) f32, depth (h, w) f32, ns (h, w) u32) rendered from cur_cam; history = (rgb, depth,
+    length (h, w) f32) accumulated under prev_cam; origin: the image pixel (x0, y0) of the frames' first pixel; ids / hist_ids:
+    (h, w, 2) i32, both or neither.  out / out_length: float32 arrays to write (out may be cur's rgb itself) -> (out (h, w, 3),
+    out_length (h, w)).  The other inputs are not modified.  No GPU needed."""
+    _, head, keep, out, out_length = _reproject_host_planes(cur, history, prev_cam, cur_cam, origin, ids, hist_ids, out, out_length)
     p = ReprojectParams.of(params, depth_tolerance, max_history)
-    c0, c1 = _camera_record(prev_cam), _camera_record(cur_cam)
-    _check(lib().qa_test_reproject_host(c0.ctypes.data, c1.ctypes.data, int(origin[0]), int(origin[1]), w, h, rgb.ctypes.data, depth.ctypes.data,
-                                        ns.ctypes.data, None if idp[0] is None else idp[0].ctypes.data, hist[0].ctypes.data, hist[1].ctypes.data,
-                                        hist[2].ctypes.data, None if idp[1] is None else idp[1].ctypes.data, C.byref(p), out.ctypes.data,
-                                        out_length.ctypes.data))
+    _check(lib().qa_test_reproject_host(*head, C.byref(p), _ptr(out), _ptr(out_length)))
     return out, out_length
 
 
@@ -545,28 +600,10 @@ def reproject_motion_host(cur, history, prev_cam, cur_cam, origin=(0, 0), ids=No
     from; the arguments of reproject_host, and motion: a table of NODE_MOTION_DTYPE (node_motion()) - given, it sets
     QA_REPROJECT_MOTION; clamp (bool) sets or clears QA_REPROJECT_CLAMP, clamp_radius / clamp_gamma override params' values.
     -> (out (h, w, 3), out_length (h, w)).  No GPU needed."""
-    rgb, depth, ns = cur
-    rgb = rgb if out is rgb and rgb is not None else np.ascontiguousarray(rgb, dtype=np.float32)
-    depth = np.ascontiguousarray(depth, dtype=np.float32)
-    ns = np.ascontiguousarray(ns, dtype=np.uint32)
-    assert rgb.ndim == 3 and rgb.shape[2] == 3 and depth.shape == rgb.shape[:2] and ns.shape == rgb.shape[:2]
-    h, w = depth.shape
-    hist = [np.ascontiguousarray(a, dtype=np.float32) for a in history]
-    assert hist[0].shape == (h, w, 3) and hist[1].shape == (h, w) and hist[2].shape == (h, w)
-    idp = [None if a is None else np.ascontiguousarray(a, dtype=np.int32) for a in (ids, hist_ids)]
-    assert all(a is None or a.shape == (h, w, 2) for a in idp)
-    out = np.zeros((h, w, 3), np.float32) if out is None else out
-    out_length = np.zeros((h, w), np.float32) if out_length is None else out_length
-    for a, shape in ((out, (h, w, 3)), (out_length, (h, w))):
-        assert a.dtype == np.float32 and a.flags.c_contiguous and a.shape == shape
+    _, head, keep, out, out_length = _reproject_host_planes(cur, history, prev_cam, cur_cam, origin, ids, hist_ids, out, out_length)
     table = None if motion is None else np.ascontiguousarray(motion, dtype=NODE_MOTION_DTYPE).reshape(-1)
     p = ReprojectMotionParams.of(params, depth_tolerance, max_history, True if table is not None else None, clamp, clamp_radius, clamp_gamma)
-    c0, c1 = _camera_record(prev_cam), _camera_record(cur_cam)
-    _check(lib().qa_test_reproject_motion_host(c0.ctypes.data, c1.ctypes.data, int(origin[0]), int(origin[1]), w, h, rgb.ctypes.data, depth.ctypes.data,
-                                               ns.ctypes.data, None if idp[0] is None else idp[0].ctypes.data, hist[0].ctypes.data, hist[1].ctypes.data,
-                                               hist[2].ctypes.data, None if idp[1] is None else idp[1].ctypes.data,
-                                               None if table is None else table.ctypes.data, 0 if table is None else len(table), C.byref(p),
-                                               out.ctypes.data, out_length.ctypes.data))
+    _check(lib().qa_test_reproject_motion_host(*head, _ptr(table), 0 if table is None else len(table), C.byref(p), _ptr(out), _ptr(out_length)))
     return out, out_length
 
 
@@ -578,34 +615,19 @@ def reproject_moments_host(cur, history, prev_cam, cur_cam, origin=(0, 0), ids=N
     shorten (bool) set or clear QA_REPROJECT_MOMENTS / QA_REPROJECT_SHORTEN, min_frames / shorten_rate override params' values (a
     ReprojectMomentsParams).  -> (out (h, w, 3), out_length (h, w), out_moments (h, w, 2), out_variance (h, w)); the last two are
     None when QA_REPROJECT_MOMENTS is clear and they were not given.  No GPU needed."""
-    rgb, depth, ns = cur
-    rgb = rgb if out is rgb and rgb is not None else np.ascontiguousarray(rgb, dtype=np.float32)
-    depth = np.ascontiguousarray(depth, dtype=np.float32)
-    ns = np.ascontiguousarray(ns, dtype=np.uint32)
-    assert rgb.ndim == 3 and rgb.shape[2] == 3 and depth.shape == rgb.shape[:2] and ns.shape == rgb.shape[:2]
-    h, w = depth.shape
-    hist = [np.ascontiguousarray(a, dtype=np.float32) for a in history]
-    assert hist[0].shape == (h, w, 3) and hist[1].shape == (h, w) and hist[2].shape == (h, w)
-    idp = [None if a is None else np.ascontiguousarray(a, dtype=np.int32) for a in (ids, hist_ids)]
-    assert all(a is None or a.shape == (h, w, 2) for a in idp)
+    (h, w), head, keep, out, out_length = _reproject_host_planes(cur, history, prev_cam, cur_cam, origin, ids, hist_ids, out, out_length)
     hmom = None if hist_moments is None else np.ascontiguousarray(hist_moments, dtype=np.float32)
     assert hmom is None or hmom.shape == (h, w, 2)
     table = None if motion is None else np.ascontiguousarray(motion, dtype=NODE_MOTION_DTYPE).reshape(-1)
     p = ReprojectMomentsParams.of(params, depth_tolerance, max_history, True if table is not None else None, clamp, clamp_radius, clamp_gamma, moments,
                                   shorten, min_frames, shorten_rate)
-    out = np.zeros((h, w, 3), np.float32) if out is None else out
-    out_length = np.zeros((h, w), np.float32) if out_length is None else out_length
     if p.flags & QA_REPROJECT_MOMENTS:
         out_moments = np.zeros((h, w, 2), np.float32) if out_moments is None else out_moments
         out_variance = np.zeros((h, w), np.float32) if out_variance is None else out_variance
-    for a, shape in ((out, (h, w, 3)), (out_length, (h, w)), (out_moments, (h, w, 2)), (out_variance, (h, w))):
+    for a, shape in ((out_moments, (h, w, 2)), (out_variance, (h, w))):
         assert a is None or (a.dtype == np.float32 and a.flags.c_contiguous and a.shape == shape)
-    c0, c1 = _camera_record(prev_cam), _camera_record(cur_cam)
-    ptr = lambda a: None if a is None else a.ctypes.data   # noqa: E731
-    _check(lib().qa_test_reproject_moments_host(c0.ctypes.data, c1.ctypes.data, int(origin[0]), int(origin[1]), w, h, rgb.ctypes.data, depth.ctypes.data,
-                                                ns.ctypes.data, ptr(idp[0]), hist[0].ctypes.data, hist[1].ctypes.data, hist[2].ctypes.data, ptr(idp[1]),
-                                                ptr(hmom), ptr(table), 0 if table is None else len(table), C.byref(p), out.ctypes.data,
-                                                out_length.ctypes.data, ptr(out_moments), ptr(out_variance)))
+    _check(lib().qa_test_reproject_moments_host(*head, _ptr(hmom), _ptr(table), 0 if table is None else len(table), C.byref(p), _ptr(out),
+                                                _ptr(out_length), _ptr(out_moments), _ptr(out_variance)))
     return out, out_length, out_moments, out_variance
 
 
@@ -1026,31 +1048,17 @@ class Context:
         (None: new ones); neither may be a history plane.  params: a ReprojectParams; the keyword arguments override its fields.
         -> (out, out_length), the history of the next call together with cur's depth and ids.  Only enqueues (see
         render_region_device for the stream)."""
-        import torch
-        rgb, depth, ns = cur
-        hrgb, hdepth, hlen = history
-        assert rgb.is_cuda and rgb.is_contiguous() and rgb.dim() == 3 and rgb.shape[2] == 3 and rgb.dtype == torch.float32
-        h, w = rgb.shape[:2]
-        n = h * w
-        for t in (depth, ns, hdepth, hlen):
-            assert t.is_cuda and t.is_contiguous() and t.numel() == n and t.element_size() == 4
-        assert depth.dtype == torch.float32 and hdepth.dtype == torch.float32 and hlen.dtype == torch.float32
-        assert hrgb.is_cuda and hrgb.is_contiguous() and hrgb.numel() == 3 * n and hrgb.dtype == torch.float32
-        for t in (ids, hist_ids):
-            assert t is None or (t.is_cuda and t.is_contiguous() and t.numel() == 2 * n and t.dtype == torch.int32)
-        if out is None:
-            out = torch.empty_like(rgb)
-        if out_length is None:
-            out_length = torch.empty((h, w), dtype=torch.float32, device=rgb.device)
-        assert out.is_cuda and out.is_contiguous() and out.numel() == 3 * n and out.dtype == torch.float32
-        assert out_length.is_cuda and out_length.is_contiguous() and out_length.numel() == n and out_length.dtype == torch.float32
+        _, head, keep, out, out_length = _reproject_device_planes(cur, history, prev_cam, cur_cam, origin, ids, hist_ids, out, out_length)
         p = ReprojectParams.of(params, depth_tolerance, max_history)
-        c0, c1 = _camera_record(prev_cam), _camera_record(cur_cam)
-        sptr = self._stream_arg(stream, rgb)
-        _check(lib().qa_reproject_device(self._h, c0.ctypes.data, c1.ctypes.data, int(origin[0]), int(origin[1]), w, h, rgb.data_ptr(), depth.data_ptr(),
-                                         ns.data_ptr(), None if ids is None else ids.data_ptr(), hrgb.data_ptr(), hdepth.data_ptr(), hlen.data_ptr(),
-                                         None if hist_ids is None else hist_ids.data_ptr(), C.byref(p), out.data_ptr(), out_length.data_ptr(), sptr))
+        sptr = self._stream_arg(stream, out)
+        _check(lib().qa_reproject_device(self._h, *head, C.byref(p), _ptr(out), _ptr(out_length), sptr))
         return out, out_length
+
+    def _upload_motion(self, motion, device, stream):
+        """_motion_tensor(motion) for a reprojection of this context's -> (its pointer or None, records)."""
+        # (kept until the next call: without a stream of the caller's the kernel is not ordered against torch's allocator)
+        self._motion_upload, count = _motion_tensor(motion, device, stream)
+        return _ptr(self._motion_upload), count
 
     def reproject_motion_device(self, cur, history, prev_cam, cur_cam, origin=(0, 0), ids=None, hist_ids=None, motion=None, out=None, out_length=None,
                                 params=None, depth_tolerance=None, max_history=None, clamp=None, clamp_radius=None, clamp_gamma=None, stream=None):
@@ -1059,34 +1067,11 @@ class Context:
         or a CUDA tensor of its 64-byte records - given, it sets QA_REPROJECT_MOTION and wants both ids planes; clamp (bool) sets
         or clears QA_REPROJECT_CLAMP (out may then not be cur's rgb), clamp_radius / clamp_gamma override params' values (a
         ReprojectMotionParams).  With neither, the result is reproject_device's.  -> (out, out_length); only enqueues."""
-        import torch
-        rgb, depth, ns = cur
-        hrgb, hdepth, hlen = history
-        assert rgb.is_cuda and rgb.is_contiguous() and rgb.dim() == 3 and rgb.shape[2] == 3 and rgb.dtype == torch.float32
-        h, w = rgb.shape[:2]
-        n = h * w
-        for t in (depth, ns, hdepth, hlen):
-            assert t.is_cuda and t.is_contiguous() and t.numel() == n and t.element_size() == 4
-        assert depth.dtype == torch.float32 and hdepth.dtype == torch.float32 and hlen.dtype == torch.float32
-        assert hrgb.is_cuda and hrgb.is_contiguous() and hrgb.numel() == 3 * n and hrgb.dtype == torch.float32
-        for t in (ids, hist_ids):
-            assert t is None or (t.is_cuda and t.is_contiguous() and t.numel() == 2 * n and t.dtype == torch.int32)
-        if out is None:
-            out = torch.empty_like(rgb)
-        if out_length is None:
-            out_length = torch.empty((h, w), dtype=torch.float32, device=rgb.device)
-        assert out.is_cuda and out.is_contiguous() and out.numel() == 3 * n and out.dtype == torch.float32
-        assert out_length.is_cuda and out_length.is_contiguous() and out_length.numel() == n and out_length.dtype == torch.float32
-        # (kept until the next call: without a stream of the caller's the kernel is not ordered against torch's allocator)
-        self._motion_upload, count = _motion_tensor(motion, rgb.device, stream)
+        _, head, keep, out, out_length = _reproject_device_planes(cur, history, prev_cam, cur_cam, origin, ids, hist_ids, out, out_length)
+        table, count = self._upload_motion(motion, out.device, stream)
         p = ReprojectMotionParams.of(params, depth_tolerance, max_history, True if motion is not None else None, clamp, clamp_radius, clamp_gamma)
-        c0, c1 = _camera_record(prev_cam), _camera_record(cur_cam)
-        sptr = self._stream_arg(stream, rgb)
-        _check(lib().qa_reproject_motion_device(self._h, c0.ctypes.data, c1.ctypes.data, int(origin[0]), int(origin[1]), w, h, rgb.data_ptr(),
-                                                depth.data_ptr(), ns.data_ptr(), None if ids is None else ids.data_ptr(), hrgb.data_ptr(),
-                                                hdepth.data_ptr(), hlen.data_ptr(), None if hist_ids is None else hist_ids.data_ptr(),
-                                                None if motion is None else self._motion_upload.data_ptr(), count, C.byref(p), out.data_ptr(),
-                                                out_length.data_ptr(), sptr))
+        sptr = self._stream_arg(stream, out)
+        _check(lib().qa_reproject_motion_device(self._h, *head, table, count, C.byref(p), _ptr(out), _ptr(out_length), sptr))
         return out, out_length
 
     def reproject_moments_device(self, cur, history, prev_cam, cur_cam, origin=(0, 0), ids=None, hist_ids=None, hist_moments=None, motion=None, out=None,
@@ -1100,36 +1085,14 @@ class Context:
         values (a ReprojectMomentsParams).  With neither flag the result is reproject_motion_device's.
         -> (out, out_length, out_moments, out_variance), the last two None when the flag is clear and they were not given; only
         enqueues."""
-        import torch
-        rgb, depth, ns = cur
-        hrgb, hdepth, hlen = history
-        assert rgb.is_cuda and rgb.is_contiguous() and rgb.dim() == 3 and rgb.shape[2] == 3 and rgb.dtype == torch.float32
-        h, w = rgb.shape[:2]
-        n = h * w
-        for t in (depth, ns, hdepth, hlen):
-            assert t.is_cuda and t.is_contiguous() and t.numel() == n and t.element_size() == 4
-        assert depth.dtype == torch.float32 and hdepth.dtype == torch.float32 and hlen.dtype == torch.float32
-        assert hrgb.is_cuda and hrgb.is_contiguous() and hrgb.numel() == 3 * n and hrgb.dtype == torch.float32
-        for t in (ids, hist_ids):
-            assert t is None or (t.is_cuda and t.is_contiguous() and t.numel() == 2 * n and t.dtype == torch.int32)
-        if out is None:
-            out = torch.empty_like(rgb)
-        if out_length is None:
-            out_length = torch.empty((h, w), dtype=torch.float32, device=rgb.device)
-        assert out.is_cuda and out.is_contiguous() and out.numel() == 3 * n and out.dtype == torch.float32
-        assert out_length.is_cuda and out_length.is_contiguous() and out_length.numel() == n and out_length.dtype == torch.float32
+        (h, w), head, keep, out, out_length = _reproject_device_planes(cur, history, prev_cam, cur_cam, origin, ids, hist_ids, out, out_length)
         p = ReprojectMomentsParams.of(params, depth_tolerance, max_history, True if motion is not None else None, clamp, clamp_radius, clamp_gamma,
                                       moments, shorten, min_frames, shorten_rate)
-        out_moments, out_variance = _moments_tensors(p, h, w, rgb.device, hist_moments, out_moments, out_variance)
-        # (kept until the next call: without a stream of the caller's the kernel is not ordered against torch's allocator)
-        self._motion_upload, count = _motion_tensor(motion, rgb.device, stream)
-        c0, c1 = _camera_record(prev_cam), _camera_record(cur_cam)
-        sptr = self._stream_arg(stream, rgb)
-        ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731
-        _check(lib().qa_reproject_moments_device(self._h, c0.ctypes.data, c1.ctypes.data, int(origin[0]), int(origin[1]), w, h, rgb.data_ptr(),
-                                                 depth.data_ptr(), ns.data_ptr(), ptr(ids), hrgb.data_ptr(), hdepth.data_ptr(), hlen.data_ptr(),
-                                                 ptr(hist_ids), ptr(hist_moments), None if motion is None else self._motion_upload.data_ptr(), count,
-                                                 C.byref(p), out.data_ptr(), out_length.data_ptr(), ptr(out_moments), ptr(out_variance), sptr))
+        out_moments, out_variance = _moments_tensors(p, h, w, out.device, hist_moments, out_moments, out_variance)
+        table, count = self._upload_motion(motion, out.device, stream)
+        sptr = self._stream_arg(stream, out)
+        _check(lib().qa_reproject_moments_device(self._h, *head, _ptr(hist_moments), table, count, C.byref(p), _ptr(out), _ptr(out_length),
+                                                 _ptr(out_moments), _ptr(out_variance), sptr))
         return out, out_length, out_moments, out_variance
 
     def gbuffer(self, region, seed=DEFAULT_SEED):
@@ -1577,27 +1540,10 @@ class Progressive:
         from its slabs), its region and the resident scene's camera as the current frame; history = (rgb, depth, length) torch CUDA
         tensors accumulated under prev_cam.  With hist_ids (int32 [h,w,2]) the frame's own ids are computed as gbuffer_device does.
         -> (out, out_length); only enqueues.  The frame is not changed; a stale frame (after an edit) wants restart() first."""
-        import torch
-        device = torch.device("cuda", self._ctx.device_id)
-        x0, y0, x1, y1 = self.region
-        h, w = y1 - y0, x1 - x0
-        n = h * w
-        hrgb, hdepth, hlen = history
-        for t, k in ((hrgb, 3), (hdepth, 1), (hlen, 1)):
-            assert t.is_cuda and t.is_contiguous() and t.numel() == k * n and t.dtype == torch.float32
-        assert hist_ids is None or (hist_ids.is_cuda and hist_ids.is_contiguous() and hist_ids.numel() == 2 * n and hist_ids.dtype == torch.int32)
-        if out is None:
-            out = torch.empty((h, w, 3), dtype=torch.float32, device=device)
-        if out_length is None:
-            out_length = torch.empty((h, w), dtype=torch.float32, device=device)
-        assert out.is_cuda and out.is_contiguous() and out.numel() == 3 * n and out.dtype == torch.float32
-        assert out_length.is_cuda and out_length.is_contiguous() and out_length.numel() == n and out_length.dtype == torch.float32
+        _, _, head, keep, out, out_length = _reproject_progressive_planes(self, history, prev_cam, hist_ids, out, out_length)
         p = ReprojectParams.of(params, depth_tolerance, max_history)
-        c0 = _camera_record(prev_cam)
         sptr = Context._stream_arg(stream, out)
-        _check(lib().qa_progressive_reproject_device(self._ctx._h, c0.ctypes.data, hrgb.data_ptr(), hdepth.data_ptr(), hlen.data_ptr(),
-                                                     None if hist_ids is None else hist_ids.data_ptr(), C.byref(p), out.data_ptr(), out_length.data_ptr(),
-                                                     sptr))
+        _check(lib().qa_progressive_reproject_device(*head, C.byref(p), _ptr(out), _ptr(out_length), sptr))
         return out, out_length
 
     def reproject_motion_device(self, history, prev_cam, hist_ids=None, motion=None, out=None, out_length=None, params=None, depth_tolerance=None,
@@ -1605,29 +1551,11 @@ class Progressive:
         """qa_progressive_reproject_motion_device: reproject_device of this frame with Context.reproject_motion_device's additions
         (motion: a numpy table or a CUDA tensor, wants hist_ids; clamp, clamp_radius, clamp_gamma).  -> (out, out_length); only
         enqueues.  The frame is not changed; a stale frame wants restart() first."""
-        import torch
-        device = torch.device("cuda", self._ctx.device_id)
-        x0, y0, x1, y1 = self.region
-        h, w = y1 - y0, x1 - x0
-        n = h * w
-        hrgb, hdepth, hlen = history
-        for t, k in ((hrgb, 3), (hdepth, 1), (hlen, 1)):
-            assert t.is_cuda and t.is_contiguous() and t.numel() == k * n and t.dtype == torch.float32
-        assert hist_ids is None or (hist_ids.is_cuda and hist_ids.is_contiguous() and hist_ids.numel() == 2 * n and hist_ids.dtype == torch.int32)
-        if out is None:
-            out = torch.empty((h, w, 3), dtype=torch.float32, device=device)
-        if out_length is None:
-            out_length = torch.empty((h, w), dtype=torch.float32, device=device)
-        assert out.is_cuda and out.is_contiguous() and out.numel() == 3 * n and out.dtype == torch.float32
-        assert out_length.is_cuda and out_length.is_contiguous() and out_length.numel() == n and out_length.dtype == torch.float32
-        self._ctx._motion_upload, count = _motion_tensor(motion, device, stream)
+        _, device, head, keep, out, out_length = _reproject_progressive_planes(self, history, prev_cam, hist_ids, out, out_length)
+        table, count = self._ctx._upload_motion(motion, device, stream)
         p = ReprojectMotionParams.of(params, depth_tolerance, max_history, True if motion is not None else None, clamp, clamp_radius, clamp_gamma)
-        c0 = _camera_record(prev_cam)
         sptr = Context._stream_arg(stream, out)
-        _check(lib().qa_progressive_reproject_motion_device(self._ctx._h, c0.ctypes.data, hrgb.data_ptr(), hdepth.data_ptr(), hlen.data_ptr(),
-                                                            None if hist_ids is None else hist_ids.data_ptr(),
-                                                            None if motion is None else self._ctx._motion_upload.data_ptr(), count, C.byref(p),
-                                                            out.data_ptr(), out_length.data_ptr(), sptr))
+        _check(lib().qa_progressive_reproject_motion_device(*head, table, count, C.byref(p), _ptr(out), _ptr(out_length), sptr))
         return out, out_length
 
     def reproject_moments_device(self, history, prev_cam, hist_ids=None, hist_moments=None, motion=None, out=None, out_length=None, out_moments=None,
@@ -1636,32 +1564,14 @@ class Progressive:
         """qa_progressive_reproject_moments_device: reproject_motion_device of this frame with Context.reproject_moments_device's
         additions (hist_moments, moments, shorten, min_frames, shorten_rate).  -> (out, out_length, out_moments, out_variance); only
         enqueues.  The frame is not changed; a stale frame wants restart() first."""
-        import torch
-        device = torch.device("cuda", self._ctx.device_id)
-        x0, y0, x1, y1 = self.region
-        h, w = y1 - y0, x1 - x0
-        n = h * w
-        hrgb, hdepth, hlen = history
-        for t, k in ((hrgb, 3), (hdepth, 1), (hlen, 1)):
-            assert t.is_cuda and t.is_contiguous() and t.numel() == k * n and t.dtype == torch.float32
-        assert hist_ids is None or (hist_ids.is_cuda and hist_ids.is_contiguous() and hist_ids.numel() == 2 * n and hist_ids.dtype == torch.int32)
-        if out is None:
-            out = torch.empty((h, w, 3), dtype=torch.float32, device=device)
-        if out_length is None:
-            out_length = torch.empty((h, w), dtype=torch.float32, device=device)
-        assert out.is_cuda and out.is_contiguous() and out.numel() == 3 * n and out.dtype == torch.float32
-        assert out_length.is_cuda and out_length.is_contiguous() and out_length.numel() == n and out_length.dtype == torch.float32
+        (h, w), device, head, keep, out, out_length = _reproject_progressive_planes(self, history, prev_cam, hist_ids, out, out_length)
         p = ReprojectMomentsParams.of(params, depth_tolerance, max_history, True if motion is not None else None, clamp, clamp_radius, clamp_gamma,
                                       moments, shorten, min_frames, shorten_rate)
         out_moments, out_variance = _moments_tensors(p, h, w, device, hist_moments, out_moments, out_variance)
-        self._ctx._motion_upload, count = _motion_tensor(motion, device, stream)
-        c0 = _camera_record(prev_cam)
+        table, count = self._ctx._upload_motion(motion, device, stream)
         sptr = Context._stream_arg(stream, out)
-        ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731
-        _check(lib().qa_progressive_reproject_moments_device(self._ctx._h, c0.ctypes.data, hrgb.data_ptr(), hdepth.data_ptr(), hlen.data_ptr(),
-                                                             ptr(hist_ids), ptr(hist_moments),
-                                                             None if motion is None else self._ctx._motion_upload.data_ptr(), count, C.byref(p),
-                                                             out.data_ptr(), out_length.data_ptr(), ptr(out_moments), ptr(out_variance), sptr))
+        _check(lib().qa_progressive_reproject_moments_device(*head, _ptr(hist_moments), table, count, C.byref(p), _ptr(out), _ptr(out_length),
+                                                             _ptr(out_moments), _ptr(out_variance), sptr))
         return out, out_length, out_moments, out_variance
 
     def status(self):

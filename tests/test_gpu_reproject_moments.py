@@ -1,5 +1,5 @@
 """Reprojection with luminance moments and a shortened length on the device (qa_reproject_moments_device,
-qa_progressive_reproject_moments_device: the kernel qa_reproject_moments of qa_reproject.hip): the device build of
+qa_progressive_reproject_moments_device: the kernel qa_reproject_k<2> of qa_reproject.hip): the device build of
 qa_reproject_moments_dev.h equals the host build (qa_test_reproject_moments_host, pinned to a restatement of the specification by
 tests/test_reproject_moments_host.py) bit for bit on every output plane; on a progressive frame's slabs; and through
 hip.TemporalPreview on the renderer's own frames, where the shortened length lets go of the history a light edit made wrong."""

@@ -1,5 +1,5 @@
 """Reprojection with node motion and colour clamp on the device (qa_reproject_motion_device, qa_progressive_reproject_motion_device:
-the kernel qa_reproject_motion of qa_reproject.hip): the device build of qa_reproject_motion_dev.h equals the host build
+the kernel qa_reproject_k<1> of qa_reproject.hip): the device build of qa_reproject_motion_dev.h equals the host build
 (qa_test_reproject_motion_host, pinned to a restatement of the specification by tests/test_reproject_motion_host.py) bit for bit, at
 the sizes where the clamp's staged halo is wider than the frame, fills one tile and crosses tiles; on a progressive frame's slabs;
 and through hip.TemporalPreview on the renderer's own frames, previews follow moved nodes and drop the history a light edit made
