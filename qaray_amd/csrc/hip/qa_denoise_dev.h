@@ -189,53 +189,7 @@ __host__ __device__ __forceinline__ void denoiseGuideVariance(const Src &src, co
   c.var = varianceScale * (st / sw);
 }
 
-// One iteration of pixel (x, y) at step s.  tap(x, y, c, g) fetches a pixel's planes, called for pixels inside the image only
-template <class Tap>
-__host__ __device__ __forceinline__ DenoiseColor denoiseIterate(const Tap &tap, int x, int y, int W, int H, int s, float sigmaColor, float sigmaDepth)
-{
-  DenoiseColor P;
-  DenoiseGuide GP;
-  tap(x, y, P, GP);
-  if (GP.slope < 0.f) return P;
-  const bool miss = GP.z == QA_DENOISE_MISS;
-  const float lp = denoiseLuma(P.r, P.g, P.b);
-  const float denL = sigmaColor * qsqrt(P.var) + 1e-4f;
-  const float denZ = sigmaDepth * GP.slope * (float) s;
-  const float h[5] = {0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f};
-  float sw = 0.f, sr = 0.f, sg = 0.f, sb = 0.f, sv = 0.f;
-#pragma unroll
-  for (int dy = -2; dy <= 2; ++dy) {
-#pragma unroll
-    for (int dx = -2; dx <= 2; ++dx) {
-      if (dx == 0 && dy == 0) {
-        const float w = 0.140625f;
-        sw += w; sv += (w * w) * P.var;
-        continue;
-      }
-      const int qx = x + s * dx, qy = y + s * dy;
-      if (qx < 0 || qy < 0 || qx >= W || qy >= H) continue;
-      DenoiseColor Q;
-      DenoiseGuide GQ;
-      tap(qx, qy, Q, GQ);
-      if (GQ.slope < 0.f || (GQ.z == QA_DENOISE_MISS) != miss) continue;
-      float e = qabs(lp - denoiseLuma(Q.r, Q.g, Q.b)) / denL;
-      if (!miss && GP.z != GQ.z) {
-        const int ax = dx < 0 ? -dx : dx, ay = dy < 0 ? -dy : dy;
-        e = e + qabs(GP.z - GQ.z) / (denZ * (float) (ax > ay ? ax : ay));
-      }
-      const float w = (h[dx + 2] * h[dy + 2]) * qexpf(-e);
-      sw += w;
-      sr += w * (Q.r - P.r); sg += w * (Q.g - P.g); sb += w * (Q.b - P.b);
-      sv += (w * w) * Q.var;
-    }
-  }
-  DenoiseColor o;
-  o.r = P.r + sr / sw; o.g = P.g + sg / sw; o.b = P.b + sb / sw;
-  o.var = sv / (sw * sw);
-  return o;
-}
-
-// ---- the guided form ----
+// ---- the guided form: its pass 0 (the aux plane) ----
 __host__ __device__ __forceinline__ float denoiseDn(const DenoiseAux &p, const DenoiseAux &q) { return 1.f - (p.nx * q.nx + p.ny * q.ny + p.nz * q.nz); }
 __host__ __device__ __forceinline__ float denoiseDa(const DenoiseAux &p, const DenoiseAux &q)
 {
@@ -284,17 +238,26 @@ __host__ __device__ __forceinline__ DenoiseAux denoiseAux(const Src &src, const 
   return P;
 }
 
-// One iteration of the guided form.  tap as for denoiseIterate; aux(x, y) -> DenoiseAux of a pixel inside the image
-template <class Tap, class Aux>
-__host__ __device__ __forceinline__ DenoiseColor denoiseIterateGuided(const Tap &tap, const Aux &aux, int x, int y, int W, int H, int s, float sigmaColor,
-                                                                      float sigmaDepth, float sigmaNormal)
+// ---- the iterations of every form ----
+// the aux argument of the forms without guides: never called
+struct DenoiseNoAux {};
+
+// One iteration of pixel (x, y) at step s.  tap(x, y, c, g) fetches a pixel's planes, called for pixels inside the image only.
+// GUIDED: aux(x, y) -> DenoiseAux of a pixel inside the image, and its guides add their terms to a tap's exponent
+template <bool GUIDED, class Tap, class Aux>
+__host__ __device__ __forceinline__ DenoiseColor denoiseIterate(const Tap &tap, const Aux &aux, int x, int y, int W, int H, int s, float sigmaColor,
+                                                                float sigmaDepth, float sigmaNormal)
 {
   DenoiseColor P;
   DenoiseGuide GP;
   tap(x, y, P, GP);
   if (GP.slope < 0.f) return P;
-  const DenoiseAux AP = aux(x, y);
-  const uint32_t guided = (AP.bits & QA_DENOISE_AUX_RELIABLE) ? AP.bits : 0u;
+  [[maybe_unused]] DenoiseAux AP;
+  [[maybe_unused]] uint32_t guided = 0u;
+  if constexpr (GUIDED) {
+    AP = aux(x, y);
+    guided = (AP.bits & QA_DENOISE_AUX_RELIABLE) ? AP.bits : 0u;
+  }
   const bool miss = GP.z == QA_DENOISE_MISS;
   const float lp = denoiseLuma(P.r, P.g, P.b);
   const float denL = sigmaColor * qsqrt(P.var) + 1e-4f;
@@ -321,13 +284,15 @@ __host__ __device__ __forceinline__ DenoiseColor denoiseIterateGuided(const Tap 
         const int ax = dx < 0 ? -dx : dx, ay = dy < 0 ? -dy : dy;
         e = e + qabs(GP.z - GQ.z) / (denZ * (float) (ax > ay ? ax : ay));
       }
-      if (guided & (QA_DENOISE_AUX_VALID_N | QA_DENOISE_AUX_VALID_A)) {
-        const DenoiseAux AQ = aux(qx, qy);
-        if (guided & AQ.bits & QA_DENOISE_AUX_VALID_N) {
-          const float dn = denoiseDn(AP, AQ);
-          if (dn > 0.f) e = e + dn / sigmaNormal;
+      if constexpr (GUIDED) {
+        if (guided & (QA_DENOISE_AUX_VALID_N | QA_DENOISE_AUX_VALID_A)) {
+          const DenoiseAux AQ = aux(qx, qy);
+          if (guided & AQ.bits & QA_DENOISE_AUX_VALID_N) {
+            const float dn = denoiseDn(AP, AQ);
+            if (dn > 0.f) e = e + dn / sigmaNormal;
+          }
+          if (guided & AQ.bits & QA_DENOISE_AUX_VALID_A) e = e + denoiseDa(AP, AQ) / QA_DENOISE_SIGMA_ALBEDO;
         }
-        if (guided & AQ.bits & QA_DENOISE_AUX_VALID_A) e = e + denoiseDa(AP, AQ) / QA_DENOISE_SIGMA_ALBEDO;
       }
       const float w = (h[dx + 2] * h[dy + 2]) * qexpf(-e);
       sw += w;

@@ -114,14 +114,7 @@ class DenoiseParams(C.Structure):   # qa_denoise_params; DenoiseParams.default()
     @classmethod
     def of(cls, params=None, iterations=None, sigma_color=None, sigma_depth=None):
         """params (a DenoiseParams) or the library's defaults, with the keyword arguments that are given written over them."""
-        p = cls.default() if params is None else cls(params.iterations, params.sigma_color, params.sigma_depth, params.flags)
-        if iterations is not None:
-            p.iterations = int(iterations)
-        if sigma_color is not None:
-            p.sigma_color = float(sigma_color)
-        if sigma_depth is not None:
-            p.sigma_depth = float(sigma_depth)
-        return p
+        return _params_of(cls, params, dict(iterations=iterations, sigma_color=sigma_color, sigma_depth=sigma_depth))
 
 
 QA_DENOISE_GUIDE_NORMAL, QA_DENOISE_GUIDE_ALBEDO = 1, 2
@@ -163,15 +156,7 @@ class DenoiseGuidedParams(C.Structure):   # qa_denoise_guided_params; .default()
     @classmethod
     def of(cls, params=None, flags=None, iterations=None, sigma_color=None, sigma_depth=None, sigma_normal=None):
         """params (a DenoiseGuidedParams) or the library's defaults, with the arguments that are given written over them."""
-        p = cls.default() if params is None else cls(params.iterations, params.sigma_color, params.sigma_depth, params.sigma_normal, params.flags)
-        if flags is not None:
-            p.flags = int(flags)
-        if iterations is not None:
-            p.iterations = int(iterations)
-        for name, v in (("sigma_color", sigma_color), ("sigma_depth", sigma_depth), ("sigma_normal", sigma_normal)):
-            if v is not None:
-                setattr(p, name, float(v))
-        return p
+        return _params_of(cls, params, dict(flags=flags, iterations=iterations, sigma_color=sigma_color, sigma_depth=sigma_depth, sigma_normal=sigma_normal))
 
 
 QA_DENOISE_GUIDE_VARIANCE = 4
@@ -190,26 +175,18 @@ class DenoiseVarianceParams(C.Structure):   # qa_denoise_variance_params; .defau
     @classmethod
     def of(cls, params=None, flags=None, iterations=None, sigma_color=None, sigma_depth=None, sigma_normal=None, variance_scale=None):
         """params (a DenoiseVarianceParams) or the library's defaults, with the arguments that are given written over them."""
-        p = cls.default() if params is None else cls(*(getattr(params, name) for name, _ in cls._fields_))
-        if flags is not None:
-            p.flags = int(flags)
-        if iterations is not None:
-            p.iterations = int(iterations)
-        for name, v in (("sigma_color", sigma_color), ("sigma_depth", sigma_depth), ("sigma_normal", sigma_normal), ("variance_scale", variance_scale)):
-            if v is not None:
-                setattr(p, name, float(v))
-        return p
+        return _params_of(cls, params, dict(flags=flags, iterations=iterations, sigma_color=sigma_color, sigma_depth=sigma_depth, sigma_normal=sigma_normal,
+                                            variance_scale=variance_scale))
 
 
-def _reproject_params_of(cls, params, floats, clamp_radius=None, bits=()):
-    """The override logic of the three Reproject*Params.of: a copy of params (or cls.default()) with the floats that are not None
-    written over its fields, clamp_radius likewise, and every (flag bit, bool or None) of bits set, cleared or left."""
+def _params_of(cls, params, values, bits=()):
+    """The override rule of the Denoise*Params.of and Reproject*Params.of: a copy of params (or cls.default()) with the values that
+    are not None written over its fields (iterations, clamp_radius and flags as int, every other as float), and every (flag bit,
+    bool or None) of bits set, cleared or left."""
     p = cls.default() if params is None else cls(*(getattr(params, name) for name, _ in cls._fields_))
-    for name, v in floats.items():
+    for name, v in values.items():
         if v is not None:
-            setattr(p, name, float(v))
-    if clamp_radius is not None:
-        p.clamp_radius = int(clamp_radius)
+            setattr(p, name, int(v) if name in ("iterations", "clamp_radius", "flags") else float(v))
     for bit, v in bits:
         if v is not None:
             p.flags = (p.flags | bit) if v else (p.flags & ~bit)
@@ -228,7 +205,7 @@ class ReprojectParams(C.Structure):   # qa_reproject_params; ReprojectParams.def
     @classmethod
     def of(cls, params=None, depth_tolerance=None, max_history=None):
         """params (a ReprojectParams) or the library's defaults, with the keyword arguments that are given written over them."""
-        return _reproject_params_of(cls, params, dict(depth_tolerance=depth_tolerance, max_history=max_history))
+        return _params_of(cls, params, dict(depth_tolerance=depth_tolerance, max_history=max_history))
 
 
 QA_REPROJECT_MOTION, QA_REPROJECT_CLAMP = 1, 2
@@ -250,8 +227,8 @@ class ReprojectMotionParams(C.Structure):   # qa_reproject_motion_params; .defau
     def of(cls, params=None, depth_tolerance=None, max_history=None, motion=None, clamp=None, clamp_radius=None, clamp_gamma=None):
         """params (a ReprojectMotionParams) or the library's defaults, with the keyword arguments that are given written over them;
         motion / clamp (bool) set or clear QA_REPROJECT_MOTION / QA_REPROJECT_CLAMP of the flags."""
-        return _reproject_params_of(cls, params, dict(depth_tolerance=depth_tolerance, max_history=max_history, clamp_gamma=clamp_gamma), clamp_radius,
-                                    ((QA_REPROJECT_MOTION, motion), (QA_REPROJECT_CLAMP, clamp)))
+        return _params_of(cls, params, dict(depth_tolerance=depth_tolerance, max_history=max_history, clamp_gamma=clamp_gamma, clamp_radius=clamp_radius),
+                          ((QA_REPROJECT_MOTION, motion), (QA_REPROJECT_CLAMP, clamp)))
 
 
 QA_REPROJECT_MOMENTS, QA_REPROJECT_SHORTEN = 4, 8
@@ -272,10 +249,9 @@ class ReprojectMomentsParams(C.Structure):   # qa_reproject_moments_params; .def
            shorten=None, min_frames=None, shorten_rate=None):
         """params (a ReprojectMomentsParams) or the library's defaults, with the keyword arguments that are given written over them;
         motion / clamp / moments / shorten (bool) set or clear the four flags."""
-        return _reproject_params_of(cls, params, dict(depth_tolerance=depth_tolerance, max_history=max_history, clamp_gamma=clamp_gamma,
-                                                      min_frames=min_frames, shorten_rate=shorten_rate), clamp_radius,
-                                    ((QA_REPROJECT_MOTION, motion), (QA_REPROJECT_CLAMP, clamp), (QA_REPROJECT_MOMENTS, moments),
-                                     (QA_REPROJECT_SHORTEN, shorten)))
+        return _params_of(cls, params, dict(depth_tolerance=depth_tolerance, max_history=max_history, clamp_gamma=clamp_gamma, min_frames=min_frames,
+                                            shorten_rate=shorten_rate, clamp_radius=clamp_radius),
+                          ((QA_REPROJECT_MOTION, motion), (QA_REPROJECT_CLAMP, clamp), (QA_REPROJECT_MOMENTS, moments), (QA_REPROJECT_SHORTEN, shorten)))
 
 
 QA_GBUFFER_BACKFACE = 0x40000000
@@ -433,17 +409,30 @@ def display_host(rgb, depth, ns, spp_max, srgb=True):
     return Display(*out, st.as_dict())
 
 
+def _denoise_flags(normal, albedo, variance):
+    """The flag word of a denoise call: the planes that are given."""
+    return ((QA_DENOISE_GUIDE_NORMAL if normal is not None else 0) | (QA_DENOISE_GUIDE_ALBEDO if albedo is not None else 0)
+            | (QA_DENOISE_GUIDE_VARIANCE if variance is not None else 0))
+
+
+def _denoise_host_planes(rgb, depth, ns, normal=None, albedo=None, variance=None):
+    """What the three denoise*_host calls share: the planes as contiguous arrays of their types, their shapes checked, and a new
+    output -> ((h, w), the pointers of the six planes in the C ABI's order (None for a plane that is not given), keep, out, flags):
+    keep, the arrays behind the pointers, for the caller to hold until the call has returned; flags, the planes given."""
+    keep = [np.ascontiguousarray(rgb, dtype=np.float32), np.ascontiguousarray(depth, dtype=np.float32), np.ascontiguousarray(ns, dtype=np.uint32)]
+    keep += [None if g is None else np.ascontiguousarray(g, dtype=np.float32) for g in (normal, albedo, variance)]
+    rgb, depth, ns, *guides = keep
+    assert rgb.ndim == 3 and rgb.shape[2] == 3 and depth.shape == rgb.shape[:2] and ns.shape == rgb.shape[:2]
+    assert all(g is None or g.shape == rgb.shape for g in guides[:2]) and (guides[2] is None or guides[2].shape == depth.shape)
+    return depth.shape, [_ptr(a) for a in keep], keep, np.zeros(rgb.shape, np.float32), _denoise_flags(normal, albedo, variance)
+
+
 def denoise_host(rgb, depth, ns, params=None, iterations=None, sigma_color=None, sigma_depth=None):
     """qa_test_denoise_host: the edge-avoiding filter of Context.denoise_device on the CPU, from the source the device kernels are
     compiled from: rgb (h, w, 3), depth (h, w), ns (h, w) -> float32 (h, w, 3).  The inputs are not modified.  No GPU needed."""
-    rgb = np.ascontiguousarray(rgb, dtype=np.float32)
-    depth = np.ascontiguousarray(depth, dtype=np.float32)
-    ns = np.ascontiguousarray(ns, dtype=np.uint32)
-    assert rgb.ndim == 3 and rgb.shape[2] == 3 and depth.shape == rgb.shape[:2] and ns.shape == rgb.shape[:2]
-    h, w = depth.shape
-    out = np.zeros((h, w, 3), np.float32)
+    (h, w), ptrs, keep, out, _ = _denoise_host_planes(rgb, depth, ns)
     p = DenoiseParams.of(params, iterations, sigma_color, sigma_depth)
-    _check(lib().qa_test_denoise_host(rgb.ctypes.data, depth.ctypes.data, ns.ctypes.data, w, h, C.byref(p), out.ctypes.data))
+    _check(lib().qa_test_denoise_host(*ptrs[:3], w, h, C.byref(p), out.ctypes.data))
     return out
 
 
@@ -451,18 +440,9 @@ def denoise_guided_host(rgb, depth, ns, normal=None, albedo=None, params=None, i
                         sigma_normal=None):
     """qa_test_denoise_guided_host: the guided filter of Context.denoise_guided_device on the CPU, from the source the device kernels
     are compiled from; normal / albedo (h, w, 3) or None: the flags are the guides given.  -> float32 (h, w, 3).  No GPU needed."""
-    rgb = np.ascontiguousarray(rgb, dtype=np.float32)
-    depth = np.ascontiguousarray(depth, dtype=np.float32)
-    ns = np.ascontiguousarray(ns, dtype=np.uint32)
-    assert rgb.ndim == 3 and rgb.shape[2] == 3 and depth.shape == rgb.shape[:2] and ns.shape == rgb.shape[:2]
-    guides = [None if g is None else np.ascontiguousarray(g, dtype=np.float32) for g in (normal, albedo)]
-    assert all(g is None or g.shape == rgb.shape for g in guides)
-    h, w = depth.shape
-    out = np.zeros((h, w, 3), np.float32)
-    flags = (QA_DENOISE_GUIDE_NORMAL if normal is not None else 0) | (QA_DENOISE_GUIDE_ALBEDO if albedo is not None else 0)
+    (h, w), ptrs, keep, out, flags = _denoise_host_planes(rgb, depth, ns, normal, albedo)
     p = DenoiseGuidedParams.of(params, flags, iterations, sigma_color, sigma_depth, sigma_normal)
-    _check(lib().qa_test_denoise_guided_host(rgb.ctypes.data, depth.ctypes.data, ns.ctypes.data, *(None if g is None else g.ctypes.data for g in guides),
-                                             w, h, C.byref(p), out.ctypes.data))
+    _check(lib().qa_test_denoise_guided_host(*ptrs[:5], w, h, C.byref(p), out.ctypes.data))
     return out
 
 
@@ -470,20 +450,28 @@ def denoise_variance_host(rgb, depth, ns, normal=None, albedo=None, variance=Non
                           sigma_depth=None, sigma_normal=None, variance_scale=None):
     """qa_test_denoise_variance_host: Context.denoise_variance_device on the CPU, from the source the device kernels are compiled
     from; normal / albedo (h, w, 3) and variance (h, w) or None: the flags are the planes given.  -> float32 (h, w, 3).  No GPU needed."""
-    rgb = np.ascontiguousarray(rgb, dtype=np.float32)
-    depth = np.ascontiguousarray(depth, dtype=np.float32)
-    ns = np.ascontiguousarray(ns, dtype=np.uint32)
-    assert rgb.ndim == 3 and rgb.shape[2] == 3 and depth.shape == rgb.shape[:2] and ns.shape == rgb.shape[:2]
-    guides = [None if g is None else np.ascontiguousarray(g, dtype=np.float32) for g in (normal, albedo, variance)]
-    assert all(g is None or g.shape == rgb.shape for g in guides[:2]) and (guides[2] is None or guides[2].shape == depth.shape)
-    h, w = depth.shape
-    out = np.zeros((h, w, 3), np.float32)
-    flags = ((QA_DENOISE_GUIDE_NORMAL if normal is not None else 0) | (QA_DENOISE_GUIDE_ALBEDO if albedo is not None else 0)
-             | (QA_DENOISE_GUIDE_VARIANCE if variance is not None else 0))
+    (h, w), ptrs, keep, out, flags = _denoise_host_planes(rgb, depth, ns, normal, albedo, variance)
     p = DenoiseVarianceParams.of(params, flags, iterations, sigma_color, sigma_depth, sigma_normal, variance_scale)
-    _check(lib().qa_test_denoise_variance_host(rgb.ctypes.data, depth.ctypes.data, ns.ctypes.data, *(None if g is None else g.ctypes.data for g in guides),
-                                               w, h, C.byref(p), out.ctypes.data))
+    _check(lib().qa_test_denoise_variance_host(*ptrs, w, h, C.byref(p), out.ctypes.data))
     return out
+
+
+def _denoise_device_planes(rgb, depth, ns, out, normal=None, albedo=None, variance=None):
+    """What the three Context.denoise*_device calls share: the torch planes checked (float32 [h,w,3], float32 [h,w], int32/uint32
+    [h,w]; the guides float32 [h,w,3], the variance float32 [h,w], or None) and out checked, or allocated where it is None
+    -> ((h, w), the pointers of the six planes in the C ABI's order (None for a plane that is not given), out, flags: the planes given)."""
+    import torch
+    assert rgb.is_cuda and rgb.is_contiguous() and rgb.dim() == 3 and rgb.shape[2] == 3 and rgb.dtype == torch.float32
+    h, w = rgb.shape[:2]
+    n = h * w
+    assert depth.is_cuda and depth.is_contiguous() and depth.numel() == n and depth.element_size() == 4
+    assert ns.is_cuda and ns.is_contiguous() and ns.numel() == n and ns.element_size() == 4
+    for g, k in ((normal, 3), (albedo, 3), (variance, 1)):
+        assert g is None or (g.is_cuda and g.is_contiguous() and g.numel() == k * n and g.dtype == torch.float32)
+    if out is None:
+        out = torch.empty_like(rgb)
+    assert out.is_cuda and out.is_contiguous() and out.shape == rgb.shape and out.dtype == torch.float32
+    return (h, w), [_ptr(t) for t in (rgb, depth, ns, normal, albedo, variance)], out, _denoise_flags(normal, albedo, variance)
 
 
 def _camera_record(cam):
@@ -975,40 +963,18 @@ class Context:
         the float32 [h,w,3] tensor to write (may be rgb itself; None: a new one).  params: a DenoiseParams; the keyword arguments
         override its fields (defaults: the library's).  -> out.  Only enqueues (see render_region_device for the stream).  The
         8-bit picture: display_device(out, depth, ns, spp_max)."""
-        import torch
-        assert rgb.is_cuda and rgb.is_contiguous() and rgb.dim() == 3 and rgb.shape[2] == 3 and rgb.dtype == torch.float32
-        h, w = rgb.shape[:2]
-        n = h * w
-        assert depth.is_cuda and depth.is_contiguous() and depth.numel() == n and depth.element_size() == 4
-        assert ns.is_cuda and ns.is_contiguous() and ns.numel() == n and ns.element_size() == 4
-        if out is None:
-            out = torch.empty_like(rgb)
-        assert out.is_cuda and out.is_contiguous() and out.shape == rgb.shape and out.dtype == torch.float32
+        (h, w), ptrs, out, _ = _denoise_device_planes(rgb, depth, ns, out)
         p = DenoiseParams.of(params, iterations, sigma_color, sigma_depth)
-        sptr = self._stream_arg(stream, rgb)
-        _check(lib().qa_denoise_device(self._h, rgb.data_ptr(), depth.data_ptr(), ns.data_ptr(), w, h, C.byref(p), out.data_ptr(), sptr))
+        _check(lib().qa_denoise_device(self._h, *ptrs[:3], w, h, C.byref(p), out.data_ptr(), self._stream_arg(stream, rgb)))
         return out
 
     def denoise_guided_device(self, rgb, depth, ns, normal=None, albedo=None, out=None, params=None, iterations=None, sigma_color=None,
                               sigma_depth=None, sigma_normal=None, stream=None):
         """qa_denoise_guided_device: denoise_device guided by the first-hit planes of gbuffer_device as well (float32 [h,w,3] CUDA
         tensors; the flags are the guides given, and with neither the result is denoise_device's).  -> out; only enqueues."""
-        import torch
-        assert rgb.is_cuda and rgb.is_contiguous() and rgb.dim() == 3 and rgb.shape[2] == 3 and rgb.dtype == torch.float32
-        h, w = rgb.shape[:2]
-        n = h * w
-        assert depth.is_cuda and depth.is_contiguous() and depth.numel() == n and depth.element_size() == 4
-        assert ns.is_cuda and ns.is_contiguous() and ns.numel() == n and ns.element_size() == 4
-        for g in (normal, albedo):
-            assert g is None or (g.is_cuda and g.is_contiguous() and g.numel() == 3 * n and g.dtype == torch.float32)
-        if out is None:
-            out = torch.empty_like(rgb)
-        assert out.is_cuda and out.is_contiguous() and out.shape == rgb.shape and out.dtype == torch.float32
-        flags = (QA_DENOISE_GUIDE_NORMAL if normal is not None else 0) | (QA_DENOISE_GUIDE_ALBEDO if albedo is not None else 0)
+        (h, w), ptrs, out, flags = _denoise_device_planes(rgb, depth, ns, out, normal, albedo)
         p = DenoiseGuidedParams.of(params, flags, iterations, sigma_color, sigma_depth, sigma_normal)
-        sptr = self._stream_arg(stream, rgb)
-        _check(lib().qa_denoise_guided_device(self._h, rgb.data_ptr(), depth.data_ptr(), ns.data_ptr(), None if normal is None else normal.data_ptr(),
-                                              None if albedo is None else albedo.data_ptr(), w, h, C.byref(p), out.data_ptr(), sptr))
+        _check(lib().qa_denoise_guided_device(self._h, *ptrs[:5], w, h, C.byref(p), out.data_ptr(), self._stream_arg(stream, rgb)))
         return out
 
     def denoise_variance_device(self, rgb, depth, ns, normal=None, albedo=None, variance=None, out=None, params=None, iterations=None,
@@ -1017,25 +983,9 @@ class Context:
         (include/qaray_hip.h): variance, a float32 [h,w] CUDA tensor, -1 where there is none - TemporalPreview(moments=True).variance
         or the out_variance of reproject_moments_device.  The flags are the planes given; without variance the result is
         denoise_guided_device's.  -> out; only enqueues."""
-        import torch
-        assert rgb.is_cuda and rgb.is_contiguous() and rgb.dim() == 3 and rgb.shape[2] == 3 and rgb.dtype == torch.float32
-        h, w = rgb.shape[:2]
-        n = h * w
-        assert depth.is_cuda and depth.is_contiguous() and depth.numel() == n and depth.element_size() == 4
-        assert ns.is_cuda and ns.is_contiguous() and ns.numel() == n and ns.element_size() == 4
-        for g in (normal, albedo):
-            assert g is None or (g.is_cuda and g.is_contiguous() and g.numel() == 3 * n and g.dtype == torch.float32)
-        assert variance is None or (variance.is_cuda and variance.is_contiguous() and variance.numel() == n and variance.dtype == torch.float32)
-        if out is None:
-            out = torch.empty_like(rgb)
-        assert out.is_cuda and out.is_contiguous() and out.shape == rgb.shape and out.dtype == torch.float32
-        flags = ((QA_DENOISE_GUIDE_NORMAL if normal is not None else 0) | (QA_DENOISE_GUIDE_ALBEDO if albedo is not None else 0)
-                 | (QA_DENOISE_GUIDE_VARIANCE if variance is not None else 0))
+        (h, w), ptrs, out, flags = _denoise_device_planes(rgb, depth, ns, out, normal, albedo, variance)
         p = DenoiseVarianceParams.of(params, flags, iterations, sigma_color, sigma_depth, sigma_normal, variance_scale)
-        sptr = self._stream_arg(stream, rgb)
-        ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731
-        _check(lib().qa_denoise_variance_device(self._h, rgb.data_ptr(), depth.data_ptr(), ns.data_ptr(), ptr(normal), ptr(albedo), ptr(variance), w, h,
-                                                C.byref(p), out.data_ptr(), sptr))
+        _check(lib().qa_denoise_variance_device(self._h, *ptrs, w, h, C.byref(p), out.data_ptr(), self._stream_arg(stream, rgb)))
         return out
 
     def reproject_device(self, cur, history, prev_cam, cur_cam, origin=(0, 0), ids=None, hist_ids=None, out=None, out_length=None, params=None,
@@ -1479,11 +1429,22 @@ class Progressive:
         _check(lib().qa_progressive_display_device(self._ctx._h, int(bool(srgb)), *ptrs, sptr))
         return out
 
+    def _denoise_out(self, out=None, tensor=False):
+        """The float32 [h,w,3] output of the four denoise* calls: a new numpy array, or (tensor) out checked, a new CUDA tensor on the
+        context's device where it is None."""
+        x0, y0, x1, y1 = self.region
+        if not tensor:
+            return np.zeros((y1 - y0, x1 - x0, 3), np.float32)
+        import torch
+        if out is None:
+            out = torch.empty((y1 - y0, x1 - x0, 3), dtype=torch.float32, device=torch.device("cuda", self._ctx.device_id))
+        assert out.is_cuda and out.is_contiguous() and out.numel() == 3 * (x1 - x0) * (y1 - y0) and out.dtype == torch.float32
+        return out
+
     def denoise(self, params=None, iterations=None, sigma_color=None, sigma_depth=None):
         """qa_progressive_denoise: the preview read() returns, filtered on the device straight from the frame's slabs (see
         Context.denoise_device) -> rgb[h,w,3] f32; synchronises.  The frame is not changed."""
-        x0, y0, x1, y1 = self.region
-        rgb = np.zeros((y1 - y0, x1 - x0, 3), np.float32)
+        rgb = self._denoise_out()
         p = DenoiseParams.of(params, iterations, sigma_color, sigma_depth)
         _check(lib().qa_progressive_denoise(self._ctx._h, C.byref(p), rgb.ctypes.data))
         return rgb
@@ -1491,22 +1452,15 @@ class Progressive:
     def denoise_device(self, out=None, params=None, iterations=None, sigma_color=None, sigma_depth=None, stream=None):
         """qa_progressive_denoise_device: the same into a torch CUDA tensor (float32 [h,w,3]; None: a new one) on the context's
         device -> out; only enqueues."""
-        import torch
-        device = torch.device("cuda", self._ctx.device_id)
-        x0, y0, x1, y1 = self.region
-        if out is None:
-            out = torch.empty((y1 - y0, x1 - x0, 3), dtype=torch.float32, device=device)
-        assert out.is_cuda and out.is_contiguous() and out.numel() == 3 * (x1 - x0) * (y1 - y0) and out.dtype == torch.float32
+        out = self._denoise_out(out, tensor=True)
         p = DenoiseParams.of(params, iterations, sigma_color, sigma_depth)
-        sptr = Context._stream_arg(stream, out)
-        _check(lib().qa_progressive_denoise_device(self._ctx._h, C.byref(p), out.data_ptr(), sptr))
+        _check(lib().qa_progressive_denoise_device(self._ctx._h, C.byref(p), out.data_ptr(), Context._stream_arg(stream, out)))
         return out
 
     def denoise_guided(self, params=None, flags=None, iterations=None, sigma_color=None, sigma_depth=None, sigma_normal=None):
         """qa_progressive_denoise_guided: denoise() guided by the frame's own first-hit planes, which the call computes from the scene
         as it now stands (flags: which guides; default both) -> rgb[h,w,3] f32; synchronises.  The frame is not changed."""
-        x0, y0, x1, y1 = self.region
-        rgb = np.zeros((y1 - y0, x1 - x0, 3), np.float32)
+        rgb = self._denoise_out()
         p = DenoiseGuidedParams.of(params, flags, iterations, sigma_color, sigma_depth, sigma_normal)
         _check(lib().qa_progressive_denoise_guided(self._ctx._h, C.byref(p), rgb.ctypes.data))
         return rgb
@@ -1515,14 +1469,9 @@ class Progressive:
                               stream=None):
         """qa_progressive_denoise_guided_device: the same into a torch CUDA tensor (float32 [h,w,3]; None: a new one) -> out; only
         enqueues."""
-        import torch
-        x0, y0, x1, y1 = self.region
-        if out is None:
-            out = torch.empty((y1 - y0, x1 - x0, 3), dtype=torch.float32, device=torch.device("cuda", self._ctx.device_id))
-        assert out.is_cuda and out.is_contiguous() and out.numel() == 3 * (x1 - x0) * (y1 - y0) and out.dtype == torch.float32
+        out = self._denoise_out(out, tensor=True)
         p = DenoiseGuidedParams.of(params, flags, iterations, sigma_color, sigma_depth, sigma_normal)
-        sptr = Context._stream_arg(stream, out)
-        _check(lib().qa_progressive_denoise_guided_device(self._ctx._h, C.byref(p), out.data_ptr(), sptr))
+        _check(lib().qa_progressive_denoise_guided_device(self._ctx._h, C.byref(p), out.data_ptr(), Context._stream_arg(stream, out)))
         return out
 
     def gbuffer_device(self, normal=None, albedo=None, depth=None, ids=None, stream=None):

@@ -109,6 +109,9 @@ def test_progressive_frames_compute_their_own_guides(ctx):
             side.synchronize()
             assert np.array_equal(bits(out.cpu().numpy()), bits(hip.denoise_guided_host(*frame, normal, None, iterations=2)))
             assert np.array_equal(bits(prog.denoise_guided(flags=0)), bits(prog.denoise()))
+            plain, unguided = prog.denoise_device(), prog.denoise_guided_device(flags=0)
+            ctx.synchronize()
+            assert np.array_equal(bits(unguided.cpu().numpy()), bits(plain.cpu().numpy()))
             assert np.array_equal(bits(prog.denoise_guided(iterations=0)), bits(frame[0]))
             assert all(np.array_equal(np.ascontiguousarray(a).view(np.uint32), np.ascontiguousarray(b).view(np.uint32)) for a, b in zip(prog.read(), frame))
         assert not np.array_equal(bits(want), bits(hip.denoise_host(*frame)))

@@ -1,4 +1,4 @@
-"""The variance form of the filter on the device (qa_denoise_variance_device: the pass-0 kernel qa_denoise_guide_variance of
+"""The variance form of the filter on the device (qa_denoise_variance_device: the pass-0 kernel qa_denoise_pass0<true> of
 qa_denoise.hip ahead of the iterate kernels as they are): the device build of the VARIANCE FORM of qa_denoise_dev.h equals the host
 build (qa_test_denoise_variance_host, pinned to a restatement of the specification by tests/test_denoise_variance_host.py) bit for
 bit; and the claim about quality on the renderer's own frames, accumulated by hip.TemporalPreview(moments=True)."""
