@@ -251,6 +251,51 @@ int qa_progressive_status(qa_ctx *ctx, int *spp_reached, uint64_t *pixels_finish
 int qa_progressive_end(qa_ctx *ctx);
 int qa_progressive_restart(qa_ctx *ctx);
 
+/* Passes over some of a progressive frame's tiles: the caller's choice, or the noisiest first.  A pass changes when a pixel takes
+ * its samples, never which: the finished frame keeps the one-shot frame's bits.  The region's 8x8 tiles are counted row-major from
+ * its top left corner, tiles_x = (x1 - x0 + 7) / 8 a row (qa_progressive_tile_count); a mask has one byte per tile, non-zero =
+ * selected.
+ *   qa_progressive_advance_tiles         qa_progressive_advance(T = min(spp_target, spp_max)) restricted to the mask: the selected
+ *   qa_progressive_advance_tiles_device  tiles whose level is below T end at T, nothing else takes a sample (an empty choice still
+ *                           launches and takes none).  The tiles are chosen on the device, in the frame's tile order; both
+ *                           variants only enqueue on hip_stream: the host variant copies its mask to pinned memory first (and
+ *                           waits there for its own previous copy alone), the device variant's mask must stay valid until the
+ *                           pass has run.  Afterwards qa_progressive_status counts the tiles left below T as behind, and a
+ *                           qa_progressive_advance to T (or above) completes them.  Refuses as qa_progressive_advance does
+ *                           (no frame, a stale frame, spp_target < 1) and a null mask: QA_EINVAL.
+ *   qa_progressive_tile_levels[_device]  per tile, the samples every unfinished pixel of it has (uint32).  The host forms of this
+ *   qa_progressive_tile_error[_device]   and the next synchronise, the device forms only enqueue.  The error (float): the mean
+ *                           over the tile's 64 slots of the estimated variance of each live pixel's mean in its worst channel
+ *                           (running variance / samples taken; finished pixels and slots outside the region count 0), summed in
+ *                           a fixed order; +inf while a live pixel has fewer than 2 samples; 0 where all are finished.  The
+ *                           opening comment of qaray_amd/csrc/hip/qa_prog_error_dev.h is the exact rule.
+ *   qa_progressive_advance_adaptive      one pass to T over the noisiest tiles: of the candidates (level < T and error > min_error;
+ *                           min_error 0 leaves finished tiles out) the max_tiles of greatest error, +inf first, equal errors by
+ *                           ascending tile index; max_tiles 0: every candidate.  Error map, selection and pass are enqueued on
+ *                           hip_stream and nothing is read back.  QA_EINVAL also for a min_error that is negative or a NaN.
+ *   qa_progressive_adaptive_info         (synchronises) of the last adaptive pass: out[0] tiles selected, out[1] candidates,
+ *                           out[2] the bits of the smallest selected error (0: none selected), out[3] the bits of the largest
+ *                           finite error among the candidates (0: none).  All 0 before the first such pass of the frame.
+ *   qa_progressive_state    (synchronises) the frame's state slab, 8 words per pixel of the region, row-major: RNG state,
+ *                           samples taken | bit 31 finished, the running mean (3 floats) and variance (3 floats).
+ * A frame begun with spp_min == spp_max keeps no variance: qa_progressive_tile_error* and qa_progressive_advance_adaptive return
+ * QA_EUNSUPPORTED on it (begin with spp_min < spp_max for the estimate); levels and masked passes work on every frame.
+ * qa_test_tile_error_host / qa_test_tile_select_host: the error map of a state slab and the selection rule on the CPU, compiled
+ * from the kernels' source (no context, no GPU); mask gets 1 / 0 per tile, info (may be NULL) qa_progressive_adaptive_info's words. */
+int qa_progressive_tile_count(qa_ctx *ctx, int *tiles_x, int *tiles_y);
+int qa_progressive_advance_tiles(qa_ctx *ctx, int spp_target, const uint8_t *tile_mask, void *hip_stream);
+int qa_progressive_advance_tiles_device(qa_ctx *ctx, int spp_target, const uint8_t *d_tile_mask, void *hip_stream);
+int qa_progressive_tile_levels(qa_ctx *ctx, uint32_t *levels);
+int qa_progressive_tile_levels_device(qa_ctx *ctx, uint32_t *d_levels, void *hip_stream);
+int qa_progressive_tile_error(qa_ctx *ctx, float *error);
+int qa_progressive_tile_error_device(qa_ctx *ctx, float *d_error, void *hip_stream);
+int qa_progressive_advance_adaptive(qa_ctx *ctx, int spp_target, uint32_t max_tiles, float min_error, void *hip_stream);
+int qa_progressive_adaptive_info(qa_ctx *ctx, uint64_t out[4]);
+int qa_progressive_state(qa_ctx *ctx, uint32_t *state);
+int qa_test_tile_error_host(const uint32_t *state, int width, int height, float *error);
+int qa_test_tile_select_host(const float *error, const uint32_t *levels, uint32_t tiles, uint32_t target, uint32_t max_tiles, float min_error,
+                             uint8_t *mask, uint64_t info[4]);
+
 /* The FrameBuffer's 8-bit products of a frame of float results, computed on the device: byte for byte what the host FrameBuffer
  * (Deposit + ComputeZBufferImage + ComputeSampleCountImage) makes of the same floats.  Per pixel:
  *   color     3 bytes: LinearToSRGB when use_srgb, MIN(1, .), MAX(0, .), roundf(c * 255)

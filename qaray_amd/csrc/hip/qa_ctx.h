@@ -233,6 +233,13 @@ struct qa_ctx {
     DevBuf prevRgb, prevDepth, prevNs;   // qa_progressive_read's preview (made on first use)
     unsigned long long *dStatus = nullptr;   // qa_progressive_status: finished pixels, tiles behind, lowest level
     StreamFence done;             // end of the frame's setup / last pass, on whatever stream it ran
+    // tile-selective and noisiest-first passes (made on first use, freed with the frame): the error map, the pass's mask, the host
+    // variant's pinned mask and the end of its last copy, qa_progressive_adaptive_info's four words
+    float *dError = nullptr;
+    uint8_t *dMask = nullptr, *hMask = nullptr;
+    uint32_t *dKeys = nullptr;    // the adaptive selection's key per tile
+    hipEvent_t maskCopied = nullptr;
+    unsigned long long *dInfo = nullptr;
   } prog;
   // the 8-bit products (qa_display.hip): the statistics block (4 working words, then their initial values) and the staging of
   // qa_progressive_display's host variant are made on first use and live as long as the context
@@ -277,10 +284,13 @@ inline void EndProgressive(qa_ctx *c, const char *why)
   qa_ctx::Progressive &f = c->prog;
   if (f.active && why) f.ended = why;
   f.active = false;
-  void *slabs[] = {f.dState, f.dLevel, f.dList, f.dProgress, f.args.rgb, f.args.depth, f.args.ns, f.dStatus};
+  void *slabs[] = {f.dState, f.dLevel, f.dList, f.dProgress, f.args.rgb, f.args.depth, f.args.ns, f.dStatus, f.dError, f.dMask, f.dKeys, f.dInfo};
   if (f.dState) (void) hipDeviceSynchronize();   // (a pass may still run on a stream of the caller's)
   for (void *p : slabs)
     if (p) (void) hipFree(p);
+  if (f.hMask) (void) hipHostFree(f.hMask);
+  if (f.maskCopied) (void) hipEventDestroy(f.maskCopied);
+  f.dError = nullptr; f.dMask = f.hMask = nullptr; f.dKeys = nullptr; f.dInfo = nullptr; f.maskCopied = nullptr;
   f.dState = f.dLevel = f.dList = f.dProgress = f.args.ns = nullptr;
   f.args.rgb = f.args.depth = nullptr;
   f.dStatus = nullptr;

@@ -381,6 +381,18 @@ def lib():
         L.qa_scene_download.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
         L.qa_get_scene_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
         L.qa_progressive_restart.argtypes = [C.c_void_p]
+        L.qa_progressive_tile_count.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.qa_progressive_advance_tiles.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.qa_progressive_advance_tiles_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.qa_progressive_tile_levels.argtypes = [C.c_void_p, C.c_void_p]
+        L.qa_progressive_tile_levels_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.qa_progressive_tile_error.argtypes = [C.c_void_p, C.c_void_p]
+        L.qa_progressive_tile_error_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.qa_progressive_advance_adaptive.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_float, C.c_void_p]
+        L.qa_progressive_adaptive_info.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        L.qa_progressive_state.argtypes = [C.c_void_p, C.c_void_p]
+        L.qa_test_tile_error_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        L.qa_test_tile_select_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p, C.POINTER(C.c_uint64)]
         L.qa_photon_maps_build.argtypes = [C.c_void_p, C.POINTER(PhotonParams), C.c_uint32]
         L.qa_photon_maps_clear.argtypes = [C.c_void_p]
         L.qa_photon_maps_info.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
@@ -392,6 +404,35 @@ def lib():
 def _check(rc):
     if rc != 0:
         raise HipError(rc, lib().qa_last_error().decode())
+
+
+def tile_error_host(state):
+    """qa_test_tile_error_host: the per-tile error map (Progressive.tile_error) of a state slab, uint32 [h,w,8] as
+    Progressive.state() returns it, on the CPU from the source the device kernel is compiled from -> float32 [ty,tx].  No GPU needed."""
+    if not isinstance(state, np.ndarray) or state.dtype != np.uint32 or state.ndim != 3 or state.shape[2] != 8 or state.shape[0] < 1 or state.shape[1] < 1:
+        raise ValueError("state: a uint32 array of shape (h, w, 8) is expected")
+    state = np.ascontiguousarray(state)
+    h, w = state.shape[:2]
+    out = np.zeros(((h + 7) // 8, (w + 7) // 8), np.float32)
+    _check(lib().qa_test_tile_error_host(state.ctypes.data, w, h, out.ctypes.data))
+    return out
+
+
+def tile_select_host(error, levels, target, max_tiles=0, min_error=0.0):
+    """qa_test_tile_select_host: the tiles Progressive.advance_adaptive(target, max_tiles, min_error=min_error) takes, given the
+    tiles' error (float32) and levels (uint32) of one shape, on the CPU from the source the device kernel is compiled from ->
+    (mask, bool of that shape; info dict as Progressive.adaptive_info, the two errors as their uint32 bits).  No GPU needed."""
+    error = np.ascontiguousarray(error, dtype=np.float32)
+    levels = np.ascontiguousarray(levels, dtype=np.uint32)
+    if error.shape != levels.shape or error.size < 1:
+        raise ValueError("error and levels must have one shape and at least one tile")
+    if not min_error >= 0.0:
+        raise ValueError("min_error must not be negative or a NaN")
+    mask = np.zeros(error.shape, np.uint8)
+    v = (C.c_uint64 * 4)()
+    _check(lib().qa_test_tile_select_host(error.ctypes.data, levels.ctypes.data, error.size, int(target), int(max_tiles), float(min_error),
+                                          mask.ctypes.data, v))
+    return mask.astype(bool), {"selected": int(v[0]), "candidates": int(v[1]), "cut_bits": int(v[2]), "max_finite_bits": int(v[3])}
 
 
 def display_host(rgb, depth, ns, spp_max, srgb=True):
@@ -1381,6 +1422,107 @@ class Progressive:
         """Bring every unfinished pixel to min(spp_target, spp_max) samples (one megakernel launch, enqueued on `stream`,
         a HIP stream handle; None = the context's own stream)."""
         _check(lib().qa_progressive_advance(self._ctx._h, int(spp_target), C.c_void_p(stream) if stream else None))
+
+    @property
+    def tile_shape(self):
+        """(tiles_y, tiles_x) of the region's 8x8 tiles (qa_progressive_tile_count): the shape of every per-tile array."""
+        x0, y0, x1, y1 = self.region
+        return (y1 - y0 + 7) // 8, (x1 - x0 + 7) // 8
+
+    def _tile_tensor(self, out, dtype, what):
+        """The (ty, tx) CUDA tensor of a per-tile device call, checked (or made where it is None)."""
+        import torch
+        device = torch.device("cuda", self._ctx.device_id)
+        if out is None:
+            return torch.empty(self.tile_shape, dtype=dtype, device=device)
+        if not isinstance(out, torch.Tensor):
+            raise TypeError(f"{what}: a torch tensor is expected")
+        if not out.is_cuda or out.device != device:
+            raise ValueError(f"{what}: the tensor must be on {device}")
+        if out.dtype != dtype or tuple(out.shape) != self.tile_shape:
+            raise ValueError(f"{what}: {dtype} of shape {self.tile_shape} is expected, not {out.dtype} {tuple(out.shape)}")
+        if not out.is_contiguous():
+            raise ValueError(f"{what}: the tensor must be contiguous")
+        return out
+
+    def advance_tiles(self, spp_target, tiles, stream=None):
+        """qa_progressive_advance_tiles[_device]: advance(spp_target) for the selected tiles alone.  tiles: a numpy bool / uint8
+        array of tile_shape, or a torch uint8 tensor of that shape on the context's device, which must stay as it is until the
+        pass has run; non-zero = selected.  Only enqueues; a later advance(spp_target) completes the other tiles."""
+        if isinstance(tiles, np.ndarray):
+            if tiles.dtype not in (np.bool_, np.uint8):
+                raise TypeError(f"tiles: bool or uint8 is expected, not {tiles.dtype}")
+            if tiles.shape != self.tile_shape:
+                raise ValueError(f"tiles: shape {self.tile_shape} is expected, not {tiles.shape}")
+            mask = np.ascontiguousarray(tiles).view(np.uint8)
+            _check(lib().qa_progressive_advance_tiles(self._ctx._h, int(spp_target), mask.ctypes.data, C.c_void_p(stream) if stream else None))
+            return
+        import torch
+        tiles = self._tile_tensor(tiles, torch.uint8, "tiles")
+        _check(lib().qa_progressive_advance_tiles_device(self._ctx._h, int(spp_target), tiles.data_ptr(), Context._stream_arg(stream, tiles)))
+
+    def tile_levels(self):
+        """qa_progressive_tile_levels -> uint32 array of tile_shape: the samples every unfinished pixel of a tile has; synchronises."""
+        out = np.zeros(self.tile_shape, np.uint32)
+        _check(lib().qa_progressive_tile_levels(self._ctx._h, out.ctypes.data))
+        return out
+
+    def tile_error(self):
+        """qa_progressive_tile_error -> float32 array of tile_shape: the estimated variance of the tiles' pixel means (+inf before a
+        live pixel's second sample, 0 where all are finished); frames begun with spp < spp_max only.  Synchronises."""
+        out = np.zeros(self.tile_shape, np.float32)
+        _check(lib().qa_progressive_tile_error(self._ctx._h, out.ctypes.data))
+        return out
+
+    def tile_levels_device(self, out=None, stream=None):
+        """qa_progressive_tile_levels_device: tile_levels() into a torch CUDA tensor (int32 of tile_shape; None: a new one) -> out;
+        only enqueues."""
+        import torch
+        out = self._tile_tensor(out, torch.int32, "out")
+        _check(lib().qa_progressive_tile_levels_device(self._ctx._h, out.data_ptr(), Context._stream_arg(stream, out)))
+        return out
+
+    def tile_error_device(self, out=None, stream=None):
+        """qa_progressive_tile_error_device: tile_error() into a torch CUDA tensor (float32 of tile_shape; None: a new one) -> out;
+        only enqueues."""
+        import torch
+        out = self._tile_tensor(out, torch.float32, "out")
+        _check(lib().qa_progressive_tile_error_device(self._ctx._h, out.data_ptr(), Context._stream_arg(stream, out)))
+        return out
+
+    def advance_adaptive(self, spp_target, max_tiles=0, fraction=None, min_error=0.0, stream=None):
+        """qa_progressive_advance_adaptive: advance(spp_target) for the noisiest tiles alone - of the tiles below the target whose
+        error exceeds min_error, the max_tiles of greatest error (0: all of them), or `fraction` of the frame's tiles (rounded up,
+        at least one).  Chosen on the device, only enqueues; adaptive_info() says afterwards how many were taken."""
+        if fraction is not None:
+            if max_tiles:
+                raise ValueError("max_tiles and fraction exclude each other")
+            if not 0.0 < fraction <= 1.0:
+                raise ValueError("fraction must be in (0, 1]")
+            ty, tx = self.tile_shape
+            max_tiles = max(1, int(np.ceil(fraction * (ty * tx))))
+        if max_tiles < 0 or max_tiles > 0xFFFFFFFF:
+            raise ValueError("max_tiles out of range")
+        if not min_error >= 0.0:
+            raise ValueError("min_error must not be negative or a NaN")
+        _check(lib().qa_progressive_advance_adaptive(self._ctx._h, int(spp_target), int(max_tiles), float(min_error),
+                                                     C.c_void_p(stream) if stream else None))
+
+    def adaptive_info(self):
+        """qa_progressive_adaptive_info -> dict of the last adaptive pass: selected, candidates, cut_error and max_finite_error
+        (floats; 0.0: none); synchronises."""
+        v = (C.c_uint64 * 4)()
+        _check(lib().qa_progressive_adaptive_info(self._ctx._h, v))
+        bits = np.array([v[2], v[3]], np.uint32).view(np.float32)
+        return {"selected": int(v[0]), "candidates": int(v[1]), "cut_error": float(bits[0]), "max_finite_error": float(bits[1])}
+
+    def state(self):
+        """qa_progressive_state -> uint32 [h,w,8]: every pixel's RNG state, samples taken | bit 31 finished, running mean (3 float
+        words) and variance (3); synchronises."""
+        x0, y0, x1, y1 = self.region
+        out = np.zeros((y1 - y0, x1 - x0, 8), np.uint32)
+        _check(lib().qa_progressive_state(self._ctx._h, out.ctypes.data))
+        return out
 
     def read(self):
         """-> (rgb[h,w,3] f32, depth[h,w] f32, ns[h,w] u32), as render_region returns them; synchronises."""
