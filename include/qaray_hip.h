@@ -192,6 +192,14 @@ int qa_render_strips_device(qa_ctx *ctx, int x0, int y0, int x1, int y1, int fir
                             int spp_min, int spp_max, int max_bounce, uint32_t seed, uint32_t flags,
                             float *d_rgb, float *d_depth, uint32_t *d_nsamples, void *hip_stream);
 int qa_strip_count(int y0, int y1, int first_strip, int strip_step);
+/* Which 8x8 tiles of such a launch does the frame finish in closed form, because no camera ray of theirs can hit anything (option
+ * "empty_tiles"; qaray_amd/csrc/hip/qa_emptytile.h)?  One byte per tile, 1 = empty, strip after strip as above: (x1-x0+7)/8 tiles per
+ * strip, qa_strip_count() strips.  The decision the frame's kernel takes, by the same device function; all zero where a frame of
+ * this context with its current options takes none (another kernel, the option off, depth of field, no tile lists).  Nothing of it
+ * is read back inside a frame.  qa_test_empty_tiles_host: the same from the host build of that header, for a context with default
+ * options (no GPU and no context needed).  No reference counterpart. */
+int qa_empty_tiles_device(qa_ctx *ctx, int x0, int y0, int x1, int y1, int first_strip, int strip_step, uint8_t *d_mask, void *hip_stream);
+int qa_test_empty_tiles_host(const void *blob, int x0, int y0, int x1, int y1, int first_strip, int strip_step, uint8_t *mask);
 /* Wait for everything enqueued by this context. */
 int qa_synchronize(qa_ctx *ctx);
 
@@ -659,6 +667,10 @@ int qa_set_pipeline(qa_ctx *ctx, int mode);
  *   "tile_lists"     -1 (default: on, limit 8) / 0 / n: LDS-resident scenes without depth of field - a wave lists, once per tile,
  *                    the leaves of every mesh's own tree its camera rays can enter, and those rays test the listed triangles
  *                    instead of walking the tree; a mesh whose list for a tile is longer than n leaves is walked (same bits)
+ *   "empty_tiles"    -1 (default) / 1: where "last_cast" and "tile_lists" apply, a one-shot frame finishes the 8x8 tiles whose camera
+ *                    rays can hit nothing - every node's bounds lie outside the tile's pyramid - in closed form: rgb = background,
+ *                    depth = QA_BIGFLOAT, nsamples = spp_min; their samples and casts are counted as the frame holds them, derived
+ *                    and not traced.  0: every tile is traced (same bits, same counters; tests and A/B runs)
  *   "tile_order"     1 (default) / 0: tiles handed out centre-first
  *   "progressive_tile_limit"  tests: n > 0 = a progressive pass takes at most n tiles, then ends as if stopped; 0 (default) = none
  *   "staged_groups"  1 (default) .. 8 tile groups of the staged pipeline, each on its own stream; more than one only pays

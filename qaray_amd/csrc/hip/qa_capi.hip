@@ -455,6 +455,8 @@ int qa_get_counters(qa_ctx *c, qa_counters *out)
     if (h.stamp[19] || h.stamp[21])
       fprintf(stderr, "[stamps] waves without a camera ray: mesh walks of their closest-hit sweeps %.3f (the camera rays': %.3f), after the sweep %.3f | last-cast queries %.3f (mesh walks %.3f), %llu lanes asked again (of %llu casts)\n",
               h.stamp[19] / k, (h.stamp[3] - (double) h.stamp[19]) / k, h.stamp[20] / k, h.stamp[21] / k, h.stamp[22] / k, h.stamp[23], (unsigned long long) h.casts_normal);
+    if (!c->integ[kCs].fn && h.stamp[16])   // qa_integrate_lastcast: slots 15 / 16 (the cooperative kernel's otherwise) are the turns of tiles that tileIsEmpty calls empty (qa_emptytile.h)
+      fprintf(stderr, "[stamps] turns of empty tiles: %llu of %llu turns (%.3f), share of wave time %.4f\n", h.stamp[16], h.stamp[8], (double) h.stamp[16] / (double) std::max<unsigned long long>(h.stamp[8], 1), h.stamp[15] / k);
     if (c->integ[kCs].fn && h.stamp[11])   // qa_integrate_cs reuses slots 10 / 11: items taken from the pool / rounds of the cooperative walks
       fprintf(stderr, "[stamps] cooperative walks: %llu rounds, %.1f of 64 lanes hold an item on average (lane occupancy of the walks %.3f); %.3f of the rounds are leaf rounds; 'mesh walks' above = the rounds alone\n", h.stamp[11],
               (double) h.stamp[10] / (double) h.stamp[11], (double) h.stamp[10] / (64.0 * (double) h.stamp[11]), (double) h.stamp[12] / (double) h.stamp[11]);
@@ -535,6 +537,7 @@ int qa_set_option(qa_ctx *c, const char *name, long long value)
   else if (n == "walk_zero_terms") c->optWalkZeroTerms = value ? 1u : 0u;
   else if (n == "last_cast") c->optLastCast = value < 0 ? -1 : (value ? 1 : 0);
   else if (n == "leaf_sweep") c->optLeafSweep = value < 0 ? -1 : (value ? 1 : 0);
+  else if (n == "empty_tiles") c->optEmptyTiles = value < 0 ? -1 : (value ? 1 : 0);
   else if (n == "chunk_spp") c->optChunkSpp = value < 0 ? -1 : (int) (value > 65535 ? 65535 : value);
   else if (n == "chunk_tail") c->optChunkTail = value < 0 ? 0 : (int) (value > 65535 ? 65535 : value);
   else if (n == "tile_lists") c->optTileLists = value < 0 ? -1 : (int) (value > QA_TILE_LEAF_CAP ? QA_TILE_LEAF_CAP : value);

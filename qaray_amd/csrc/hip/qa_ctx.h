@@ -17,6 +17,8 @@ typedef void (*KernelFn)(const DScene, const RenderParams);
 // What crosses from qa_mega.hip and qa_coop.hip: the pickers, and three sizes of the kernel headers the host needs
 KernelFn PickKernel(bool resident, bool lights, bool tex, bool area, bool stats);
 KernelFn PickLastCastKernel();   // qa_lastcast.hip: resident scenes without lights whose plan has lastCastQuery
+// qa_lastcast.hip: one byte per tile of the launch rp describes - would qa_integrate_lastcast finish it in closed form (qa_emptytile.h)?
+int LaunchEmptyTileMask(const DScene &ds, const RenderParams &rp, unsigned tiles, uint8_t *d_mask, hipStream_t s);
 KernelFn PickCs(bool lights, bool tex, bool cull, bool many, bool area);
 KernelFn PickCsResume(bool lights, bool cull, bool many, bool area);   // (untextured rows only)
 extern const int kMaxPath;             // QA_MAX_PATH: hits per path an AREA variant can log
@@ -211,6 +213,7 @@ struct qa_ctx {
   bool optCsCull = true;        // "cs_cull": instance culling in the cooperative kernel's sweeps (0: every instance is visited; A/B tests)
   int optLastCast = -1;           // "last_cast": -1 / 1 the bounce rays of qa_integrate_lastcast ask which emitter they meet, 0 they run the closest-hit sweep (same kernel, same frame)
   int optLeafSweep = -1;          // "leaf_sweep": -1 / 1 those queries sweep a mesh's leaf table where it has one (DScene::lastCast = 2; qa_kernel.h sweepLeaves), 0 they walk its own tree (same frame)
+  int optEmptyTiles = -1;         // "empty_tiles": -1 / 1 one-shot frames of qa_integrate_lastcast finish the tiles no camera ray can hit anything from in closed form (qa_emptytile.h), 0 they trace them (same frame)
   uint32_t optWalkZeroTerms = 0; // "walk_zero_terms": tests - also walk the shadow rays of lights whose term is zero whatever they find
   uint32_t optCsForceExact = 0; // "cs_force_exact": tests of the exact walks (bit 0 closest-hit, bit 1 shadow queries)
   uint32_t optCsPool = 0;       // "cs_pool_limit": upper bound for the walks' pool capacity (tests force the overflow path)

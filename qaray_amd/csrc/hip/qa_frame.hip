@@ -4,6 +4,7 @@
 #include <cstring>
 
 #include "qa_ctx.h"
+#include "qa_emptytile.h"
 
 // The Halton table of at least `count` samples, made or grown as needed, and the scene record's pointer to it
 int EnsureHalton(qa_ctx *c, int count)
@@ -31,6 +32,13 @@ int EnsureHalton(qa_ctx *c, int count)
 static bool CsManyVariant(const qa_ctx *c) { return c->plan.shadowLights.size() > QA_CS_LIGHT_BATCH && !c->plan.area; }
 // The resident variant whose bounce rays ask which emitter they meet (qa_kernel.h lastCastQuery)
 static bool LastCastVariant(const qa_ctx *c) { return c->plan.resident && c->plan.lastCastQuery && c->ds.num_lights == 0; }
+// Do one-shot frames finish empty tiles in closed form (qa_emptytile.h)?  The kernel that carries the shortcut, the option, and what the
+// kernel itself asks for: tile lists (their LDS row holds the test's pyramid) and no depth of field
+static int TileListLimit(const qa_ctx *c) { return c->plan.tileListBytes ? (c->optTileLists < 0 ? QA_TILE_LISTS_AUTO : c->optTileLists) : 0; }
+static bool EmptyTilesOn(const qa_ctx *c)
+{
+  return QA_EMPTY_TILES && LastCastVariant(c) && c->optEmptyTiles != 0 && TileListLimit(c) > 0 && !(c->ds.cam.dof > 0.1f);
+}
 static bool CsCullVariant(const qa_ctx *c) { return c->plan.csCullOk && (CsManyVariant(c) || c->plan.area || c->plan.textured || c->ds.num_inst > 12); }
 
 // The name of a slot's integrator for the uploaded scene (qa_get_kernel_name)
@@ -134,7 +142,7 @@ int LaunchSetup(qa_ctx *c, Launch &L, const FrameArgs &a, int ownRows, unsigned 
   rp.seed = a.seed;
   rp.tile_row0 = a.tileRow0; rp.tile_row_step = a.tileRowStep; rp.own_tile_rows = ownRows;
   // camera rays on per-tile leaf lists (qa_tilecull.h): where the scene's LDS plan has room for the lists (PlanScene)
-  rp.tile_lists = c->plan.tileListBytes ? (c->optTileLists < 0 ? QA_TILE_LISTS_AUTO : c->optTileLists) : 0;
+  rp.tile_lists = TileListLimit(c);
   rp.sync_samples = c->syncSamples < 0 ? c->plan.syncAuto : c->syncSamples;
   rp.rgb = a.rgb; rp.depth = a.depth; rp.ns = a.ns;
   rp.work_counter = work;
@@ -207,7 +215,8 @@ int LaunchSetup(qa_ctx *c, Launch &L, const FrameArgs &a, int ownRows, unsigned 
   if (pmOn && L.blocks > (long long) c->numCUs * 8) L.blocks = (long long) c->numCUs * 8;   // the heap scratch is sized for this
   if (L.blocks > needBlocks) L.blocks = needBlocks;
   if (L.blocks < 1) L.blocks = 1;
-  rp.chunk_spp = 0; rp.chunk_tail = 0; rp.num_chunks = 1; rp.chunk_pad = 0; rp.tile_progress = nullptr; rp.pix_state = nullptr;
+  rp.chunk_spp = 0; rp.chunk_tail = 0; rp.num_chunks = 1; rp.tile_progress = nullptr; rp.pix_state = nullptr;
+  rp.empty_tiles = (!resume && EmptyTilesOn(c)) ? 1u : 0u;
   return QA_OK;
 }
 
@@ -318,6 +327,27 @@ int qa_render_strips_device(qa_ctx *c, int x0, int y0, int x1, int y1, int first
 {
   if (int rc = Enter(c)) return rc;
   return Render(c, {x0, y0, x1, y1, first_strip, strip_step, spp_min, spp_max, max_bounce, seed, flags, d_rgb, d_depth, d_ns, StreamOf(c, hip_stream)});
+}
+
+int qa_empty_tiles_device(qa_ctx *c, int x0, int y0, int x1, int y1, int first_strip, int strip_step, uint8_t *d_mask, void *hip_stream)
+{
+  if (int rc = Enter(c)) return rc;
+  if (!c->haveScene) return Fail(QA_ENOSCENE, "no scene uploaded");
+  if (x0 < 0 || y0 < 0 || x1 > c->ds.cam.width || y1 > c->ds.cam.height || x1 <= x0 || y1 <= y0) return Fail(QA_EINVAL, "region outside the image");
+  if (!d_mask || first_strip < 0 || strip_step < 1) return Fail(QA_EINVAL, "bad argument");
+  const int ownRows = OwnTileRows(y0, y1, first_strip, strip_step);
+  if (ownRows == 0) return QA_OK;
+  const hipStream_t s = StreamOf(c, hip_stream);
+  const unsigned tiles = (unsigned) ((x1 - x0 + 7) / 8) * (unsigned) ownRows;
+  HIP_TRY(c->lastEdit.WaitOn(s));   // a scene edit's copies run on the context's stream
+  if (!EmptyTilesOn(c)) {           // a frame of this context finishes no tile in closed form
+    HIP_TRY(hipMemsetAsync(d_mask, 0, tiles, s));
+    return QA_OK;
+  }
+  RenderParams rp = {};
+  rp.x0 = x0; rp.y0 = y0; rp.x1 = x1; rp.y1 = y1;
+  rp.tile_row0 = first_strip; rp.tile_row_step = strip_step; rp.own_tile_rows = ownRows;
+  return LaunchEmptyTileMask(c->ds, rp, tiles, d_mask, s);
 }
 
 int qa_strip_count(int y0, int y1, int first_strip, int strip_step)

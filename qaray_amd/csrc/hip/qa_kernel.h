@@ -36,6 +36,7 @@
 #include "qa_seed.h"
 #include "qa_texture_dev.h"
 #include "qa_tilecull.h"
+#include "qa_emptytile.h"
 
 namespace qa {
 
@@ -1709,6 +1710,14 @@ __device__ __forceinline__ void buildTileLists(const DScene &sc, uint32_t limit,
   }
   __builtin_amdgcn_wave_barrier();
 }
+
+// The kernel's scene tables as tileIsEmpty reads them (qa_emptytile.h)
+template <bool RES>
+struct EmptyTileScene {
+  const DScene &sc;
+  __device__ __forceinline__ decltype(auto) inst(int k) const { return instAt<RES>(sc, k); }
+  __device__ __forceinline__ decltype(auto) mesh(int i) const { return meshAt<RES>(sc, i); }
+};
 
 // ---------------------------------------------------------------------------------------------
 // Per-lane path state

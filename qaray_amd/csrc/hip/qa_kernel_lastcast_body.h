@@ -3,7 +3,8 @@
 // scope.  The general body runs such a path as two turns of its per-lane state machine (needSample / done / primary / fromDiffuse as
 // exec masks, throughput and radiance through six LDS columns); here ONE turn of the loop runs one whole sample of every lane that
 // holds a pixel:
-//   A  tile and chunk fetch, hand-over, tile lists, ragged tiles, stop_flag: the text of qa_kernel_body.h section A
+//   A  tile and chunk fetch, hand-over, tile lists, ragged tiles, stop_flag: the text of qa_kernel_body.h section A; and between
+//      the fetch and the hand-over's wait, a tile that no camera ray can hit anything from is written in closed form (qa_emptytile.h)
 //   B  camera ray (DoF draws included)
 //   C  trip 1 of a two-trip loop over (ray, primary): closest-hit sweep of the camera ray, depth at sample 0, miss or shading;
 //      between the trips the bounce rays ask which emitter they meet (lastCastQuery); trip 2, the closest-hit sweep and shading once
@@ -63,6 +64,21 @@
   // what a lane carries from one turn to the next: its random stream, and whether it holds a pixel
   uint32_t rng = 1;
   bool alive = true, needPixel = true;
+#if QA_EMPTY_TILES
+  // n samples, casts or pixels at once, by QA_TALLY's rule (section A: the derived samples of an empty tile)
+#ifdef QA_WAVE_TALLIES
+#define QA_TALLY_N(x, n) (x) += (unsigned long long) (n) * (unsigned long long) __popcll(__ballot(1))
+#else
+#define QA_TALLY_N(x, n) (x) += (unsigned long long) (n)
+#endif
+#ifdef QA_STAMPS
+  // diagnostic builds ask of every tile, whatever the option says: slot 15 = cycles of the turns of tiles the test calls empty, 16 = those turns
+  bool tileEmpty = false;   // (wave-uniform) the tile in hand
+#define QA_EMPTY_ASK true
+#else
+#define QA_EMPTY_ASK (rp.empty_tiles != 0)
+#endif
+#endif
 
   for (;;) {
     QA_T(tA)
@@ -86,6 +102,47 @@
         item -= curChunk * numTiles;
         curTile = item;
         chunkEnd = (int) (rp.chunk_spp + curChunk * rp.chunk_tail);
+#if QA_EMPTY_TILES
+      }   // (the chunk block ends here and opens again for its wait below; without the shortcut it is one block, the parent's text)
+      // ---- a tile no camera ray can hit anything from (qa_emptytile.h) is finished here, in closed form: every sample of every pixel
+      // is the background.  The item that starts the tile's pixels writes them; the tile's later chunks are nothing but this test.
+      // Decided BEFORE the progress wait below: the answer depends on the scene, the camera and the tile alone, so every item of a
+      // tile decides alike in a launch, no item of an empty tile ever publishes progress - and none ever waits for it.
+      if (tileList && QA_EMPTY_ASK && base < total) {
+        const unsigned tile = rp.tile_order ? rp.tile_order[item] : item;
+        const unsigned otr = tile / tilesX;
+        const bool emptyTile = __builtin_amdgcn_readfirstlane((int) tileIsEmpty(
+            EmptyTileScene<RES>{sc}, sc.cam, sc.background, sc.num_inst, sc.rootIdentity != 0, (float) (rp.x0 + (int) ((tile % tilesX) * 8)),
+            (float) (rp.y0 + (int) (((unsigned) rp.tile_row0 + otr * (unsigned) rp.tile_row_step) * 8)), reinterpret_cast<TileCone *>(stack - lane)));
+#ifdef QA_STAMPS
+        tileEmpty = emptyTile;
+#endif
+        if (emptyTile && rp.empty_tiles) {
+          if (alive && (!rp.chunk_spp || curChunk == 0)) {
+            const unsigned tx = (tile % tilesX) * 8 + (lane % 8);
+            const unsigned ty = ((unsigned) rp.tile_row0 + otr * (unsigned) rp.tile_row_step) * 8 + (lane / 8);
+            if (tx < (unsigned) rw && ty < (unsigned) rh) {   // (padding lanes of a ragged tile write nothing)
+              const unsigned q = (otr * 8 + (lane / 8)) * (unsigned) rw + tx;
+              // sample 0 as sections C and E form it: L = 0 + 1 * background, mean = 0 + (L - 0) / 1; no later sample moves it
+              const f3 L0 = F3(0, 0, 0) + F3(1, 1, 1) * ld3(sc.background);
+              const f3 mean = F3(0, 0, 0) + (L0 - F3(0, 0, 0)) / 1.f;
+              rp.rgb[3 * q + 0] = mean.x;
+              rp.rgb[3 * q + 1] = mean.y;
+              rp.rgb[3 * q + 2] = mean.z;
+              rp.depth[q] = QA_BIGFLOAT;
+              rp.ns[q] = (uint32_t) rp.spp_min;
+              // the frame holds these samples and casts: derived, not traced
+              QA_TALLY_N(cnt.samples, rp.spp_min);
+              QA_TALLY_N(cnt.casts_normal, rp.spp_min);
+              QA_TALLY_N(cnt.pixels, 1);
+            }
+          }
+          curTile = 0xFFFFFFFFu;   // nothing to publish
+          continue;                // every lane that is alive still asks for a pixel: the next turn fetches
+        }
+      }
+      if (rp.chunk_spp && base < total) {
+#endif
         if (curChunk > 0) {
           // (the bound is a guard against a lost update, not a path that is taken: qa_kernel_body.h)
           for (int spins = 0; spins < (1 << 22); ++spins) {
@@ -344,7 +401,17 @@
       }
     }
     QA_TACC(cnt.sl[7], tE)
+#if QA_EMPTY_TILES && defined(QA_STAMPS)
+    if (tileEmpty) {
+      QA_TACC(cnt.sl[15], tA)
+      if (lane == 0) cnt.sl[16] += 1;
+    }
+#endif
   }
+#if QA_EMPTY_TILES
+#undef QA_TALLY_N
+#undef QA_EMPTY_ASK
+#endif
 
   // ---- counters: wave reduction, one atomic per wave and counter -----------------------------
   unsigned long long v[6] = {cnt.samples, cnt.casts_normal, cnt.casts_shadow, cnt.bvh_nodes, cnt.tri_tests, cnt.pixels};

@@ -5,6 +5,7 @@
 #include "qa_device_math.h"
 #include "qa_texture_dev.h"
 #include "qa_ctx.h"
+#include "qa_emptytile.h"
 
 namespace qa {
 // qa_debug_scrub_scratch: every lane fills its private segment (2 KB here, more than any kernel of this library uses) with one
@@ -215,6 +216,38 @@ int qa_test_texture_host(const void *blob, int op, int index, int n, const float
   const DTri *tris = op == 8 ? t.mesh[mesh].tris.data() + elem : nullptr;
   const float *vt = op == 8 ? t.mesh[mesh].vt.data() + 6 * (size_t) elem : nullptr;
   for (int i = 0; i < n; ++i) TexProbeOne(tt, tris, vt, op, index, in + (size_t) QA_TEXPROBE_IN * i, out + (size_t) QA_TEXPROBE_OUT * i);
+  return QA_OK;
+}
+
+// The scene tables of a host build as tileIsEmpty reads them (qa_emptytile.h)
+struct EmptyTileSceneHost {
+  const qa_instance *insts;
+  const DMesh *meshes;
+  const qa_instance &inst(int k) const { return insts[k]; }
+  const DMesh &mesh(int i) const { return meshes[i]; }
+};
+
+int qa_test_empty_tiles_host(const void *blob, int x0, int y0, int x1, int y1, int first_strip, int strip_step, uint8_t *mask)
+{
+  if (!blob || !mask || first_strip < 0 || strip_step < 1) return QA_EINVAL;
+  const qa_flat_header *h = static_cast<const qa_flat_header *>(blob);
+  if (h->magic != QA_FLAT_MAGIC || h->version != QA_FLAT_VERSION) return QA_EINVAL;
+  SceneTables t;
+  std::string err;
+  const int rc = BuildScene(static_cast<const unsigned char *>(blob), h->total_bytes, BuildKnobs(), t, &err);
+  if (rc != QA_OK) return rc;
+  const DScene &ds = t.ds;
+  if (x0 < 0 || y0 < 0 || x1 > ds.cam.width || y1 > ds.cam.height || x1 <= x0 || y1 <= y0) return QA_EINVAL;
+  const int tilesX = (x1 - x0 + 7) / 8, tilesY = (y1 - y0 + 7) / 8;
+  // what a context's default options make of the scene (qa_frame.hip EmptyTilesOn)
+  const bool on = QA_EMPTY_TILES && t.plan.resident && t.plan.lastCastQuery && ds.num_lights == 0 && t.plan.tileListBytes && !(ds.cam.dof > 0.1f);
+  const EmptyTileSceneHost s = {QA_BLOB_PTR(qa_instance, blob, h->off_instances), t.plan.meshes.data()};
+  size_t n = 0;
+  for (int row = first_strip; row < tilesY; row += strip_step)
+    for (int tx = 0; tx < tilesX; ++tx) {
+      TileCone cone;
+      mask[n++] = on && tileIsEmpty(s, ds.cam, ds.background, ds.num_inst, ds.rootIdentity != 0, (float) (x0 + tx * 8), (float) (y0 + row * 8), &cone) ? 1 : 0;
+    }
   return QA_OK;
 }
 

@@ -281,7 +281,11 @@ struct RenderParams {
   // Tiles in sample chunks (qa_integrate, section A): chunk_spp > 0 = a work item is (chunk, tile) - a tile's pixels for chunk_spp
   // samples; a pixel's state between chunks (RNG state, samples taken | finished flag, running mean and variance: 8 words) waits in
   // pix_state[8 x output index], tile_progress[tile] = chunks of the tile that are complete (zeroed before the launch)
-  uint32_t chunk_spp, chunk_tail, num_chunks, chunk_pad;   // the first chunk's samples, every further chunk's, how many chunks
+  uint32_t chunk_spp, chunk_tail, num_chunks;   // the first chunk's samples, every further chunk's, how many chunks
+  // qa_integrate_lastcast alone reads this word (it was padding: no field moves, no kernel's arguments change): 1 = one-shot frames
+  // finish the tiles no camera ray can hit anything from in closed form (qa_emptytile.h; option "empty_tiles"), 0 = every tile is traced.
+  // Always 0 for a progressive pass: its work items resume pixels that come with state
+  uint32_t empty_tiles;
   uint32_t *tile_progress;
   uint32_t *pix_state;
   // PHOTON kernel variants (Scene::usePhotonMap): [0] photon map, [1] caustics map, and the per-lane

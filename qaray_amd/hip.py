@@ -302,6 +302,8 @@ def lib():
         L.qa_render_strips_device.argtypes = [C.c_void_p] + [C.c_int] * 9 + [C.c_uint32, C.c_uint32, C.c_void_p,
                                                                             C.c_void_p, C.c_void_p, C.c_void_p]
         L.qa_strip_count.argtypes = [C.c_int] * 4
+        L.qa_empty_tiles_device.argtypes = [C.c_void_p] + [C.c_int] * 6 + [C.c_void_p, C.c_void_p]
+        L.qa_test_empty_tiles_host.argtypes = [C.c_void_p] + [C.c_int] * 6 + [C.c_void_p]
         L.qa_synchronize.argtypes = [C.c_void_p]
         L.qa_request_stop.argtypes = [C.c_void_p]
         L.qa_clear_stop.argtypes = [C.c_void_p]
@@ -416,6 +418,20 @@ def tile_error_host(state):
     out = np.zeros(((h + 7) // 8, (w + 7) // 8), np.float32)
     _check(lib().qa_test_tile_error_host(state.ctypes.data, w, h, out.ctypes.data))
     return out
+
+
+def empty_tiles_host(blob, region, first_strip=0, strip_step=1):
+    """qa_test_empty_tiles_host: the 8x8 tiles of `region` (its strips first_strip, first_strip + strip_step, ...) that a one-shot
+    frame of a context with default options finishes in closed form, because no camera ray of theirs can hit anything (option
+    'empty_tiles'), on the CPU from the source the kernel is compiled from -> bool [strips, tiles per strip].  All False for a scene
+    that does not run on qa_integrate_lastcast with tile lists.  No GPU needed."""
+    blob = np.ascontiguousarray(blob)
+    x0, y0, x1, y1 = (int(v) for v in region)
+    mask = np.zeros((strip_count(y0, y1, first_strip, strip_step), (x1 - x0 + 7) // 8), np.uint8)
+    rc = lib().qa_test_empty_tiles_host(blob.ctypes.data, x0, y0, x1, y1, int(first_strip), int(strip_step), mask.ctypes.data)
+    if rc != 0:
+        raise HipError(rc, "qa_test_empty_tiles_host: bad scene or region")
+    return mask.astype(bool)
 
 
 def tile_select_host(error, levels, target, max_tiles=0, min_error=0.0):
@@ -1325,6 +1341,28 @@ class Context:
                                              max_bounce, seed, QA_RENDER_STATS if stats else 0, rgb.data_ptr(),
                                              depth.data_ptr(), ns.data_ptr(), sptr))
 
+    def empty_tiles_device(self, region, mask, first_strip=0, strip_step=1, stream=None):
+        """qa_empty_tiles_device: which 8x8 tiles of such a launch the frame finishes in closed form, because no camera ray of theirs
+        can hit anything (option 'empty_tiles': rgb = background, depth = 1e30, ns = spp_min, samples derived and not traced) - the
+        decision of the frame's kernel, by the same device function, into `mask`, a torch CUDA uint8 tensor of
+        strip_count(...) * ((x1 - x0 + 7) // 8) elements (1 = empty).  All zero where a frame of this context takes no such decision
+        (another kernel, the option off, depth of field, tile lists off).  Only enqueues."""
+        x0, y0, x1, y1 = (int(v) for v in region)
+        n = strip_count(y0, y1, first_strip, strip_step) * ((x1 - x0 + 7) // 8)
+        assert mask.is_cuda and mask.is_contiguous() and mask.numel() == n and mask.element_size() == 1
+        sptr = self._stream_arg(stream, mask)
+        _check(lib().qa_empty_tiles_device(self._h, x0, y0, x1, y1, int(first_strip), int(strip_step), mask.data_ptr(), sptr))
+
+    def empty_tiles(self, region, first_strip=0, strip_step=1):
+        """empty_tiles_device to host memory -> bool [strips, tiles per strip].  Synchronises."""
+        import torch
+        x0, y0, x1, y1 = (int(v) for v in region)
+        shape = (strip_count(y0, y1, first_strip, strip_step), (x1 - x0 + 7) // 8)
+        mask = torch.zeros(shape, dtype=torch.uint8, device=torch.device("cuda", self.device_id))
+        self.empty_tiles_device(region, mask, first_strip, strip_step)
+        self.synchronize()
+        return mask.cpu().numpy().astype(bool)
+
     @staticmethod
     def _stream_arg(stream, tensor):
         """No stream given: the render runs on the context's own non-blocking stream, which is not ordered against
@@ -1367,7 +1405,7 @@ class Context:
         _check(lib().qa_set_pipeline(self._h, self.PIPELINES[mode]))
 
     def set_option(self, name, value):
-        """qa_set_option: 'coop', 'cs_cull', 'cs_force_exact', 'walk_zero_terms', 'cs_pool_limit', 'chunk_spp', 'chunk_tail', 'tile_lists', 'last_cast', 'leaf_sweep', 'sync_samples', 'tile_order', 'staged_groups', 'verbose',
+        """qa_set_option: 'coop', 'cs_cull', 'cs_force_exact', 'walk_zero_terms', 'cs_pool_limit', 'chunk_spp', 'chunk_tail', 'tile_lists', 'last_cast', 'leaf_sweep', 'empty_tiles', 'sync_samples', 'tile_order', 'staged_groups', 'verbose',
         'progressive_tile_limit'."""
         _check(lib().qa_set_option(self._h, name.encode(), int(value)))
 

@@ -1,6 +1,7 @@
 """Section shares of the megakernel's wave time (diagnostic build: make hip LIBDIR=../lib_stamp OBJDIR=../lib_stamp/obj EXTRA=-DQA_STAMPS).
    QA_HIP_LIB=qaray_amd/lib_stamp/libqaray_hip.so python tools/gpu_stamps.py [spp]
-   QA_LAST_CAST=0: option "last_cast" off (the bounce rays of qa_integrate_lastcast run the closest-hit sweep and shading)"""
+   QA_LAST_CAST=0: option "last_cast" off (the bounce rays of qa_integrate_lastcast run the closest-hit sweep and shading)
+   QA_EMPTY_TILES=0: option "empty_tiles" off - the stamps then show what the turns of empty tiles cost (qa_emptytile.h)"""
 import os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -14,6 +15,7 @@ CASES = [("c2", "example_project12_box.xml", (1920, 1080), 4 * spp), ("c3", "exa
          ("c4", "example_project12_caustics_glossy.xml", (3840, 2160), spp), ("c5", "trc_scene_tower.xml", (3840, 2160), spp)]
 ctx = hip.Context(0)
 if "QA_LAST_CAST" in os.environ: ctx.set_option("last_cast", int(os.environ["QA_LAST_CAST"]))
+if "QA_EMPTY_TILES" in os.environ: ctx.set_option("empty_tiles", int(os.environ["QA_EMPTY_TILES"]))
 for tag, scene, size, n in CASES:
     if tag not in only: continue
     ctx.upload_scene(load_scene_blob(scene, size=size))
