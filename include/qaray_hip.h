@@ -38,6 +38,9 @@
  *   qa_progressive_denoise*        filter for the few-sample previews of an interactive session)
  *   qa_gbuffer_region*,            (no counterpart: what the camera ray of a pixel's first sample sees - depth, normal, diffuse
  *   qa_progressive_gbuffer_device  colour, node and material - for picking in a viewer and as guides for a preview filter)
+ *   qa_matte_region*,              (no counterpart: the same over the camera rays of all of a pixel's samples - coverage, mean
+ *   qa_progressive_matte_device,   albedo, normal and backdrop - and the straight-alpha RGBA picture made from them)
+ *   qa_matte_rgba_device
  *   qa_cast_rays*, qa_occluded*,   (no counterpart: Scene::TraceNodeNormal / TraceNodeShadow for rays of the caller's, and the camera
  *   qa_camera_rays_device          rays PixelRender starts from, handed out)       src/scene/scene.cpp:35-74
  *   qa_denoise_guided_device,      (no counterpart: the preview filter with those normal and albedo planes as two more
@@ -395,6 +398,38 @@ int qa_gbuffer_region(qa_ctx *ctx, int x0, int y0, int x1, int y1, uint32_t seed
                       int32_t *ids);
 int qa_progressive_gbuffer_device(qa_ctx *ctx, float *d_normal, float *d_albedo, float *d_depth, int32_t *d_ids, void *hip_stream);
 
+/* Matte planes of pixels [x0,x1) x [y0,y1): the camera rays of ALL of a pixel's samples, each exactly as qa_render_region builds it
+ * (Halton pair of the sample, texture differentials) and as qa_gbuffer_region casts sample 0, reduced per pixel in sample order (the
+ * opening comment of qaray_amd/csrc/hip/qa_matte_dev.h is the specification).  A pixel takes samples 0 .. n - 1: n = spp, or with a
+ * d_ns plane (region-local, one uint32 per pixel: a frame's sample counts) n = min(ns, spp); n = 0 writes 0 to every plane of the
+ * pixel.  Region-local, row-major planes; every pointer may be NULL (not wanted), but not all of them:
+ *   coverage  1 float    (float) hits / (float) n: the fraction of the samples' camera rays that hit something - a frame's alpha
+ *   albedo    3 floats   the running mean (m += (x - m) / (s + 1), a frame's own rule) of what qa_gbuffer_region's albedo plane holds
+ *                        for each sample's ray: bit for bit the frame of the scene's "emission := diffuse" twin at n samples and no bounce
+ *   normal    3 floats   the running mean of the hit normals over the samples that hit (the divisor counts hits); 0 when none does;
+ *                        not normalised
+ *   backdrop  3 floats   the same mean as albedo's of the backdrop colour on a miss and 0 on a hit: the part of a frame's colour that
+ *                        came from camera rays which met nothing; rgb - backdrop is the premultiplied foreground
+ * With spp = 1 and no ns plane, albedo and normal are qa_gbuffer_region's bits and coverage is 0 or 1.
+ * The kernel only reads the scene: no frame, progressive frame or counter (qa_get_counters) changes.  Codes: QA_ENOSCENE; QA_EINVAL
+ * for an empty region, one outside the image, spp = 0 or no plane at all; QA_EUNSUPPORTED for a camera with depth of field (dof > 0.1),
+ * as qa_camera_sample_rays_device.  A refused call writes nothing.  Ordered as qa_gbuffer_region_device: the device variants only
+ * enqueue on hip_stream (NULL = the context's stream), behind the context's last frame and last edit, and a later edit waits for
+ * them; the host variant (ns and the planes in host memory) copies and synchronises.
+ *   qa_progressive_matte_device   the planes of the progressive frame's region, n = the samples each pixel holds now (read from the
+ *                                 frame's slabs as qa_progressive_read reads them), from the scene as it now stands
+ *   qa_matte_rgba_device          npix pixels of device buffers -> 4 bytes each, straight (unassociated) alpha as PNG stores it:
+ *                                 ns == 0 gives 0, 0, 0, 0; else a = coverage, per component c = a > 0 ? (rgb - backdrop) / a : 0, the
+ *                                 colour byte of c as qa_display_device makes it (sRGB when srgb != 0) and the alpha byte that of a
+ *                                 without sRGB.  Non-finite values end as those bytes do (a NaN: byte 0).  Only enqueues. */
+int qa_matte_region_device(qa_ctx *ctx, int x0, int y0, int x1, int y1, uint32_t spp, const uint32_t *d_ns, float *d_coverage,
+                           float *d_albedo, float *d_normal, float *d_backdrop, void *hip_stream);
+int qa_matte_region(qa_ctx *ctx, int x0, int y0, int x1, int y1, uint32_t spp, const uint32_t *ns, float *coverage, float *albedo,
+                    float *normal, float *backdrop);
+int qa_progressive_matte_device(qa_ctx *ctx, float *d_coverage, float *d_albedo, float *d_normal, float *d_backdrop, void *hip_stream);
+int qa_matte_rgba_device(qa_ctx *ctx, const float *d_rgb, const float *d_backdrop, const float *d_coverage, const uint32_t *d_ns,
+                         uint64_t npix, int srgb, uint8_t *d_rgba, void *hip_stream);
+
 /* Ray queries: n rays of the caller's against the resident scene, through the integrators' own closest-hit and shadow walks (the
  * opening comment of qa_ray_query.hip is the specification).  Ray i has origin origins[3i .. 3i+2] and direction dirs[3i .. 3i+2],
  * world space, fp32, contiguous.  The direction is used as given and NOT normalised: t is the parameter along it (the hit is at
@@ -713,6 +748,15 @@ int qa_test_texture_host(const void *blob, int op, int index, int n, const float
  * for the host, pixel after pixel over host arrays (no GPU and no context needed). */
 int qa_test_display_host(const float *rgb, const float *depth, const uint32_t *nsamples, uint64_t npix, int spp_max, int use_srgb,
                          uint8_t *color, uint8_t *count, uint8_t *zimg, uint8_t *countimg, uint8_t *mask, qa_display_stats *stats);
+
+/* Self-test hooks for the matte planes (qaray_amd/csrc/hip/qa_matte_dev.h): the source of qa_matte_region_device's and
+ * qa_matte_rgba_device's kernels compiled for the host (no GPU and no context needed).  accumulate: one pixel's n samples - values
+ * [n][3] (what the albedo plane of qa_gbuffer_region would hold for each ray), normals [n][3] (read where hit[s] != 0), hit [n] ->
+ * coverage [1], albedo [3], normal [3], backdrop [3]; an output may be NULL.  rgba: npix pixels over host arrays -> rgba [npix][4]. */
+int qa_test_matte_accumulate_host(const float *values, const float *normals, const uint8_t *hit, uint32_t n, float *coverage,
+                                  float *albedo, float *normal, float *backdrop);
+int qa_test_matte_rgba_host(const float *rgb, const float *backdrop, const float *coverage, const uint32_t *nsamples, uint64_t npix,
+                            int srgb, uint8_t *rgba);
 
 /* Self-test hook for the texel conversion (qaray_amd/csrc/hip/qa_texel_dev.h): the source of qa_scene_edit_texels' kernel and of an
  * upload's texel table compiled for the host: h rows of w RGB8 texels, `stride` bytes apart -> w * h entries {r, g, b, 0} / 255.0f

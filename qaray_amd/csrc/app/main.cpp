@@ -9,7 +9,10 @@
 // library's - and encoded as colorBuffer.png is; with -progressive rewritten after each pass; the other three images do not change.
 // N is optional: an argument made of digits alone right after -denoise is taken as N, so a scene file with such a name goes elsewhere
 // on the line or is written ./123), -denoise-guided [N] (as -denoise, through the guided filter with the frame's first-hit normal
-// and albedo planes; the same file).
+// and albedo planes; the same file), -alpha (a fourth image, <prefix>rgbaBuffer.png: the frame with straight alpha, 4 channels - alpha is
+// the fraction of a pixel's camera rays that hit something, the colour the frame's without the backdrop's part; made on the device from
+// the frame's own sample counts (qa_matte_region_device, qa_matte_rgba_device); with -progressive rewritten after each pass; the other
+// three images do not change.  Not with -devices, and not for a camera with depth of field: refused before anything is rendered).
 // The reference's `-sppMax` sets sppMin by mistake (main.cpp:27-28); here it sets sppMax.
 // Flow: Init -> LoadScene -> ComputeScene -> Render -> Terminate (main.cpp:55-59).
 #include <cstdio>
@@ -29,7 +32,7 @@ int main(int argc, char **argv)
   const char *file = nullptr;
   std::string out, root;
   int device = 0, w = -1, h = -1, devices = 0, progressive = 0, denoiseIterations = -1;
-  bool denoise = false, denoiseGuided = false;
+  bool denoise = false, denoiseGuided = false, alpha = false;
   if (argc < 2) { fprintf(stderr, "Error: insufficient input\n"); return -1; }
   for (int i = 1; i < argc; ++i) {
     const std::string s(argv[i]);
@@ -59,6 +62,7 @@ int main(int argc, char **argv)
       if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9' && std::string(argv[i + 1]).find_first_not_of("0123456789") == std::string::npos)
         denoiseIterations = atoi(argv[++i]);
     }
+    else if (s == "-alpha") alpha = true;
     else if (s == "-out") out = next();
     else if (s == "-root") root = next();
     else file = argv[i];
@@ -66,8 +70,10 @@ int main(int argc, char **argv)
   if (!file) { fprintf(stderr, "Error: no scene file\n"); return -1; }
   if (progressive > 0 && devices > 0) { fprintf(stderr, "Error: -progressive renders on one device and cannot be combined with -devices\n"); return -1; }
   if (denoise && devices > 0) { fprintf(stderr, "Error: -denoise filters on one device and cannot be combined with -devices\n"); return -1; }
+  if (alpha && devices > 0) { fprintf(stderr, "Error: -alpha makes its image on one device and cannot be combined with -devices\n"); return -1; }
   try {
     Renderer renderer(param, device);
+    renderer.alpha = alpha;
     renderer.denoise = denoise;
     renderer.denoiseIterations = denoiseIterations;
     renderer.denoiseGuided = denoiseGuided;
@@ -84,6 +90,10 @@ int main(int argc, char **argv)
     LoadSceneInSilentMode(false);
     if (!LoadScene(file, scene)) { fprintf(stderr, "Failed to load %s\n", file); return 1; }
     if (w > 0 && h > 0) { scene.camera.imgWidth = w; scene.camera.imgHeight = h; }
+    if (alpha && scene.camera.depthOfField > 0.1f) {   // (the library's own threshold: qa_matte_region_device refuses such a camera)
+      fprintf(stderr, "Error: -alpha needs a pinhole camera: with depth of field the samples' camera rays cannot be cast again\n");
+      return 1;
+    }
     renderer.ComputeScene(renderImage, scene);
     if (progressive > 0) renderer.RenderProgressive((size_t) progressive);
     else renderer.Render();

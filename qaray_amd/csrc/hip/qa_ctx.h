@@ -1,5 +1,5 @@
 // qa_ctx.h — internals shared by the translation units of libqaray_hip.so (the README's layout line says which unit holds what).
-// Only qa_mega.hip, qa_coop.hip, qa_photon.hip, qa_wf.hip and qa_gbuffer.hip include the kernel headers.  Not part of the C ABI.
+// Only qa_mega.hip, qa_coop.hip, qa_photon.hip, qa_wf.hip, qa_gbuffer.hip and qa_matte.hip include the kernel headers.  Not part of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -183,7 +183,7 @@ struct qa_ctx {
   DCounters *dCounters = nullptr;
   // host-variant staging
   DevBuf stageRgb, stageDepth, stageNs;
-  DevBuf stageGbuffer;            // qa_gbuffer_region: 36 bytes per pixel of the largest region asked for
+  DevBuf stageGbuffer;            // qa_gbuffer_region (36 bytes per pixel) and qa_matte_region (44): sized for the largest region asked for
   // timing
   std::vector<EventPair> pending, freeEvents;
   double totalMs = 0;

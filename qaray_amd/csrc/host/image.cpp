@@ -316,7 +316,7 @@ static void PutChunk(FILE *f, const char *type, const std::vector<unsigned char>
 
 bool SavePNG(const char *filename, const unsigned char *data, int width, int height, int comps)
 {
-  if (comps != 1 && comps != 3) return false;
+  if (comps != 1 && comps != 3 && comps != 4) return false;
   FILE *f = fopen(filename, "wb");
   if (!f) return false;
   static const unsigned char sig[8] = {0x89, 'P', 'N', 'G', 0x0D, 0x0A, 0x1A, 0x0A};
@@ -324,7 +324,7 @@ bool SavePNG(const char *filename, const unsigned char *data, int width, int hei
   std::vector<unsigned char> ihdr(13);
   ihdr[0] = width >> 24; ihdr[1] = width >> 16; ihdr[2] = width >> 8; ihdr[3] = width;
   ihdr[4] = height >> 24; ihdr[5] = height >> 16; ihdr[6] = height >> 8; ihdr[7] = height;
-  ihdr[8] = 8; ihdr[9] = comps == 1 ? 0 : 2; ihdr[10] = 0; ihdr[11] = 0; ihdr[12] = 0;
+  ihdr[8] = 8; ihdr[9] = comps == 1 ? 0 : comps == 3 ? 2 : 6; ihdr[10] = 0; ihdr[11] = 0; ihdr[12] = 0;   // colour type: grey, RGB, RGB with (straight) alpha
   PutChunk(f, "IHDR", ihdr);
   // filter type 0 scanlines in stored (uncompressed) deflate blocks
   const size_t stride = (size_t) width * comps;

@@ -14,7 +14,7 @@ namespace qaray_hip {
 // Decodes to tightly packed RGB8 (alpha dropped, grey replicated, 16-bit -> high byte).
 bool LoadPNG(const char *filename, int &width, int &height, std::vector<unsigned char> &rgb, std::string *err = nullptr);
 bool LoadPPM(const char *filename, int &width, int &height, std::vector<unsigned char> &rgb);
-// comps: 1 (grey) or 3 (RGB), 8 bits per component.
+// comps: 1 (grey), 3 (RGB) or 4 (RGBA, straight alpha), 8 bits per component.
 bool SavePNG(const char *filename, const unsigned char *data, int width, int height, int comps);
 
 // Exposed for tests.

@@ -181,10 +181,10 @@ void Renderer::ThreadRender()
   if (tasking::has_stop_signal()) qa_request_stop(ctx);
   else qa_clear_stop(ctx);
   qa_reset_counters(ctx);
-  if (denoise) {
-    // the frame stays on the device for the filter (Render: SaveDenoised, after the timer has stopped); the FrameBuffer gets the
-    // same floats qa_render_region would have copied back
-    if (!multi.empty() || mpiSize != 1) throw std::runtime_error("-denoise filters on one device and cannot be combined with -devices");
+  if (denoise || alpha) {
+    // the frame stays on the device for the filter and the matte (Render: SaveAlpha, SaveDenoised, after the timer has stopped); the
+    // FrameBuffer gets the same floats qa_render_region would have copied back
+    if (!multi.empty() || mpiSize != 1) throw std::runtime_error("-denoise and -alpha work on one device and cannot be combined with -devices");
     const size_t n = (size_t) W * H;
     denoiseFrame.Alloc(n);
     if (qa_render_region_device(ctx, 0, 0, W, H, (int) param.sppMin, (int) param.sppMax, Material::maxBounce, param.seed, 0, denoiseFrame.rgb,
@@ -242,10 +242,10 @@ void Renderer::Render()
 {
   ThreadRender();
   SaveImages();
-  if (denoise) {   // outside the timed span: the printed time and rate are the render's, with or without the flag
-    SaveDenoised(denoiseFrame.rgb, denoiseFrame.depth, denoiseFrame.ns);
-    denoiseFrame.Free();
-  }
+  // outside the timed span: the printed time and rate are the render's, with or without the flags
+  if (alpha) SaveAlpha(denoiseFrame.rgb, denoiseFrame.ns, false);   // (first: the filter works in place)
+  if (denoise) SaveDenoised(denoiseFrame.rgb, denoiseFrame.depth, denoiseFrame.ns);
+  if (denoise || alpha) denoiseFrame.Free();
 }
 
 // The batch counterpart of Renderer_GUI's progressive display (src/renderers/Renderer_GUI.cpp:37-97, which shows renderImage while
@@ -267,7 +267,7 @@ void Renderer::RenderProgressive(size_t passSpp)
     throw std::runtime_error(std::string("qa_progressive_begin: ") + qa_last_error());
   const size_t n = (size_t) W * H;
   std::vector<uint8_t> color(3 * n), count(n), zimg(n), countimg(n), mask(n);
-  if (denoise) denoiseFrame.Alloc(n);   // -denoise: the preview of each pass, filtered in place
+  if (denoise || alpha) denoiseFrame.Alloc(n);   // -denoise: the preview of each pass, filtered in place; -alpha: its colour and sample counts
   for (size_t spp = 0; spp < param.sppMax;) {
     spp = std::min(spp + passSpp, param.sppMax);
     const bool last = spp >= param.sppMax;
@@ -289,10 +289,11 @@ void Renderer::RenderProgressive(size_t passSpp)
     image->SaveImage((outputPrefix + "colorBuffer.png").c_str());
     image->SaveZImage((outputPrefix + "depthBuffer.png").c_str());
     image->SaveSampleCountImage((outputPrefix + "sampleBuffer.png").c_str());
-    if (denoise) {
+    if (denoise || alpha) {
       if (qa_progressive_read_device(ctx, denoiseFrame.rgb, denoiseFrame.depth, denoiseFrame.ns, nullptr) != QA_OK)
         throw std::runtime_error(std::string("qa_progressive_read_device: ") + qa_last_error());
-      SaveDenoised(denoiseFrame.rgb, denoiseFrame.depth, denoiseFrame.ns);
+      if (alpha) SaveAlpha(denoiseFrame.rgb, denoiseFrame.ns, true);
+      if (denoise) SaveDenoised(denoiseFrame.rgb, denoiseFrame.depth, denoiseFrame.ns);
     }
   }
   denoiseFrame.Free();
@@ -357,6 +358,32 @@ void Renderer::SaveDenoised(float *dRgb, const float *dDepth, const uint32_t *dN
   std::vector<uint8_t> color(3 * n);
   HIP_OR_THROW(hipMemcpy(color.data(), dColor.p, 3 * n, hipMemcpyDeviceToHost));
   SavePNG((outputPrefix + "denoisedBuffer.png").c_str(), color.data(), (int) pixelW, (int) pixelH, 3);
+}
+
+// The frame's colour and sample counts in device buffers -> coverage and backdrop of exactly the samples each pixel holds (the
+// progressive frame's own call while one is open, else the region call with the frame's ns plane) -> straight-alpha bytes ->
+// <prefix>rgbaBuffer.png.  Everything runs on the context's stream, behind the frame
+void Renderer::SaveAlpha(const float *dRgb, const uint32_t *dNs, bool progressive)
+{
+  if (!multi.empty() || mpiSize != 1) throw std::runtime_error("-alpha makes its image on one device and cannot be combined with -devices");
+  const size_t n = pixelW * pixelH;
+  struct Bytes {   // (freed on every way out)
+    uint8_t *p = nullptr;
+    ~Bytes() { if (p) (void) hipFree(p); }
+  } dPlanes;
+  HIP_OR_THROW(hipMalloc((void **) &dPlanes.p, 20 * n));   // [backdrop 12 | coverage 4 | rgba 4] bytes per pixel
+  float *dBackdrop = reinterpret_cast<float *>(dPlanes.p), *dCoverage = dBackdrop + 3 * n;
+  uint8_t *dRgba = reinterpret_cast<uint8_t *>(dCoverage + n);
+  const int rc = progressive ? qa_progressive_matte_device(ctx, dCoverage, nullptr, nullptr, dBackdrop, nullptr)
+                             : qa_matte_region_device(ctx, 0, 0, (int) pixelW, (int) pixelH, (uint32_t) param.sppMax, dNs, dCoverage, nullptr, nullptr,
+                                                      dBackdrop, nullptr);
+  if (rc != QA_OK || qa_matte_rgba_device(ctx, dRgb, dBackdrop, dCoverage, dNs, n, param.useSRGB ? 1 : 0, dRgba, nullptr) != QA_OK)
+    throw std::runtime_error(std::string("-alpha: ") + qa_last_error());
+  qa_synchronize(ctx);
+  std::vector<uint8_t> rgba(4 * n);
+  HIP_OR_THROW(hipMemcpy(rgba.data(), dRgba, 4 * n, hipMemcpyDeviceToHost));
+  if (!SavePNG((outputPrefix + "rgbaBuffer.png").c_str(), rgba.data(), (int) pixelW, (int) pixelH, 4))
+    throw std::runtime_error("-alpha: " + outputPrefix + "rgbaBuffer.png could not be written");
 }
 
 void Renderer::Terminate()

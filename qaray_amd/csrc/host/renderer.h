@@ -70,6 +70,9 @@ class Renderer {
   bool denoise = false;
   int denoiseIterations = -1;
   bool denoiseGuided = false;   // -denoise-guided [N]: the same image through qa_denoise_guided_device with the frame's normal and albedo planes
+  // -alpha: another image, <prefix>rgbaBuffer.png, the frame with straight alpha (4 channels): coverage and backdrop of the frame's own
+  // sample counts (qa_matte_region_device / qa_progressive_matte_device), then qa_matte_rgba_device.  One device only
+  bool alpha = false;
 
  protected:
   RendererParam &param;
@@ -84,7 +87,8 @@ class Renderer {
   void ThreadRenderMulti();
   void SaveImages();                                    // the three PNGs of the FrameBuffer
   void SaveDenoised(float *dRgb, const float *dDepth, const uint32_t *dNs);   // the fourth; dRgb is filtered in place
-  struct DeviceFrame {                                  // -denoise: the frame's floats on the device, freed with the Renderer at the latest
+  void SaveAlpha(const float *dRgb, const uint32_t *dNs, bool progressive);   // rgbaBuffer.png of the frame in device buffers
+  struct DeviceFrame {                                  // -denoise, -alpha: the frame's floats on the device, freed with the Renderer at the latest
     float *rgb = nullptr, *depth = nullptr;
     uint32_t *ns = nullptr;
     void Alloc(size_t npix);

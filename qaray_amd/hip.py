@@ -256,6 +256,7 @@ class ReprojectMomentsParams(C.Structure):   # qa_reproject_moments_params; .def
 
 QA_GBUFFER_BACKFACE = 0x40000000
 GBUFFER_PLANES = ("normal", "albedo", "depth", "ids")   # in the C ABI's order: float32 [h,w,3], [h,w,3], [h,w], int32 [h,w,2]
+MATTE_PLANES = ("coverage", "albedo", "normal", "backdrop")   # in the C ABI's order: float32 [h,w], [h,w,3], [h,w,3], [h,w,3]
 QA_RAY_MISS = 1e30   # the t of a ray that hits nothing (exactly np.float32(1e30))
 RAY_OUTPUTS = ("t", "ids", "normal", "point")   # in the C ABI's order: float32 [n], int32 [n,2], float32 [n,3], [n,3]
 QA_MAX_RAYS = 2 ** 31 - 1
@@ -362,6 +363,12 @@ def lib():
         L.qa_gbuffer_region_device.argtypes = [C.c_void_p] + [C.c_int] * 4 + [C.c_uint32] + [C.c_void_p] * 5
         L.qa_gbuffer_region.argtypes = [C.c_void_p] + [C.c_int] * 4 + [C.c_uint32] + [C.c_void_p] * 4
         L.qa_progressive_gbuffer_device.argtypes = [C.c_void_p] * 6
+        L.qa_matte_region_device.argtypes = [C.c_void_p] + [C.c_int] * 4 + [C.c_uint32] + [C.c_void_p] * 6
+        L.qa_matte_region.argtypes = [C.c_void_p] + [C.c_int] * 4 + [C.c_uint32] + [C.c_void_p] * 5
+        L.qa_progressive_matte_device.argtypes = [C.c_void_p] * 6
+        L.qa_matte_rgba_device.argtypes = [C.c_void_p] * 5 + [C.c_uint64, C.c_int, C.c_void_p, C.c_void_p]
+        L.qa_test_matte_accumulate_host.argtypes = [C.c_void_p] * 3 + [C.c_uint32] + [C.c_void_p] * 4
+        L.qa_test_matte_rgba_host.argtypes = [C.c_void_p] * 4 + [C.c_uint64, C.c_int, C.c_void_p]
         L.qa_cast_rays_device.argtypes = [C.c_void_p, C.c_uint64] + [C.c_void_p] * 7
         L.qa_cast_rays.argtypes = [C.c_void_p, C.c_uint64] + [C.c_void_p] * 6
         L.qa_occluded_device.argtypes = [C.c_void_p, C.c_uint64] + [C.c_void_p] * 5
@@ -464,6 +471,54 @@ def display_host(rgb, depth, ns, spp_max, srgb=True):
     _check(lib().qa_test_display_host(rgb.ctypes.data, depth.ctypes.data, ns.ctypes.data, n, int(spp_max), int(bool(srgb)),
                                       *(a.ctypes.data for a in out), C.addressof(st)))
     return Display(*out, st.as_dict())
+
+
+def matte_accumulate_host(values, normals, hit):
+    """qa_test_matte_accumulate_host: one pixel's matte planes from its n samples on the CPU, from the source the device kernel is
+    compiled from.  values (n, 3) f32: what gbuffer's albedo plane would hold for each sample's ray; normals (n, 3) f32: the hits'
+    normals (read where hit is set); hit (n,) bool -> dict coverage () f32, albedo / normal / backdrop (3,) f32.  No GPU needed."""
+    values = np.ascontiguousarray(values, dtype=np.float32).reshape(-1, 3)
+    normals = np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
+    hit = np.ascontiguousarray(hit).astype(np.uint8).reshape(-1)
+    n = len(hit)
+    if values.shape != (n, 3) or normals.shape != (n, 3):
+        raise ValueError(f"values and normals: shape ({n}, 3) is expected, not {values.shape} and {normals.shape}")
+    out = {"coverage": np.zeros(1, np.float32), "albedo": np.zeros(3, np.float32), "normal": np.zeros(3, np.float32), "backdrop": np.zeros(3, np.float32)}
+    _check(lib().qa_test_matte_accumulate_host(values.ctypes.data, normals.ctypes.data, hit.ctypes.data, n, *(out[k].ctypes.data for k in MATTE_PLANES)))
+    out["coverage"] = out["coverage"].reshape(())
+    return out
+
+
+def matte_rgba_host(rgb, backdrop, coverage, ns, srgb=True):
+    """qa_test_matte_rgba_host: the straight-alpha RGBA bytes of a frame (rgb, backdrop (.., 3) f32; coverage (..) f32; ns (..) u32) on
+    the CPU, from the source the device kernel is compiled from -> uint8 (coverage's shape, 4).  No GPU needed."""
+    rgb = np.ascontiguousarray(rgb, dtype=np.float32)
+    backdrop = np.ascontiguousarray(backdrop, dtype=np.float32)
+    coverage = np.ascontiguousarray(coverage, dtype=np.float32)
+    ns = np.ascontiguousarray(ns, dtype=np.uint32)
+    n = coverage.size
+    if not n or rgb.size != 3 * n or backdrop.size != 3 * n or ns.size != n:
+        raise ValueError("rgb and backdrop hold 3 floats, coverage and ns one value per pixel of a frame that is not empty")
+    out = np.zeros(coverage.shape + (4,), np.uint8)
+    _check(lib().qa_test_matte_rgba_host(rgb.ctypes.data, backdrop.ctypes.data, coverage.ctypes.data, ns.ctypes.data, n, int(bool(srgb)), out.ctypes.data))
+    return out
+
+
+def _matte_tensors(region, device, ns, given):
+    """The device planes of a matte call: the ones given (torch tensors), or all four allocated when none is given, and the
+    optional sample-count plane checked -> (dict name -> tensor, pointers in the C ABI's order, ns pointer or None)."""
+    import torch
+    x0, y0, x1, y1 = region
+    h, w = y1 - y0, x1 - x0
+    shapes = {"coverage": (h, w), "albedo": (h, w, 3), "normal": (h, w, 3), "backdrop": (h, w, 3)}
+    out = {k: v for k, v in given.items() if v is not None}
+    if not out:
+        out = {k: torch.empty(shapes[k], dtype=torch.float32, device=device) for k in MATTE_PLANES}
+    for k, t in out.items():
+        assert t.is_cuda and t.is_contiguous() and t.dtype == torch.float32 and t.numel() == int(np.prod(shapes[k])), k
+    if ns is not None:
+        assert ns.is_cuda and ns.is_contiguous() and ns.element_size() == 4 and not ns.dtype.is_floating_point and ns.numel() == h * w, "ns"
+    return out, [out[k].data_ptr() if k in out else None for k in MATTE_PLANES], None if ns is None else ns.data_ptr()
 
 
 def _denoise_flags(normal, albedo, variance):
@@ -1123,6 +1178,53 @@ class Context:
         _check(lib().qa_gbuffer_region_device(self._h, x0, y0, x1, y1, seed, *ptrs, sptr))
         return out
 
+    def matte(self, region, spp, ns=None):
+        """qa_matte_region: the matte planes of a region over the camera rays of all of a pixel's samples -> dict of numpy arrays:
+        coverage [h,w] f32 (hits / samples: alpha), albedo [h,w,3] f32 (the running mean of gbuffer's albedo over the samples),
+        normal [h,w,3] f32 (the mean hit normal, not normalised; 0 where nothing is hit), backdrop [h,w,3] f32 (the part of a
+        frame's colour that came from rays which met nothing).  ns: uint32 [h,w] sample counts (a frame's ns plane): a pixel takes
+        min(ns, spp) samples, and 0 gives zeros; None: spp everywhere.  A camera with depth of field is refused.  Synchronises."""
+        x0, y0, x1, y1 = region
+        h, w = y1 - y0, x1 - x0
+        if ns is not None:
+            ns = np.ascontiguousarray(ns, dtype=np.uint32)
+            if ns.shape != (h, w):
+                raise ValueError(f"ns: shape {(h, w)} is expected, not {ns.shape}")
+        out = {"coverage": np.zeros((h, w), np.float32), "albedo": np.zeros((h, w, 3), np.float32), "normal": np.zeros((h, w, 3), np.float32),
+               "backdrop": np.zeros((h, w, 3), np.float32)}
+        _check(lib().qa_matte_region(self._h, x0, y0, x1, y1, int(spp), _ptr(ns), *(out[k].ctypes.data for k in MATTE_PLANES)))
+        return out
+
+    def matte_device(self, region, spp, ns=None, coverage=None, albedo=None, normal=None, backdrop=None, stream=None):
+        """qa_matte_region_device into torch CUDA tensors (see matte for the shapes; ns: an int32 / uint32 CUDA tensor [h,w] or None):
+        the planes given are written; when none is given all four are allocated.  -> dict name -> tensor.  Only enqueues (see
+        render_region_device for the stream)."""
+        import torch
+        out, ptrs, nptr = _matte_tensors(region, torch.device("cuda", self.device_id), ns,
+                                         dict(coverage=coverage, albedo=albedo, normal=normal, backdrop=backdrop))
+        sptr = self._stream_arg(stream, next(iter(out.values())))
+        x0, y0, x1, y1 = region
+        _check(lib().qa_matte_region_device(self._h, x0, y0, x1, y1, int(spp), nptr, *ptrs, sptr))
+        return out
+
+    def rgba_device(self, rgb, backdrop, coverage, ns, srgb=True, out=None, stream=None):
+        """qa_matte_rgba_device: the straight-alpha 8-bit RGBA picture of a frame (rgb float32 [h,w,3] and ns int32 / uint32 [h,w] as
+        render_region_device fills them, backdrop and coverage as matte_device(region, spp, ns=ns) does), what a PNG stores: the
+        colour is (rgb - backdrop) / coverage, alpha the coverage, pixels with ns == 0 are 0, 0, 0, 0.  out: the uint8 [h,w,4]
+        tensor to write (None: a new one) -> out.  Only enqueues (see render_region_device for the stream)."""
+        import torch
+        n = coverage.numel()
+        for t, k in ((rgb, 3), (backdrop, 3), (coverage, 1)):
+            assert t.is_cuda and t.is_contiguous() and t.dtype == torch.float32 and t.numel() == k * n
+        assert ns.is_cuda and ns.is_contiguous() and ns.numel() == n and ns.element_size() == 4 and not ns.dtype.is_floating_point
+        if out is None:
+            out = torch.empty(tuple(coverage.shape) + (4,), dtype=torch.uint8, device=rgb.device)
+        assert out.is_cuda and out.is_contiguous() and out.dtype == torch.uint8 and out.numel() == 4 * n
+        sptr = self._stream_arg(stream, rgb)
+        _check(lib().qa_matte_rgba_device(self._h, rgb.data_ptr(), backdrop.data_ptr(), coverage.data_ptr(), ns.data_ptr(), n, int(bool(srgb)),
+                                          out.data_ptr(), sptr))
+        return out
+
     # -- ray queries (qa_ray_query.hip) -----------------------------------------------------------
     def cast_rays_device(self, origins, dirs, t=None, ids=None, normal=None, point=None, stream=None):
         """qa_cast_rays_device: the closest hit of n rays of the caller's, as a path segment of the renderer with that ray meets it.
@@ -1661,6 +1763,17 @@ class Progressive:
         out, ptrs = _gbuffer_tensors(self.region, torch.device("cuda", self._ctx.device_id), dict(normal=normal, albedo=albedo, depth=depth, ids=ids))
         sptr = Context._stream_arg(stream, next(iter(out.values())))
         _check(lib().qa_progressive_gbuffer_device(self._ctx._h, *ptrs, sptr))
+        return out
+
+    def matte_device(self, coverage=None, albedo=None, normal=None, backdrop=None, stream=None):
+        """qa_progressive_matte_device: the matte planes of the frame's region over the samples each pixel holds now, of the scene as
+        it now stands (see Context.matte_device: its planes for spp_max and the ns plane read() gives) -> dict name -> tensor; only
+        enqueues."""
+        import torch
+        out, ptrs, _ = _matte_tensors(self.region, torch.device("cuda", self._ctx.device_id), None,
+                                      dict(coverage=coverage, albedo=albedo, normal=normal, backdrop=backdrop))
+        sptr = Context._stream_arg(stream, next(iter(out.values())))
+        _check(lib().qa_progressive_matte_device(self._ctx._h, *ptrs, sptr))
         return out
 
     def reproject_device(self, history, prev_cam, hist_ids=None, out=None, out_length=None, params=None, depth_tolerance=None, max_history=None,
