@@ -9,8 +9,6 @@
 #include <new>
 
 #include "qa_ctx.h"
-#include "qa_radiance.h"
-#include "qa_ray_query.h"
 
 // The per-thread slab c->plan needs, if any, made on first need and kept with the scene; c->ds points at the one the plan uses
 static int EnsurePlanSlab(qa_ctx *c)
@@ -157,9 +155,7 @@ int qa_ctx_destroy(qa_ctx *c)
     if (p) (void) hipFree(p);
   for (void *p : {(void *) c->hEditStage, (void *) c->hStop})
     if (p) (void) hipHostFree(p);
-  for (DevBuf *b : {&c->pixState, &c->tileProgress, &c->stageRgb, &c->stageDepth, &c->stageNs, &c->stageGbuffer, &c->displayStage, &c->denoisePlanes, &c->reprojectIds}) b->Free();
-  FreeRayQueryStage(c);
-  FreeRadianceStage(c);
+  for (DevBuf *b : {&c->pixState, &c->tileProgress, &c->stageRgb, &c->stageDepth, &c->stageNs, &c->stageQuery, &c->displayStage, &c->denoisePlanes, &c->reprojectIds}) b->Free();
   for (StreamFence *f : {&c->lastFrame, &c->lastEdit, &c->lastDisplay, &c->lastDenoise, &c->lastReproject, &c->texSource, &c->prog.done})
     if (f->ev) (void) hipEventDestroy(f->ev);
   if (c->stream) (void) hipStreamDestroy(c->stream);

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <string>
 #include <vector>
@@ -183,7 +184,8 @@ struct qa_ctx {
   DCounters *dCounters = nullptr;
   // host-variant staging
   DevBuf stageRgb, stageDepth, stageNs;
-  DevBuf stageGbuffer;            // qa_gbuffer_region (36 bytes per pixel) and qa_matte_region (44): sized for the largest region asked for
+  DevBuf stageQuery;              // the host forms of the guide planes, the matte planes, the ray queries and the radiance queries: one buffer, sized
+                                  // for the largest call so far - each of them ends with hipStreamSynchronize(stream), so no two use it at once
   // timing
   std::vector<EventPair> pending, freeEvents;
   double totalMs = 0;
@@ -310,6 +312,39 @@ inline int Enter(qa_ctx *c)
 inline hipStream_t StreamOf(qa_ctx *c, void *hip_stream) { return hip_stream ? (hipStream_t) hip_stream : c->stream; }
 // where the upload report goes ("verbose", QA_FAST_VERBOSE), else null
 inline FILE *Report(const qa_ctx *c) { return (c->optVerbose || DevEnv("QA_FAST_VERBOSE")) ? stderr : nullptr; }
+
+// A region checked as a frame's is (CheckFrame), for the calls that take nothing else of a frame
+inline int CheckRegion(qa_ctx *c, int x0, int y0, int x1, int y1)
+{
+  FrameArgs a;
+  a.x0 = x0; a.y0 = y0; a.x1 = x1; a.y1 = y1;
+  return CheckFrame(c, a);
+}
+
+// Enqueues a kernel that only reads the scene (guide planes, matte planes, ray queries): fn(DScene, Params).  Ordered as a frame
+// is: behind the context's last frame and last edit, and the next edit waits for it (it reads the tables an edit rewrites).  The
+// kernel's dynamic LDS is laid out as a prefix of the megakernel's, so it gets that kernel's LDS size and stack depth; the grid
+// is persistent (what is resident at once, a workgroup of a resident scene first copies the scene image), at most needBlocks
+template <class Fn, class Params>
+inline int LaunchSceneKernel(qa_ctx *c, Fn fn, const Params &p, long long needBlocks, hipStream_t s)
+{
+  HIP_TRY(c->lastFrame.WaitOn(s));
+  HIP_TRY(c->lastEdit.WaitOn(s));
+  const Integrator &mega = c->integ[kMega];
+  DScene ds = c->ds;
+  ds.stackDepth = mega.stackDepth;
+  const long long blocks = std::max<long long>(1, std::min<long long>(needBlocks, (long long) c->numCUs * OccupancyBlocks((KernelFn) fn, mega.ldsBytes)));
+  hipLaunchKernelGGL(fn, dim3((unsigned) blocks), dim3(QA_BLOCK), (unsigned) mega.ldsBytes, s, ds, p);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(c->lastFrame.Record(s));
+  return QA_OK;
+}
+// the workgroups a region's 8x8 tiles need, one wave per tile
+inline long long TileBlocks(int x0, int y0, int x1, int y1)
+{
+  const long long tiles = (long long) ((x1 - x0 + 7) / 8) * ((y1 - y0 + 7) / 8);
+  return (tiles + QA_BLOCK / 64 - 1) / (QA_BLOCK / 64);
+}
 
 // What every qa_progressive_* call on a frame says when there is none (or why the last one ended)
 inline int ProgActive(qa_ctx *c)

@@ -221,6 +221,8 @@
     if (!__any(alive)) break;
 
     // ---- B. start a sample: camera ray (src/renderers/renderer.cpp:312-328) ------------------
+    // (qa_firsthit.h restates the camera ray of this section, the reset of section C and the material lookup of section D for the
+    // read-only passes: camTexpos / camLensPos / camPoint, hitInit / texHitInit, hitMaterial.  A change here is a change there.)
     // sync_samples: lanes wait until the whole wave is between samples, so that the coherent
     // camera rays of a tile are traced together instead of next to incoherent secondary rays
     const bool goSample = !rp.sync_samples || (__ballot(needSample) == __ballot(alive && !needPixel));

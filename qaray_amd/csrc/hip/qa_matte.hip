@@ -10,7 +10,7 @@
 // wave takes its next tile from a counter with one atomic, as section A does, not by stride as qa_gbuffer's one-cast frames do.
 #include <algorithm>
 
-#include "qa_kernel.h"
+#include "qa_firsthit.h"
 #include "qa_ctx.h"
 #include "qa_matte_dev.h"
 
@@ -28,23 +28,12 @@ struct MatteParams {
 template <bool RES, bool TEX>
 __global__ __launch_bounds__(QA_BLOCK) void qa_matte(const DScene sc, const MatteParams mp)
 {
-  // dynamic LDS as qa_integrate lays it out: [resident scene image (RES) | traversal stacks (stackDepth x 256)]
   extern __shared__ uint4 s_dyn[];
   SceneMem<RES> mem;
   mem.img = s_dyn;
-  if (RES) {
-    for (uint32_t i = threadIdx.x; i < sc.residentVec4; i += QA_BLOCK) s_dyn[i] = sc.resident[i];
-    __syncthreads();
-  }
-  uint32_t *stack = reinterpret_cast<uint32_t *>(s_dyn + (RES ? sc.residentVec4 : 0)) + threadIdx.x;
-  const uint4 *mtlTable = RES ? s_dyn + sc.resMaterials : reinterpret_cast<const uint4 *>(sc.mtl);
-  TexTables tt;
-  tt.blob = sc.blob;
-  tt.texels = sc.texels;
-  tt.texOff = sc.texOff;
-  tt.texmap = sc.texmap;
-  tt.tex = sc.tex;
-  tt.filter = sc.texFilter;
+  uint32_t *stack = sceneToLds<RES>(sc, s_dyn);
+  const uint4 *mtlTable = materialTable<RES>(sc, s_dyn);
+  const TexTables tt = texTables(sc);
   DCounters cnt = {};   // (traceClosest tallies into it; never written out)
 
   const int rw = mp.x1 - mp.x0, rh = mp.y1 - mp.y0;
@@ -53,7 +42,6 @@ __global__ __launch_bounds__(QA_BLOCK) void qa_matte(const DScene sc, const Matt
   const unsigned lane = __lane_id();
   // the colour of a sample feeds albedo and backdrop alone: a call for coverage and / or normals looks no material or texture up
   const bool wantColor = mp.albedo || mp.backdrop;
-  const f3 A = ld3(sc.cam.screenA), U = ld3(sc.cam.screenU), V = ld3(sc.cam.screenV);
   const f3 campos = ld3(sc.cam.pos);   // (pinhole: a camera with dof > 0.1 is refused by the host)
 
   for (;;) {
@@ -84,60 +72,32 @@ __global__ __launch_bounds__(QA_BLOCK) void qa_matte(const DScene sc, const Matt
     for (int off = 32; off > 0; off >>= 1) nmax = max(nmax, (uint32_t) __shfl_xor(nmax, off));
     for (uint32_t s = 0; s < nmax; ++s) {
       if (s >= n) continue;
-      // ---- the camera ray of sample s: qa_kernel.h section B, the same operations in the same order
-      const float hx = sc.halton[2 * s], hy = sc.halton[2 * s + 1];
-      const f3 texpos = F3(hx, hy, 0.f) + F3((float) px, (float) py, 0.f);
-      const f3 cpt = (A + U * texpos.x) + V * texpos.y;
+      // the camera ray of sample s, and its cast
+      const f3 texpos = camTexpos(sc.halton, (int) s, px, py);
       Ray ray;
       ray.p = campos;
-      ray.d = normalize(cpt - campos);
+      ray.d = normalize(camPoint(sc.cam, texpos.x, texpos.y) - campos);
       RayDiff diff;
       diff.dx = diff.dy = F3(0, 0, 1);
       if (TEX) {
-        const f3 xpt = (A + U * (texpos.x + QA_DX)) + V * texpos.y;
-        const f3 ypt = (A + U * texpos.x) + V * (texpos.y + QA_DX);
-        diff.dx = normalize(xpt - campos);
-        diff.dy = normalize(ypt - campos);
+        diff.dx = normalize(camPoint(sc.cam, texpos.x + QA_DX, texpos.y) - campos);
+        diff.dy = normalize(camPoint(sc.cam, texpos.x, texpos.y + QA_DX) - campos);
       }
-
-      // ---- the cast: section C
       Hit h;
-      h.z = QA_BIGFLOAT;
-      h.node = -1;
-      h.mtlID = 0;
-      h.front = true;
-      h.p = F3(0, 0, 0);
-      h.N = F3(0, 0, 0);
+      hitInit(h);
       TexHit th;
-      th.uvw = F3(0.5f, 0.5f, 0.5f);
-      th.duvw0 = th.duvw1 = F3(0, 0, 0);
-      th.hasTexture = false;
+      texHitInit(th);
       const bool found = traceClosest<RES, TEX, false>(mem, sc, ray, diff, h, th, stack, cnt);
 
-      // ---- x_s: what qa_gbuffer writes to its albedo plane for this ray
+      // x_s: what qa_gbuffer writes to its albedo plane for this ray
       f3 kd = F3(0, 0, 0);
       if (wantColor) {
         if (!found) {
-          kd = ld3(sc.background);
-          if (TEX) kd = texColorSample(tt, kd, sc.bgTexmap, F3(texpos.x / (float) sc.cam.width, texpos.y / (float) sc.cam.height, 0.f));
+          kd = missColor<TEX>(sc, tt, texpos);
         } else {
-          const qa_instance &in = instAt<RES>(sc, h.node);
-          int mi = -1;
-          bool white = false;
-          if (in.mtlset >= 0) {
-            const qa_mtlset ms = sc.mtlset[in.mtlset];
-            if (ms.multi) {
-              if (h.mtlID >= 0 && h.mtlID < ms.count) mi = ms.first + h.mtlID;
-              else white = true;
-            } else mi = ms.first;
-          }
-          if (mi < 0) {
-            kd = white ? F3(1, 1, 1) : F3(0, 0, 0);
-          } else {
-            const uint4 m0 = mtlTable[6 * (size_t) mi];
-            kd = F3(asF(m0.x), asF(m0.y), asF(m0.z));
-            if (TEX) kd = mtlSample(tt, th, kd, sc.mtlTex[8 * (size_t) mi]);
-          }
+          bool white;
+          const int mi = hitMaterial(sc.mtlset, instAt<RES>(sc, h.node).mtlset, h.mtlID, white);
+          kd = hitColor<TEX>(sc, tt, mtlTable, th, mi, white);
         }
       }
       matteAccSample(acc, s, found, kd.x, kd.y, kd.z, h.N.x, h.N.y, h.N.z);
@@ -175,12 +135,10 @@ static MatteFn PickMatte(bool resident, bool tex)
 
 struct MattePlanes { float *coverage, *albedo, *normal, *backdrop; };
 
-// What every entry refuses, before anything is written or sized: the region as a frame's is checked (CheckFrame), then the call's own
+// What every entry refuses, before anything is written or sized: the region as a frame's is checked (CheckRegion), then the call's own
 static int CheckMatte(qa_ctx *c, int x0, int y0, int x1, int y1, uint32_t spp, const MattePlanes &o)
 {
-  FrameArgs a;
-  a.x0 = x0; a.y0 = y0; a.x1 = x1; a.y1 = y1;
-  if (int rc = CheckFrame(c, a)) return rc;
+  if (int rc = CheckRegion(c, x0, y0, x1, y1)) return rc;
   if (spp == 0 || spp > 0x7FFFFFFFu) return Fail(QA_EINVAL, "bad spp");
   if (!o.coverage && !o.albedo && !o.normal && !o.backdrop) return Fail(QA_EINVAL, "no output plane");
   if (c->ds.cam.dof > 0.1f)
@@ -188,35 +146,16 @@ static int CheckMatte(qa_ctx *c, int x0, int y0, int x1, int y1, uint32_t spp, c
   return QA_OK;
 }
 
-// One launch.  Ordered as GBuffer's: behind the context's last frame and last edit, and the next edit waits for it (it reads the
-// tables an edit rewrites).  The tile counter is one of the context's ring of work counters, cleared on s ahead of the launch
+// One launch, as GBuffer's.  The tile counter is one of the context's ring of work counters, cleared on s ahead of the launch
 static int Matte(qa_ctx *c, int x0, int y0, int x1, int y1, uint32_t spp, const uint32_t *ns, const uint32_t *state, const MattePlanes &o, hipStream_t s)
 {
   if (int rc = CheckMatte(c, x0, y0, x1, y1, spp, o)) return rc;
   if (int rc = EnsureHalton(c, (int) spp)) return rc;
-  HIP_TRY(c->lastFrame.WaitOn(s));
-  HIP_TRY(c->lastEdit.WaitOn(s));
   unsigned int *work = c->dWork + c->workNext;
   c->workNext = (c->workNext + 1) % qa_ctx::kCounterRing;
   HIP_TRY(hipMemsetAsync(work, 0, sizeof(unsigned int), s));
-  // the <RES, TEX> instance by the frame launcher's predicate (plan.resident, plan.textured), with the megakernel's LDS size and
-  // stack depth, as PickGBuffer's
-  const ScenePlan &p = c->plan;
-  const MatteFn fn = PickMatte(p.resident, p.textured);
-  const size_t lds = c->integ[kMega].ldsBytes;
-  DScene ds = c->ds;
-  ds.stackDepth = c->integ[kMega].stackDepth;
   const MatteParams mp = {x0, y0, x1, y1, spp, ns, state, o.coverage, o.albedo, o.normal, o.backdrop, work};
-  const long long tiles = (long long) ((x1 - x0 + 7) / 8) * ((y1 - y0 + 7) / 8);
-  const long long needBlocks = (tiles + QA_BLOCK / 64 - 1) / (QA_BLOCK / 64);
-  int perCU = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, (const void *) fn, QA_BLOCK, lds) != hipSuccess || perCU < 1) perCU = 2;
-  long long blocks = std::min<long long>(needBlocks, (long long) c->numCUs * std::min(perCU, 8));
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(fn, dim3((unsigned) blocks), dim3(QA_BLOCK), (unsigned) lds, s, ds, mp);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(c->lastFrame.Record(s));
-  return QA_OK;
+  return LaunchSceneKernel(c, PickMatte(c->plan.resident, c->plan.textured), mp, TileBlocks(x0, y0, x1, y1), s);
 }
 
 extern "C" {
@@ -235,11 +174,10 @@ int qa_matte_region(qa_ctx *c, int x0, int y0, int x1, int y1, uint32_t spp, con
   if (int rc = Enter(c)) return rc;
   const MattePlanes host = {coverage, albedo, normal, backdrop};
   if (int rc = CheckMatte(c, x0, y0, x1, y1, spp, host)) return rc;   // before anything is sized by the region
-  // staging [coverage 4 | albedo 12 | normal 12 | backdrop 12 | ns 4] bytes per pixel in qa_gbuffer_region's buffer: it only grows,
-  // and is only used synchronously
+  // staging [coverage 4 | albedo 12 | normal 12 | backdrop 12 | ns 4] bytes per pixel: only grows, and is only used synchronously
   const size_t npix = (size_t) (x1 - x0) * (size_t) (y1 - y0);
-  HIP_TRY(c->stageGbuffer.Reserve(npix * 44));
-  float *dC = (float *) c->stageGbuffer.p, *dA = dC + npix, *dN = dA + 3 * npix, *dB = dN + 3 * npix;
+  HIP_TRY(c->stageQuery.Reserve(npix * 44));
+  float *dC = (float *) c->stageQuery.p, *dA = dC + npix, *dN = dA + 3 * npix, *dB = dN + 3 * npix;
   uint32_t *dS = (uint32_t *) (dB + 3 * npix);
   if (ns) HIP_TRY(hipMemcpyAsync(dS, ns, npix * 4, hipMemcpyHostToDevice, c->stream));
   const MattePlanes dev = {coverage ? dC : nullptr, albedo ? dA : nullptr, normal ? dN : nullptr, backdrop ? dB : nullptr};

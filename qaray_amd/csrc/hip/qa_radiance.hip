@@ -51,12 +51,9 @@
 // order (not sorted).
 #include <algorithm>
 #include <cstring>
-#include <mutex>
-#include <unordered_map>
 
-#include "qa_kernel.h"
+#include "qa_firsthit.h"
 #include "qa_ctx.h"
-#include "qa_radiance.h"
 
 static_assert(QA_RAYS_PER_SAMPLE == QA_RADIANCE_PER_SAMPLE && QA_RAYS_MISS_ENVIRONMENT == QA_RADIANCE_MISS_ENVIRONMENT, "RayBatch::flags are the C ABI's");
 
@@ -80,23 +77,18 @@ __global__ __launch_bounds__(QA_BLOCK) void qa_camera_sample_rays(const DCamera 
   const int k = (int) (i % (uint64_t) cs.count), si = cs.first + k;
   const int px = cs.x0 + (int) (q % rw), py = cs.y0 + (int) (q / rw);
 
-  // ---- the camera ray of sample si: qa_kernel_body.h section B, the same operations in the same order (pinhole: dof <= 0.1)
-  const float hx = halton[2 * si], hy = halton[2 * si + 1];
-  const f3 texpos = F3(hx, hy, 0.f) + F3((float) px, (float) py, 0.f);
-  const f3 A = ld3(cam.screenA), U = ld3(cam.screenU), V = ld3(cam.screenV);
-  const f3 cpt = (A + U * texpos.x) + V * texpos.y;
+  // (pinhole: a camera with dof > 0.1 is refused by the host)
+  const f3 texpos = camTexpos(halton, si, px, py);
   const f3 campos = ld3(cam.pos);
-  const f3 dir = normalize(cpt - campos);
+  const f3 dir = normalize(camPoint(cam, texpos.x, texpos.y) - campos);
   if (cs.o) { cs.o[3 * i] = campos.x; cs.o[3 * i + 1] = campos.y; cs.o[3 * i + 2] = campos.z; }
   if (cs.d) { cs.d[3 * i] = dir.x; cs.d[3 * i + 1] = dir.y; cs.d[3 * i + 2] = dir.z; }
   if (cs.dx) {
-    const f3 xpt = (A + U * (texpos.x + QA_DX)) + V * texpos.y;
-    const f3 v = normalize(xpt - campos);
+    const f3 v = normalize(camPoint(cam, texpos.x + QA_DX, texpos.y) - campos);
     cs.dx[3 * i] = v.x; cs.dx[3 * i + 1] = v.y; cs.dx[3 * i + 2] = v.z;
   }
   if (cs.dy) {
-    const f3 ypt = (A + U * texpos.x) + V * (texpos.y + QA_DX);
-    const f3 v = normalize(ypt - campos);
+    const f3 v = normalize(camPoint(cam, texpos.x, texpos.y + QA_DX) - campos);
     cs.dy[3 * i] = v.x; cs.dy[3 * i + 1] = v.y; cs.dy[3 * i + 2] = v.z;
   }
   if (cs.screen) { cs.screen[2 * i] = texpos.x; cs.screen[2 * i + 1] = texpos.y; }
@@ -121,24 +113,6 @@ static RaysFn PickRays(const qa_ctx *c)
   const ScenePlan &p = c->plan;
   const bool lights = c->ds.num_lights > 0;
   return p.resident ? PickRaysShading<true>(lights, p.textured, p.area) : PickRaysShading<false>(lights, p.textured, p.area);
-}
-
-// The host forms' staging: one device buffer per context that only grows and is only used synchronously, kept here as
-// qa_ray_query.hip keeps its own (qa_ctx.h is part of the integrator units).  qa_ctx_destroy frees it (FreeRadianceStage)
-static std::mutex g_stageLock;
-static std::unordered_map<const qa_ctx *, DevBuf> g_stage;
-static DevBuf &StageOf(const qa_ctx *c)
-{
-  std::lock_guard<std::mutex> hold(g_stageLock);
-  return g_stage[c];
-}
-void FreeRadianceStage(qa_ctx *c)
-{
-  std::lock_guard<std::mutex> hold(g_stageLock);
-  auto it = g_stage.find(c);
-  if (it == g_stage.end()) return;
-  it->second.Free();
-  g_stage.erase(it);
 }
 
 #define QA_MAX_RAYS 0x7FFFFFFFull
@@ -244,9 +218,8 @@ int qa_radiance_rays(qa_ctx *c, uint64_t n, const float *origins, const float *d
   if (n == 0) return QA_OK;
   // staging, in floats per ray: [rgb 3 | t 1 | ns 1 | stream 1] then per record [origins 3 | dirs 3 | dx 3 | dy 3 | screen 2]
   const uint64_t r = n * ((params->flags & QA_RADIANCE_PER_SAMPLE) ? (uint64_t) params->spp : 1ull);
-  DevBuf &stage = StageOf(c);
-  HIP_TRY(stage.Reserve((size_t) (n * 6 + r * 14) * sizeof(float)));
-  float *dRgb = (float *) stage.p, *dT = dRgb + 3 * n;
+  HIP_TRY(c->stageQuery.Reserve((size_t) (n * 6 + r * 14) * sizeof(float)));
+  float *dRgb = (float *) c->stageQuery.p, *dT = dRgb + 3 * n;
   uint32_t *dNs = (uint32_t *) (dT + n), *dStream = dNs + n;
   float *dO = (float *) (dStream + n), *dD = dO + 3 * r, *dDx = dD + 3 * r, *dDy = dDx + 3 * r, *dScreen = dDy + 3 * r;
   HIP_TRY(hipMemcpyAsync(dO, origins, r * 12, hipMemcpyHostToDevice, c->stream));
@@ -270,9 +243,7 @@ int qa_camera_sample_rays_device(qa_ctx *c, int x0, int y0, int x1, int y1, int 
                                  float *d_dy, float *d_screen, uint32_t *d_stream, void *hip_stream)
 {
   if (int rc = Enter(c)) return rc;
-  FrameArgs a;   // the region is checked as a frame's is
-  a.x0 = x0; a.y0 = y0; a.x1 = x1; a.y1 = y1;
-  if (int rc = CheckFrame(c, a)) return rc;
+  if (int rc = CheckRegion(c, x0, y0, x1, y1)) return rc;
   if (first < 0 || count < 1 || (long long) first + count > 0x7FFFFFFFll) return Fail(QA_EINVAL, "bad sample range");
   if (!d_origins && !d_dirs && !d_dx && !d_dy && !d_screen && !d_stream) return Fail(QA_EINVAL, "no output");
   if (c->ds.cam.dof > 0.1f)

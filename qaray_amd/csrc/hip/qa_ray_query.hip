@@ -32,12 +32,9 @@
 // calls on the same operands, so the hits of a textured scene come out the same (tests/test_gpu_ray_query.py holds both to the
 // guide planes and the CPU restatement bit for bit on textured scenes).
 #include <algorithm>
-#include <mutex>
-#include <unordered_map>
 
-#include "qa_kernel.h"
+#include "qa_firsthit.h"
 #include "qa_ctx.h"
-#include "qa_ray_query.h"
 
 namespace qa {
 
@@ -59,25 +56,12 @@ struct CamRayParams {
   float *o, *d;             // [(y1 - y0) * (x1 - x0)][3] each
 };
 
-#define QA_RAY_BACK 0x40000000   /* bit 30 of the material word, as QA_GBUF_BACK */
-
 __device__ __forceinline__ bool loadRay(const float *o, const float *d, uint64_t i, Ray &ray)
 {
   ray.p = F3(o[3 * i], o[3 * i + 1], o[3 * i + 2]);
   ray.d = F3(d[3 * i], d[3 * i + 1], d[3 * i + 2]);
   const bool finite = isfinite(ray.p.x) && isfinite(ray.p.y) && isfinite(ray.p.z) && isfinite(ray.d.x) && isfinite(ray.d.y) && isfinite(ray.d.z);
   return finite && !(ray.d.x == 0.f && ray.d.y == 0.f && ray.d.z == 0.f);   // false: a void ray
-}
-
-// dynamic LDS as qa_integrate lays it out: [resident scene image (RES) | traversal stacks (stackDepth x 256)]; -> the lane's stack
-template <bool RES>
-__device__ __forceinline__ uint32_t *sceneToLds(const DScene &sc, uint4 *dyn)
-{
-  if (RES) {
-    for (uint32_t i = threadIdx.x; i < sc.residentVec4; i += QA_BLOCK) dyn[i] = sc.resident[i];
-    __syncthreads();
-  }
-  return reinterpret_cast<uint32_t *>(dyn + (RES ? sc.residentVec4 : 0)) + threadIdx.x;
 }
 
 template <bool RES>
@@ -93,22 +77,14 @@ __global__ __launch_bounds__(QA_BLOCK) void qa_cast_rays(const DScene sc, const 
   for (uint64_t i = (uint64_t) blockIdx.x * QA_BLOCK + threadIdx.x; i < cp.n; i += stride) {   // (i >= n: padding lane of the last batch)
     Ray ray;
     const bool walk = loadRay(cp.o, cp.d, i, ray);
-    // ---- the cast: qa_kernel.h section C, as qa_gbuffer.hip restates it
     Hit h;
-    h.z = QA_BIGFLOAT;
-    h.node = -1;
-    h.mtlID = 0;
-    h.front = true;
-    h.p = F3(0, 0, 0);
-    h.N = F3(0, 0, 0);
+    hitInit(h);
     bool found = false;
     if (walk) {
       RayDiff diff;   // (read by the TEX instance only)
       diff.dx = diff.dy = ray.d;
       TexHit th;
-      th.uvw = F3(0.5f, 0.5f, 0.5f);
-      th.duvw0 = th.duvw1 = F3(0, 0, 0);
-      th.hasTexture = false;
+      texHitInit(th);
       found = traceClosest<RES, false, false>(mem, sc, ray, diff, h, th, stack, cnt);
     }
     int node = -1, mword = -1;
@@ -117,19 +93,9 @@ __global__ __launch_bounds__(QA_BLOCK) void qa_cast_rays(const DScene sc, const 
       N = h.N;
       P = h.p;
       node = h.node;
-      // the hit's material: section D, the lines qa_gbuffer.hip restates (its :107-127)
-      const qa_instance &in = instAt<RES>(sc, h.node);
-      int mi = -1;
-      bool white = false;
-      if (in.mtlset >= 0) {
-        const qa_mtlset ms = sc.mtlset[in.mtlset];
-        if (ms.multi) {
-          if (h.mtlID >= 0 && h.mtlID < ms.count) mi = ms.first + h.mtlID;
-          else white = true;
-        } else mi = ms.first;
-      }
-      mword = mi < 0 ? (white ? -2 : -1) : mi;
-      if (!h.front) mword = (int) ((uint32_t) mword | (uint32_t) QA_RAY_BACK);
+      bool white;
+      const int mi = hitMaterial(sc.mtlset, instAt<RES>(sc, h.node).mtlset, h.mtlID, white);
+      mword = materialWord(mi, white, h.front);
     }
     if (cp.t) cp.t[i] = found ? h.z : QA_BIGFLOAT;
     if (cp.ids) { cp.ids[2 * i] = node; cp.ids[2 * i + 1] = mword; }
@@ -169,18 +135,9 @@ __global__ __launch_bounds__(QA_BLOCK) void qa_camera_rays(const DCamera cam, co
   const int px = cr.x0 + (int) (q % rw), py = cr.y0 + (int) (q / rw);
   uint32_t rng = qa_pixel_seed(cr.seed, (uint32_t) py * (uint32_t) cam.width + (uint32_t) px);
 
-  // ---- the camera ray of sample 0: qa_kernel.h section B, the same operations in the same order (as qa_gbuffer.hip :59-73)
-  const float hx = halton[0], hy = halton[1];
-  const f3 texpos = F3(hx, hy, 0.f) + F3((float) px, (float) py, 0.f);
-  const f3 A = ld3(cam.screenA), U = ld3(cam.screenU), V = ld3(cam.screenV);
-  const f3 cpt = (A + U * texpos.x) + V * texpos.y;
-  f3 campos = ld3(cam.pos);
-  if (cam.dof > 0.1f) {
-    const float r1 = rng1(rng), r2 = rng1(rng);
-    const float r = cam.dof * qsqrt(r1);
-    const float t = r2 * 2.f * QA_PI;
-    campos = campos + (ld3(cam.screenX) * (r * qcosf(t)) + ld3(cam.screenY) * (r * qsinf(t)));
-  }
+  const f3 texpos = camTexpos(halton, 0, px, py);
+  const f3 cpt = camPoint(cam, texpos.x, texpos.y);
+  const f3 campos = camLensPos(cam, rng);
   const f3 dir = normalize(cpt - campos);
   cr.o[3 * q] = campos.x; cr.o[3 * q + 1] = campos.y; cr.o[3 * q + 2] = campos.z;
   cr.d[3 * q] = dir.x; cr.d[3 * q + 1] = dir.y; cr.d[3 * q + 2] = dir.z;
@@ -188,26 +145,7 @@ __global__ __launch_bounds__(QA_BLOCK) void qa_camera_rays(const DCamera cam, co
 
 }  // namespace qa
 
-// The host forms' staging: one device buffer per context that only grows and is only used synchronously.  It is kept here and not
-// in qa_ctx: qa_ctx.h is part of the integrator units, which stay as they are.  qa_ctx_destroy frees it (FreeRayQueryStage)
-static std::mutex g_stageLock;
-static std::unordered_map<const qa_ctx *, DevBuf> g_stage;
-static DevBuf &StageOf(const qa_ctx *c)
-{
-  std::lock_guard<std::mutex> hold(g_stageLock);
-  return g_stage[c];   // (references into an unordered_map stay valid when others are added)
-}
-void FreeRayQueryStage(qa_ctx *c)
-{
-  std::lock_guard<std::mutex> hold(g_stageLock);
-  auto it = g_stage.find(c);
-  if (it == g_stage.end()) return;
-  it->second.Free();
-  g_stage.erase(it);
-}
-
-// What both query launches share: the checks, the waits a guide-plane call begins with, the scene record with the megakernel's
-// stack depth, and a persistent grid of at most what is resident at once.  n == 0 comes first: an empty batch has no arrays
+// What both queries refuse alike, before anything is sized by n.  n == 0 comes first: an empty batch has no arrays
 #define QA_MAX_RAYS 0x7FFFFFFFull
 static int QueryChecks(qa_ctx *c, uint64_t n, bool arraysGiven, bool outputGiven)
 {
@@ -218,23 +156,7 @@ static int QueryChecks(qa_ctx *c, uint64_t n, bool arraysGiven, bool outputGiven
   if (!outputGiven) return Fail(QA_EINVAL, "no output");
   return QA_OK;
 }
-template <class Fn, class Params>
-static int LaunchQuery(qa_ctx *c, Fn fn, const Params &p, hipStream_t s)
-{
-  HIP_TRY(c->lastFrame.WaitOn(s));
-  HIP_TRY(c->lastEdit.WaitOn(s));
-  const size_t lds = c->integ[kMega].ldsBytes;
-  DScene ds = c->ds;
-  ds.stackDepth = c->integ[kMega].stackDepth;
-  const long long needBlocks = (long long) ((p.n + QA_BLOCK - 1) / QA_BLOCK);
-  int perCU = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, (const void *) fn, QA_BLOCK, lds) != hipSuccess || perCU < 1) perCU = 2;
-  const long long blocks = std::max<long long>(1, std::min<long long>(needBlocks, (long long) c->numCUs * std::min(perCU, 8)));
-  hipLaunchKernelGGL(fn, dim3((unsigned) blocks), dim3(QA_BLOCK), (unsigned) lds, s, ds, p);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(c->lastFrame.Record(s));   // (the next edit waits for it: the kernel reads the tables an edit rewrites)
-  return QA_OK;
-}
+static long long RayBlocks(uint64_t n) { return (long long) ((n + QA_BLOCK - 1) / QA_BLOCK); }   // lane = ray
 
 // the <RES> instance by the frame launcher's predicate (SelectKernel: plan.resident), as PickGBuffer picks
 typedef void (*CastFn)(const DScene, const CastParams);
@@ -247,7 +169,7 @@ static int CastRays(qa_ctx *c, uint64_t n, const float *o, const float *d, float
   if (int rc = QueryChecks(c, n, o && d, t || ids || normal || point)) return rc;
   if (n == 0) return QA_OK;
   const CastParams cp = {n, o, d, t, ids, normal, point};
-  return LaunchQuery(c, PickCast(c->plan.resident), cp, s);
+  return LaunchSceneKernel(c, PickCast(c->plan.resident), cp, RayBlocks(n), s);
 }
 
 static int Occluded(qa_ctx *c, uint64_t n, const float *o, const float *d, const float *tmax, uint8_t *out, hipStream_t s)
@@ -255,7 +177,7 @@ static int Occluded(qa_ctx *c, uint64_t n, const float *o, const float *d, const
   if (int rc = QueryChecks(c, n, o && d && tmax, out != nullptr)) return rc;
   if (n == 0) return QA_OK;
   const OccludedParams op = {n, o, d, tmax, out};
-  return LaunchQuery(c, PickOccluded(c->plan.resident), op, s);
+  return LaunchSceneKernel(c, PickOccluded(c->plan.resident), op, RayBlocks(n), s);
 }
 
 extern "C" {
@@ -273,9 +195,8 @@ int qa_cast_rays(qa_ctx *c, uint64_t n, const float *origins, const float *dirs,
   if (int rc = QueryChecks(c, n, origins && dirs, t || ids || normal || point)) return rc;   // before anything is sized by n
   if (n == 0) return QA_OK;
   // staging [origins 12 | dirs 12 | normal 12 | point 12 | t 4 | ids 8] bytes per ray
-  DevBuf &stage = StageOf(c);
-  HIP_TRY(stage.Reserve((size_t) n * 60));
-  float *dO = (float *) stage.p, *dD = dO + 3 * n, *dN = dD + 3 * n, *dP = dN + 3 * n, *dT = dP + 3 * n;
+  HIP_TRY(c->stageQuery.Reserve((size_t) n * 60));
+  float *dO = (float *) c->stageQuery.p, *dD = dO + 3 * n, *dN = dD + 3 * n, *dP = dN + 3 * n, *dT = dP + 3 * n;
   int32_t *dI = (int32_t *) (dT + n);
   HIP_TRY(hipMemcpyAsync(dO, origins, n * 12, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemcpyAsync(dD, dirs, n * 12, hipMemcpyHostToDevice, c->stream));
@@ -300,9 +221,8 @@ int qa_occluded(qa_ctx *c, uint64_t n, const float *origins, const float *dirs, 
   if (int rc = QueryChecks(c, n, origins && dirs && tmax, out != nullptr)) return rc;
   if (n == 0) return QA_OK;
   // staging [origins 12 | dirs 12 | tmax 4 | out 1] bytes per ray
-  DevBuf &stage = StageOf(c);
-  HIP_TRY(stage.Reserve((size_t) n * 29));
-  float *dO = (float *) stage.p, *dD = dO + 3 * n, *dT = dD + 3 * n;
+  HIP_TRY(c->stageQuery.Reserve((size_t) n * 29));
+  float *dO = (float *) c->stageQuery.p, *dD = dO + 3 * n, *dT = dD + 3 * n;
   uint8_t *dOut = (uint8_t *) (dT + n);
   HIP_TRY(hipMemcpyAsync(dO, origins, n * 12, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemcpyAsync(dD, dirs, n * 12, hipMemcpyHostToDevice, c->stream));
@@ -316,9 +236,7 @@ int qa_occluded(qa_ctx *c, uint64_t n, const float *origins, const float *dirs, 
 int qa_camera_rays_device(qa_ctx *c, int x0, int y0, int x1, int y1, uint32_t seed, float *d_origins, float *d_dirs, void *hip_stream)
 {
   if (int rc = Enter(c)) return rc;
-  FrameArgs a;   // the region is checked as a frame's is
-  a.x0 = x0; a.y0 = y0; a.x1 = x1; a.y1 = y1;
-  if (int rc = CheckFrame(c, a)) return rc;
+  if (int rc = CheckRegion(c, x0, y0, x1, y1)) return rc;
   if (!d_origins || !d_dirs) return Fail(QA_EINVAL, "null ray array");
   if (int rc = EnsureHalton(c, 1)) return rc;
   const hipStream_t s = StreamOf(c, hip_stream);

@@ -504,23 +504,6 @@ def matte_rgba_host(rgb, backdrop, coverage, ns, srgb=True):
     return out
 
 
-def _matte_tensors(region, device, ns, given):
-    """The device planes of a matte call: the ones given (torch tensors), or all four allocated when none is given, and the
-    optional sample-count plane checked -> (dict name -> tensor, pointers in the C ABI's order, ns pointer or None)."""
-    import torch
-    x0, y0, x1, y1 = region
-    h, w = y1 - y0, x1 - x0
-    shapes = {"coverage": (h, w), "albedo": (h, w, 3), "normal": (h, w, 3), "backdrop": (h, w, 3)}
-    out = {k: v for k, v in given.items() if v is not None}
-    if not out:
-        out = {k: torch.empty(shapes[k], dtype=torch.float32, device=device) for k in MATTE_PLANES}
-    for k, t in out.items():
-        assert t.is_cuda and t.is_contiguous() and t.dtype == torch.float32 and t.numel() == int(np.prod(shapes[k])), k
-    if ns is not None:
-        assert ns.is_cuda and ns.is_contiguous() and ns.element_size() == 4 and not ns.dtype.is_floating_point and ns.numel() == h * w, "ns"
-    return out, [out[k].data_ptr() if k in out else None for k in MATTE_PLANES], None if ns is None else ns.data_ptr()
-
-
 def _denoise_flags(normal, albedo, variance):
     """The flag word of a denoise call: the planes that are given."""
     return ((QA_DENOISE_GUIDE_NORMAL if normal is not None else 0) | (QA_DENOISE_GUIDE_ALBEDO if albedo is not None else 0)
@@ -762,21 +745,6 @@ def _motion_tensor(motion, device, stream):
     return t, len(table)
 
 
-def _gbuffer_tensors(region, device, given):
-    """The device planes of a G-buffer call: the ones given (torch tensors), or all four allocated when none is given
-    -> (dict name -> tensor, pointers in the C ABI's order)."""
-    import torch
-    x0, y0, x1, y1 = region
-    h, w = y1 - y0, x1 - x0
-    shapes = {"normal": (h, w, 3), "albedo": (h, w, 3), "depth": (h, w), "ids": (h, w, 2)}
-    out = {k: v for k, v in given.items() if v is not None}
-    if not out:
-        out = {k: torch.empty(shapes[k], dtype=torch.int32 if k == "ids" else torch.float32, device=device) for k in GBUFFER_PLANES}
-    for k, t in out.items():
-        assert t.is_cuda and t.is_contiguous() and t.element_size() == 4 and t.numel() == int(np.prod(shapes[k])), k
-    return out, [out[k].data_ptr() if k in out else None for k in GBUFFER_PLANES]
-
-
 def _ray_tensor(name, t, shape, dtype, device):
     """A tensor of a ray-query call, checked before anything reaches the library: a contiguous torch tensor of that shape and dtype on
     the context's device."""
@@ -792,6 +760,28 @@ def _ray_tensor(name, t, shape, dtype, device):
     if not t.is_contiguous():
         raise ValueError(f"{name}: the tensor is not contiguous")
     return t
+
+
+def _output_tensors(names, shapes, dtypes, device, given):
+    """The output tensors of a device call: the ones given are written; when none is given all of `names` are allocated.  Each is
+    checked as _ray_tensor checks -> (dict name -> tensor, pointers in the order of `names`: None for one that is not written)."""
+    import torch
+    out = {k: v for k, v in given.items() if v is not None}
+    if not out:
+        out = {k: torch.empty(shapes[k], dtype=dtypes[k], device=device) for k in names}
+    for k, t in out.items():
+        _ray_tensor(k, t, shapes[k], dtypes[k], device)
+    return out, [out[k].data_ptr() if k in out else None for k in names]
+
+
+def _region_planes(region, names):
+    """Shapes and dtypes of the guide and matte planes of a region: coverage and depth one float per pixel, ids two int32, the rest
+    three floats."""
+    import torch
+    x0, y0, x1, y1 = region
+    h, w = y1 - y0, x1 - x0
+    shapes = {k: (h, w) if k in ("coverage", "depth") else (h, w, 2) if k == "ids" else (h, w, 3) for k in names}
+    return shapes, {k: torch.int32 if k == "ids" else torch.float32 for k in names}
 
 
 def _ray_count(name, t):
@@ -1172,7 +1162,8 @@ class Context:
         """qa_gbuffer_region_device into torch CUDA tensors (see gbuffer for the shapes): the planes given are written; when none is
         given all four are allocated.  -> dict name -> tensor.  Only enqueues (see render_region_device for the stream)."""
         import torch
-        out, ptrs = _gbuffer_tensors(region, torch.device("cuda", self.device_id), dict(normal=normal, albedo=albedo, depth=depth, ids=ids))
+        out, ptrs = _output_tensors(GBUFFER_PLANES, *_region_planes(region, GBUFFER_PLANES), torch.device("cuda", self.device_id),
+                                    dict(normal=normal, albedo=albedo, depth=depth, ids=ids))
         sptr = self._stream_arg(stream, next(iter(out.values())))
         x0, y0, x1, y1 = region
         _check(lib().qa_gbuffer_region_device(self._h, x0, y0, x1, y1, seed, *ptrs, sptr))
@@ -1200,10 +1191,13 @@ class Context:
         the planes given are written; when none is given all four are allocated.  -> dict name -> tensor.  Only enqueues (see
         render_region_device for the stream)."""
         import torch
-        out, ptrs, nptr = _matte_tensors(region, torch.device("cuda", self.device_id), ns,
-                                         dict(coverage=coverage, albedo=albedo, normal=normal, backdrop=backdrop))
-        sptr = self._stream_arg(stream, next(iter(out.values())))
+        out, ptrs = _output_tensors(MATTE_PLANES, *_region_planes(region, MATTE_PLANES), torch.device("cuda", self.device_id),
+                                    dict(coverage=coverage, albedo=albedo, normal=normal, backdrop=backdrop))
         x0, y0, x1, y1 = region
+        if ns is not None:
+            assert ns.is_cuda and ns.is_contiguous() and ns.element_size() == 4 and not ns.dtype.is_floating_point and ns.numel() == (y1 - y0) * (x1 - x0), "ns"
+        nptr = None if ns is None else ns.data_ptr()
+        sptr = self._stream_arg(stream, next(iter(out.values())))
         _check(lib().qa_matte_region_device(self._h, x0, y0, x1, y1, int(spp), nptr, *ptrs, sptr))
         return out
 
@@ -1238,15 +1232,10 @@ class Context:
         _ray_tensor("origins", origins, (n, 3), torch.float32, dev)
         _ray_tensor("dirs", dirs, (n, 3), torch.float32, dev)
         shapes = {"t": (n,), "ids": (n, 2), "normal": (n, 3), "point": (n, 3)}
-        dtype = lambda k: torch.int32 if k == "ids" else torch.float32   # noqa: E731
-        out = {k: v for k, v in dict(t=t, ids=ids, normal=normal, point=point).items() if v is not None}
-        if not out:
-            out = {k: torch.empty(shapes[k], dtype=dtype(k), device=dev) for k in RAY_OUTPUTS}
-        for k, v in out.items():
-            _ray_tensor(k, v, shapes[k], dtype(k), dev)
+        dtypes = {k: torch.int32 if k == "ids" else torch.float32 for k in RAY_OUTPUTS}
+        out, ptrs = _output_tensors(RAY_OUTPUTS, shapes, dtypes, dev, dict(t=t, ids=ids, normal=normal, point=point))
         sptr = self._stream_arg(stream, origins)
-        _check(lib().qa_cast_rays_device(self._h, n, origins.data_ptr(), dirs.data_ptr(),
-                                         *(out[k].data_ptr() if k in out else None for k in RAY_OUTPUTS), sptr))
+        _check(lib().qa_cast_rays_device(self._h, n, origins.data_ptr(), dirs.data_ptr(), *ptrs, sptr))
         return out
 
     def cast_rays(self, origins, dirs):
@@ -1760,7 +1749,8 @@ class Progressive:
         """qa_progressive_gbuffer_device: the guide planes of the frame's region and seed, of the scene as it now stands (see
         Context.gbuffer_device) -> dict name -> tensor; only enqueues."""
         import torch
-        out, ptrs = _gbuffer_tensors(self.region, torch.device("cuda", self._ctx.device_id), dict(normal=normal, albedo=albedo, depth=depth, ids=ids))
+        out, ptrs = _output_tensors(GBUFFER_PLANES, *_region_planes(self.region, GBUFFER_PLANES), torch.device("cuda", self._ctx.device_id),
+                                    dict(normal=normal, albedo=albedo, depth=depth, ids=ids))
         sptr = Context._stream_arg(stream, next(iter(out.values())))
         _check(lib().qa_progressive_gbuffer_device(self._ctx._h, *ptrs, sptr))
         return out
@@ -1770,8 +1760,8 @@ class Progressive:
         it now stands (see Context.matte_device: its planes for spp_max and the ns plane read() gives) -> dict name -> tensor; only
         enqueues."""
         import torch
-        out, ptrs, _ = _matte_tensors(self.region, torch.device("cuda", self._ctx.device_id), None,
-                                      dict(coverage=coverage, albedo=albedo, normal=normal, backdrop=backdrop))
+        out, ptrs = _output_tensors(MATTE_PLANES, *_region_planes(self.region, MATTE_PLANES), torch.device("cuda", self._ctx.device_id),
+                                    dict(coverage=coverage, albedo=albedo, normal=normal, backdrop=backdrop))
         sptr = Context._stream_arg(stream, next(iter(out.values())))
         _check(lib().qa_progressive_matte_device(self._ctx._h, *ptrs, sptr))
         return out
