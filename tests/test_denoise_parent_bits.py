@@ -8,13 +8,13 @@ No GPU.
 Run this file as a program to record the digests anew (only where a change of the outputs is meant):
     python tests/test_denoise_parent_bits.py"""
 import hashlib
-import json
 import os
 
 import numpy as np
 import pytest
 
 import conftest  # noqa: F401  (first: it puts the repository on sys.path when this file runs as a program)
+import parent_bits_util as pb
 from denoise_guided_util import GUIDED_SIZES, guided_frame
 from denoise_util import HOST_SIZES, random_frame
 from denoise_variance_util import VARIANCE_SIZES, variance_frame
@@ -67,31 +67,18 @@ def digest(a):
 
 
 def record(commit):
-    doc = {"commit": commit,
-           "what": "SHA-256 of the output of hip.denoise_host / denoise_guided_host / denoise_variance_host over cases() of "
-                   "tests/test_denoise_parent_bits.py, taken with the library built from that commit",
-           "digests": {name: digest(thunk()) for name, thunk in cases()}}
-    with open(GOLDEN, "w") as f:
-        json.dump(doc, f, indent=1, sort_keys=True)
-        f.write("\n")
-    return doc
-
-
-def recorded():
-    with open(GOLDEN) as f:
-        return json.load(f)["digests"]
+    return pb.save(GOLDEN, commit, "SHA-256 of the output of hip.denoise_host / denoise_guided_host / denoise_variance_host over cases() of "
+                   "tests/test_denoise_parent_bits.py, taken with the library built from that commit", {name: digest(thunk()) for name, thunk in cases()})
 
 
 def test_the_record_names_every_case_and_nothing_else():
-    assert sorted(recorded()) == sorted(name for name, _ in cases())
+    assert pb.names_match(GOLDEN, [name for name, _ in cases()])
 
 
 @pytest.mark.parametrize("name,thunk", cases(), ids=[n for n, _ in cases()])
 def test_host_forms_keep_the_parents_bits(name, thunk):
-    assert digest(thunk()) == recorded()[name], name
+    assert digest(thunk()) == pb.load(GOLDEN)[name], name
 
 
 if __name__ == "__main__":
-    import subprocess
-    head = subprocess.run(["git", "rev-parse", "HEAD"], cwd=os.path.dirname(GOLDEN), check=True, stdout=subprocess.PIPE, text=True).stdout.strip()
-    print(f"{len(record(head)['digests'])} cases recorded at {head}")
+    pb.main(record)

@@ -14,13 +14,13 @@ Run this file as a program to record the digests anew (only where a change of th
 library to record from:
     QA_HIP_LIB=.../libqaray_hip.so python tests/test_gpu_firsthit_parent_bits.py [commit]"""
 import hashlib
-import json
 import os
 
 import numpy as np
 import pytest
 
 import conftest  # noqa: F401  (first: it puts the repository on sys.path when this file runs as a program)
+import parent_bits_util as pb
 from gbuffer_util import REGION, SCENES, SEEDS, scene_blob
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "firsthit_parent_bits.json")
@@ -101,23 +101,12 @@ def record(commit):
     digests = {}
     for scene in ALL_SCENES:
         digests.update(run_scene(scene))
-    doc = {"commit": commit,
-           "what": "dtype, shape and SHA-256 of every output plane of the calls in cases() of tests/test_gpu_firsthit_parent_bits.py, "
-                   "taken on an MI355X with the library built from that commit",
-           "digests": digests}
-    with open(GOLDEN, "w") as f:
-        json.dump(doc, f, indent=1, sort_keys=True)
-        f.write("\n")
-    return doc
-
-
-def recorded():
-    with open(GOLDEN) as f:
-        return json.load(f)["digests"]
+    return pb.save(GOLDEN, commit, "dtype, shape and SHA-256 of every output plane of the calls in cases() of tests/test_gpu_firsthit_parent_bits.py, "
+                   "taken on an MI355X with the library built from that commit", digests)
 
 
 def test_the_record_names_every_case_and_nothing_else():
-    assert sorted(recorded()) == sorted(case_id(scene, name) for scene, name in cases())
+    assert pb.names_match(GOLDEN, [case_id(scene, name) for scene, name in cases()])
 
 
 @pytest.fixture(scope="module")
@@ -135,16 +124,10 @@ def computed():
 @pytest.mark.gpu
 @pytest.mark.parametrize("scene,name", cases(), ids=[case_id(s, n) for s, n in cases()])
 def test_first_hit_passes_keep_the_parents_bits(computed, scene, name):
-    got, want = computed(scene)[case_id(scene, name)], recorded()[case_id(scene, name)]
+    got, want = computed(scene)[case_id(scene, name)], pb.load(GOLDEN)[case_id(scene, name)]
     print(case_id(scene, name), got)
     assert got == want
 
 
 if __name__ == "__main__":
-    import subprocess
-    import sys
-    if len(sys.argv) > 1:
-        head = sys.argv[1]
-    else:
-        head = subprocess.run(["git", "rev-parse", "HEAD"], cwd=os.path.dirname(GOLDEN), check=True, stdout=subprocess.PIPE, text=True).stdout.strip()
-    print(f"{len(record(head)['digests'])} cases recorded at {head} from {os.environ.get('QA_HIP_LIB', 'qaray_amd/lib')}")
+    pb.main(record, f" from {os.environ.get('QA_HIP_LIB', 'qaray_amd/lib')}")

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import conftest  # noqa: F401  (first: it puts the repository on sys.path when this file runs as a program)
+import parent_bits_util as pb
 import reproject_motion_util as mu
 import reproject_util as ru
 from qaray_amd import hip
@@ -55,31 +56,18 @@ def digests(planes):
 
 
 def record(commit):
-    doc = {"commit": commit,
-           "what": "SHA-256 of every output plane of hip.reproject_host / reproject_motion_host / reproject_moments_host over cases() of "
-                   "tests/test_reproject_parent_bits.py, taken with the library built from that commit",
-           "digests": {name: digests(thunk()) for name, thunk in cases()}}
-    with open(GOLDEN, "w") as f:
-        json.dump(doc, f, indent=1, sort_keys=True)
-        f.write("\n")
-    return doc
-
-
-def recorded():
-    with open(GOLDEN) as f:
-        return json.load(f)["digests"]
+    return pb.save(GOLDEN, commit, "SHA-256 of every output plane of hip.reproject_host / reproject_motion_host / reproject_moments_host over cases() of "
+                   "tests/test_reproject_parent_bits.py, taken with the library built from that commit", {name: digests(thunk()) for name, thunk in cases()})
 
 
 def test_the_record_names_every_case_and_nothing_else():
-    assert sorted(recorded()) == sorted(name for name, _ in cases())
+    assert pb.names_match(GOLDEN, [name for name, _ in cases()])
 
 
 @pytest.mark.parametrize("name,thunk", cases(), ids=[n for n, _ in cases()])
 def test_host_forms_keep_the_parents_bits(name, thunk):
-    assert digests(thunk()) == recorded()[name], name
+    assert digests(thunk()) == pb.load(GOLDEN)[name], name
 
 
 if __name__ == "__main__":
-    import subprocess
-    head = subprocess.run(["git", "rev-parse", "HEAD"], cwd=os.path.dirname(GOLDEN), check=True, stdout=subprocess.PIPE, text=True).stdout.strip()
-    print(f"{len(record(head)['digests'])} cases recorded at {head}")
+    pb.main(record)

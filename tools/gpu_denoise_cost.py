@@ -8,32 +8,23 @@ and variance 16, depth and slope 8); an iteration reads 24 and writes 16, the la
 n iterations.  The 24 neighbour taps of a pixel are re-reads of those bytes (LDS at steps 1 and 2, the caches beyond).
 
 The frame is synthetic (a noisy colour gradient on a slanted plane, a tenth of the pixels missing the scene): the filter's
-work does not depend on what the pixels show, only on how many taps share a class.  Needs a GPU: there is no fallback."""
-import argparse
-import json
-import os
+work does not depend on what the pixels show, only on how many taps share a class.  The measurement runs in a child process under a
+time limit (--limit seconds), by the rule of tools/cost.py.  Needs a GPU: there is no fallback."""
 import statistics
 import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import cost
 
+TOOL = "gpu_denoise_cost"
 SIZES = ((1920, 1080), (3840, 2160))
 ITERATIONS = (1, 3, 5)
 HBM_PEAK = 8.0e12
 
 
-def main():
-    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--repeats", type=int, default=7)
-    a = ap.parse_args()
-    import torch
-    from qaray_amd import hip
-    if not torch.cuda.is_available():
-        raise SystemExit("gpu_denoise_cost: no GPU (nothing is measured without one)")
+def measure(a):
+    torch, hip = cost.gpu(TOOL)
     dev = torch.device("cuda", 0)
     ctx = hip.Context(0)
     s = torch.cuda.Stream(dev)
@@ -47,22 +38,19 @@ def main():
         out = torch.empty_like(t[0])
         torch.cuda.synchronize()
         for iterations in ITERATIONS:
-            spans = []
-            for _ in range(a.warmup + a.repeats):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                with torch.cuda.stream(s):
-                    e0.record()
-                    ctx.denoise_device(*t, out=out, iterations=iterations, stream=s.cuda_stream)
-                    e1.record()
-                s.synchronize()
-                spans.append(e0.elapsed_time(e1))
-            spans = spans[a.warmup:]
+            spans = cost.timed(s, lambda: ctx.denoise_device(*t, out=out, iterations=iterations, stream=s.cuda_stream), a.warmup, a.repeats)
             ms = statistics.median(spans)
             moved = w * h * (44 + 40 * iterations - 4)
-            print(json.dumps({"size": [w, h], "iterations": iterations, "median_ms": round(ms, 4), "min_ms": round(min(spans), 4),
-                              "max_ms": round(max(spans), 4), "algorithmic_bytes": moved, "GBps": round(moved / (ms * 1e-3) / 1e9, 1),
-                              "share_of_hbm_peak_8TBps": round(moved / (ms * 1e-3) / HBM_PEAK, 4), "library": os.path.relpath(hip.HIP_LIB_PATH, ROOT)}), flush=True)
+            cost.emit(TOOL, f"{w}x{h} iterations {iterations}", size=[w, h], iterations=iterations, **cost.summary(spans), algorithmic_bytes=moved,
+                      GBps=round(moved / (ms * 1e-3) / 1e9, 1), share_of_hbm_peak_8TBps=round(moved / (ms * 1e-3) / HBM_PEAK, 4))
     ctx.close()
+
+
+def main():
+    a = cost.arguments(__doc__, one=("all",)).parse_args()
+    if a.one:
+        return measure(a)
+    cost.run_children(__file__, [["all"]], sys.argv[1:], a.limit)
 
 
 if __name__ == "__main__":

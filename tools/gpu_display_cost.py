@@ -12,58 +12,33 @@ statistics block, the statistics kernel and the encode kernel) on a stream of it
 derived from what the kernels read and write (csrc/hip/qa_display.hip); their sum over the kernel time is the achieved bandwidth,
 given as a share of the HBM peak (8.0 TB/s specified; about 6.3 TB/s is what a float4 copy reaches).
 
-Needs a GPU: there is no fallback, and without one this fails."""
-import argparse
+The measurement runs in a child process under a time limit (--limit seconds), by the rule of tools/cost.py.  Needs a GPU: there is no
+fallback, and without one this fails."""
 import ctypes as C
-import json
-import os
 import statistics
 import sys
-import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import cost
 
+TOOL = "gpu_display_cost"
 HBM_PEAK = 8.0e12
 # bytes per pixel of the two kernels, all seven product bytes wanted (qa_display.hip)
 BYTES = {"unfinished": {"statistics": 32 + 4 + 4, "encode": 32 + 4 + 4 + 7}, "finished": {"statistics": 32 + 4 + 4, "encode": 32 + 4 + 4 + 12 + 7},
          "plain": {"statistics": 4 + 4, "encode": 12 + 4 + 4 + 7}}
-FRAMES = {"C2": ("example_project12_box.xml", (1920, 1080)), "C5": ("trc_scene_tower.xml", (3840, 2160))}
 
 
-def median_ms(fn, warmup, repeats):
-    for _ in range(warmup):
-        fn()
-    t = []
-    for _ in range(repeats):
-        t0 = time.perf_counter()
-        fn()
-        t.append((time.perf_counter() - t0) * 1e3)
-    return statistics.median(t), min(t), max(t)
-
-
-def main():
-    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--frames", default="C2,C5")
-    ap.add_argument("--spp", type=int, default=8, help="the frame's spp; the mid-frame preview is taken at half of it")
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--repeats", type=int, default=7)
-    a = ap.parse_args()
-    import torch
-    from qaray_amd import hip, host
-    if not torch.cuda.is_available():
-        raise SystemExit("gpu_display_cost: no GPU (nothing is measured without one)")
-    subprocess_assets = os.path.join(ROOT, "scenes", "gen_assets.py")
-    import subprocess
-    subprocess.run([sys.executable, subprocess_assets], check=True, stdout=subprocess.DEVNULL)
+def measure(a):
+    torch, hip = cost.gpu(TOOL)
+    from qaray_amd import host
+    cost.assets()
     L, H = hip.lib(), host.lib()
     ctx = hip.Context(0)
     dev = torch.device("cuda", 0)
     stream = torch.cuda.Stream()
     for name in a.frames.split(","):
-        scene, (w, h) = FRAMES[name]
+        scene, w, h = cost.frame(name)
         n = w * h
         ctx.upload_scene(host.load_scene_blob(scene, size=(w, h)))
         prog = ctx.progressive((0, 0, w, h), a.spp)
@@ -74,52 +49,52 @@ def main():
         dout["stats"] = torch.empty(4, dtype=torch.int32, device=dev)
         st = hip.DisplayStats()
 
-        def way_a():
+        def way_a(k):
             hip._check(L.qa_progressive_read(ctx._h, rgb.ctypes.data, depth.ctypes.data, ns.ctypes.data))
             host._check(H.qa_fb_deposit(fb._h, 0, 0, w, h, rgb.ctypes.data, depth.ctypes.data, ns.ctypes.data, a.spp, 1))
             H.qa_fb_z_image(fb._h)
             H.qa_fb_sample_count_image(fb._h)
 
-        def way_b():
+        def way_b(k):
             hip._check(L.qa_progressive_display(ctx._h, 1, *(x.ctypes.data for x in out), C.byref(st)))
 
         def kernels_ms(fn):
-            t = []
-            for i in range(a.warmup + a.repeats):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record(stream)
-                fn()
-                e1.record(stream)
-                e1.synchronize()
-                if i >= a.warmup:
-                    t.append(e0.elapsed_time(e1))
-            return statistics.median(t)
+            return statistics.median(cost.timed(stream, fn, a.warmup, a.repeats))
 
         for state, target in (("unfinished", max(1, a.spp // 2)), ("finished", a.spp)):
             prog.advance(target)
             ctx.synchronize()
-            ma, lo_a, hi_a = median_ms(way_a, a.warmup, a.repeats)
-            mb, lo_b, hi_b = median_ms(way_b, a.warmup, a.repeats)
+            ta, tb = cost.walls(way_a, a.warmup, a.repeats), cost.walls(way_b, a.warmup, a.repeats)
+            ma, mb = statistics.median(ta), statistics.median(tb)
             same = bool(np.array_equal(out[0], fb.pixels) and np.array_equal(out[2], fb.z_image) and np.array_equal(out[3], fb.sample_count_image))
             k_ms = kernels_ms(lambda: prog.display_device(srgb=True, stream=stream.cuda_stream, **dout))
             bpp = sum(BYTES[state].values())
-            rec = {"frame": name, "size": [w, h], "pixels_state": state, "spp_reached": target, "A_read_deposit_images_ms": round(ma, 3),
-                   "A_min_max_ms": [round(lo_a, 3), round(hi_a, 3)], "B_progressive_display_ms": round(mb, 3), "B_min_max_ms": [round(lo_b, 3), round(hi_b, 3)],
-                   "A_over_B": round(ma / mb, 2), "products_equal": same, "kernels_ms": round(k_ms, 4), "bytes_per_pixel": BYTES[state],
-                   "kernel_GBps": round(bpp * n / (k_ms * 1e-3) / 1e9, 1), "share_of_hbm_peak_8TBps": round(bpp * n / (k_ms * 1e-3) / HBM_PEAK, 4),
-                   "bytes_to_host_per_pixel": {"A": 20, "B": 7}}
-            print(json.dumps(rec), flush=True)
+            cost.emit(TOOL, f"{name} {state}", frame=name, size=[w, h], pixels_state=state, spp_reached=target, A_read_deposit_images_ms=round(ma, 3),
+                      A_min_max_ms=[round(min(ta), 3), round(max(ta), 3)], B_progressive_display_ms=round(mb, 3), B_min_max_ms=[round(min(tb), 3), round(max(tb), 3)],
+                      A_over_B=round(ma / mb, 2), products_equal=same, kernels_ms=round(k_ms, 4), bytes_per_pixel=BYTES[state],
+                      kernel_GBps=round(bpp * n / (k_ms * 1e-3) / 1e9, 1), share_of_hbm_peak_8TBps=round(bpp * n / (k_ms * 1e-3) / HBM_PEAK, 4),
+                      bytes_to_host_per_pixel={"A": 20, "B": 7})
         # the plain-buffer source: the same two kernels over the float preview of the finished frame
         t = (torch.empty(3 * n, dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.int32, device=dev))
         prog.read_device(*t)
         ctx.synchronize()
         k_ms = kernels_ms(lambda: ctx.display_device(*t, a.spp, srgb=True, stream=stream.cuda_stream, **dout))
         bpp = sum(BYTES["plain"].values())
-        print(json.dumps({"frame": name, "size": [w, h], "pixels_state": "plain buffers (qa_display_device)", "kernels_ms": round(k_ms, 4), "bytes_per_pixel": BYTES["plain"],
-                          "kernel_GBps": round(bpp * n / (k_ms * 1e-3) / 1e9, 1), "share_of_hbm_peak_8TBps": round(bpp * n / (k_ms * 1e-3) / HBM_PEAK, 4)}), flush=True)
+        cost.emit(TOOL, f"{name} plain", frame=name, size=[w, h], pixels_state="plain buffers (qa_display_device)", kernels_ms=round(k_ms, 4), bytes_per_pixel=BYTES["plain"],
+                  kernel_GBps=round(bpp * n / (k_ms * 1e-3) / 1e9, 1), share_of_hbm_peak_8TBps=round(bpp * n / (k_ms * 1e-3) / HBM_PEAK, 4))
         prog.close()
         fb.close()
     ctx.close()
+
+
+def main():
+    ap = cost.arguments(__doc__, one=("all",))
+    ap.add_argument("--frames", default="C2,C5")
+    ap.add_argument("--spp", type=int, default=8, help="the frame's spp; the mid-frame preview is taken at half of it")
+    a = ap.parse_args()
+    if a.one:
+        return measure(a)
+    cost.run_children(__file__, [["all"]], sys.argv[1:], a.limit)
 
 
 if __name__ == "__main__":

@@ -8,25 +8,19 @@
                   every sample and writes rgb, depth and ns: 20 bytes per pixel)
   rgba            Context.rgba_device over the frame's rgb, the matte's backdrop and coverage and the frame's ns
 The expectation is: matte all <= twin frame's median + the twin frame's own min-max spread; `within` says whether it held.  Each
-configuration and spp runs in a child process of its own under a time limit (--limit seconds); the parent never opens the GPU and
-stops at the first child that fails.  Needs a GPU: there is no fallback."""
-import argparse
-import json
-import os
+configuration and spp runs in a child process of its own under a time limit (--limit seconds), by the rule of tools/cost.py.  Needs
+a GPU: there is no fallback."""
 import statistics
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import cost
 
-CONFIGS = {"c2": ("example_project12_box.xml", 1920, 1080), "c5": ("trc_scene_tower.xml", 3840, 2160)}
+TOOL = "gpu_matte_cost"
 SPPS = (4, 64)
 
 
-def emission_twin(blob):
+def emission_twin(blob, hip):
     """A copy of the blob in which every material emits its diffuse colour (texture included) and does nothing else"""
-    from qaray_amd import hip
     twin = blob.copy()
     m = hip.blob_table(twin, "materials")
     m["emission"] = m["diffuse"]
@@ -36,77 +30,40 @@ def emission_twin(blob):
 
 
 def measure(tag, spp, warmup, repeats):
-    import torch
-    from qaray_amd import hip
-    from qaray_amd.host import SCENES_DIR, load_scene_blob
-    if not torch.cuda.is_available():
-        raise SystemExit("gpu_matte_cost: no GPU (nothing is measured without one)")
-    scene, w, h = CONFIGS[tag]
-    dev = torch.device("cuda", 0)
-    blob = load_scene_blob(os.path.join(SCENES_DIR, scene), size=(w, h))
-    ctx, twin = hip.Context(0), hip.Context(0)
-    ctx.upload_scene(blob)
-    twin.upload_scene(emission_twin(blob))
-    region = (0, 0, w, h)
-    s = torch.cuda.Stream(dev)
-    rgb = torch.empty((h, w, 3), dtype=torch.float32, device=dev)
-    depth = torch.empty((h, w), dtype=torch.float32, device=dev)
-    ns = torch.empty((h, w), dtype=torch.int32, device=dev)
+    ctx, blob, region, dev, s = cost.open_scene(TOOL, tag)
+    torch, hip = cost.gpu(TOOL)
+    scene, w, h = cost.CONFIGS[tag]
+    twin = hip.Context(0)
+    twin.upload_scene(emission_twin(blob, hip))
+    rgb, depth, ns = cost.frame_tensors(dev, w, h)
     m = ctx.matte_device(region, spp, stream=s.cuda_stream)
     rgba = torch.empty((h, w, 4), dtype=torch.uint8, device=dev)
     twin.render_region_device(region, spp, rgb, depth, ns, max_bounce=0, stream=s.cuda_stream)
     s.synchronize()
-
-    def timed(call):
-        spans = []
-        for _ in range(warmup + repeats):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            with torch.cuda.stream(s):
-                e0.record()
-                call()
-                e1.record()
-            s.synchronize()
-            spans.append(e0.elapsed_time(e1))
-        spans = spans[warmup:]
-        return statistics.median(spans), min(spans), max(spans)
-
     steps = [("twin frame", lambda: twin.render_region_device(region, spp, rgb, depth, ns, max_bounce=0, stream=s.cuda_stream)),
              ("matte all", lambda: ctx.matte_device(region, spp, stream=s.cuda_stream, **m)),
              ("matte coverage", lambda: ctx.matte_device(region, spp, coverage=m["coverage"], stream=s.cuda_stream)),
              ("rgba", lambda: ctx.rgba_device(rgb, m["backdrop"], m["coverage"], ns, out=rgba, stream=s.cuda_stream))]
     yard = None
     for name, call in steps:
-        ms, lo, hi = timed(call)
+        spans = cost.timed(s, call, warmup, repeats)
+        ms = statistics.median(spans)
         if name == "twin frame":
-            yard = (ms, hi - lo)
-        rec = {"config": tag, "scene": scene, "size": [w, h], "spp": spp, "what": name, "median_ms": round(ms, 4), "min_ms": round(lo, 4), "max_ms": round(hi, 4),
-               "share_of_twin_frame": round(ms / yard[0], 4), "library": os.path.relpath(hip.HIP_LIB_PATH, ROOT)}
-        if name.startswith("matte"):
-            rec["within"] = bool(ms <= yard[0] + yard[1])
-        print(json.dumps(rec), flush=True)
+            yard = (ms, max(spans) - min(spans))
+        within = {"library": cost.library(), "within": bool(ms <= yard[0] + yard[1])} if name.startswith("matte") else {}
+        cost.emit(TOOL, f"{tag} {spp} spp {name}", config=tag, scene=scene, size=[w, h], spp=spp, what=name, **cost.summary(spans),
+                  share_of_twin_frame=round(ms / yard[0], 4), **within)
     ctx.close()
     twin.close()
 
 
 def main():
-    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--repeats", type=int, default=7)
-    ap.add_argument("--limit", type=int, default=240, help="seconds a configuration's child process may take")
-    ap.add_argument("--one", choices=sorted(CONFIGS), help="measure this configuration in this process (with --spp)")
+    ap = cost.arguments(__doc__, one=cost.TAGS)
     ap.add_argument("--spp", type=int, choices=SPPS)
     a = ap.parse_args()
     if a.one:
         return measure(a.one, a.spp or SPPS[0], a.warmup, a.repeats)
-    for tag in sorted(CONFIGS):
-        for spp in SPPS:
-            try:
-                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--one", tag, "--spp", str(spp), "--warmup", str(a.warmup), "--repeats", str(a.repeats)],
-                                   timeout=a.limit)
-            except subprocess.TimeoutExpired:
-                raise SystemExit(f"gpu_matte_cost: {tag} at {spp} spp did not finish in {a.limit} s; nothing more is started")
-            if r.returncode != 0:
-                raise SystemExit(f"gpu_matte_cost: {tag} at {spp} spp ended with {r.returncode}; nothing more is started")
+    cost.run_children(__file__, [[tag, "--spp", str(spp)] for tag in cost.TAGS for spp in SPPS], sys.argv[1:], a.limit)
 
 
 if __name__ == "__main__":

@@ -18,38 +18,24 @@ of its own (the caller gives each its own time limit):
                  within that budget (its last whole pass), its next pass, and what a uniform pass stopped at that budget would
                  show if all its tiles were alike (the mean square error interpolated linearly in the samples).
 
-Needs a GPU: there is no fallback."""
-import argparse
-import json
+The step runs in a child process under a time limit (--limit seconds), by the rule of tools/cost.py.  Needs a GPU: there is no
+fallback."""
 import os
-import statistics
-import subprocess
 import sys
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import cost
+
+TOOL = "gpu_progressive_adaptive_cost"
 
 QUALITY = (("example_project3_sphere.xml", (64, 48), 4, 32),      # the adaptive golden's scene and frame
            ("example_project12_box.xml", (256, 256), 8, 512),
            ("example_project7_object.xml", (256, 144), 4, 256))    # the scene of the C3 crop
 
 
-def timed(torch, stream, a, before, call):
-    spans = []
-    for _ in range(a.warmup + a.repeats):
-        if before:
-            before()
-        stream.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        with torch.cuda.stream(stream):
-            e0.record()
-            call()
-            e1.record()
-        stream.synchronize()
-        spans.append(e0.elapsed_time(e1))
-    spans = spans[a.warmup:]
-    return {"median_ms": round(statistics.median(spans), 4), "min_ms": round(min(spans), 4), "max_ms": round(max(spans), 4)}
+def timed(stream, a, before, call):
+    return cost.summary(cost.timed(stream, call, a.warmup, a.repeats, before=before))
 
 
 def overhead(a, torch, hip, blob_of, uniform_only):
@@ -59,14 +45,14 @@ def overhead(a, torch, hip, blob_of, uniform_only):
     ctx.upload_scene(blob_of("example_project12_box.xml", (w, h)))
     s = torch.cuda.Stream(dev)
     region = (0, 0, w, h)
-    row = {"step": "uniform" if uniform_only else "overhead", "size": [w, h], "library": os.path.relpath(hip.HIP_LIB_PATH, HERE), "kernel": None}
+    row = {"step": "uniform" if uniform_only else "overhead", "size": [w, h], "library": cost.library(), "kernel": None}
     with ctx.progressive(region, 4, spp_max=64) as prog:
 
         def fresh():
             prog.restart()
             ctx.synchronize()
 
-        row["U_uniform_advance_4spp"] = timed(torch, s, a, fresh, lambda: prog.advance(4, stream=s.cuda_stream))
+        row["U_uniform_advance_4spp"] = timed(s, a, fresh, lambda: prog.advance(4, stream=s.cuda_stream))
         row["kernel"] = ctx.kernel_name()
         if not uniform_only:
             ty, tx = prog.tile_shape
@@ -78,17 +64,17 @@ def overhead(a, torch, hip, blob_of, uniform_only):
             d_mask = torch.from_numpy(mask.astype(np.uint8)).to(dev)
             d_err = torch.empty((ty, tx), dtype=torch.float32, device=dev)
             torch.cuda.synchronize()
-            row["E_error_map"] = timed(torch, s, a, None, lambda: prog.tile_error_device(out=d_err, stream=s.cuda_stream))
+            row["E_error_map"] = timed(s, a, None, lambda: prog.tile_error_device(out=d_err, stream=s.cuda_stream))
             ctx.set_option("progressive_tile_limit", 1)
-            row["A_masked_pass_of_one_tile"] = timed(torch, s, a, None, lambda: prog.advance_tiles(8, d_mask, stream=s.cuda_stream))
-            row["B_adaptive_pass_of_one_tile"] = timed(torch, s, a, None, lambda: prog.advance_adaptive(8, fraction=0.25, stream=s.cuda_stream))
+            row["A_masked_pass_of_one_tile"] = timed(s, a, None, lambda: prog.advance_tiles(8, d_mask, stream=s.cuda_stream))
+            row["B_adaptive_pass_of_one_tile"] = timed(s, a, None, lambda: prog.advance_adaptive(8, fraction=0.25, stream=s.cuda_stream))
             ctx.set_option("progressive_tile_limit", 0)
             b, m, e = (row[k]["median_ms"] for k in ("B_adaptive_pass_of_one_tile", "A_masked_pass_of_one_tile", "E_error_map"))
             row["B_minus_A_ms"] = round(b - m, 4)
             row["select_alone_ms"] = round(b - m - e, 4)
             row["B_minus_A_share_of_U"] = round((b - m) / row["U_uniform_advance_4spp"]["median_ms"], 4)
     ctx.close()
-    print(json.dumps(row), flush=True)
+    cost.emit(TOOL, f"{row['step']} {w}x{h}", **row)
 
 
 def quality(a, torch, hip, blob_of):
@@ -127,10 +113,9 @@ def quality(a, torch, hip, blob_of):
                     prog.advance_adaptive(t, fraction=0.25)
                     curve.append(point(prog))
             curves[policy] = curve
-        print(json.dumps({"step": "quality", "scene": scene, "size": list(size), "spp": [lo, hi], "kernel": ctx.kernel_name(),
-                          "uniform_total_samples": uniform[-1][1], "uniform_final_rmse": uniform[-1][2],
-                          **{f"{p}_{k}": v for p, c in curves.items() for k, v in (("passes", len(c)), ("total_samples", c[-1][0]), ("final_rmse", c[-1][1]))}}),
-              flush=True)
+        cost.emit(TOOL, f"quality {scene}", step="quality", scene=scene, size=list(size), spp=[lo, hi], kernel=ctx.kernel_name(),
+                  uniform_total_samples=uniform[-1][1], uniform_final_rmse=uniform[-1][2],
+                  **{f"{p}_{k}": v for p, c in curves.items() for k, v in (("passes", len(c)), ("total_samples", c[-1][0]), ("final_rmse", c[-1][1]))})
         # at every budget an adaptive pass ended on: what the uniform frame showed by then (its last pass within the budget), and its next pass
         for policy, curve in curves.items():
             for samples, rmse in curve:
@@ -140,28 +125,25 @@ def quality(a, torch, hip, blob_of):
                 if had and nxt:
                     f = (samples - had[-1][1]) / (nxt[0][1] - had[-1][1])
                     mix = round(float(np.sqrt((1 - f) * had[-1][2] ** 2 + f * nxt[0][2] ** 2)), 6)
-                print(json.dumps({"step": "quality_row", "scene": scene, "policy": policy, "samples": samples, "rmse": round(rmse, 6), "uniform_stopped_here_if_tiles_alike": mix,
-                                  "uniform_within_budget": [had[-1][1], round(had[-1][2], 6)] if had else None,
-                                  "uniform_next_pass": [nxt[0][1], round(nxt[0][2], 6)] if nxt else None}), flush=True)
+                cost.emit(TOOL, f"quality {scene} {policy} {samples}", step="quality_row", scene=scene, policy=policy, samples=samples, rmse=round(rmse, 6),
+                          uniform_stopped_here_if_tiles_alike=mix, uniform_within_budget=[had[-1][1], round(had[-1][2], 6)] if had else None,
+                          uniform_next_pass=[nxt[0][1], round(nxt[0][2], 6)] if nxt else None)
     ctx.close()
 
 
 def main():
-    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap = cost.arguments(__doc__, one=("all",))
     ap.add_argument("step", choices=("overhead", "uniform", "quality"))
     ap.add_argument("size", type=int, nargs="*", default=[1920, 1080])
-    ap.add_argument("--tree", default=HERE, help="the checkout whose package and library are measured (default: this one)")
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--repeats", type=int, default=7)
+    ap.add_argument("--tree", default=cost.ROOT, help="the checkout whose package and library are measured (default: this one)")
     a = ap.parse_args()
-    sys.path.insert(0, os.path.abspath(a.tree))
-    import torch
-    from qaray_amd import hip
+    if not a.one:
+        cost.run_children(__file__, [["all"]], sys.argv[1:], a.limit)
+        return
+    torch, hip = cost.gpu(TOOL, os.path.abspath(a.tree))
     from qaray_amd.host import load_scene_blob
-    if not torch.cuda.is_available():
-        raise SystemExit("gpu_progressive_adaptive_cost: no GPU (nothing is measured without one)")
     assert os.path.abspath(hip.__file__).startswith(os.path.abspath(a.tree)), hip.__file__
-    subprocess.run([sys.executable, os.path.join(a.tree, "scenes", "gen_assets.py")], check=True, stdout=subprocess.DEVNULL)   # the object scene's stand-in mesh
+    cost.assets(a.tree)   # the object scene's stand-in mesh
     if a.step == "quality":
         quality(a, torch, hip, lambda scene, size: load_scene_blob(scene, size=size))
     else:

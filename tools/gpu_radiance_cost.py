@@ -8,36 +8,25 @@ only), warm-up windows, then the median, minimum and maximum of --repeats window
   radiance        Context.radiance_rays_device of that frame's own camera_sample_rays_device (all outputs, rays per sample)
   radiance shuffled  the same rays, pixel by pixel, in a fixed random permutation: what divergence costs
 Every figure in milliseconds and Msamples/s, and as a multiple of the yardstick.  Each configuration runs in a child process of
-its own under a time limit (--limit seconds); the parent never opens the GPU and stops at the first child that fails.  The lines
-are printed and written to --out (default profiles/radiance_cost.txt).  Needs a GPU: there is no fallback."""
-import argparse
+its own under a time limit (--limit seconds), by the rule of tools/cost.py.  The lines are printed and written to --out (default
+profiles/radiance_cost.txt).  Needs a GPU: there is no fallback."""
 import json
 import os
 import statistics
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import cost
 
-CONFIGS = {"c2": ("example_project12_box.xml", 1920, 1080), "c5": ("trc_scene_tower.xml", 3840, 2160)}
+TOOL = "gpu_radiance_cost"
 SPP = 16
 
 
 def measure(tag, warmup, repeats, launches, hold_cycles, frame_only, root):
-    import torch
-    sys.path.insert(0, root)   # (the package of the parent checkout for its row, else this tree's)
-    from qaray_amd import hip
-    from qaray_amd.host import SCENES_DIR, load_scene_blob
-    if not torch.cuda.is_available():
-        raise SystemExit("gpu_radiance_cost: no GPU (nothing is measured without one)")
-    scene, w, h = CONFIGS[tag]
-    dev = torch.device("cuda", 0)
-    ctx = hip.Context(0)
-    ctx.set_option("coop", 0)
-    ctx.upload_scene(load_scene_blob(os.path.join(SCENES_DIR, scene), size=(w, h)))
-    region = (0, 0, w, h)
+    # (the package of the parent checkout for its row, else this tree's)
+    ctx, _, region, dev, s = cost.open_scene(TOOL, tag, root=root, options=(("coop", 0),))
+    torch, hip = cost.gpu(TOOL, root)
+    scene, w, h = cost.CONFIGS[tag]
     n = w * h
-    s = torch.cuda.Stream(dev)
     with torch.cuda.stream(s):
         rgb = torch.zeros((h, w, 3), dtype=torch.float32, device=dev)
         depth = torch.zeros((h, w), dtype=torch.float32, device=dev)
@@ -45,23 +34,6 @@ def measure(tag, warmup, repeats, launches, hold_cycles, frame_only, root):
         ctx.render_region_device(region, SPP, rgb, depth, ns, stream=s.cuda_stream)
     s.synchronize()
     kernel = ctx.kernel_name()
-
-    def timed(call):
-        # a window = `launches` calls back to back behind a held stream (tools/gpu_ray_query_cost.py has the reasons)
-        spans = []
-        for _ in range(warmup + repeats):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            with torch.cuda.stream(s):
-                torch.cuda._sleep(hold_cycles)
-                e0.record()
-                for _ in range(launches):
-                    call()
-                e1.record()
-            s.synchronize()
-            spans.append(e0.elapsed_time(e1) / launches)
-        spans = spans[warmup:]
-        return statistics.median(spans), min(spans), max(spans)
-
     steps = [("frame (parent)" if frame_only else "frame", lambda: ctx.render_region_device(region, SPP, rgb, depth, ns, stream=s.cuda_stream))]
     bytes_per_sample = 0
     if not frame_only:
@@ -79,48 +51,35 @@ def measure(tag, warmup, repeats, launches, hold_cycles, frame_only, root):
                                                     rgb=out[0], t=out[1], ns=out[2], stream=s.cuda_stream)
         steps += [("radiance", radiance(rays)), ("radiance shuffled", radiance(shuffled))]
     for name, call in steps:
-        ms, lo, hi = timed(call)
-        print(json.dumps({"config": tag, "scene": scene, "size": [w, h], "spp": SPP, "what": name, "median_ms": round(ms, 4), "min_ms": round(lo, 4),
-                          "max_ms": round(hi, 4), "msamples_per_s": round(n * SPP / ms / 1e3, 1), "ray_bytes_per_sample": bytes_per_sample,
-                          "launches_per_window": launches, "kernel": kernel, "tree": "parent" if frame_only else "this", "library": os.path.relpath(hip.HIP_LIB_PATH, root)}), flush=True)
+        spans = cost.timed(s, call, warmup, repeats, launches=launches, hold_cycles=hold_cycles)   # (windows behind a held stream: cost._span has the reasons)
+        ms = statistics.median(spans)
+        cost.emit(TOOL, f"{tag} {SPP} spp {name}", config=tag, scene=scene, size=[w, h], spp=SPP, what=name, **cost.summary(spans),
+                  msamples_per_s=round(n * SPP / ms / 1e3, 1), ray_bytes_per_sample=bytes_per_sample, launches_per_window=launches, kernel=kernel,
+                  tree="parent" if frame_only else "this", library=cost.library(root))
     ctx.close()
 
 
 def main():
-    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--repeats", type=int, default=7)
+    ap = cost.arguments(__doc__, one=cost.TAGS)
     ap.add_argument("--launches", type=int, default=3, help="calls per timed window; a figure is the window over this")
     ap.add_argument("--hold", type=int, default=40_000_000, help="device clock cycles the stream is held busy before a window, so that its calls queue up")
-    ap.add_argument("--limit", type=int, default=240, help="seconds a configuration's child process may take")
     ap.add_argument("--parent", default=None, help="a built checkout of the parent commit: its frame is the yardstick")
-    ap.add_argument("--root", default=ROOT, help="with --one: the tree whose package is imported")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "radiance_cost.txt"))
-    ap.add_argument("--one", choices=sorted(CONFIGS), help="measure this configuration in this process")
+    ap.add_argument("--root", default=cost.ROOT, help="with --one: the tree whose package is imported")
+    ap.add_argument("--out", default=os.path.join(cost.ROOT, "profiles", "radiance_cost.txt"))
     ap.add_argument("--frame-only", action="store_true", help="with --one: the frame row alone (the parent library's child)")
     a = ap.parse_args()
     if a.one:
         return measure(a.one, a.warmup, a.repeats, a.launches, a.hold, a.frame_only, os.path.abspath(a.root))
-    for root in [ROOT] + ([a.parent] if a.parent else []):   # the stand-in meshes of C5, in each tree's own scenes
-        subprocess.run([sys.executable, os.path.join(root, "scenes", "gen_assets.py")], check=True, stdout=subprocess.DEVNULL)
+    for root in [cost.ROOT] + ([a.parent] if a.parent else []):   # the stand-in meshes of C5, in each tree's own scenes
+        cost.assets(root)
     lines = [f"# tools/gpu_radiance_cost.py (median of {a.repeats} windows after {a.warmup} warm-ups, each {a.launches} queued calls between two events on the caller's stream, per call), "
              f"{SPP} spp, coop 0, one run on one MI355X"]
-    for tag in sorted(CONFIGS):
-        rows = []
-        for parent in ([a.parent] if a.parent else []) + [None]:
-            cmd = [sys.executable, os.path.abspath(__file__), "--one", tag, "--warmup", str(a.warmup), "--repeats", str(a.repeats), "--launches", str(a.launches),
-                   "--hold", str(a.hold)] + (["--frame-only", "--root", parent] if parent else [])
-            try:
-                r = subprocess.run(cmd, timeout=a.limit, stdout=subprocess.PIPE, text=True)
-            except subprocess.TimeoutExpired:
-                raise SystemExit(f"gpu_radiance_cost: {tag} did not finish in {a.limit} s; nothing more is started")
-            if r.returncode != 0:
-                print(r.stdout, end="", flush=True)
-                raise SystemExit(f"gpu_radiance_cost: {tag} ended with {r.returncode}; nothing more is started")
-            rows += [json.loads(line) for line in r.stdout.splitlines() if line.startswith("{")]
+    for tag in cost.TAGS:
+        rows = cost.run_children(__file__, ([[tag, "--frame-only", "--root", a.parent]] if a.parent else []) + [[tag]], sys.argv[1:], a.limit, through=False)
         yard = rows[0]["median_ms"]   # the parent's frame when there is one, else this library's
         for row in rows:
             row["times_" + rows[0]["what"].replace(" ", "_").replace("(", "").replace(")", "")] = round(row["median_ms"] / yard, 3)
+            row.update(tool=row.pop("tool"), id=row.pop("id"))   # (they stay last)
             print(json.dumps(row), flush=True)
             lines.append(json.dumps(row))
     os.makedirs(os.path.dirname(a.out), exist_ok=True)

@@ -8,34 +8,23 @@ stream is held busy while the host enqueues them, so a window holds device time 
   cast shuffled  the same rays in a fixed random permutation: what divergence costs
   occluded       Context.occluded_device of the rays of `cast` with tmax = 1e30
 Every figure in milliseconds and Mrays/s, and as a multiple of gbuffer.  Each configuration runs in a child process of its own
-under a time limit (--limit seconds); the parent never opens the GPU and stops at the first child that fails.  The lines are printed
-and written to --out (default profiles/ray_query_cost.txt).  Needs a GPU: there is no fallback."""
-import argparse
+under a time limit (--limit seconds), by the rule of tools/cost.py.  The lines are printed and written to --out (default
+profiles/ray_query_cost.txt).  Needs a GPU: there is no fallback."""
 import json
 import os
 import statistics
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import cost
 
-CONFIGS = {"c2": ("example_project12_box.xml", 1920, 1080), "c5": ("trc_scene_tower.xml", 3840, 2160)}
+TOOL = "gpu_ray_query_cost"
 
 
 def measure(tag, warmup, repeats, launches, hold_cycles):
-    import torch
-    from qaray_amd import hip
-    from qaray_amd.host import SCENES_DIR, load_scene_blob
-    if not torch.cuda.is_available():
-        raise SystemExit("gpu_ray_query_cost: no GPU (nothing is measured without one)")
-    scene, w, h = CONFIGS[tag]
-    dev = torch.device("cuda", 0)
-    ctx = hip.Context(0)
-    ctx.upload_scene(load_scene_blob(os.path.join(SCENES_DIR, scene), size=(w, h)))
-    region = (0, 0, w, h)
+    ctx, _, region, dev, s = cost.open_scene(TOOL, tag)
+    torch, hip = cost.gpu(TOOL)
+    scene, w, h = cost.CONFIGS[tag]
     n = w * h
-    s = torch.cuda.Stream(dev)
     with torch.cuda.stream(s):
         g = ctx.gbuffer_device(region, stream=s.cuda_stream)
         o, d = ctx.camera_rays_device(region, stream=s.cuda_stream)
@@ -46,65 +35,33 @@ def measure(tag, warmup, repeats, launches, hold_cycles):
         out = ctx.cast_rays_device(o, d, stream=s.cuda_stream)
     s.synchronize()
     hits = int((out["t"] != hip.QA_RAY_MISS).sum())
-
-    def timed(call):
-        # a window = `launches` calls back to back.  The stream is first held busy (torch.cuda._sleep) so that the host - the Python
-        # wrapper's checks, the ctypes call, the launcher's occupancy query - runs ahead and the calls queue up: the window between
-        # the events is then the device's time for them and not the host's latency, which would be a sizeable share of a 0.05 ms call
-        spans = []
-        for _ in range(warmup + repeats):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            with torch.cuda.stream(s):
-                torch.cuda._sleep(hold_cycles)
-                e0.record()
-                for _ in range(launches):
-                    call()
-                e1.record()
-            s.synchronize()
-            spans.append(e0.elapsed_time(e1) / launches)
-        spans = spans[warmup:]
-        return statistics.median(spans), min(spans), max(spans)
-
     steps = [("gbuffer", lambda: ctx.gbuffer_device(region, stream=s.cuda_stream, **g)),
              ("cast", lambda: ctx.cast_rays_device(o, d, stream=s.cuda_stream, **out)),
              ("cast shuffled", lambda: ctx.cast_rays_device(so, sd, stream=s.cuda_stream, **out)),
              ("occluded", lambda: ctx.occluded_device(o, d, tmax, out=occ, stream=s.cuda_stream))]
     yard = None
     for name, call in steps:
-        ms, lo, hi = timed(call)
+        spans = cost.timed(s, call, warmup, repeats, launches=launches, hold_cycles=hold_cycles)   # (windows behind a held stream: cost._span has the reasons)
+        ms = statistics.median(spans)
         yard = ms if name == "gbuffer" else yard
-        print(json.dumps({"config": tag, "scene": scene, "size": [w, h], "rays": n, "hits": hits, "what": name, "median_ms": round(ms, 4), "min_ms": round(lo, 4),
-                          "max_ms": round(hi, 4), "mrays_per_s": round(n / ms / 1e3, 1), "times_gbuffer": round(ms / yard, 3), "launches_per_window": launches, "kernel": ctx.kernel_name(),
-                          "library": os.path.relpath(hip.HIP_LIB_PATH, ROOT)}), flush=True)
+        cost.emit(TOOL, f"{tag} {name}", config=tag, scene=scene, size=[w, h], rays=n, hits=hits, what=name, **cost.summary(spans), mrays_per_s=round(n / ms / 1e3, 1),
+                  times_gbuffer=round(ms / yard, 3), launches_per_window=launches, kernel=ctx.kernel_name())
     ctx.close()
 
 
 def main():
-    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--repeats", type=int, default=7)
+    ap = cost.arguments(__doc__, one=cost.TAGS)
     ap.add_argument("--launches", type=int, default=20, help="calls per timed window; a figure is the window over this")
     ap.add_argument("--hold", type=int, default=40_000_000, help="device clock cycles the stream is held busy before a window, so that its calls queue up")
-    ap.add_argument("--limit", type=int, default=240, help="seconds a configuration's child process may take")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ray_query_cost.txt"))
-    ap.add_argument("--one", choices=sorted(CONFIGS), help="measure this configuration in this process")
+    ap.add_argument("--out", default=os.path.join(cost.ROOT, "profiles", "ray_query_cost.txt"))
     a = ap.parse_args()
     if a.one:
         return measure(a.one, a.warmup, a.repeats, a.launches, a.hold)
+    rows = cost.run_children(__file__, [[tag] for tag in cost.TAGS], sys.argv[1:], a.limit)
     lines = [f"# tools/gpu_ray_query_cost.py (median of {a.repeats} windows after {a.warmup} warm-ups, each {a.launches} queued calls between two events on the caller's stream, per call), one run on one MI355X"]
-    for tag in sorted(CONFIGS):
-        try:
-            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--one", tag, "--warmup", str(a.warmup), "--repeats", str(a.repeats), "--launches", str(a.launches), "--hold", str(a.hold)], timeout=a.limit,
-                               stdout=subprocess.PIPE, text=True)
-        except subprocess.TimeoutExpired:
-            raise SystemExit(f"gpu_ray_query_cost: {tag} did not finish in {a.limit} s; nothing more is started")
-        print(r.stdout, end="", flush=True)
-        if r.returncode != 0:
-            raise SystemExit(f"gpu_ray_query_cost: {tag} ended with {r.returncode}; nothing more is started")
-        lines += r.stdout.splitlines()
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as f:
-        f.write("\n".join(lines) + "\n")
+        f.write("\n".join(lines + [json.dumps(row) for row in rows]) + "\n")
 
 
 if __name__ == "__main__":

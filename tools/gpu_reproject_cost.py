@@ -11,21 +11,18 @@ current frame 20 (rgb, depth, sample count), the history about 20 unique (rgb, d
 neighbours' taps too, so every history pixel is needed about once), the outputs 16; the ids planes add 8 to each side: 56 without
 ids, 72 with.
 
-Each configuration runs in a child process of its own under a time limit (--limit seconds); the parent never opens the GPU, stops
-at the first child that fails and writes the table to --out.  Needs a GPU: there is no fallback."""
-import argparse
-import json
+Each configuration runs in a child process of its own under a time limit (--limit seconds), by the rule of tools/cost.py; the parent
+writes the table to --out.  Needs a GPU: there is no fallback."""
 import os
 import statistics
-import subprocess
 import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import cost
+from cost import CONFIGS   # noqa: F401  (the frames of the three reprojection tools)
 
-CONFIGS = {"c2": ("example_project12_box.xml", 1920, 1080), "c5": ("trc_scene_tower.xml", 3840, 2160)}
+TOOL = "gpu_reproject_cost"
 HBM_PEAK = 8.0e12
 BYTES = {False: 56, True: 72}
 
@@ -50,69 +47,51 @@ def turned(cam, w, h, distance, degrees):
     return out
 
 
-def measure(tag, warmup, repeats):
-    import torch
-    from qaray_amd import hip
-    from qaray_amd.host import SCENES_DIR, load_scene_blob
-    if not torch.cuda.is_available():
-        raise SystemExit("gpu_reproject_cost: no GPU (nothing is measured without one)")
-    scene, w, h = CONFIGS[tag]
-    dev = torch.device("cuda", 0)
-    ctx = hip.Context(0)
-    blob = load_scene_blob(os.path.join(SCENES_DIR, scene), size=(w, h))
-    ctx.upload_scene(blob)
-    region = (0, 0, w, h)
-    s = torch.cuda.Stream(dev)
+def two_views(ctx, blob, region, s, dev, guides=False):
+    """4-spp frames of the scene's own view (seed 1) and of the view one degree round what it shows (seed 2, the context is left at
+    it), each as rgb, depth, ns, ids, normal, albedo - the last two None but for the second frame with `guides` -> cam0, cam1,
+    frame 0, frame 1"""
+    hip = sys.modules["qaray_amd.hip"]
+    w, h = region[2:]
 
-    def frame(seed):
-        rgb = torch.empty((h, w, 3), dtype=torch.float32, device=dev)
-        depth = torch.empty((h, w), dtype=torch.float32, device=dev)
-        ns = torch.empty((h, w), dtype=torch.int32, device=dev)
-        ids = torch.empty((h, w, 2), dtype=torch.int32, device=dev)
+    def frame(seed, guides):
+        rgb, depth, ns, ids = cost.frame_tensors(dev, w, h, ids=True)
+        normal, albedo = (rgb.new_empty(rgb.shape), rgb.new_empty(rgb.shape)) if guides else (None, None)
         ctx.render_region_device(region, 4, rgb, depth, ns, seed=seed, stream=s.cuda_stream)
-        ctx.gbuffer_device(region, seed, ids=ids, stream=s.cuda_stream)
+        ctx.gbuffer_device(region, seed, normal=normal, albedo=albedo, ids=ids, stream=s.cuda_stream)
         s.synchronize()
-        return rgb, depth, ns, ids
+        return rgb, depth, ns, ids, normal, albedo
 
     cam0 = hip.blob_camera(blob).copy()
-    rgb0, depth0, ns0, ids0 = frame(1)
-    hits = depth0[depth0 < 1e29]
-    distance = float(hits.median()) if hits.numel() else 1.0
-    cam1 = turned(cam0, w, h, distance, 1.0)
+    frame0 = frame(1, False)
+    hits = frame0[1][frame0[1] < 1e29]
+    cam1 = turned(cam0, w, h, float(hits.median()) if hits.numel() else 1.0, 1.0)
     ctx.edit_camera(cam1)
-    rgb1, depth1, ns1, ids1 = frame(2)
+    return cam0, cam1, frame0, frame(2, guides)
+
+
+def measure(tag, warmup, repeats):
+    ctx, blob, region, dev, s = cost.open_scene(TOOL, tag)
+    torch, _ = cost.gpu(TOOL)
+    scene, w, h = CONFIGS[tag]
+    cam0, cam1, (rgb0, depth0, ns0, ids0, _, _), (rgb1, depth1, ns1, ids1, _, _) = two_views(ctx, blob, region, s, dev)
     history = (rgb0, depth0, ns0.to(torch.float32))
     out, out_length = torch.empty_like(rgb1), torch.empty_like(depth1)
     torch.cuda.synchronize()
-
-    def timed(call):
-        spans = []
-        for _ in range(warmup + repeats):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            with torch.cuda.stream(s):
-                e0.record()
-                call()
-                e1.record()
-            s.synchronize()
-            spans.append(e0.elapsed_time(e1))
-        spans = spans[warmup:]
-        return statistics.median(spans), min(spans), max(spans)
 
     def reproject(with_ids):
         return ctx.reproject_device((rgb1, depth1, ns1), history, cam0, cam1, ids=ids1 if with_ids else None, hist_ids=ids0 if with_ids else None, out=out,
                                     out_length=out_length, stream=s.cuda_stream)
 
-    frame_ms = timed(lambda: ctx.render_region_device(region, 4, rgb1, depth1, ns1, seed=2, stream=s.cuda_stream))[0]
+    frame_ms = statistics.median(cost.timed(s, lambda: ctx.render_region_device(region, 4, rgb1, depth1, ns1, seed=2, stream=s.cuda_stream), warmup, repeats))
     for with_ids in (True, False):
-        ms, lo, hi = timed(lambda: reproject(with_ids))
-        s.synchronize()
+        spans = cost.timed(s, lambda: reproject(with_ids), warmup, repeats)
+        ms = statistics.median(spans)
         kept = float((out_length > ns1).float().mean())
         moved = w * h * BYTES[with_ids]
-        print(json.dumps({"config": tag, "scene": scene, "size": [w, h], "ids": with_ids, "median_ms": round(ms, 4), "min_ms": round(lo, 4),
-                          "max_ms": round(hi, 4), "frame4_ms": round(frame_ms, 4), "share_of_4spp_frame": round(ms / frame_ms, 4),
-                          "bytes_per_pixel": BYTES[with_ids], "GBps": round(moved / (ms * 1e-3) / 1e9, 1),
-                          "share_of_hbm_peak_8TBps": round(moved / (ms * 1e-3) / HBM_PEAK, 4), "pixels_with_history": round(kept, 4),
-                          "library": os.path.relpath(hip.HIP_LIB_PATH, ROOT)}), flush=True)
+        cost.emit(TOOL, f"{tag} ids={with_ids}", config=tag, scene=scene, size=[w, h], ids=with_ids, **cost.summary(spans), frame4_ms=round(frame_ms, 4),
+                  share_of_4spp_frame=round(ms / frame_ms, 4), bytes_per_pixel=BYTES[with_ids], GBps=round(moved / (ms * 1e-3) / 1e9, 1),
+                  share_of_hbm_peak_8TBps=round(moved / (ms * 1e-3) / HBM_PEAK, 4), pixels_with_history=round(kept, 4))
     ctx.close()
 
 
@@ -130,27 +109,15 @@ def write_table(rows, out, warmup, repeats):
                     f"{r['GBps']:<9.1f}{r['share_of_hbm_peak_8TBps']:<9.4f}{r['pixels_with_history']:.4f}\n")
 
 
-def main():
-    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--repeats", type=int, default=7)
-    ap.add_argument("--limit", type=int, default=240, help="seconds a configuration's child process may take")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "reproject_cost.txt"))
-    ap.add_argument("--one", choices=sorted(CONFIGS), help="measure this configuration in this process")
+def main(script=__file__, doc=__doc__, measure=measure, write_table=write_table, repeats=7):
+    """(also the main of the two tools that extend this one, with their own measure and table)"""
+    name = os.path.basename(script)[len("gpu_"):-len(".py")]
+    ap = cost.arguments(doc, repeats=repeats, one=cost.TAGS)
+    ap.add_argument("--out", default=os.path.join(cost.ROOT, "profiles", name + ".txt"))
     a = ap.parse_args()
     if a.one:
         return measure(a.one, a.warmup, a.repeats)
-    rows = []
-    for tag in sorted(CONFIGS):
-        try:
-            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--one", tag, "--warmup", str(a.warmup), "--repeats", str(a.repeats)],
-                               timeout=a.limit, stdout=subprocess.PIPE, text=True)
-        except subprocess.TimeoutExpired:
-            raise SystemExit(f"gpu_reproject_cost: {tag} did not finish in {a.limit} s; nothing more is started")
-        sys.stdout.write(r.stdout)
-        if r.returncode != 0:
-            raise SystemExit(f"gpu_reproject_cost: {tag} ended with {r.returncode}; nothing more is started")
-        rows += [json.loads(line) for line in r.stdout.splitlines() if line.startswith("{")]
+    rows = cost.run_children(script, [[tag] for tag in cost.TAGS], sys.argv[1:], a.limit)
     write_table(rows, a.out, a.warmup, a.repeats)
     print(f"wrote {a.out}")
 

@@ -8,61 +8,36 @@ hit pixel loads its record and is taken through it (the scene itself is not edit
 
 The variants take turns inside every repeat (old, off, motion, ...; then again), each call between two events on the caller's
 stream: warm-up rounds, then the median of --repeats per variant and its ratio to the old call's.  The 4-spp frame is timed the
-same way.  Each configuration runs in a child process of its own under a time limit (--limit seconds); the parent never opens the
-GPU, stops at the first child that fails and writes the table to --out.  Needs a GPU: there is no fallback."""
-import argparse
-import json
+same way.  Each configuration runs in a child process of its own under a time limit (--limit seconds), by the rule of
+tools/cost.py; the parent writes the table to --out.  Needs a GPU: there is no fallback."""
 import os
 import statistics
-import subprocess
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+import cost
+from gpu_reproject_cost import CONFIGS, main, two_views
 
-from gpu_reproject_cost import CONFIGS, turned   # noqa: E402
-
+TOOL = "gpu_reproject_motion_cost"
 VARIANTS = ("old call", "flags off", "motion", "clamp r=1", "clamp r=2", "motion + clamp r=1")
 
 
-def measure(tag, warmup, repeats):
+def motion_table(hip, blob, dev):
+    """Every node but the root moved by a thousandth of a unit -> the table on the host, its bytes on the device"""
     import torch
-    from qaray_amd import hip
-    from qaray_amd.host import SCENES_DIR, load_scene_blob
-    if not torch.cuda.is_available():
-        raise SystemExit("gpu_reproject_motion_cost: no GPU (nothing is measured without one)")
-    scene, w, h = CONFIGS[tag]
-    dev = torch.device("cuda", 0)
-    ctx = hip.Context(0)
-    blob = load_scene_blob(os.path.join(SCENES_DIR, scene), size=(w, h))
-    ctx.upload_scene(blob)
-    region = (0, 0, w, h)
-    s = torch.cuda.Stream(dev)
-
-    def frame(seed):
-        rgb = torch.empty((h, w, 3), dtype=torch.float32, device=dev)
-        depth = torch.empty((h, w), dtype=torch.float32, device=dev)
-        ns = torch.empty((h, w), dtype=torch.int32, device=dev)
-        ids = torch.empty((h, w, 2), dtype=torch.int32, device=dev)
-        ctx.render_region_device(region, 4, rgb, depth, ns, seed=seed, stream=s.cuda_stream)
-        ctx.gbuffer_device(region, seed, ids=ids, stream=s.cuda_stream)
-        s.synchronize()
-        return rgb, depth, ns, ids
-
-    cam0 = hip.blob_camera(blob).copy()
-    rgb0, depth0, ns0, ids0 = frame(1)
-    hits = depth0[depth0 < 1e29]
-    cam1 = turned(cam0, w, h, float(hits.median()) if hits.numel() else 1.0, 1.0)
-    ctx.edit_camera(cam1)
-    rgb1, depth1, ns1, ids1 = frame(2)
-    history = (rgb0, depth0, ns0.to(torch.float32))
-    out, out_length = torch.empty_like(rgb1), torch.empty_like(depth1)
     inst = hip.blob_table(blob, "instances")
     nudged = inst.copy()
     nudged["pos"][1:] += 1e-3
     table_host = hip.node_motion(inst, nudged)
-    table = torch.from_numpy(table_host.view("u1")).to(dev)
+    return table_host, torch.from_numpy(table_host.view("u1")).to(dev)
+
+
+def measure(tag, warmup, repeats):
+    ctx, blob, region, dev, s = cost.open_scene(TOOL, tag)
+    torch, hip = cost.gpu(TOOL)
+    scene, w, h = CONFIGS[tag]
+    cam0, cam1, (rgb0, depth0, ns0, ids0, _, _), (rgb1, depth1, ns1, ids1, _, _) = two_views(ctx, blob, region, s, dev)
+    history = (rgb0, depth0, ns0.to(torch.float32))
+    out, out_length = torch.empty_like(rgb1), torch.empty_like(depth1)
+    table_host, table = motion_table(hip, blob, dev)
     torch.cuda.synchronize()
     common = dict(ids=ids1, hist_ids=ids0, out=out, out_length=out_length, stream=s.cuda_stream)
 
@@ -73,29 +48,21 @@ def measure(tag, warmup, repeats):
              "flags off": motion_call(), "motion": motion_call(motion=table), "clamp r=1": motion_call(clamp=True, clamp_radius=1),
              "clamp r=2": motion_call(clamp=True, clamp_radius=2), "motion + clamp r=1": motion_call(motion=table, clamp=True, clamp_radius=1),
              "4-spp frame": lambda: ctx.render_region_device(region, 4, rgb1, depth1, ns1, seed=2, stream=s.cuda_stream)}
-    spans = {k: [] for k in calls}
     kept = {}
-    for i in range(warmup + repeats):
-        for name in (*VARIANTS, "4-spp frame"):    # (the frame last: it rewrites rgb1 with the same seed, so with the same bits)
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            with torch.cuda.stream(s):
-                e0.record()
-                calls[name]()
-                e1.record()
-            s.synchronize()
-            if i >= warmup:
-                spans[name].append(e0.elapsed_time(e1))
-            if name != "4-spp frame":
-                kept[name] = float((out_length > ns1).float().mean())
+
+    def with_history(name):
+        if name != "4-spp frame":
+            kept[name] = float((out_length > ns1).float().mean())
+
+    # (the frame last: it rewrites rgb1 with the same seed, so with the same bits)
+    spans = cost.timed_turns(s, calls, (*VARIANTS, "4-spp frame"), warmup, repeats, after=with_history)
     frame_ms = statistics.median(spans["4-spp frame"])
     old_ms = statistics.median(spans["old call"])
     for name in VARIANTS:
         ms = statistics.median(spans[name])
-        print(json.dumps({"config": tag, "scene": scene, "size": [w, h], "variant": name, "median_ms": round(ms, 4), "min_ms": round(min(spans[name]), 4),
-                          "max_ms": round(max(spans[name]), 4), "ratio_to_old_call": round(ms / old_ms, 3), "frame4_ms": round(frame_ms, 4),
-                          "share_of_4spp_frame": round(ms / frame_ms, 4), "pixels_with_history": round(kept[name], 4),
-                          "nodes_moved": int(table_host["moved"].sum()), "nodes": len(table_host), "library": os.path.relpath(hip.HIP_LIB_PATH, ROOT)}),
-              flush=True)
+        cost.emit(TOOL, f"{tag} {name}", config=tag, scene=scene, size=[w, h], variant=name, **cost.summary(spans[name]), ratio_to_old_call=round(ms / old_ms, 3),
+                  frame4_ms=round(frame_ms, 4), share_of_4spp_frame=round(ms / frame_ms, 4), pixels_with_history=round(kept[name], 4),
+                  nodes_moved=int(table_host["moved"].sum()), nodes=len(table_host))
     ctx.close()
 
 
@@ -118,30 +85,5 @@ def write_table(rows, out, warmup, repeats):
         f.write("\n")
 
 
-def main():
-    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--repeats", type=int, default=9)
-    ap.add_argument("--limit", type=int, default=240, help="seconds a configuration's child process may take")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "reproject_motion_cost.txt"))
-    ap.add_argument("--one", choices=sorted(CONFIGS), help="measure this configuration in this process")
-    a = ap.parse_args()
-    if a.one:
-        return measure(a.one, a.warmup, a.repeats)
-    rows = []
-    for tag in sorted(CONFIGS):
-        try:
-            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--one", tag, "--warmup", str(a.warmup), "--repeats", str(a.repeats)],
-                               timeout=a.limit, stdout=subprocess.PIPE, text=True)
-        except subprocess.TimeoutExpired:
-            raise SystemExit(f"gpu_reproject_motion_cost: {tag} did not finish in {a.limit} s; nothing more is started")
-        sys.stdout.write(r.stdout)
-        if r.returncode != 0:
-            raise SystemExit(f"gpu_reproject_motion_cost: {tag} ended with {r.returncode}; nothing more is started")
-        rows += [json.loads(line) for line in r.stdout.splitlines() if line.startswith("{")]
-    write_table(rows, a.out, a.warmup, a.repeats)
-    print(f"wrote {a.out}")
-
-
 if __name__ == "__main__":
-    main()
+    main(__file__, __doc__, measure, write_table, repeats=9)

@@ -10,51 +10,30 @@ after an upload against the first frame after an edit (kernel time by HIP events
 what the context's counters say the two ways did (mesh-table builds, device allocations, bytes copied).
 
 --package DIR times (a) only, with the qaray_amd package of another checkout (DIR/qaray_amd with its built libraries and
-DIR/scenes: the parent commit's, which has no edits): the yardstick.  Needs a GPU: there is no fallback, and without one this fails."""
-import argparse
-import json
+DIR/scenes: the parent commit's, which has no edits): the yardstick.  The measurement runs in a child process under a time limit
+(--limit seconds), by the rule of tools/cost.py.  Needs a GPU: there is no fallback, and without one this fails."""
 import os
 import statistics
-import subprocess
 import sys
-import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import cost
 
-FRAMES = {"C2": ("example_project12_box.xml", (1920, 1080)), "C5": ("trc_scene_tower.xml", (3840, 2160))}
-
-
-def timed(fn):
-    t0 = time.perf_counter()
-    fn()
-    return (time.perf_counter() - t0) * 1e3
+TOOL = "gpu_scene_edit_cost"
 
 
 def summary(t):
-    return {"median_ms": round(statistics.median(t), 3), "min_ms": round(min(t), 3), "max_ms": round(max(t), 3)}
+    return cost.summary(t, 3)
 
 
-def main():
-    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--frames", default="C2,C5")
-    ap.add_argument("--spp", type=int, default=4, help="samples per pixel of the first-frame comparison")
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--repeats", type=int, default=7)
-    ap.add_argument("--package", default=None, help="another checkout's root: its qaray_amd is imported, only the upload is timed")
-    a = ap.parse_args()
-    if a.package:
-        sys.path.insert(0, os.path.abspath(a.package))
-    import torch
-    from qaray_amd import hip, host
-    if not torch.cuda.is_available():
-        raise SystemExit("gpu_scene_edit_cost: no GPU (nothing is measured without one)")
-    subprocess.run([sys.executable, os.path.join(ROOT, "scenes", "gen_assets.py")], check=True, stdout=subprocess.DEVNULL)
+def measure(a):
+    _, hip = cost.gpu(TOOL, os.path.abspath(a.package) if a.package else cost.ROOT)
+    from qaray_amd import host
+    cost.assets()
     ctx = hip.Context(0)
     for name in a.frames.split(","):
-        scene, (w, h) = FRAMES[name]
+        scene, w, h = cost.frame(name)
         region = (0, 0, w, h)
         s = host.HostScene(os.path.join(host.SCENES_DIR, scene), size=(w, h))
         blobs = [s.flatten()]
@@ -78,9 +57,8 @@ def main():
             ctx.upload_scene(blobs[k % 2])
             ctx.synchronize()
 
-        t = [timed(lambda: upload(k)) for k in range(a.warmup + a.repeats)][a.warmup:]
         rec = {"frame": name, "size": [w, h], "blob_bytes": int(blobs[0].size), "library": hip.HIP_LIB_PATH,
-               "a_upload_scene": summary(t)}
+               "a_upload_scene": summary(cost.walls(upload, a.warmup, a.repeats))}
         if not a.package:
             rec["context_stats_after_these_uploads"] = dict(zip(("mesh_builds", "allocations", "bytes_copied", "edits"), ctx.scene_stats()))
 
@@ -89,14 +67,12 @@ def main():
                 ctx.synchronize()
 
             before = ctx.scene_stats()
-            t = [timed(lambda: edit(k)) for k in range(a.warmup + a.repeats)][a.warmup:]
+            rec["b_edit_camera_synchronize"] = summary(cost.walls(edit, a.warmup, a.repeats))
             after = ctx.scene_stats()
-            rec["b_edit_camera_synchronize"] = summary(t)
             rec["edit_stats"] = {"mesh_builds": after[0] - before[0], "allocations": after[1] - before[1], "bytes_copied_per_edit": after[2]}
             rec["a_over_b"] = round(rec["a_upload_scene"]["median_ms"] / rec["b_edit_camera_synchronize"]["median_ms"], 1)
-            t = [timed(lambda: ctx.edit_camera(cams[k % 2])) for k in range(a.warmup + a.repeats)][a.warmup:]
+            rec["edit_camera_call_alone"] = summary(cost.walls(lambda k: ctx.edit_camera(cams[k % 2]), a.warmup, a.repeats))
             ctx.synchronize()
-            rec["edit_camera_call_alone"] = summary(t)
 
             # the first frame after an upload of B against the first frame after an edit to B
             first = {}
@@ -111,13 +87,24 @@ def main():
                         ctx.edit_camera(cams[1])
                     ctx.synchronize()
                     ctx.reset_kernel_time()
-                    wall.append(timed(lambda: ctx.render_region(region, a.spp)))
+                    wall.append(cost.wall(lambda: ctx.render_region(region, a.spp)))
                     kern.append(ctx.kernel_time()[0])
                 first[how] = {"wall_ms": round(statistics.median(wall), 3), "kernel_ms": round(statistics.median(kern), 3)}
             rec["first_frame_after"] = first
             rec["first_frame_spp"] = a.spp
-        print(json.dumps(rec), flush=True)
+        cost.emit(TOOL, name, **rec)
     ctx.close()
+
+
+def main():
+    ap = cost.arguments(__doc__, one=("all",))
+    ap.add_argument("--frames", default="C2,C5")
+    ap.add_argument("--spp", type=int, default=4, help="samples per pixel of the first-frame comparison")
+    ap.add_argument("--package", default=None, help="another checkout's root: its qaray_amd is imported, only the upload is timed")
+    a = ap.parse_args()
+    if a.one:
+        return measure(a)
+    cost.run_children(__file__, [["all"]], sys.argv[1:], a.limit)
 
 
 if __name__ == "__main__":

@@ -11,48 +11,25 @@ on the C3 frame (the textured objects, 1920x1080) and on custom_textures.xml (16
 --repeats calls, each ending in a device synchronise (two images alternate, so that every call changes the scene).
 
 --package DIR times (a) only, with the qaray_amd package of another checkout (DIR/qaray_amd with its built libraries and
-DIR/scenes: the parent commit's, which has no texture edits): the yardstick.  Needs a GPU: there is no fallback."""
-import argparse
-import json
+DIR/scenes: the parent commit's, which has no texture edits): the yardstick.  The measurement runs in a child process under a time
+limit (--limit seconds), by the rule of tools/cost.py.  Needs a GPU: there is no fallback."""
+import itertools
 import os
-import statistics
-import subprocess
 import sys
-import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import cost
 
+TOOL = "gpu_texture_edit_cost"
 FRAMES = {"C3": ("example_project7_object.xml", (1920, 1080)), "custom_textures": ("custom_textures.xml", (160, 120))}
 PEAK_GBS = 8000.0
 
 
-def timed(fn):
-    t0 = time.perf_counter()
-    fn()
-    return (time.perf_counter() - t0) * 1e3
-
-
-def summary(t):
-    return {"median_ms": round(statistics.median(t), 4), "min_ms": round(min(t), 4), "max_ms": round(max(t), 4)}
-
-
-def main():
-    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--frames", default="C3,custom_textures")
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--repeats", type=int, default=7)
-    ap.add_argument("--package", default=None, help="another checkout's root: its qaray_amd is imported, only the upload is timed")
-    a = ap.parse_args()
-    if a.package:
-        sys.path.insert(0, os.path.abspath(a.package))
-    import torch
-    from qaray_amd import hip, host
-    if not torch.cuda.is_available():
-        raise SystemExit("gpu_texture_edit_cost: no GPU (nothing is measured without one)")
-    subprocess.run([sys.executable, os.path.join(ROOT, "scenes", "gen_assets.py")], check=True, stdout=subprocess.DEVNULL)
+def measure(a):
+    torch, hip = cost.gpu(TOOL, os.path.abspath(a.package) if a.package else cost.ROOT)
+    from qaray_amd import host
+    cost.assets()
     dev = torch.device("cuda", 0)
     ctx = hip.Context(0)
     n = a.warmup + a.repeats
@@ -75,7 +52,7 @@ def main():
             ctx.upload_scene(blobs[k % 2])
             ctx.synchronize()
 
-        rec["a_upload_scene"] = summary([timed(lambda: upload(k)) for k in range(n)][a.warmup:])
+        rec["a_upload_scene"] = cost.summary(cost.walls(upload, a.warmup, a.repeats))
         if not a.package:
             before = ctx.scene_stats()
 
@@ -83,7 +60,7 @@ def main():
                 ctx.edit_texels(ti, images[k % 2])
                 ctx.synchronize()
 
-            rec["b_edit_texels_host_synchronize"] = summary([timed(lambda: edit_host(k)) for k in range(n)][a.warmup:])
+            rec["b_edit_texels_host_synchronize"] = cost.summary(cost.walls(edit_host, a.warmup, a.repeats))
             rec["host_edit_bytes_over_the_link"] = ctx.scene_stats()[2]
             tensors = [torch.from_numpy(x).to(dev) for x in images]
             torch.cuda.synchronize()
@@ -92,32 +69,36 @@ def main():
                 ctx.edit_texels(ti, tensors[k % 2])
                 ctx.synchronize()
 
-            rec["b_edit_texels_device_synchronize"] = summary([timed(lambda: edit_device(k)) for k in range(n)][a.warmup:])
+            rec["b_edit_texels_device_synchronize"] = cost.summary(cost.walls(edit_device, a.warmup, a.repeats))
             rec["device_edit_bytes_over_the_link"] = ctx.scene_stats()[2]
             after = ctx.scene_stats()
             rec["edit_stats"] = {"mesh_builds": after[0] - before[0], "allocations": after[1] - before[1], "edits": after[3] - before[3]}
             rec["a_over_b_host"] = round(rec["a_upload_scene"]["median_ms"] / rec["b_edit_texels_host_synchronize"]["median_ms"], 1)
             rec["a_over_b_device"] = round(rec["a_upload_scene"]["median_ms"] / rec["b_edit_texels_device_synchronize"]["median_ms"], 1)
             s = torch.cuda.Stream(dev)
-            spans = []
-            for k in range(n):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                with torch.cuda.stream(s):
-                    e0.record()
-                    ctx.edit_texels(ti, tensors[k % 2], stream=s.cuda_stream)
-                    e1.record()
-                s.synchronize()
-                ctx.synchronize()
-                spans.append(e0.elapsed_time(e1))
-            rec["c_kernel_between_events"] = summary(spans[a.warmup:])
+            k = itertools.count()
+            # (the context's stream is drained before every window, and after the last)
+            rec["c_kernel_between_events"] = cost.summary(cost.timed(s, lambda: ctx.edit_texels(ti, tensors[next(k) % 2], stream=s.cuda_stream), a.warmup, a.repeats,
+                                                                     before=ctx.synchronize))
+            ctx.synchronize()
             moved = tw * th * (3 + 3 + 16)
             gbs = moved / (rec["c_kernel_between_events"]["median_ms"] * 1e-3) / 1e9
             rec["kernel_bytes_moved"] = moved
             rec["kernel_gb_per_s"] = round(gbs, 2)
             rec["share_of_8_tb_per_s"] = round(gbs / PEAK_GBS, 5)
             assert np.array_equal(ctx.download_scene(), blobs[(n - 1) % 2])
-        print(json.dumps(rec), flush=True)
+        cost.emit(TOOL, name, **rec)
     ctx.close()
+
+
+def main():
+    ap = cost.arguments(__doc__, one=("all",))
+    ap.add_argument("--frames", default="C3,custom_textures")
+    ap.add_argument("--package", default=None, help="another checkout's root: its qaray_amd is imported, only the upload is timed")
+    a = ap.parse_args()
+    if a.one:
+        return measure(a)
+    cost.run_children(__file__, [["all"]], sys.argv[1:], a.limit)
 
 
 if __name__ == "__main__":
