@@ -453,6 +453,9 @@ int qa_get_counters(qa_ctx *c, qa_counters *out)
               h.stamp[19] / k, (h.stamp[3] - (double) h.stamp[19]) / k, h.stamp[20] / k, h.stamp[21] / k, h.stamp[22] / k, h.stamp[23], (unsigned long long) h.casts_normal);
     if (!c->integ[kCs].fn && h.stamp[16])   // qa_integrate_lastcast: slots 15 / 16 (the cooperative kernel's otherwise) are the turns of tiles that tileIsEmpty calls empty (qa_emptytile.h)
       fprintf(stderr, "[stamps] turns of empty tiles: %llu of %llu turns (%.3f), share of wave time %.4f\n", h.stamp[16], h.stamp[8], (double) h.stamp[16] / (double) std::max<unsigned long long>(h.stamp[8], 1), h.stamp[15] / k);
+    if (!c->integ[kCs].fn && h.stamp[17])   // qa_integrate_lastcast: slots 13 / 14 / 17 / 18 are the two phases of the queries' leaf sweep (qa_kernel.h sweepLeaves)
+      fprintf(stderr, "[stamps] leaf sweep: box phase %.4f, triangle phase %.4f of wave time | triangle phase: %.1f turns per wave, %.2f of 64 lanes in a turn, %.1f cycles per turn\n", h.stamp[13] / k, h.stamp[14] / k,
+              h.stamp[17] / w, (double) h.stamp[18] / (double) h.stamp[17], (double) h.stamp[14] / (double) h.stamp[17]);
     if (c->integ[kCs].fn && h.stamp[11])   // qa_integrate_cs reuses slots 10 / 11: items taken from the pool / rounds of the cooperative walks
       fprintf(stderr, "[stamps] cooperative walks: %llu rounds, %.1f of 64 lanes hold an item on average (lane occupancy of the walks %.3f); %.3f of the rounds are leaf rounds; 'mesh walks' above = the rounds alone\n", h.stamp[11],
               (double) h.stamp[10] / (double) h.stamp[11], (double) h.stamp[10] / (64.0 * (double) h.stamp[11]), (double) h.stamp[12] / (double) h.stamp[11]);

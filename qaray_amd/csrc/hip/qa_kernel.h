@@ -1030,6 +1030,24 @@ __device__ __forceinline__ float shadow(const SceneMem<RES> mem, const DScene &s
 #define QA_LEAF_SWEEP_SORTED 1   /* 0: a lane takes its candidates in the leaf table's order, not largest box first (the copy behind the table) */
 #endif
 
+// A/B switch (profiles/leaf_pair_cost.txt): make hip EXTRA="-DQA_LEAF_PAIR=0"
+#ifndef QA_LEAF_PAIR
+#define QA_LEAF_PAIR 1   /* 0: a lane of the sweep fetches its candidate's leaf word from global memory and tests the leaf's triangles one per turn */
+// (1: the sweep needs the meshes' leaf-pair bytes in LDS, which qa_kernel_lastcast_body.h provides; with -DQA_LASTCAST_STRAIGHT=0, whose
+// body uses that room for a lane's state, and for a mesh without the bytes the query walks the own tree: the same answers)
+#endif
+#if defined(QA_STAMPS)
+// diagnostic builds: slots 13 / 14 = cycles of the sweep's box phase / triangle phase, 17 = turns of the triangle phase's loop,
+// 18 = lanes that ran those turns (one popcount a turn); the cooperative kernel's slots otherwise
+#define QA_SWEEP_TURN(cnt)                                                                          \
+  {                                                                                                 \
+    const unsigned long long in_ = __ballot(1);                                                     \
+    if ((int) __lane_id() == __ffsll((long long) in_) - 1) { cnt.sl[17] += 1; cnt.sl[18] += (unsigned long long) __popcll(in_); } \
+  }
+#else
+#define QA_SWEEP_TURN(cnt)
+#endif
+
 // Box phase of sweepLeaves: leaves j0 .. j1 - 1 (at most 32) of a leaf table -> bit j - j0 = this lane's ray passes the test that
 // walkBVH<true> applies to a child's box when it visits the parent (the same operands, the same form), against `limit`.  `rec`: the
 // table through the constant address space (no kernel writes it) at a wave-uniform index: scalar loads, the boxes arrive in SGPRs.
@@ -1063,14 +1081,47 @@ __device__ __forceinline__ uint32_t sweepLeafBoxes(QaLeafPtr rec, uint32_t j0, u
 // below the limit, and the caller asks refReaches about the found triangle as it does for the walk's.
 // `table`: global memory, wave-uniform; `ftris`: DMesh::ftris in LDS.  hz: the limit, the accepted distance on return.
 __device__ __forceinline__ bool sweepLeaves(const uint4 *table, uint32_t numLeaves, const uint4 *ftris, const Ray &ray, f3 drcp, bool fastSlab,
-                                            float &hz, uint32_t &best, bool &tie, float pad)
+                                            float &hz, uint32_t &best, bool &tie, float pad, DCounters &cnt, const uint8_t *pairs = nullptr)
 {
   f3 pLo = ray.p + F3(pad, pad, pad), pHi = ray.p - F3(pad, pad, pad);
   if (QA_FMA_SLAB && fastSlab) { pLo = slabRayTerm(pLo, drcp); pHi = slabRayTerm(pHi, drcp); }
   QaLeafPtr rec = (QaLeafPtr) table;
   const uint32_t n0 = numLeaves < 32u ? numLeaves : 32u;
+  QA_T(tBox)
   uint32_t lo = sweepLeafBoxes(rec, 0, n0, ray, pLo, pHi, drcp, fastSlab, hz), hi = 0;
   if (numLeaves > 32u) hi = sweepLeafBoxes(rec, 32, numLeaves, ray, pLo, pHi, drcp, fastSlab, hz);
+  QA_TACC(cnt.sl[13], tBox)
+  QA_T(tTri)
+#if QA_LEAF_PAIR
+  // `pairs` (LDS, wave-uniform): byte j = first | (count - 1) << 7 of leaf j (qa_scene_build.cpp LeafPairBytes; the caller sweeps only
+  // meshes that have them).  One turn is one leaf: both of its triangles are tested against the same limit in straight-line code,
+  // and nothing comes from vector memory.  A leaf of one triangle tests that record twice - the second result is the first's, so
+  // it neither wins nor adds a tie of its own, and no address leaves the mesh.  The outcome is that of one triangle per turn with a
+  // return at the first accepted one (the form below): the second triangle counts, its acceptance and its tie, only where the first
+  // was not accepted.
+  bool found = false;
+  while ((lo | hi) && !found) {
+    QA_SWEEP_TURN(cnt)
+    uint32_t j;
+    if (lo) { j = (uint32_t) __ffs((int) lo) - 1u; lo &= lo - 1u; }
+    else { j = 31u + (uint32_t) __ffs((int) hi); hi &= hi - 1u; }
+    const uint32_t byte = pairs[j];
+    const uint4 *t = ftris + 3 * (size_t) (byte & 127u), *u = t + 3 * (size_t) (byte >> 7);
+    const uint4 t2 = t[2], u2 = u[2];
+    float h1 = hz, h2 = hz;
+    bool tie1 = false, tie2 = false;
+    const bool ok1 = hitTriangleZTie<true>(t[0], t[1], t2, ray, h1, tie1);
+    const bool ok2 = hitTriangleZTie<true>(u[0], u[1], u2, ray, h2, tie2);
+    tie = tie || tie1 || (!ok1 && tie2);
+    found = ok1 || ok2;
+    if (found) {
+      best = (ok1 ? t2.w : u2.w) >> 2;   // element | reference leaf << 15 (DMesh::ftris)
+      hz = ok1 ? h1 : h2;
+    }
+  }
+  QA_TACC(cnt.sl[14], tTri)
+  return found;
+#else
   typedef const __attribute__((address_space(1))) uint32_t *WordPtr;
   WordPtr words = (WordPtr) table;
   while (lo | hi) {
@@ -1081,22 +1132,26 @@ __device__ __forceinline__ bool sweepLeaves(const uint4 *table, uint32_t numLeav
     const uint32_t count = ((word >> QA_BVH_COUNT_SHIFT) & QA_BVH_COUNT_MASK) + 1;
     const uint32_t first = word & QA_BVH_OFFSET_MASK;
     for (uint32_t i = 0; i < count; ++i) {
+      QA_SWEEP_TURN(cnt)
       const uint4 *t = ftris + 3 * (size_t) (first + i);
       const uint4 t2 = t[2];
       if (hitTriangleZTie<true>(t[0], t[1], t2, ray, hz, tie)) {
         best = t2.w >> 2;   // element | reference leaf << 15 (DMesh::ftris)
+        QA_TACC(cnt.sl[14], tTri)
         return true;
       }
     }
   }
+  QA_TACC(cnt.sl[14], tTri)
   return false;
+#endif
 }
 
 // One mesh: is there a triangle nearer than `limit`?  `again`: the answer is not known to be the reference's.
 // leafTable: where the mesh has a leaf table, sweep it instead of walking the own tree (DScene::lastCast = 2; null: walk)
 template <bool RES>
 __device__ __forceinline__ bool blocksMesh(const SceneMem<RES> mem, const DMesh &m, const Ray &ray, float limit, uint32_t *stack,
-                                           DCounters &cnt, bool &again, const uint4 *leafTable = nullptr)
+                                           DCounters &cnt, bool &again, const uint4 *leafTable = nullptr, const uint8_t *leafPairs = nullptr)
 {
   const f3 drcp = F3(1.f / ray.d.x, 1.f / ray.d.y, 1.f / ray.d.z);
   const bool fastSlab = !__any(qabs(ray.d.x) < 1e-7f || qabs(ray.d.y) < 1e-7f || qabs(ray.d.z) < 1e-7f);
@@ -1127,9 +1182,14 @@ __device__ __forceinline__ bool blocksMesh(const SceneMem<RES> mem, const DMesh 
 #if QA_LEAF_SWEEP
   // (a tree that is a single leaf is walked without a box test; numLeaves is 0 for a mesh without a table, and wave-uniform)
   const uint32_t numLeaves = __builtin_amdgcn_readfirstlane(m.numLeaves);
+#if QA_LEAF_PAIR
+  // (a mesh whose leaves do not fit the bytes - DMesh::leafPairs - and a caller without them keep the walk)
+  if (leafTable && numLeaves >= 2 && numLeaves <= QA_TILE_LEAF_CAP && m.leafPairs && leafPairs)
+#else
   if (leafTable && numLeaves >= 2 && numLeaves <= QA_TILE_LEAF_CAP)
+#endif
     hit = sweepLeaves(leafTable + __builtin_amdgcn_readfirstlane(m.resLeaves) + (QA_LEAF_SWEEP_SORTED ? 2 * (size_t) numLeaves : 0), numLeaves, ftris, ray,
-                      drcp, fastSlab, hz, bestF, tie, pad);
+                      drcp, fastSlab, hz, bestF, tie, pad, cnt, leafPairs);
   else
 #endif
   hit = walkBVH<true, false, false, QA_BLOCK, QA_FMA_SLAB != 0>(fnodes, ftris, m.frootData, ray, drcp, fastSlab, hz, false, stack, cnt, bestF, tie, pad);
@@ -1204,7 +1264,7 @@ __device__ __forceinline__ void closestEmitter(const SceneMem<RES> mem, const DS
 // the nearest thing, -1: none (blocked, or nothing hit)
 template <bool RES>
 __device__ __forceinline__ bool lastCastQuery(const SceneMem<RES> mem, const DScene &sc, const Ray &world, uint32_t *stack,
-                                              DCounters &cnt, bool &drawn, int &emitSet)
+                                              DCounters &cnt, bool &drawn, int &emitSet, const uint8_t *leafPairs = nullptr)
 {
   const Ray r0 = rootRay<RES>(sc, world);
   const uint32_t glow = sc.lastCastGlow;
@@ -1242,7 +1302,14 @@ __device__ __forceinline__ bool lastCastQuery(const SceneMem<RES> mem, const DSc
       else if (type == QA_OBJ_PLANE) blocked = hitPlane(r, b, k, false);
       else {
         QA_T(tm0)
+#if QA_LEAF_PAIR
+        // (leafPairs: QA_TILE_LEAF_CAP bytes per mesh of the kernel's arguments, in LDS - qa_kernel_lastcast_body.h; null elsewhere)
+        const int mi = instAt<RES>(sc, k).mesh;
+        blocked = blocksMesh<RES>(mem, meshAt<RES>(sc, mi), r, limit, stack, cnt, again, sc.lastCast == 2u ? sc.resident : nullptr,
+                                  leafPairs ? leafPairs + QA_TILE_LEAF_CAP * (size_t) mi : nullptr);
+#else
         blocked = blocksMesh<RES>(mem, meshAt<RES>(sc, instAt<RES>(sc, k).mesh), r, limit, stack, cnt, again, sc.lastCast == 2u ? sc.resident : nullptr);
+#endif
         QA_TACC(cnt.sl[22], tm0)
       }
     }

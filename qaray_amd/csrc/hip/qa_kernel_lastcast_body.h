@@ -14,7 +14,8 @@
 //   E  the sample's end: running mean / variance, hand-over or output
 // Same float expressions in the same order on the same operands, same random draws in the same order: same bits as the general body
 // (-DQA_LASTCAST_STRAIGHT=0 compiles this kernel from it).  Throughput and radiance are registers that die inside the turn; LDS
-// columns 6 to 11 are not touched (the launch keeps their room: the layout is shared).  Option sync_samples has no effect: the lanes
+// columns 6 to 11 hold nothing of a lane's (the launch keeps their room: the layout is shared; their first 256 bytes carry the meshes'
+// leaf-pair bytes, below).  Option sync_samples has no effect: the lanes
 // of a wave move in lockstep by construction.  No material of these scenes has reflective or refractive lobes (PlanLastCast), so
 // shadeSurface is compiled without them (LOBES = false).
   extern __shared__ uint4 s_dyn[];
@@ -22,6 +23,17 @@
   mem.img = s_dyn;
   static_assert(RES, "the last-cast query belongs to the resident variant without lights");
   for (uint32_t i = threadIdx.x; i < sc.residentVec4; i += QA_BLOCK) s_dyn[i] = sc.resident[i];
+#if QA_LEAF_PAIR
+  // The start of column 6 holds the leaf-pair bytes of the scene's meshes, QA_TILE_LEAF_CAP each (DMesh::leafPairs; qa_kernel.h
+  // sweepLeaves reads them): 256 of the 6 144 bytes this kernel leaves alone, so the launch's LDS size is what it was
+  static_assert(QA_KARG_MESH * QA_TILE_LEAF_CAP <= 6 * QA_BLOCK * sizeof(uint32_t), "the leaf-pair bytes live in columns 6 to 11");
+  uint32_t *const leafPairWords = reinterpret_cast<uint32_t *>(s_dyn + sc.residentVec4) + ((size_t) sc.stackDepth + 6) * QA_BLOCK;
+  for (int mi = 0; mi < QA_KARG_MESH; ++mi) {
+    const DMesh &pm = sc.meshv[mi];
+    if (pm.leafPairs && threadIdx.x < QA_TILE_LEAF_CAP / 4)
+      leafPairWords[mi * (QA_TILE_LEAF_CAP / 4) + threadIdx.x] = reinterpret_cast<const uint32_t *>(sc.resident + pm.resLeaves + 4 * (size_t) pm.numLeaves)[threadIdx.x];
+  }
+#endif
   __syncthreads();
   uint32_t *stack = reinterpret_cast<uint32_t *>(s_dyn + sc.residentVec4) + threadIdx.x;
   // per-lane sample accumulators (columns 0 - 5), the pixel (12), its output index (13) and the sample index (14) live in LDS
@@ -322,7 +334,11 @@
         bool drawn;
         int emitSet;
 #if QA_LAST_CAST_ANYHIT
+#if QA_LEAF_PAIR
+        go = !lastCastQuery<RES>(mem, sc, ray, stack, cnt, drawn, emitSet, reinterpret_cast<const uint8_t *>(s_dyn + sc.residentVec4) + ((size_t) sc.stackDepth + 6) * QA_BLOCK * sizeof(uint32_t));
+#else
         go = !lastCastQuery<RES>(mem, sc, ray, stack, cnt, drawn, emitSet);
+#endif
 #else
         closestEmitter<RES>(mem, sc, ray, stack, cnt, drawn, emitSet);
         go = false;

@@ -621,6 +621,9 @@ void BuildImage(SceneTables &out)
     dm.numLeaves = dm.useFast ? (uint32_t) out.mesh[mi].leaves.size() : 0u;
     dm.resLeaves = dm.numLeaves ? append(out.mesh[mi].leaves.data(), out.mesh[mi].leaves.size() * sizeof(DNode)) : 0u;
     if (dm.numLeaves) append(out.mesh[mi].sweepLeaves.data(), out.mesh[mi].sweepLeaves.size() * sizeof(DNode));   // at resLeaves + 2 * numLeaves
+    unsigned char pairs[QA_TILE_LEAF_CAP];
+    dm.leafPairs = dm.numLeaves && LeafPairBytes(out.mesh[mi].sweepLeaves, pairs) ? 1u : 0u;
+    if (dm.numLeaves) append(pairs, sizeof(pairs));   // at resLeaves + 4 * numLeaves, always all 64 bytes: the kernel copies them whole
   }
 }
 
@@ -767,6 +770,25 @@ void PlanLastCast(const Blob &b, SceneTables &out)
 int SyncAuto(const ScenePlan &plan, bool anySpecularLobes) { return (!anySpecularLobes || plan.textured) ? 1 : 0; }
 
 }  // namespace
+
+// Where the leaves of a sorted leaf table have their triangles in DMesh::ftris, one byte a leaf: first | (count - 1) << 7.  A lane of
+// qa_integrate_lastcast's sweep reads its candidate's byte from LDS instead of the leaf word from global memory (qa_kernel.h
+// sweepLeaves, QA_LEAF_PAIR).  -> false, and all bytes zero, where some leaf has more than two triangles or starts beyond 127
+bool LeafPairBytes(const std::vector<DNode> &sorted, unsigned char bytes[QA_TILE_LEAF_CAP])
+{
+  memset(bytes, 0, QA_TILE_LEAF_CAP);
+  if (sorted.empty() || sorted.size() > QA_TILE_LEAF_CAP) return false;
+  for (size_t j = 0; j < sorted.size(); ++j) {
+    const uint32_t word = sorted[j].data;
+    const uint32_t count = ((word >> QA_BVH_COUNT_SHIFT) & QA_BVH_COUNT_MASK) + 1, first = word & QA_BVH_OFFSET_MASK;
+    if (count > 2 || first > 127) {
+      memset(bytes, 0, QA_TILE_LEAF_CAP);
+      return false;
+    }
+    bytes[j] = (unsigned char) (first | (count - 1) << 7);
+  }
+  return true;
+}
 
 // core/sampler.cpp:31-40, evaluated on the host in the reference's fp32 order
 float HaltonF(int index, int base)

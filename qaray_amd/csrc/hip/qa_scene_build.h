@@ -83,6 +83,8 @@ struct SceneTables {
   uint32_t meshBuilds = 0;               // calls of the per-mesh builder this BuildScene made
 };
 
+// byte j = first | (count - 1) << 7 of leaf j of a sorted leaf table (MeshTables::sweepLeaves); false, and zeros, where a leaf does not fit
+bool LeafPairBytes(const std::vector<DNode> &sorted, unsigned char bytes[QA_TILE_LEAF_CAP]);
 float HaltonF(int index, int base);   // Halton sequence in the reference's fp32 order
 // QA_OK, or a QA_E* code with the reason in *err
 int BuildScene(const unsigned char *blob, size_t nbytes, const BuildKnobs &knobs, SceneTables &out, std::string *err);

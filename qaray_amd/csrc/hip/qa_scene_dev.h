@@ -126,9 +126,11 @@ struct DMesh {
   // leaf table of the own tree (qa_tilecull.h): numLeaves DNode records (a leaf's stored box and its leaf word) at
   // DScene::resident + resLeaves, behind the part of the image that is copied into LDS; 0 = none (no own tree, or more than
   // QA_TILE_LEAF_CAP leaves); behind it, at resLeaves + 2 * numLeaves, the same records once more, largest box first (qa_kernel.h sweepLeaves)
+  // leafPairs = 1: and behind that copy, at resLeaves + 4 * numLeaves, 64 bytes of which byte j says where the sorted copy's leaf j has
+  // its triangles in ftris: first | (count - 1) << 7 (qa_scene_build.cpp LeafPairBytes); 0: some leaf does not fit a byte, the bytes are zero
   uint32_t resLeaves;
   uint32_t numLeaves;
-  uint32_t leafPad;
+  uint32_t leafPairs;
 };
 
 // The widening of the own search trees' boxes and the parallelism / cancellation guards (qa_kernel.h hitMesh, qa_wf.h,
@@ -237,7 +239,8 @@ struct DCounters {
   // 11 hit before shading, 12 spawn.
   // The resident variant without lights also: 19 the part of 3 in waves that hold no camera ray (the bounce rays' walks), 20 what follows
   // the sweep in those waves (miss branch, hit before shading, shadeSurface, spawn), 21 last-cast queries (lastCastQuery), 22 of which mesh walks,
-  // 23 lanes whose query answered "ask again" (a count).
+  // 23 lanes whose query answered "ask again" (a count); 13 / 14 cycles of the box phase / triangle phase of the queries' leaf sweep, 17 turns of
+  // the triangle phase's loop, 18 lanes in those turns (qa_kernel.h sweepLeaves; the cooperative kernel's slots otherwise).
   // qa_integrate_cs also: 13 closest-hit sweep without the rounds, 14 details of the winners, 15 lanes sent to the exact closest-hit
   // walk, 16 (lane, light) pairs sent to the exact shadow walk, 17 shadow sweeps without the rounds, 18 light terms
 #define QA_NSTAMPS 24

@@ -1,7 +1,10 @@
 """Section shares of the megakernel's wave time (diagnostic build: make hip LIBDIR=../lib_stamp OBJDIR=../lib_stamp/obj EXTRA=-DQA_STAMPS).
    QA_HIP_LIB=qaray_amd/lib_stamp/libqaray_hip.so python tools/gpu_stamps.py [spp]
    QA_LAST_CAST=0: option "last_cast" off (the bounce rays of qa_integrate_lastcast run the closest-hit sweep and shading)
-   QA_EMPTY_TILES=0: option "empty_tiles" off - the stamps then show what the turns of empty tiles cost (qa_emptytile.h)"""
+   QA_EMPTY_TILES=0: option "empty_tiles" off - the stamps then show what the turns of empty tiles cost (qa_emptytile.h)
+   The library prints the shares when the counters are read.  On qa_integrate_lastcast the line "[stamps] leaf sweep" splits the
+   queries' leaf sweep (qa_kernel.h sweepLeaves; slots 13, 14, 17, 18): box phase and triangle phase as shares of wave time, the
+   triangle phase's turns per wave, lanes per turn and cycles per turn - a turn is one triangle with -DQA_LEAF_PAIR=0, one leaf without."""
 import os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
