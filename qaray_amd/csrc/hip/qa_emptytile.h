@@ -37,10 +37,7 @@
 #pragma once
 #include "qa_tilecull.h"
 
-// A/B switch: make hip EXTRA="-DQA_EMPTY_TILES=0" compiles the shortcut out of qa_integrate_lastcast (profiles/empty_tiles_cost.txt)
-#ifndef QA_EMPTY_TILES
-#define QA_EMPTY_TILES 1
-#endif
+// (what the shortcut costs and returns: profiles/empty_tiles_cost.txt; the run-time option "empty_tiles" turns it off)
 #define QA_EMPTY_TILE_NODES 64   /* scenes of more nodes have no empty tile (a resident scene has at most QA_KARG_INST) */
 
 namespace qa {

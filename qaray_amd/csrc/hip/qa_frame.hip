@@ -37,7 +37,7 @@ static bool LastCastVariant(const qa_ctx *c) { return c->plan.resident && c->pla
 static int TileListLimit(const qa_ctx *c) { return c->plan.tileListBytes ? (c->optTileLists < 0 ? QA_TILE_LISTS_AUTO : c->optTileLists) : 0; }
 static bool EmptyTilesOn(const qa_ctx *c)
 {
-  return QA_EMPTY_TILES && LastCastVariant(c) && c->optEmptyTiles != 0 && TileListLimit(c) > 0 && !(c->ds.cam.dof > 0.1f);
+  return LastCastVariant(c) && c->optEmptyTiles != 0 && TileListLimit(c) > 0 && !(c->ds.cam.dof > 0.1f);
 }
 static bool CsCullVariant(const qa_ctx *c) { return c->plan.csCullOk && (CsManyVariant(c) || c->plan.area || c->plan.textured || c->ds.num_inst > 12); }
 

@@ -495,14 +495,6 @@ __device__ __forceinline__ void triangleDetails(const uint4 q0, const uint4 q1, 
   h.front = (dz <= 0);
 }
 
-// A/B switches of the cast's two shortcuts (profiles/cast_cost.txt): make hip EXTRA="-DQA_FMA_SLAB=0" etc.
-#ifndef QA_FMA_SLAB
-#define QA_FMA_SLAB 1         /* 0: the own tree's fast slab step subtracts and multiplies in every variant (boxEntryExitPadFast) */
-#endif
-#ifndef QA_REACH_AT_FOUND
-#define QA_REACH_AT_FOUND 1   /* 0: refReaches tests entry < t for closest-hit queries too */
-#endif
-
 // TriObj::IntersectRay + TraceBVHNode (src/objects/objects.cpp:310-420).  The traversal stack
 // holds node DATA words (leaf flag + range, or child index) instead of ids: the word arrives with
 // the node's box when the parent tests its two children, so an inner visit is a single 64-byte
@@ -723,7 +715,7 @@ __device__ __forceinline__ bool refReaches(const uint4 *nodes, uint32_t leaf, co
   const f3 bmin = F3(asF(n0.x), asF(n0.y), asF(n0.z)), bmax = F3(asF(n0.w), asF(n1.x), asF(n1.y));
   if (fastSlab) boxEntryExitFast(ray, drcp, bmin, bmax, entry, exit_);
   else boxEntryExit(ray, drcp, bmin, bmax, entry, exit_);
-  return refLeafReached(entry, exit_, limit, QA_REACH_AT_FOUND && atFound);
+  return refLeafReached(entry, exit_, limit, atFound);
 }
 
 // TriObj::IntersectRay + TraceBVHNode (src/objects/objects.cpp:310-420).
@@ -740,8 +732,7 @@ __device__ __forceinline__ bool refReaches(const uint4 *nodes, uint32_t leaf, co
 // TL: `tileList` may point at the wave's tile lists (qa_tilecull.h; qa_integrate, section A), `listHdr` is this node's header word
 // there (0: none) and `primary` says which lanes hold a camera ray: where the node has a list, those lanes test the listed
 // leaves' triangles instead of walking the own tree.
-// DETAILS = false (closest-hit queries whose caller wants the winning node alone: closestEmitter): h.z and h.node, nothing else.
-template <bool RES, bool STATS, bool TL = false, bool DETAILS = true>
+template <bool RES, bool STATS, bool TL = false>
 __device__ __forceinline__ bool hitMesh(const SceneMem<RES> mem, const DMesh &m, const Ray &ray, Hit &h, int k,
                                         bool closest, uint32_t *stack /* LDS, stride QA_BLOCK */, DCounters &cnt,
                                         TriPick &pick, uint32_t stackCap = 0xFFFFu, const uint32_t *tileList = nullptr, uint32_t listHdr = 0,
@@ -840,7 +831,7 @@ __device__ __forceinline__ bool hitMesh(const SceneMem<RES> mem, const DMesh &m,
       }
     }
     if (!listed)
-      hasHit = walkBVH<true, false, false, QA_BLOCK, TL && QA_FMA_SLAB>(fnodes, ftris, m.frootData, ray, drcp, fastSlab, h.z, closest, stack, cnt, bestF, tie, pad);
+      hasHit = walkBVH<true, false, false, QA_BLOCK, TL>(fnodes, ftris, m.frootData, ray, drcp, fastSlab, h.z, closest, stack, cnt, bestF, tie, pad);
     // Beyond the mesh bounds a triangle can only be "hit" by cancellation: at a distance D from the
     // triangle the inside test is off by ~64 eps D^2 / (L h) and would have to be off by D / L, i.e.
     // D >= h / (64 eps) ~ 2.6e5 h (all three areas then round to the same product: barycentrics 0, 0, 1).
@@ -876,10 +867,6 @@ __device__ __forceinline__ bool hitMesh(const SceneMem<RES> mem, const DMesh &m,
     }
   }
   if (!closest) return hasHit;
-  if constexpr (!DETAILS) {
-    if (hasHit) h.node = k;
-    return hasHit;
-  }
   if (hasHit) {
     float ba = 0, bb = 0;
     {
@@ -1022,20 +1009,9 @@ __device__ __forceinline__ float shadow(const SceneMem<RES> mem, const DScene &s
 // A lane whose found triangle's leaf fails the strict test at the limit, which saw a triangle at exactly the limit or whose mesh has
 // no own tree answers "ask again": it repeats the ray as the closest-hit sweep and shading of every other variant.
 // ---------------------------------------------------------------------------------------------
-// A/B switch (profiles/leaf_sweep_cost.txt): make hip EXTRA="-DQA_LEAF_SWEEP=0"
-#ifndef QA_LEAF_SWEEP
-#define QA_LEAF_SWEEP 1   /* 0: the bounce rays' any-hit query walks the own tree whatever DScene::lastCast says */
-#endif
-#ifndef QA_LEAF_SWEEP_SORTED
-#define QA_LEAF_SWEEP_SORTED 1   /* 0: a lane takes its candidates in the leaf table's order, not largest box first (the copy behind the table) */
-#endif
-
-// A/B switch (profiles/leaf_pair_cost.txt): make hip EXTRA="-DQA_LEAF_PAIR=0"
-#ifndef QA_LEAF_PAIR
-#define QA_LEAF_PAIR 1   /* 0: a lane of the sweep fetches its candidate's leaf word from global memory and tests the leaf's triangles one per turn */
-// (1: the sweep needs the meshes' leaf-pair bytes in LDS, which qa_kernel_lastcast_body.h provides; with -DQA_LASTCAST_STRAIGHT=0, whose
-// body uses that room for a lane's state, and for a mesh without the bytes the query walks the own tree: the same answers)
-#endif
+// The bounce rays' any-hit query sweeps a mesh's leaf table where DScene::lastCast says so (profiles/leaf_sweep_cost.txt), a leaf per
+// turn (profiles/leaf_pair_cost.txt).  The sweep needs the meshes' leaf-pair bytes in LDS, which qa_kernel_lastcast_body.h provides;
+// for a mesh without the bytes the query walks the own tree: the same answers.
 #if defined(QA_STAMPS)
 // diagnostic builds: slots 13 / 14 = cycles of the sweep's box phase / triangle phase, 17 = turns of the triangle phase's loop,
 // 18 = lanes that ran those turns (one popcount a turn); the cooperative kernel's slots otherwise
@@ -1060,13 +1036,8 @@ __device__ __forceinline__ uint32_t sweepLeafBoxes(QaLeafPtr rec, uint32_t j0, u
     QaLeafPtr r = rec + 8 * (size_t) j;   // DNode
     const f3 bmin = F3(asF(r[0]), asF(r[1]), asF(r[2])), bmax = F3(asF(r[3]), asF(r[4]), asF(r[5]));
     float entry, exit_;
-    if (fastSlab) {
-#if QA_FMA_SLAB
-      boxEntryExitPadFma(pLo, pHi, drcp, bmin, bmax, entry, exit_);
-#else
-      boxEntryExitPadFast(pLo, pHi, drcp, bmin, bmax, entry, exit_);
-#endif
-    } else boxEntryExitPad(pLo, pHi, ray.d, drcp, bmin, bmax, entry, exit_);
+    if (fastSlab) boxEntryExitPadFma(pLo, pHi, drcp, bmin, bmax, entry, exit_);
+    else boxEntryExitPad(pLo, pHi, ray.d, drcp, bmin, bmax, entry, exit_);
     mask |= (entry <= limit && entry <= exit_) ? (1u << (j - j0)) : 0u;
   }
   return mask;
@@ -1081,10 +1052,10 @@ __device__ __forceinline__ uint32_t sweepLeafBoxes(QaLeafPtr rec, uint32_t j0, u
 // below the limit, and the caller asks refReaches about the found triangle as it does for the walk's.
 // `table`: global memory, wave-uniform; `ftris`: DMesh::ftris in LDS.  hz: the limit, the accepted distance on return.
 __device__ __forceinline__ bool sweepLeaves(const uint4 *table, uint32_t numLeaves, const uint4 *ftris, const Ray &ray, f3 drcp, bool fastSlab,
-                                            float &hz, uint32_t &best, bool &tie, float pad, DCounters &cnt, const uint8_t *pairs = nullptr)
+                                            float &hz, uint32_t &best, bool &tie, float pad, DCounters &cnt, const uint8_t *pairs)
 {
   f3 pLo = ray.p + F3(pad, pad, pad), pHi = ray.p - F3(pad, pad, pad);
-  if (QA_FMA_SLAB && fastSlab) { pLo = slabRayTerm(pLo, drcp); pHi = slabRayTerm(pHi, drcp); }
+  if (fastSlab) { pLo = slabRayTerm(pLo, drcp); pHi = slabRayTerm(pHi, drcp); }
   QaLeafPtr rec = (QaLeafPtr) table;
   const uint32_t n0 = numLeaves < 32u ? numLeaves : 32u;
   QA_T(tBox)
@@ -1092,13 +1063,12 @@ __device__ __forceinline__ bool sweepLeaves(const uint4 *table, uint32_t numLeav
   if (numLeaves > 32u) hi = sweepLeafBoxes(rec, 32, numLeaves, ray, pLo, pHi, drcp, fastSlab, hz);
   QA_TACC(cnt.sl[13], tBox)
   QA_T(tTri)
-#if QA_LEAF_PAIR
   // `pairs` (LDS, wave-uniform): byte j = first | (count - 1) << 7 of leaf j (qa_scene_build.cpp LeafPairBytes; the caller sweeps only
   // meshes that have them).  One turn is one leaf: both of its triangles are tested against the same limit in straight-line code,
   // and nothing comes from vector memory.  A leaf of one triangle tests that record twice - the second result is the first's, so
   // it neither wins nor adds a tie of its own, and no address leaves the mesh.  The outcome is that of one triangle per turn with a
-  // return at the first accepted one (the form below): the second triangle counts, its acceptance and its tie, only where the first
-  // was not accepted.
+  // return at the first accepted one (tests/cpp/leaf_pair_check.cpp holds that form): the second triangle counts, its acceptance
+  // and its tie, only where the first was not accepted.
   bool found = false;
   while ((lo | hi) && !found) {
     QA_SWEEP_TURN(cnt)
@@ -1121,37 +1091,13 @@ __device__ __forceinline__ bool sweepLeaves(const uint4 *table, uint32_t numLeav
   }
   QA_TACC(cnt.sl[14], tTri)
   return found;
-#else
-  typedef const __attribute__((address_space(1))) uint32_t *WordPtr;
-  WordPtr words = (WordPtr) table;
-  while (lo | hi) {
-    uint32_t j;
-    if (lo) { j = (uint32_t) __ffs((int) lo) - 1u; lo &= lo - 1u; }
-    else { j = 31u + (uint32_t) __ffs((int) hi); hi &= hi - 1u; }
-    const uint32_t word = words[8 * (size_t) j + 6];   // DNode::data of the lane's own leaf
-    const uint32_t count = ((word >> QA_BVH_COUNT_SHIFT) & QA_BVH_COUNT_MASK) + 1;
-    const uint32_t first = word & QA_BVH_OFFSET_MASK;
-    for (uint32_t i = 0; i < count; ++i) {
-      QA_SWEEP_TURN(cnt)
-      const uint4 *t = ftris + 3 * (size_t) (first + i);
-      const uint4 t2 = t[2];
-      if (hitTriangleZTie<true>(t[0], t[1], t2, ray, hz, tie)) {
-        best = t2.w >> 2;   // element | reference leaf << 15 (DMesh::ftris)
-        QA_TACC(cnt.sl[14], tTri)
-        return true;
-      }
-    }
-  }
-  QA_TACC(cnt.sl[14], tTri)
-  return false;
-#endif
 }
 
 // One mesh: is there a triangle nearer than `limit`?  `again`: the answer is not known to be the reference's.
 // leafTable: where the mesh has a leaf table, sweep it instead of walking the own tree (DScene::lastCast = 2; null: walk)
 template <bool RES>
 __device__ __forceinline__ bool blocksMesh(const SceneMem<RES> mem, const DMesh &m, const Ray &ray, float limit, uint32_t *stack,
-                                           DCounters &cnt, bool &again, const uint4 *leafTable = nullptr, const uint8_t *leafPairs = nullptr)
+                                           DCounters &cnt, bool &again, const uint4 *leafTable, const uint8_t *leafPairs)
 {
   const f3 drcp = F3(1.f / ray.d.x, 1.f / ray.d.y, 1.f / ray.d.z);
   const bool fastSlab = !__any(qabs(ray.d.x) < 1e-7f || qabs(ray.d.y) < 1e-7f || qabs(ray.d.z) < 1e-7f);
@@ -1179,20 +1125,16 @@ __device__ __forceinline__ bool blocksMesh(const SceneMem<RES> mem, const DMesh 
   uint32_t bestF = 0;
   bool tie = false;
   bool hit;
-#if QA_LEAF_SWEEP
   // (a tree that is a single leaf is walked without a box test; numLeaves is 0 for a mesh without a table, and wave-uniform)
   const uint32_t numLeaves = __builtin_amdgcn_readfirstlane(m.numLeaves);
-#if QA_LEAF_PAIR
-  // (a mesh whose leaves do not fit the bytes - DMesh::leafPairs - and a caller without them keep the walk)
+  // (a mesh whose leaves do not fit the bytes - DMesh::leafPairs - keeps the walk.  The one caller always has the bytes; the test of
+  // `leafPairs` stays because qa_integrate_lastcast's assembly is another without it.  The table's second copy, behind the first, is
+  // sorted largest box first)
   if (leafTable && numLeaves >= 2 && numLeaves <= QA_TILE_LEAF_CAP && m.leafPairs && leafPairs)
-#else
-  if (leafTable && numLeaves >= 2 && numLeaves <= QA_TILE_LEAF_CAP)
-#endif
-    hit = sweepLeaves(leafTable + __builtin_amdgcn_readfirstlane(m.resLeaves) + (QA_LEAF_SWEEP_SORTED ? 2 * (size_t) numLeaves : 0), numLeaves, ftris, ray,
+    hit = sweepLeaves(leafTable + __builtin_amdgcn_readfirstlane(m.resLeaves) + 2 * (size_t) numLeaves, numLeaves, ftris, ray,
                       drcp, fastSlab, hz, bestF, tie, pad, cnt, leafPairs);
   else
-#endif
-  hit = walkBVH<true, false, false, QA_BLOCK, QA_FMA_SLAB != 0>(fnodes, ftris, m.frootData, ray, drcp, fastSlab, hz, false, stack, cnt, bestF, tie, pad);
+    hit = walkBVH<true, false, false, QA_BLOCK, true>(fnodes, ftris, m.frootData, ray, drcp, fastSlab, hz, false, stack, cnt, bestF, tie, pad);
   if (tie) {
     again = true;
     return false;
@@ -1227,44 +1169,11 @@ __device__ __forceinline__ bool blocksMesh(const SceneMem<RES> mem, const DMesh 
   return true;
 }
 
-// A/B switch (profiles/last_cast_cost.txt): make hip EXTRA="-DQA_LAST_CAST_ANYHIT=0"
-#ifndef QA_LAST_CAST_ANYHIT
-#define QA_LAST_CAST_ANYHIT 1   /* 0: the last cast keeps the closest-hit search (closestEmitter) and drops only what follows it */
-#endif
-// The same two answers from the closest-hit search of every other variant, without the hit's details, the transform back and the
-// shading: the part of the gain that does not need the any-hit argument.  Never asks again.
-template <bool RES>
-__device__ __forceinline__ void closestEmitter(const SceneMem<RES> mem, const DScene &sc, const Ray &world, uint32_t *stack,
-                                               DCounters &cnt, bool &drawn, int &emitSet)
-{
-  const Ray r0 = rootRay<RES>(sc, world);
-  Hit h;
-  h.z = QA_BIGFLOAT;
-  h.node = -1;
-  for (int k = 1; k < sc.num_inst; ++k) {
-    const int type = instAt<RES>(sc, k).obj_type;
-    if (type == QA_OBJ_NONE) continue;
-    const Ray r = localRay<RES>(sc, k, r0);
-    if (type == QA_OBJ_SPHERE) hitSphere(r, h, k, true);
-    else if (type == QA_OBJ_PLANE) hitPlane(r, h, k, true);
-    else {
-      TriPick pick;
-      hitMesh<RES, false, true, false>(mem, meshAt<RES>(sc, instAt<RES>(sc, k).mesh), r, h, k, true, stack, cnt, pick, sc.stackDepth);
-    }
-  }
-  drawn = h.node >= 0;
-  emitSet = -1;
-  for (uint32_t rest = sc.lastCastGlow; rest; rest &= rest - 1) {
-    const int k = __ffs((int) rest) - 1;
-    if (k == h.node) emitSet = instAt<RES>(sc, k).mtlset;
-  }
-}
-
 // -> false: ask again with the closest-hit sweep.  Else `drawn`: something is hit; emitSet: the material set of the glow node that is
 // the nearest thing, -1: none (blocked, or nothing hit)
 template <bool RES>
 __device__ __forceinline__ bool lastCastQuery(const SceneMem<RES> mem, const DScene &sc, const Ray &world, uint32_t *stack,
-                                              DCounters &cnt, bool &drawn, int &emitSet, const uint8_t *leafPairs = nullptr)
+                                              DCounters &cnt, bool &drawn, int &emitSet, const uint8_t *leafPairs)
 {
   const Ray r0 = rootRay<RES>(sc, world);
   const uint32_t glow = sc.lastCastGlow;
@@ -1302,14 +1211,10 @@ __device__ __forceinline__ bool lastCastQuery(const SceneMem<RES> mem, const DSc
       else if (type == QA_OBJ_PLANE) blocked = hitPlane(r, b, k, false);
       else {
         QA_T(tm0)
-#if QA_LEAF_PAIR
-        // (leafPairs: QA_TILE_LEAF_CAP bytes per mesh of the kernel's arguments, in LDS - qa_kernel_lastcast_body.h; null elsewhere)
+        // (leafPairs: QA_TILE_LEAF_CAP bytes per mesh of the kernel's arguments, in LDS - qa_kernel_lastcast_body.h)
         const int mi = instAt<RES>(sc, k).mesh;
         blocked = blocksMesh<RES>(mem, meshAt<RES>(sc, mi), r, limit, stack, cnt, again, sc.lastCast == 2u ? sc.resident : nullptr,
                                   leafPairs ? leafPairs + QA_TILE_LEAF_CAP * (size_t) mi : nullptr);
-#else
-        blocked = blocksMesh<RES>(mem, meshAt<RES>(sc, instAt<RES>(sc, k).mesh), r, limit, stack, cnt, again, sc.lastCast == 2u ? sc.resident : nullptr);
-#endif
         QA_TACC(cnt.sl[22], tm0)
       }
     }
@@ -1827,15 +1732,11 @@ struct Path {
 #ifndef QA_LASTCAST_WAVES
 #define QA_LASTCAST_WAVES (QA_MIN_WAVES + QA_C2_EXTRA_WAVE)
 #endif
-// A/B switch: make hip EXTRA="-DQA_LASTCAST_STRAIGHT=0" compiles qa_integrate_lastcast from qa_kernel_body.h, as before
-#ifndef QA_LASTCAST_STRAIGHT
-#define QA_LASTCAST_STRAIGHT 1
-#endif
 
 template <bool RES, bool LIGHTS, bool TEX, bool AREA, bool STATS, bool PHOTON = false>
 __global__ __launch_bounds__(QA_BLOCK, QA_WAVES_FOR(RES, LIGHTS)) void qa_integrate(const DScene sc, const RenderParams rp)
 {
-  constexpr bool LASTQ = false, RAYS = false;
+  constexpr bool RAYS = false;
   const RayBatch rb = {};
 #include "qa_kernel_body.h"
 }
@@ -1846,24 +1747,16 @@ __global__ __launch_bounds__(QA_BLOCK, QA_WAVES_FOR(RES, LIGHTS)) void qa_integr
 template <bool RES>
 __global__ __launch_bounds__(QA_BLOCK, QA_LASTCAST_WAVES) void qa_integrate_lastcast(const DScene sc, const RenderParams rp)
 {
-#if QA_LASTCAST_STRAIGHT
 #include "qa_kernel_lastcast_body.h"
-#else
-  constexpr bool LIGHTS = false, TEX = false, AREA = false, STATS = false, PHOTON = false;
-  constexpr bool LASTQ = true;   // its bounce rays go through lastCastQuery
-  constexpr bool RAYS = false;
-  const RayBatch rb = {};
-#include "qa_kernel_body.h"
-#endif
 }
 
 // qa_integrate<RES, LIGHTS, TEX, AREA> whose paths start from rays of the caller's (qa_radiance_rays*; the opening comment of
-// qa_radiance.hip is the specification): the third entry point over the body.  The ray arrays are a third kernel argument, so that
+// qa_radiance.hip is the specification): the second entry point over the body.  The ray arrays are a third kernel argument, so that
 // RenderParams and the kernel arguments of every shipped kernel stay as they are.  Instances: qa_radiance.hip.
 template <bool RES, bool LIGHTS, bool TEX, bool AREA>
 __global__ __launch_bounds__(QA_BLOCK, QA_WAVES_FOR(RES, LIGHTS)) void qa_integrate_rays(const DScene sc, const RenderParams rp, const RayBatch rb)
 {
-  constexpr bool STATS = false, PHOTON = false, LASTQ = false;
+  constexpr bool STATS = false, PHOTON = false;
   constexpr bool RAYS = true;
 #include "qa_kernel_body.h"
 }

@@ -1,7 +1,7 @@
-// qa_kernel_body.h - the body of the per-lane megakernel (qa_kernel.h), included by its three entry points: qa_integrate,
-// qa_integrate_lastcast and qa_integrate_rays.  Not a header of its own: it is the text of a function whose parameters are `sc` and
-// `rp`, with the template parameters RES, LIGHTS, TEX, AREA, STATS, PHOTON, the constants LASTQ and RAYS and the ray batch `rb`
-// (RayBatch; empty unless RAYS) in scope.  (A text include rather than an inline function, as qa_kernel_cs_body.h: the shipped
+// qa_kernel_body.h - the body of the per-lane megakernel (qa_kernel.h), included by its two entry points: qa_integrate and
+// qa_integrate_rays (qa_integrate_lastcast has a body of its own, qa_kernel_lastcast_body.h).  Not a header of its own: it is the text
+// of a function whose parameters are `sc` and `rp`, with the template parameters RES, LIGHTS, TEX, AREA, STATS, PHOTON, the constant
+// RAYS and the ray batch `rb` (RayBatch; empty unless RAYS) in scope.  (A text include rather than an inline function, as qa_kernel_cs_body.h: the shipped
 // instances keep exactly the code they had - through a function the kernel arguments are copied to scratch and the AREA variants
 // spill a thousand registers.)
 // RAYS (qa_integrate_rays; the opening comment of qa_radiance.hip is the specification): the paths start from the rays of `rb` and
@@ -34,7 +34,6 @@
   // With depth of field the camera rays of a tile share no origin.
   // (in the variant without lights only: the lit and textured resident variants pay for the shared text in spilled registers)
   constexpr bool TL = RES && !LIGHTS && !TEX && !AREA && !STATS && !PHOTON && !RAYS;   // (rays of a batch share no tile)
-  static_assert(!LASTQ || TL, "the last-cast query belongs to the resident variant without lights");
   uint32_t *tileList = nullptr;
   if constexpr (TL)
     if (rp.tile_lists > 0 && !(sc.cam.dof > 0.1f))
@@ -297,43 +296,7 @@
       th.uvw = F3(0.5f, 0.5f, 0.5f);   // HitInfo::Init (src/core/hitinfo.cpp:31-42)
       th.duvw0 = th.duvw1 = F3(0, 0, 0);
       th.hasTexture = false;
-      bool sweep = true;   // the closest-hit sweep and shading; LASTQ: a bounce ray only when its query says "ask again"
-      if constexpr (LASTQ) {
-        if (sc.lastCast && !path.primary) {
-          // every ray that is no camera ray is its path's last (PlanLastCast): which emitter does it meet? (lastCastQuery)
-          QA_T(tQ)
-          bool drawn;
-          int emitSet;
-#if QA_LAST_CAST_ANYHIT
-          sweep = !lastCastQuery<RES>(mem, sc, path.ray, stack, cnt, drawn, emitSet);
-#else
-          closestEmitter<RES>(mem, sc, path.ray, stack, cnt, drawn, emitSet);
-          sweep = false;
-#endif
-          if (!sweep) {
-            QA_TALLY(cnt.casts_normal);
-            // the products, not their values for a finite throughput: a hit that does not emit adds T * 0
-            f3 c = ld3(sc.environment);
-            if (drawn) {
-              (void) rng1(rng);   // RandomSelectMtl's draw at the hit; nothing is spawned from a diffuse bounce's hit
-              c = F3(0, 0, 0);
-              if (emitSet >= 0) {
-                const uint4 m2 = mtlTable[6 * (size_t) sc.mtlset[emitSet].first + 2];
-                c = F3(asF(m2.x), asF(m2.y), asF(m2.z));
-              }
-            }
-            QA_PUT_L(QA_GET_L() + QA_GET_T() * c)
-            done = true;
-          }
-          QA_TACC(cnt.sl[21], tQ)
-#ifdef QA_STAMPS
-          {
-            const unsigned long long asked = __ballot(sweep);   // lanes whose query said "ask again"
-            if ((int) __lane_id() == __ffsll((long long) __ballot(1)) - 1) cnt.sl[23] += (unsigned long long) __popcll(asked);
-          }
-#endif
-        }
-      }
+      bool sweep = true;   // the closest-hit sweep and shading; RAYS: not for a void first ray
       if constexpr (RAYS) {
         // a void first ray (a component that is not finite, or direction 0) is not walked and draws nothing from the stream: the
         // sample is black, and it counts

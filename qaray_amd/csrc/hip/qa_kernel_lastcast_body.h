@@ -13,7 +13,8 @@
 //      shadeSurface and lastCastQuery - the second copy costs 900 scalar instructions and 16 more spilled registers.)
 //   E  the sample's end: running mean / variance, hand-over or output
 // Same float expressions in the same order on the same operands, same random draws in the same order: same bits as the general body
-// (-DQA_LASTCAST_STRAIGHT=0 compiles this kernel from it).  Throughput and radiance are registers that die inside the turn; LDS
+// (tests/test_gpu_lastcast_straight.py and tests/test_gpu_last_cast.py compare this kernel's frames with the counting kernel's, which
+// is the general body).  Throughput and radiance are registers that die inside the turn; LDS
 // columns 6 to 11 hold nothing of a lane's (the launch keeps their room: the layout is shared; their first 256 bytes carry the meshes'
 // leaf-pair bytes, below).  Option sync_samples has no effect: the lanes
 // of a wave move in lockstep by construction.  No material of these scenes has reflective or refractive lobes (PlanLastCast), so
@@ -23,7 +24,6 @@
   mem.img = s_dyn;
   static_assert(RES, "the last-cast query belongs to the resident variant without lights");
   for (uint32_t i = threadIdx.x; i < sc.residentVec4; i += QA_BLOCK) s_dyn[i] = sc.resident[i];
-#if QA_LEAF_PAIR
   // The start of column 6 holds the leaf-pair bytes of the scene's meshes, QA_TILE_LEAF_CAP each (DMesh::leafPairs; qa_kernel.h
   // sweepLeaves reads them): 256 of the 6 144 bytes this kernel leaves alone, so the launch's LDS size is what it was
   static_assert(QA_KARG_MESH * QA_TILE_LEAF_CAP <= 6 * QA_BLOCK * sizeof(uint32_t), "the leaf-pair bytes live in columns 6 to 11");
@@ -33,7 +33,6 @@
     if (pm.leafPairs && threadIdx.x < QA_TILE_LEAF_CAP / 4)
       leafPairWords[mi * (QA_TILE_LEAF_CAP / 4) + threadIdx.x] = reinterpret_cast<const uint32_t *>(sc.resident + pm.resLeaves + 4 * (size_t) pm.numLeaves)[threadIdx.x];
   }
-#endif
   __syncthreads();
   uint32_t *stack = reinterpret_cast<uint32_t *>(s_dyn + sc.residentVec4) + threadIdx.x;
   // per-lane sample accumulators (columns 0 - 5), the pixel (12), its output index (13) and the sample index (14) live in LDS
@@ -76,7 +75,6 @@
   // what a lane carries from one turn to the next: its random stream, and whether it holds a pixel
   uint32_t rng = 1;
   bool alive = true, needPixel = true;
-#if QA_EMPTY_TILES
   // n samples, casts or pixels at once, by QA_TALLY's rule (section A: the derived samples of an empty tile)
 #ifdef QA_WAVE_TALLIES
 #define QA_TALLY_N(x, n) (x) += (unsigned long long) (n) * (unsigned long long) __popcll(__ballot(1))
@@ -89,7 +87,6 @@
 #define QA_EMPTY_ASK true
 #else
 #define QA_EMPTY_ASK (rp.empty_tiles != 0)
-#endif
 #endif
 
   for (;;) {
@@ -114,8 +111,7 @@
         item -= curChunk * numTiles;
         curTile = item;
         chunkEnd = (int) (rp.chunk_spp + curChunk * rp.chunk_tail);
-#if QA_EMPTY_TILES
-      }   // (the chunk block ends here and opens again for its wait below; without the shortcut it is one block, the parent's text)
+      }
       // ---- a tile no camera ray can hit anything from (qa_emptytile.h) is finished here, in closed form: every sample of every pixel
       // is the background.  The item that starts the tile's pixels writes them; the tile's later chunks are nothing but this test.
       // Decided BEFORE the progress wait below: the answer depends on the scene, the camera and the tile alone, so every item of a
@@ -153,16 +149,14 @@
           continue;                // every lane that is alive still asks for a pixel: the next turn fetches
         }
       }
-      if (rp.chunk_spp && base < total) {
-#endif
-        if (curChunk > 0) {
-          // (the bound is a guard against a lost update, not a path that is taken: qa_kernel_body.h)
-          for (int spins = 0; spins < (1 << 22); ++spins) {
-            if (__hip_atomic_load(rp.tile_progress + curTile, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= curChunk) break;
-            __builtin_amdgcn_s_sleep(16);
-          }
-          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+      // ---- the hand-over's wait: a later chunk of a tile starts when the chunk before it has published its pixels' state
+      if (rp.chunk_spp && base < total && curChunk > 0) {
+        // (the bound is a guard against a lost update, not a path that is taken: qa_kernel_body.h)
+        for (int spins = 0; spins < (1 << 22); ++spins) {
+          if (__hip_atomic_load(rp.tile_progress + curTile, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= curChunk) break;
+          __builtin_amdgcn_s_sleep(16);
         }
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
       }
       if (tileList && base < total) {
         const unsigned tile = rp.tile_order ? rp.tile_order[item] : item;
@@ -333,16 +327,7 @@
         QA_T(tQ)
         bool drawn;
         int emitSet;
-#if QA_LAST_CAST_ANYHIT
-#if QA_LEAF_PAIR
         go = !lastCastQuery<RES>(mem, sc, ray, stack, cnt, drawn, emitSet, reinterpret_cast<const uint8_t *>(s_dyn + sc.residentVec4) + ((size_t) sc.stackDepth + 6) * QA_BLOCK * sizeof(uint32_t));
-#else
-        go = !lastCastQuery<RES>(mem, sc, ray, stack, cnt, drawn, emitSet);
-#endif
-#else
-        closestEmitter<RES>(mem, sc, ray, stack, cnt, drawn, emitSet);
-        go = false;
-#endif
         if (!go) {
           QA_TALLY(cnt.casts_normal);
           // the products, not their values for a finite throughput: a hit that does not emit adds T * 0
@@ -417,17 +402,15 @@
       }
     }
     QA_TACC(cnt.sl[7], tE)
-#if QA_EMPTY_TILES && defined(QA_STAMPS)
+#ifdef QA_STAMPS
     if (tileEmpty) {
       QA_TACC(cnt.sl[15], tA)
       if (lane == 0) cnt.sl[16] += 1;
     }
 #endif
   }
-#if QA_EMPTY_TILES
 #undef QA_TALLY_N
 #undef QA_EMPTY_ASK
-#endif
 
   // ---- counters: wave reduction, one atomic per wave and counter -----------------------------
   unsigned long long v[6] = {cnt.samples, cnt.casts_normal, cnt.casts_shadow, cnt.bvh_nodes, cnt.tri_tests, cnt.pixels};

@@ -240,7 +240,7 @@ int qa_test_empty_tiles_host(const void *blob, int x0, int y0, int x1, int y1, i
   if (x0 < 0 || y0 < 0 || x1 > ds.cam.width || y1 > ds.cam.height || x1 <= x0 || y1 <= y0) return QA_EINVAL;
   const int tilesX = (x1 - x0 + 7) / 8, tilesY = (y1 - y0 + 7) / 8;
   // what a context's default options make of the scene (qa_frame.hip EmptyTilesOn)
-  const bool on = QA_EMPTY_TILES && t.plan.resident && t.plan.lastCastQuery && ds.num_lights == 0 && t.plan.tileListBytes && !(ds.cam.dof > 0.1f);
+  const bool on = t.plan.resident && t.plan.lastCastQuery && ds.num_lights == 0 && t.plan.tileListBytes && !(ds.cam.dof > 0.1f);
   const EmptyTileSceneHost s = {QA_BLOB_PTR(qa_instance, blob, h->off_instances), t.plan.meshes.data()};
   size_t n = 0;
   for (int row = first_strip; row < tilesY; row += strip_step)

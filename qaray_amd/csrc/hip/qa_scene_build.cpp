@@ -773,7 +773,7 @@ int SyncAuto(const ScenePlan &plan, bool anySpecularLobes) { return (!anySpecula
 
 // Where the leaves of a sorted leaf table have their triangles in DMesh::ftris, one byte a leaf: first | (count - 1) << 7.  A lane of
 // qa_integrate_lastcast's sweep reads its candidate's byte from LDS instead of the leaf word from global memory (qa_kernel.h
-// sweepLeaves, QA_LEAF_PAIR).  -> false, and all bytes zero, where some leaf has more than two triangles or starts beyond 127
+// sweepLeaves).  -> false, and all bytes zero, where some leaf has more than two triangles or starts beyond 127
 bool LeafPairBytes(const std::vector<DNode> &sorted, unsigned char bytes[QA_TILE_LEAF_CAP])
 {
   memset(bytes, 0, QA_TILE_LEAF_CAP);

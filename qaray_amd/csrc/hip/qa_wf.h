@@ -488,20 +488,14 @@ __global__ __launch_bounds__(QA_BLOCK, TEX ? 2 : QA_WF_LOGIC_WAVES) void wf_logi
   unsigned nLive = 0, nNew = 0, nClosest = 0, nPix = 0, nShadow = 0;   // wave-uniform tallies
   // Only some of a tile's pixels have work in a given pass (their rays are back, their gate is open) and what they do
   // differs by an order of magnitude (shading a hit against adding a light term or starting a camera ray): the wave sorts
-  // the slots of its tiles into two LDS lists, "shade" and "other", and runs the slot logic on 64 of one kind at a time
-  // (QA_WF_LOGIC_COMPACT=0: one tile at a time, lane = slot).  The slot logic is the same either way, and a slot's
-  // result does not depend on its neighbours: same bits.
-#ifndef QA_WF_LOGIC_COMPACT
-#define QA_WF_LOGIC_COMPACT 1
-#endif
+  // the slots of its tiles into two LDS lists, "shade" and "other", and runs the slot logic on 64 of one kind at a time.
+  // The slot logic is what it would be one tile at a time with lane = slot, and a slot's result does not depend on its
+  // neighbours: same bits.
   const unsigned tiles = b.n / 64, wavesTotal = gridDim.x * (QA_BLOCK / 64);
-#if QA_WF_LOGIC_COMPACT
   __shared__ uint32_t s_list[QA_BLOCK / 64][2][128];
   unsigned nList[2] = {0, 0};      // wave-uniform
-#endif
   for (unsigned tile = blockIdx.x * (QA_BLOCK / 64) + wave;; tile += wavesTotal) {
     const bool last = tile >= tiles;
-#if QA_WF_LOGIC_COMPACT
     if (!last) {
       const unsigned slot = tile * 64 + lane;
       const uint32_t info = __float_as_uint(b.D[slot].w);
@@ -527,12 +521,6 @@ __global__ __launch_bounds__(QA_BLOCK, TEX ? 2 : QA_WF_LOGIC_WAVES) void wf_logi
       const unsigned slot = have ? s_list[wave][c][base + lane] : 0u;
       nList[c] = base;
       wfWaveSync();
-#else
-    if (last) break;
-    {
-      const bool have = true;
-      const unsigned slot = tile * 64 + lane;
-#endif
       const WfEmit e = wfLogicSlot<TEX>(sc, rp, b, slot, have);
       qC.push(e.closest, slot, b.rayq, &ctr->nClosest);
       for (uint32_t j = 0; j < b.numLights; ++j) qS.push((e.shadow >> j) & 1u, slot | (j << 24), b.rayq + b.n, &ctr->nShadow);
@@ -555,9 +543,7 @@ __global__ __launch_bounds__(QA_BLOCK, TEX ? 2 : QA_WF_LOGIC_WAVES) void wf_logi
       for (int off = 32; off > 0; off >>= 1) nsh += __shfl_down(nsh, off);
       nShadow += __shfl(nsh, 0);
     }
-#if QA_WF_LOGIC_COMPACT
     if (last) break;
-#endif
   }
   qC.flush(b.rayq, &ctr->nClosest);
   qS.flush(b.rayq + b.n, &ctr->nShadow);

@@ -6,7 +6,7 @@
 //     and - where the ray is accepted - once more at exactly the accepted distance (the limit at which that triangle is a tie).  For
 //     a mesh that blocksMesh sweeps, the box phase gives the lane's candidates, and the candidates go through
 //       single    one triangle per turn: the leaf word of the sorted table, first and count from it, a return from the inner loop
-//                 (the loop of -DQA_LEAF_PAIR=0)
+//                 (the sweep as commit 55d1672's parent had it: the specification)
 //       pair      one leaf per turn: first and count from the byte table (qa_scene_build.cpp LeafPairBytes), both records tested
 //                 against the same limit, then the selection; a leaf of one triangle reads its one record twice
 //     and the two must give the same hit, best, tie and hz.  Every record index the pair form reads is checked against the mesh's
@@ -60,7 +60,7 @@ static unsigned long long Candidates(const DMesh &m, const MeshTables &mt, const
   return mask;
 }
 
-// the loop of sweepLeaves as it was: while (lo | hi) around for (i < count), a return from the inner one
+// the loop of sweepLeaves as commit 55d1672's parent had it: while (lo | hi) around for (i < count), a return from the inner one
 static Found Single(const MeshTables &mt, unsigned long long cand, const Ray &ray, float limit, unsigned long long &turns)
 {
   Found f;
@@ -82,7 +82,7 @@ static Found Single(const MeshTables &mt, unsigned long long cand, const Ray &ra
   return f;
 }
 
-// the loop with QA_LEAF_PAIR: one leaf per turn, its byte, both records, one selection
+// the loop of sweepLeaves: one leaf per turn, its byte, both records, one selection
 static Found Pair(const MeshTables &mt, const unsigned char *bytes, unsigned long long cand, const Ray &ray, float limit, unsigned long long &turns,
                   unsigned long long &outside)
 {

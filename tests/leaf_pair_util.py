@@ -1,5 +1,5 @@
 """Shared by tests/test_leaf_pair_host.py and tests/test_gpu_leaf_pair.py: a scene without lights with two meshes whose leaf tables
-the last-cast query sweeps a leaf per turn (qaray_amd/csrc/hip/qa_kernel.h sweepLeaves, QA_LEAF_PAIR) - the Cornell box, and in
+the last-cast query sweeps a leaf per turn (qaray_amd/csrc/hip/qa_kernel.h sweepLeaves) - the Cornell box, and in
 front of it a floor of five triangles: an odd count, so one leaf of its own tree holds a single triangle, and some leaf ends at
 the mesh's last record."""
 import os

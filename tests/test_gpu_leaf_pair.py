@@ -1,4 +1,4 @@
-"""The leaf sweep of the last-cast query with a leaf per turn (qaray_amd/csrc/hip/qa_kernel.h sweepLeaves, QA_LEAF_PAIR: a lane reads
+"""The leaf sweep of the last-cast query with a leaf per turn (qaray_amd/csrc/hip/qa_kernel.h sweepLeaves: a lane reads
 where its candidate leaf's triangles are from one byte in LDS and tests both of them in straight-line code): every frame here is
 rendered with option "leaf_sweep" off (the walk), with it on, and by the counting kernel (the reference's tree, walked as the
 reference walks it), and the three must agree bit for bit - colour, first-hit depth and sample counts as 32-bit words, and the

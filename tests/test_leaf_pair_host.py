@@ -1,6 +1,7 @@
-"""The triangle phase of the last-cast query's leaf sweep, a leaf per turn (qa_kernel.h sweepLeaves with QA_LEAF_PAIR: a lane reads
+"""The triangle phase of the last-cast query's leaf sweep, a leaf per turn (qa_kernel.h sweepLeaves: a lane reads
 where its candidate leaf's triangles are from one byte in LDS and tests both in straight-line code), on the CPU:
-tests/cpp/leaf_pair_check.cpp restates that loop and the one it replaces from the headers the kernel uses and puts both to every
+tests/cpp/leaf_pair_check.cpp restates that loop and the one it replaced (one triangle per turn, the sweep as commit 55d1672's
+parent had it: the specification) from the headers the kernel uses and puts both to every
 bounce ray - on the five poses of the Cornell box, on the scenes made to trip the query, on a mesh of an odd triangle count and
 on meshes that keep the walk - and checks the byte table the scene builder writes.  Built stand-alone with AddressSanitizer +
 UBSan."""

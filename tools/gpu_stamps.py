@@ -4,7 +4,7 @@
    QA_EMPTY_TILES=0: option "empty_tiles" off - the stamps then show what the turns of empty tiles cost (qa_emptytile.h)
    The library prints the shares when the counters are read.  On qa_integrate_lastcast the line "[stamps] leaf sweep" splits the
    queries' leaf sweep (qa_kernel.h sweepLeaves; slots 13, 14, 17, 18): box phase and triangle phase as shares of wave time, the
-   triangle phase's turns per wave, lanes per turn and cycles per turn - a turn is one triangle with -DQA_LEAF_PAIR=0, one leaf without."""
+   triangle phase's turns per wave, lanes per turn and cycles per turn - a turn is one leaf (one triangle up to commit 55d1672's parent)."""
 import os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
