@@ -199,7 +199,8 @@ int qa_strip_count(int y0, int y1, int first_strip, int strip_step);
  * "empty_tiles"; qaray_amd/csrc/hip/qa_emptytile.h)?  One byte per tile, 1 = empty, strip after strip as above: (x1-x0+7)/8 tiles per
  * strip, qa_strip_count() strips.  The decision the frame's kernel takes, by the same device function; all zero where a frame of
  * this context with its current options takes none (another kernel, the option off, depth of field, no tile lists).  Nothing of it
- * is read back inside a frame.  qa_test_empty_tiles_host: the same from the host build of that header, for a context with default
+ * is read back inside a frame.  Only enqueues on hip_stream, ordered as the read-only passes are: behind the context's last frame
+ * and last edit, and a later edit waits for it.  qa_test_empty_tiles_host: the same from the host build of that header, for a context with default
  * options (no GPU and no context needed).  No reference counterpart. */
 int qa_empty_tiles_device(qa_ctx *ctx, int x0, int y0, int x1, int y1, int first_strip, int strip_step, uint8_t *d_mask, void *hip_stream);
 int qa_test_empty_tiles_host(const void *blob, int x0, int y0, int x1, int y1, int first_strip, int strip_step, uint8_t *mask);

@@ -146,7 +146,7 @@ int qa_ctx_destroy(qa_ctx *c)
 {
   if (!c) return QA_OK;
   (void) hipSetDevice(c->device);
-  if (c->stream) (void) hipStreamSynchronize(c->stream);
+  (void) hipDeviceSynchronize();   // the context's stream, and whatever runs on the callers' streams on this context's memory
   FreeScene(c);
   FreeStaged(c);
   for (EventPair &ev : c->pending) { (void) hipEventDestroy(ev.a); (void) hipEventDestroy(ev.b); }
@@ -168,7 +168,7 @@ static int Upload(qa_ctx *c, const void *blob, uint64_t nbytes, bool onDevice)
 {
   if (!c || !blob || nbytes == 0) return Fail(QA_EINVAL, "null argument");
   HIP_TRY(hipSetDevice(c->device));
-  HIP_TRY(hipStreamSynchronize(c->stream));
+  HIP_TRY(hipDeviceSynchronize());   // frames and passes of the old scene, on the context's stream and on the callers'
   FreeScene(c);
   try { c->hostBlob.resize(nbytes); } catch (const std::bad_alloc &) { return Fail(QA_ENOMEM, "out of memory"); }
   if (!onDevice) memcpy(c->hostBlob.data(), blob, nbytes);

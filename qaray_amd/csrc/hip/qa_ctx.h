@@ -5,6 +5,8 @@
 
 #include <algorithm>
 #include <cstdint>
+#include <cstdlib>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -65,12 +67,16 @@ inline int OccupancyBlocks(KernelFn fn, size_t ldsBytes, int fallback = 2)
   return n > 8 ? 8 : n;
 }
 
-// "The last X ended here": work on another stream that shares X's memory waits for it.  The event is made on first use
+// "The last X ended here": work on another stream that shares X's memory waits for it.  The event is made on first use.  The name is
+// the member's (DESIGN.md "Streams: who waits for whom"); QA_SKIP_WAIT=<name> (developer builds only) makes that fence's waits
+// no-ops, which is how tests/test_gpu_stream_order.py was shown to fail when a wait is lost (profiles/stream_order.txt)
 struct StreamFence {
+  const char *name = "";
   hipEvent_t ev = nullptr;
   bool set = false;
   hipStream_t stream = nullptr;
-  hipError_t WaitOn(hipStream_t s) const { return (set && s != stream) ? hipStreamWaitEvent(s, ev, 0) : hipSuccess; }
+  bool Skipped() const { const char *e = DevEnv("QA_SKIP_WAIT"); return e && !strcmp(e, name); }
+  hipError_t WaitOn(hipStream_t s) const { return (set && s != stream && !Skipped()) ? hipStreamWaitEvent(s, ev, 0) : hipSuccess; }
   hipError_t Record(hipStream_t s)
   {
     hipError_t e = ev ? hipSuccess : hipEventCreateWithFlags(&ev, hipEventDisableTiming);
@@ -162,8 +168,8 @@ struct qa_ctx {
   float *dAreaSlab = nullptr, *dSurfSlab = nullptr;
   unsigned char *hEditStage = nullptr;
   size_t editStageBytes = 0, editStageUsed = 0;
-  StreamFence lastEdit;             // end of the last edit's copies (on the context's stream)
-  StreamFence texSource;            // qa_scene_edit_texels_device: the caller's stream when its source was handed over
+  StreamFence lastEdit{"lastEdit"};             // end of the last edit's copies (on the context's stream)
+  StreamFence texSource{"texSource"};            // qa_scene_edit_texels_device: the caller's stream when its source was handed over
   std::vector<uint32_t> texOnDevice;   // file textures whose texels were edited from device memory: the host blob's bytes of
                                     // these are behind the device blob's until FetchDeviceTexels (qa_scene_download)
   uint64_t statMeshBuilds = 0, statSceneAllocs = 0, statBytesCopied = 0, statEdits = 0;   // qa_get_scene_stats
@@ -174,7 +180,7 @@ struct qa_ctx {
   unsigned int *dWork = nullptr;  // ring of work counters
   // tiles in sample chunks (qa_integrate, RenderParams::chunk_spp): per-pixel state between chunks, per-tile progress
   DevBuf pixState, tileProgress;
-  StreamFence lastFrame;          // the slabs (these, the area-light log, the many-light surface slab) are one per context: a frame on another stream waits
+  StreamFence lastFrame{"lastFrame"};          // the slabs (these, the area-light log, the many-light surface slab) are one per context: a frame on another stream waits
   int optChunkSpp = -1;           // "chunk_spp": -1 per frame (few tiles per wave), 0 off, n samples of a tile's first chunk
   int optChunkTail = 0;           // "chunk_tail": samples of every further chunk (0: an eighth of the frame's spp)
   int optTileLists = -1;          // "tile_lists": -1 on with the measured limit (QA_TILE_LISTS_AUTO), 0 off, n on with a limit of n leaves per mesh and tile
@@ -237,7 +243,7 @@ struct qa_ctx {
     uint32_t *dProgress = nullptr;   // per tile: the pass's tile_progress (1 before a pass, 2 once the tile's pass is complete)
     DevBuf prevRgb, prevDepth, prevNs;   // qa_progressive_read's preview (made on first use)
     unsigned long long *dStatus = nullptr;   // qa_progressive_status: finished pixels, tiles behind, lowest level
-    StreamFence done;             // end of the frame's setup / last pass, on whatever stream it ran
+    StreamFence done{"prog.done"};             // end of the frame's setup / last pass, on whatever stream it ran
     // tile-selective and noisiest-first passes (made on first use, freed with the frame): the error map, the pass's mask, the host
     // variant's pinned mask and the end of its last copy, qa_progressive_adaptive_info's four words
     float *dError = nullptr;
@@ -249,14 +255,14 @@ struct qa_ctx {
   // the 8-bit products (qa_display.hip): the statistics block (4 working words, then their initial values) and the staging of
   // qa_progressive_display's host variant are made on first use and live as long as the context
   uint32_t *dDisplay = nullptr;
-  StreamFence lastDisplay;      // the block is one per context: a display on another stream waits
+  StreamFence lastDisplay{"lastDisplay"};      // the block is one per context: a display on another stream waits
   DevBuf displayStage;
   // the denoiser's working planes (qa_denoise.hip): 40 bytes per pixel of the largest frame filtered so far, made on first use
   DevBuf denoisePlanes;
-  StreamFence lastDenoise;      // the planes are one per context: a filter on another stream waits
+  StreamFence lastDenoise{"lastDenoise"};      // the planes are one per context: a filter on another stream waits
   // qa_progressive_reproject_device's ids plane of the current frame (qa_reproject.hip): 8 bytes per pixel of the largest frame so far
   DevBuf reprojectIds;
-  StreamFence lastReproject;    // one per context: a call on another stream waits
+  StreamFence lastReproject{"lastReproject"};    // one per context: a call on another stream waits
 };
 
 void FreePhotonMaps(qa_ctx *c);  // qa_photon.hip

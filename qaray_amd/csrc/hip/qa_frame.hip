@@ -14,7 +14,8 @@ int EnsureHalton(qa_ctx *c, int count)
     while (n < count) n *= 2;
     std::vector<float> t(2 * (size_t) n);
     for (int s = 0; s < n; ++s) { t[2 * s] = HaltonF(s, 11); t[2 * s + 1] = HaltonF(s, 13); }
-    if (c->dHalton) (void) hipFree(c->dHalton);
+    // a frame or a pass on a stream of the caller's may still read the old table (its launch holds the old pointer)
+    if (c->dHalton) { HIP_TRY(hipDeviceSynchronize()); (void) hipFree(c->dHalton); }
     c->dHalton = nullptr;
     HIP_TRY(hipMalloc((void **) &c->dHalton, t.size() * sizeof(float)));
     HIP_TRY(hipMemcpy(c->dHalton, t.data(), t.size() * sizeof(float), hipMemcpyHostToDevice));
@@ -347,7 +348,12 @@ int qa_empty_tiles_device(qa_ctx *c, int x0, int y0, int x1, int y1, int first_s
   RenderParams rp = {};
   rp.x0 = x0; rp.y0 = y0; rp.x1 = x1; rp.y1 = y1;
   rp.tile_row0 = first_strip; rp.tile_row_step = strip_step; rp.own_tile_rows = ownRows;
-  return LaunchEmptyTileMask(c->ds, rp, tiles, d_mask, s);
+  // the kernel reads the instance and mesh tables an edit rewrites: ordered as the other read-only passes are (LaunchSceneKernel),
+  // so that the next edit waits for it
+  HIP_TRY(c->lastFrame.WaitOn(s));
+  if (int rc = LaunchEmptyTileMask(c->ds, rp, tiles, d_mask, s)) return rc;
+  HIP_TRY(c->lastFrame.Record(s));
+  return QA_OK;
 }
 
 int qa_strip_count(int y0, int y1, int first_strip, int strip_step)
