@@ -41,6 +41,9 @@
  *   qa_matte_region*,              (no counterpart: the same over the camera rays of all of a pixel's samples - coverage, mean
  *   qa_progressive_matte_device,   albedo, normal and backdrop - and the straight-alpha RGBA picture made from them)
  *   qa_matte_rgba_device
+ *   qa_idmatte_region*,            (no counterpart: which nodes or materials those samples' rays meet and how many samples each takes,
+ *   qa_progressive_idmatte_device, ranked per pixel - an anti-aliased matte per object, as compositing asks of a renderer - and the
+ *   qa_idmatte_select_device       coverage plane of a chosen set of ids made from it)
  *   qa_cast_rays*, qa_occluded*,   (no counterpart: Scene::TraceNodeNormal / TraceNodeShadow for rays of the caller's, and the camera
  *   qa_camera_rays_device          rays PixelRender starts from, handed out)       src/scene/scene.cpp:35-74
  *   qa_denoise_guided_device,      (no counterpart: the preview filter with those normal and albedo planes as two more
@@ -431,6 +434,46 @@ int qa_progressive_matte_device(qa_ctx *ctx, float *d_coverage, float *d_albedo,
 int qa_matte_rgba_device(qa_ctx *ctx, const float *d_rgb, const float *d_backdrop, const float *d_coverage, const uint32_t *d_ns,
                          uint64_t npix, int srgb, uint8_t *d_rgba, void *hip_stream);
 
+/* Id matte of pixels [x0,x1) x [y0,y1): per pixel, which nodes (key = QA_IDMATTE_NODE) or materials (QA_IDMATTE_MATERIAL) the camera
+ * rays of ALL its samples meet and how many samples each takes (the opening comment of qaray_amd/csrc/hip/qa_idmatte_dev.h is the
+ * specification).  The samples are qa_matte_region's: a pixel takes samples 0 .. n - 1, n = spp, or with a d_ns plane n = min(ns, spp).
+ * The key of a hit is word 0 of qa_gbuffer_region's ids for that ray (the node), or QA_GBUFFER_MATERIAL(word 1) (the material, back-face
+ * bit cleared; -1 and -2 for hits without a material as documented there); a miss has none.  A pixel has QA_IDMATTE_SLOTS slots:
+ * in sample order a hit adds 1 to the slot that holds its key, else takes the first free slot, else - the table is full - adds 1 to
+ * `other`.  At the end the occupied slots are ordered by count descending, equal counts by id ascending; free slots follow with id
+ * QA_IDMATTE_EMPTY (no key has that value) and count 0.  Region-local, row-major planes; every pointer may be NULL (not wanted), but
+ * not all of them; ids and counts are written 16 bytes at a time and must be 16-byte aligned:
+ *   ids      8 int32    the slots' ids
+ *   counts   8 uint32   the slots' sample counts
+ *   other    1 uint32   the samples that hit something while the table was full of other ids
+ *   samples  1 uint32   n; sum(counts) + other is the number of samples that hit, n = 0 gives empties and zeros
+ * The kernel only reads the scene: no frame, progressive frame or counter (qa_get_counters) changes.  Codes as qa_matte_region_device:
+ * QA_ENOSCENE; QA_EINVAL for an empty region, one outside the image, spp = 0, a key that is neither of the two, a misaligned plane or
+ * no plane at all; QA_EUNSUPPORTED for a camera with depth of field (dof > 0.1).  A refused call writes nothing.  Ordered as
+ * qa_matte_region_device: the device variants only enqueue on `stream` (a hipStream_t; NULL = the context's stream), behind the context's last
+ * frame and last edit, and a later edit waits for them; the host variant (ns and the planes in host memory) copies and synchronises.
+ *   qa_progressive_idmatte_device   the planes of the progressive frame's region, n = the samples each pixel holds now, from the
+ *                                   scene as it now stands (as qa_progressive_matte_device)
+ *   qa_idmatte_select_device        npix pixels of device planes and m <= QA_IDMATTE_MAX_SELECT ids in HOST memory (copied before the
+ *                                   call returns; NULL when m = 0) -> one float per pixel in d_out: (float) c / (float) n, c the integer
+ *                                   sum of the counts of the slots whose id is in the list, 0 where n = 0; and / or its 8-bit grey
+ *                                   picture in d_bytes, the byte qa_display_device makes of that value without sRGB (either may be NULL,
+ *                                   not both).  Touches no state of the context; only enqueues.  QA_EINVAL for npix = 0 or
+ *                                   > 2^31 - 1, a NULL plane or m above the limit. */
+#define QA_IDMATTE_SLOTS 8
+#define QA_IDMATTE_EMPTY INT32_MIN
+#define QA_IDMATTE_NODE 0
+#define QA_IDMATTE_MATERIAL 1
+#define QA_IDMATTE_MAX_SELECT 256
+int qa_idmatte_region_device(qa_ctx *ctx, int x0, int y0, int x1, int y1, uint32_t spp, const uint32_t *d_ns, int key, int32_t *d_ids,
+                             uint32_t *d_counts, uint32_t *d_other, uint32_t *d_samples, void *stream);
+int qa_idmatte_region(qa_ctx *ctx, int x0, int y0, int x1, int y1, uint32_t spp, const uint32_t *ns, int key, int32_t *ids,
+                      uint32_t *counts, uint32_t *other, uint32_t *samples);
+int qa_progressive_idmatte_device(qa_ctx *ctx, int key, int32_t *d_ids, uint32_t *d_counts, uint32_t *d_other, uint32_t *d_samples,
+                                  void *stream);
+int qa_idmatte_select_device(qa_ctx *ctx, const int32_t *d_ids, const uint32_t *d_counts, const uint32_t *d_samples, uint64_t npix,
+                             const int32_t *select, uint32_t m, float *d_out, uint8_t *d_bytes, void *stream);
+
 /* Ray queries: n rays of the caller's against the resident scene, through the integrators' own closest-hit and shadow walks (the
  * opening comment of qa_ray_query.hip is the specification).  Ray i has origin origins[3i .. 3i+2] and direction dirs[3i .. 3i+2],
  * world space, fp32, contiguous.  The direction is used as given and NOT normalised: t is the parameter along it (the hit is at
@@ -758,6 +801,14 @@ int qa_test_matte_accumulate_host(const float *values, const float *normals, con
                                   float *albedo, float *normal, float *backdrop);
 int qa_test_matte_rgba_host(const float *rgb, const float *backdrop, const float *coverage, const uint32_t *nsamples, uint64_t npix,
                             int srgb, uint8_t *rgba);
+
+/* Self-test hooks for the id matte (qaray_amd/csrc/hip/qa_idmatte_dev.h): the source of qa_idmatte_region_device's and
+ * qa_idmatte_select_device's kernels compiled for the host (no GPU and no context needed).  accumulate: one pixel's n samples - hit
+ * [n] flags and keys [n] (read where hit[s] != 0) -> the ranked table ids [8], counts [8], other [1]; an output may be NULL.
+ * select: npix pixels over host arrays and a list of m ids -> out [npix]. */
+int qa_test_idmatte_accumulate_host(const uint8_t *hit, const int32_t *keys, uint32_t n, int32_t *ids, uint32_t *counts, uint32_t *other);
+int qa_test_idmatte_select_host(const int32_t *ids, const uint32_t *counts, const uint32_t *samples, uint64_t npix, const int32_t *select,
+                                uint32_t m, float *out);
 
 /* Self-test hook for the texel conversion (qaray_amd/csrc/hip/qa_texel_dev.h): the source of qa_scene_edit_texels' kernel and of an
  * upload's texel table compiled for the host: h rows of w RGB8 texels, `stride` bytes apart -> w * h entries {r, g, b, 0} / 255.0f

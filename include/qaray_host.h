@@ -12,6 +12,7 @@
  *   qa_host_scene_set_camera, qa_host_scene_camera   LoadScene's <camera> block + Renderer::ComputeScene's camera frame
  *                                                                     src/parser/xmlload.cpp, src/renderers/renderer.cpp:76-93
  *   qa_host_scene_flatten   Renderer::ComputeScene + scene graph      src/renderers/renderer.cpp:71-113
+ *   qa_host_scene_node_index  (no counterpart: the reference addresses nodes by pointer; the flattener's index of a node's name)
  *   qa_fb_*                 FrameBuffer                               src/fb/framebuffer.h:35-95
  *   qa_tasking_*            tasking::signal_start/stop, thread count  src/tasking/parallel_for.h:59-68
  *   qa_host_render          Renderer::ThreadRender (+ Renderer_MPI::Render's image saves)
@@ -55,6 +56,10 @@ int qa_host_scene_set_camera(qa_host_scene *scene, const float pos[3], const flo
 int qa_host_scene_camera(const qa_host_scene *scene, qa_camera *out);
 /* Flatten into one relocatable blob (include/qa_flat_scene.h); release with qa_host_free. */
 int qa_host_scene_flatten(const qa_host_scene *scene, unsigned char **blob, uint64_t *nbytes);
+/* The index qa_host_scene_flatten gives the node whose XML `name` is this (its row of the blob's instance table: what the ids of
+ * qa_gbuffer_region and qa_idmatte_region hold) -> *index; the first in the flattener's order when several share the name, -1 when
+ * none has it (the call still succeeds).  The root node has index 0 and no name. */
+int qa_host_scene_node_index(const qa_host_scene *scene, const char *name, int *index);
 void qa_host_free(void *p);
 const char *qa_host_last_error(void);
 

@@ -12,7 +12,11 @@
 // and albedo planes; the same file), -alpha (a fourth image, <prefix>rgbaBuffer.png: the frame with straight alpha, 4 channels - alpha is
 // the fraction of a pixel's camera rays that hit something, the colour the frame's without the backdrop's part; made on the device from
 // the frame's own sample counts (qa_matte_region_device, qa_matte_rgba_device); with -progressive rewritten after each pass; the other
-// three images do not change.  Not with -devices, and not for a camera with depth of field: refused before anything is rendered).
+// three images do not change.  Not with -devices, and not for a camera with depth of field: refused before anything is rendered),
+// -matte-node NAME (may be given more than once; per NAME an image, <prefix>matte_NAME.png, 8-bit grey: the fraction of a pixel's samples
+// whose camera ray meets the node with that XML name first - an anti-aliased matte of the object; made on the device from the frame's own
+// sample counts (qa_idmatte_region_device, qa_idmatte_select_device); rewritten after each pass of -progressive; the other images do not
+// change.  Refused as -alpha is, and when no node has the name).
 // The reference's `-sppMax` sets sppMin by mistake (main.cpp:27-28); here it sets sppMax.
 // Flow: Init -> LoadScene -> ComputeScene -> Render -> Terminate (main.cpp:55-59).
 #include <cstdio>
@@ -33,6 +37,7 @@ int main(int argc, char **argv)
   std::string out, root;
   int device = 0, w = -1, h = -1, devices = 0, progressive = 0, denoiseIterations = -1;
   bool denoise = false, denoiseGuided = false, alpha = false;
+  std::vector<std::string> matteNodes;
   if (argc < 2) { fprintf(stderr, "Error: insufficient input\n"); return -1; }
   for (int i = 1; i < argc; ++i) {
     const std::string s(argv[i]);
@@ -63,6 +68,7 @@ int main(int argc, char **argv)
         denoiseIterations = atoi(argv[++i]);
     }
     else if (s == "-alpha") alpha = true;
+    else if (s == "-matte-node") { if (i + 1 < argc) matteNodes.push_back(argv[++i]); else { fprintf(stderr, "Error: -matte-node needs a node's name\n"); return -1; } }
     else if (s == "-out") out = next();
     else if (s == "-root") root = next();
     else file = argv[i];
@@ -71,6 +77,7 @@ int main(int argc, char **argv)
   if (progressive > 0 && devices > 0) { fprintf(stderr, "Error: -progressive renders on one device and cannot be combined with -devices\n"); return -1; }
   if (denoise && devices > 0) { fprintf(stderr, "Error: -denoise filters on one device and cannot be combined with -devices\n"); return -1; }
   if (alpha && devices > 0) { fprintf(stderr, "Error: -alpha makes its image on one device and cannot be combined with -devices\n"); return -1; }
+  if (!matteNodes.empty() && devices > 0) { fprintf(stderr, "Error: -matte-node makes its images on one device and cannot be combined with -devices\n"); return -1; }
   try {
     Renderer renderer(param, device);
     renderer.alpha = alpha;
@@ -93,6 +100,15 @@ int main(int argc, char **argv)
     if (alpha && scene.camera.depthOfField > 0.1f) {   // (the library's own threshold: qa_matte_region_device refuses such a camera)
       fprintf(stderr, "Error: -alpha needs a pinhole camera: with depth of field the samples' camera rays cannot be cast again\n");
       return 1;
+    }
+    if (!matteNodes.empty() && scene.camera.depthOfField > 0.1f) {   // (qa_idmatte_region_device refuses such a camera too)
+      fprintf(stderr, "Error: -matte-node needs a pinhole camera: with depth of field the samples' camera rays cannot be cast again\n");
+      return 1;
+    }
+    for (const std::string &name : matteNodes) {
+      const int index = FindNodeIndex(scene, name.c_str());
+      if (index < 0) { fprintf(stderr, "Error: -matte-node %s: the scene has no node of that name\n", name.c_str()); return 1; }
+      renderer.matteNodes.emplace_back(name, index);
     }
     renderer.ComputeScene(renderImage, scene);
     if (progressive > 0) renderer.RenderProgressive((size_t) progressive);

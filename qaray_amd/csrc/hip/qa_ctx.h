@@ -1,5 +1,5 @@
 // qa_ctx.h — internals shared by the translation units of libqaray_hip.so (the README's layout line says which unit holds what).
-// Only qa_mega.hip, qa_coop.hip, qa_photon.hip, qa_wf.hip, qa_gbuffer.hip and qa_matte.hip include the kernel headers.  Not part of the C ABI.
+// Only qa_mega.hip, qa_coop.hip, qa_photon.hip, qa_wf.hip, qa_gbuffer.hip, qa_matte.hip and qa_idmatte.hip include the kernel headers.  Not part of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 

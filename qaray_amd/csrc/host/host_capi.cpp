@@ -105,6 +105,13 @@ int qa_host_scene_flatten(const qa_host_scene *scene, unsigned char **blob, uint
   }
 }
 
+int qa_host_scene_node_index(const qa_host_scene *scene, const char *name, int *index)
+{
+  if (!scene || !name || !index) return Fail(QA_EINVAL, "null argument");
+  *index = FindNodeIndex(scene->scene, name);
+  return QA_OK;
+}
+
 void qa_host_free(void *p) { free(p); }
 
 int qa_fb_create(int width, int height, qa_fb **out)

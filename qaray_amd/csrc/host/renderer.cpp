@@ -181,10 +181,10 @@ void Renderer::ThreadRender()
   if (tasking::has_stop_signal()) qa_request_stop(ctx);
   else qa_clear_stop(ctx);
   qa_reset_counters(ctx);
-  if (denoise || alpha) {
-    // the frame stays on the device for the filter and the matte (Render: SaveAlpha, SaveDenoised, after the timer has stopped); the
-    // FrameBuffer gets the same floats qa_render_region would have copied back
-    if (!multi.empty() || mpiSize != 1) throw std::runtime_error("-denoise and -alpha work on one device and cannot be combined with -devices");
+  if (denoise || alpha || !matteNodes.empty()) {
+    // the frame stays on the device for the filter and the mattes (Render: SaveAlpha, SaveNodeMattes, SaveDenoised, after the timer has
+    // stopped); the FrameBuffer gets the same floats qa_render_region would have copied back
+    if (!multi.empty() || mpiSize != 1) throw std::runtime_error("-denoise, -alpha and -matte-node work on one device and cannot be combined with -devices");
     const size_t n = (size_t) W * H;
     denoiseFrame.Alloc(n);
     if (qa_render_region_device(ctx, 0, 0, W, H, (int) param.sppMin, (int) param.sppMax, Material::maxBounce, param.seed, 0, denoiseFrame.rgb,
@@ -244,8 +244,9 @@ void Renderer::Render()
   SaveImages();
   // outside the timed span: the printed time and rate are the render's, with or without the flags
   if (alpha) SaveAlpha(denoiseFrame.rgb, denoiseFrame.ns, false);   // (first: the filter works in place)
+  if (!matteNodes.empty()) SaveNodeMattes(denoiseFrame.ns, false);
   if (denoise) SaveDenoised(denoiseFrame.rgb, denoiseFrame.depth, denoiseFrame.ns);
-  if (denoise || alpha) denoiseFrame.Free();
+  if (denoise || alpha || !matteNodes.empty()) denoiseFrame.Free();
 }
 
 // The batch counterpart of Renderer_GUI's progressive display (src/renderers/Renderer_GUI.cpp:37-97, which shows renderImage while
@@ -268,6 +269,7 @@ void Renderer::RenderProgressive(size_t passSpp)
   const size_t n = (size_t) W * H;
   std::vector<uint8_t> color(3 * n), count(n), zimg(n), countimg(n), mask(n);
   if (denoise || alpha) denoiseFrame.Alloc(n);   // -denoise: the preview of each pass, filtered in place; -alpha: its colour and sample counts
+                                                 // (-matte-node reads the frame's own slabs: qa_progressive_idmatte_device)
   for (size_t spp = 0; spp < param.sppMax;) {
     spp = std::min(spp + passSpp, param.sppMax);
     const bool last = spp >= param.sppMax;
@@ -295,6 +297,7 @@ void Renderer::RenderProgressive(size_t passSpp)
       if (alpha) SaveAlpha(denoiseFrame.rgb, denoiseFrame.ns, true);
       if (denoise) SaveDenoised(denoiseFrame.rgb, denoiseFrame.depth, denoiseFrame.ns);
     }
+    if (!matteNodes.empty()) SaveNodeMattes(nullptr, true);
   }
   denoiseFrame.Free();
   qa_progressive_end(ctx);
@@ -384,6 +387,37 @@ void Renderer::SaveAlpha(const float *dRgb, const uint32_t *dNs, bool progressiv
   HIP_OR_THROW(hipMemcpy(rgba.data(), dRgba, 4 * n, hipMemcpyDeviceToHost));
   if (!SavePNG((outputPrefix + "rgbaBuffer.png").c_str(), rgba.data(), (int) pixelW, (int) pixelH, 4))
     throw std::runtime_error("-alpha: " + outputPrefix + "rgbaBuffer.png could not be written");
+}
+
+// The id matte of exactly the samples each pixel holds (the progressive frame's own call while one is open, else the region call
+// with the frame's ns plane), once; then per -matte-node NAME the coverage of that node as 8-bit grey -> <prefix>matte_NAME.png.
+// Everything runs on the context's stream, behind the frame
+void Renderer::SaveNodeMattes(const uint32_t *dNs, bool progressive)
+{
+  if (!multi.empty() || mpiSize != 1) throw std::runtime_error("-matte-node makes its images on one device and cannot be combined with -devices");
+  const size_t n = pixelW * pixelH;
+  struct Bytes {   // (freed on every way out)
+    uint8_t *p = nullptr;
+    ~Bytes() { if (p) (void) hipFree(p); }
+  } dPlanes;
+  HIP_OR_THROW(hipMalloc((void **) &dPlanes.p, 69 * n));   // [ids 32 | counts 32 | samples 4 | grey 1] bytes per pixel
+  int32_t *dIds = reinterpret_cast<int32_t *>(dPlanes.p);
+  uint32_t *dCounts = reinterpret_cast<uint32_t *>(dIds + 8 * n), *dSamples = dCounts + 8 * n;
+  uint8_t *dGrey = reinterpret_cast<uint8_t *>(dSamples + n);
+  const int rc = progressive ? qa_progressive_idmatte_device(ctx, QA_IDMATTE_NODE, dIds, dCounts, nullptr, dSamples, nullptr)
+                             : qa_idmatte_region_device(ctx, 0, 0, (int) pixelW, (int) pixelH, (uint32_t) param.sppMax, dNs, QA_IDMATTE_NODE, dIds, dCounts,
+                                                        nullptr, dSamples, nullptr);
+  if (rc != QA_OK) throw std::runtime_error(std::string("-matte-node: ") + qa_last_error());
+  std::vector<uint8_t> grey(n);
+  for (const std::pair<std::string, int> &node : matteNodes) {
+    const int32_t id = node.second;
+    if (qa_idmatte_select_device(ctx, dIds, dCounts, dSamples, n, &id, 1, nullptr, dGrey, nullptr) != QA_OK)
+      throw std::runtime_error(std::string("-matte-node: ") + qa_last_error());
+    qa_synchronize(ctx);
+    HIP_OR_THROW(hipMemcpy(grey.data(), dGrey, n, hipMemcpyDeviceToHost));
+    const std::string path = outputPrefix + "matte_" + node.first + ".png";
+    if (!SavePNG(path.c_str(), grey.data(), (int) pixelW, (int) pixelH, 1)) throw std::runtime_error("-matte-node: " + path + " could not be written");
+  }
 }
 
 void Renderer::Terminate()

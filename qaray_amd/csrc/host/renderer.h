@@ -11,6 +11,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "framebuffer.h"
@@ -73,6 +74,10 @@ class Renderer {
   // -alpha: another image, <prefix>rgbaBuffer.png, the frame with straight alpha (4 channels): coverage and backdrop of the frame's own
   // sample counts (qa_matte_region_device / qa_progressive_matte_device), then qa_matte_rgba_device.  One device only
   bool alpha = false;
+  // -matte-node NAME (repeatable): per node an image, <prefix>matte_NAME.png, 8-bit grey: the fraction of a pixel's samples whose camera
+  // ray meets that node first (qa_idmatte_region_device / qa_progressive_idmatte_device once, then qa_idmatte_select_device per
+  // node).  (name, the flattener's index of the node: FindNodeIndex.)  One device only
+  std::vector<std::pair<std::string, int>> matteNodes;
 
  protected:
   RendererParam &param;
@@ -88,7 +93,8 @@ class Renderer {
   void SaveImages();                                    // the three PNGs of the FrameBuffer
   void SaveDenoised(float *dRgb, const float *dDepth, const uint32_t *dNs);   // the fourth; dRgb is filtered in place
   void SaveAlpha(const float *dRgb, const uint32_t *dNs, bool progressive);   // rgbaBuffer.png of the frame in device buffers
-  struct DeviceFrame {                                  // -denoise, -alpha: the frame's floats on the device, freed with the Renderer at the latest
+  void SaveNodeMattes(const uint32_t *dNs, bool progressive);                 // matte_NAME.png of every -matte-node
+  struct DeviceFrame {                                  // -denoise, -alpha, -matte-node: the frame's floats on the device, freed with the Renderer at the latest
     float *rgb = nullptr, *depth = nullptr;
     uint32_t *ns = nullptr;
     void Alloc(size_t npix);

@@ -354,6 +354,23 @@ static uint64_t PlaceTable(std::vector<unsigned char> &blob, const std::vector<T
   return off;
 }
 
+// FlatBuilder::AddNode's order: a node, then its children's subtrees in turn
+static int FindNodeIndexFrom(const Node *n, const char *name, int &next)
+{
+  const int me = next++;
+  if (!strcmp(n->GetName(), name)) return me;
+  for (int c = 0; c < n->GetNumChild(); ++c) {
+    const int found = FindNodeIndexFrom(n->GetChild(c), name, next);
+    if (found >= 0) return found;
+  }
+  return -1;
+}
+int FindNodeIndex(const Scene &scene, const char *name)
+{
+  int next = 0;
+  return name ? FindNodeIndexFrom(&scene.rootNode, name, next) : -1;
+}
+
 std::vector<unsigned char> FlattenScene(const Scene &scene)
 {
   FlatBuilder fb;

@@ -328,5 +328,7 @@ CameraFrame ComputeCameraFrame(const Camera &cam);
 
 // Flatten the whole scene into one relocatable blob (include/qa_flat_scene.h).
 std::vector<unsigned char> FlattenScene(const Scene &scene);
+// The index FlattenScene gives the first node named `name` (its row of the instance table), or -1
+int FindNodeIndex(const Scene &scene, const char *name);
 
 }  // namespace qaray_hip

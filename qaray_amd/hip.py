@@ -257,6 +257,13 @@ class ReprojectMomentsParams(C.Structure):   # qa_reproject_moments_params; .def
 QA_GBUFFER_BACKFACE = 0x40000000
 GBUFFER_PLANES = ("normal", "albedo", "depth", "ids")   # in the C ABI's order: float32 [h,w,3], [h,w,3], [h,w], int32 [h,w,2]
 MATTE_PLANES = ("coverage", "albedo", "normal", "backdrop")   # in the C ABI's order: float32 [h,w], [h,w,3], [h,w,3], [h,w,3]
+# the id matte (qa_idmatte_dev.h): ids int32 [h,w,8], counts uint32 [h,w,8], other and samples uint32 [h,w], in the C ABI's order
+IDMATTE_PLANES = ("ids", "counts", "other", "samples")
+QA_IDMATTE_SLOTS = 8
+QA_IDMATTE_EMPTY = -2 ** 31   # the id of a free slot: no key has it
+QA_IDMATTE_NODE, QA_IDMATTE_MATERIAL = 0, 1
+QA_IDMATTE_MAX_SELECT = 256
+_IDMATTE_KEYS = {"node": QA_IDMATTE_NODE, "material": QA_IDMATTE_MATERIAL}
 QA_RAY_MISS = 1e30   # the t of a ray that hits nothing (exactly np.float32(1e30))
 RAY_OUTPUTS = ("t", "ids", "normal", "point")   # in the C ABI's order: float32 [n], int32 [n,2], float32 [n,3], [n,3]
 QA_MAX_RAYS = 2 ** 31 - 1
@@ -369,6 +376,12 @@ def lib():
         L.qa_matte_rgba_device.argtypes = [C.c_void_p] * 5 + [C.c_uint64, C.c_int, C.c_void_p, C.c_void_p]
         L.qa_test_matte_accumulate_host.argtypes = [C.c_void_p] * 3 + [C.c_uint32] + [C.c_void_p] * 4
         L.qa_test_matte_rgba_host.argtypes = [C.c_void_p] * 4 + [C.c_uint64, C.c_int, C.c_void_p]
+        L.qa_idmatte_region_device.argtypes = [C.c_void_p] + [C.c_int] * 4 + [C.c_uint32, C.c_void_p, C.c_int] + [C.c_void_p] * 5
+        L.qa_idmatte_region.argtypes = [C.c_void_p] + [C.c_int] * 4 + [C.c_uint32, C.c_void_p, C.c_int] + [C.c_void_p] * 4
+        L.qa_progressive_idmatte_device.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5
+        L.qa_idmatte_select_device.argtypes = [C.c_void_p] * 4 + [C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.qa_test_idmatte_accumulate_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32] + [C.c_void_p] * 3
+        L.qa_test_idmatte_select_host.argtypes = [C.c_void_p] * 3 + [C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p]
         L.qa_cast_rays_device.argtypes = [C.c_void_p, C.c_uint64] + [C.c_void_p] * 7
         L.qa_cast_rays.argtypes = [C.c_void_p, C.c_uint64] + [C.c_void_p] * 6
         L.qa_occluded_device.argtypes = [C.c_void_p, C.c_uint64] + [C.c_void_p] * 5
@@ -501,6 +514,57 @@ def matte_rgba_host(rgb, backdrop, coverage, ns, srgb=True):
         raise ValueError("rgb and backdrop hold 3 floats, coverage and ns one value per pixel of a frame that is not empty")
     out = np.zeros(coverage.shape + (4,), np.uint8)
     _check(lib().qa_test_matte_rgba_host(rgb.ctypes.data, backdrop.ctypes.data, coverage.ctypes.data, ns.ctypes.data, n, int(bool(srgb)), out.ctypes.data))
+    return out
+
+
+def _idmatte_key(key):
+    """The C ABI's key of "node" / "material" (or of the constant itself)"""
+    if key in _IDMATTE_KEYS:
+        return _IDMATTE_KEYS[key]
+    if key in _IDMATTE_KEYS.values():
+        return int(key)
+    raise ValueError(f"key: 'node' or 'material' is expected, not {key!r}")
+
+
+def _idmatte_select_list(select):
+    """The id list of a select call as a contiguous int32 array of at most QA_IDMATTE_MAX_SELECT entries"""
+    sel = np.ascontiguousarray(np.asarray(select, dtype=np.int64).reshape(-1))
+    if sel.size > QA_IDMATTE_MAX_SELECT:
+        raise ValueError(f"select: at most {QA_IDMATTE_MAX_SELECT} ids, not {sel.size}")
+    if sel.size and (sel.min() < -2 ** 31 or sel.max() > 2 ** 31 - 1):
+        raise ValueError("select: ids are int32")
+    return sel.astype(np.int32)
+
+
+def idmatte_accumulate_host(hit, keys):
+    """qa_test_idmatte_accumulate_host: one pixel's ranked id table from its n samples on the CPU, from the source the device kernel
+    is compiled from.  hit (n,) bool; keys (n,) int32, read where hit is set -> dict ids (8,) i32, counts (8,) u32, other () u32.
+    No GPU needed."""
+    hit = np.ascontiguousarray(hit).astype(np.uint8).reshape(-1)
+    keys = np.ascontiguousarray(keys, dtype=np.int32).reshape(-1)
+    if keys.shape != hit.shape:
+        raise ValueError(f"keys: shape {hit.shape} is expected, not {keys.shape}")
+    out = {"ids": np.zeros(QA_IDMATTE_SLOTS, np.int32), "counts": np.zeros(QA_IDMATTE_SLOTS, np.uint32), "other": np.zeros(1, np.uint32)}
+    _check(lib().qa_test_idmatte_accumulate_host(hit.ctypes.data, keys.ctypes.data, len(hit), out["ids"].ctypes.data, out["counts"].ctypes.data,
+                                                 out["other"].ctypes.data))
+    out["other"] = out["other"].reshape(())
+    return out
+
+
+def idmatte_select_host(ids, counts, samples, select):
+    """qa_test_idmatte_select_host: the coverage of the ids of `select` (at most QA_IDMATTE_MAX_SELECT) from an id matte's planes (ids
+    (.., 8) i32, counts (.., 8) u32, samples (..) u32) on the CPU, from the source the device kernel is compiled from -> float32 of
+    samples' shape.  No GPU needed."""
+    ids = np.ascontiguousarray(ids, dtype=np.int32)
+    counts = np.ascontiguousarray(counts, dtype=np.uint32)
+    samples = np.ascontiguousarray(samples, dtype=np.uint32)
+    n = samples.size
+    if not n or ids.shape != samples.shape + (QA_IDMATTE_SLOTS,) or counts.shape != ids.shape:
+        raise ValueError("ids and counts hold 8 values, samples one per pixel of a frame that is not empty")
+    sel = _idmatte_select_list(select)
+    out = np.zeros(samples.shape, np.float32)
+    _check(lib().qa_test_idmatte_select_host(ids.ctypes.data, counts.ctypes.data, samples.ctypes.data, n, sel.ctypes.data if sel.size else None,
+                                             sel.size, out.ctypes.data))
     return out
 
 
@@ -782,6 +846,16 @@ def _region_planes(region, names):
     h, w = y1 - y0, x1 - x0
     shapes = {k: (h, w) if k in ("coverage", "depth") else (h, w, 2) if k == "ids" else (h, w, 3) for k in names}
     return shapes, {k: torch.int32 if k == "ids" else torch.float32 for k in names}
+
+
+def _idmatte_planes(region):
+    """Shapes and dtypes of the id matte's planes of a region.  (torch has no uint32 worth the name: the unsigned planes are int32
+    tensors of the same bits; no count reaches 2^31)"""
+    import torch
+    x0, y0, x1, y1 = region
+    h, w = y1 - y0, x1 - x0
+    shapes = {k: (h, w, QA_IDMATTE_SLOTS) if k in ("ids", "counts") else (h, w) for k in IDMATTE_PLANES}
+    return shapes, {k: torch.int32 for k in IDMATTE_PLANES}
 
 
 def _ray_count(name, t):
@@ -1199,6 +1273,57 @@ class Context:
         nptr = None if ns is None else ns.data_ptr()
         sptr = self._stream_arg(stream, next(iter(out.values())))
         _check(lib().qa_matte_region_device(self._h, x0, y0, x1, y1, int(spp), nptr, *ptrs, sptr))
+        return out
+
+    def idmatte(self, region, spp, key="node", ns=None):
+        """qa_idmatte_region: the id matte of a region over the camera rays of all of a pixel's samples -> dict of numpy arrays: ids
+        [h,w,8] i32 and counts [h,w,8] u32 (the nodes - key="node" - or materials - key="material" - the samples meet and how many
+        samples each takes, by count descending, then id ascending; free slots QA_IDMATTE_EMPTY, 0), other [h,w] u32 (hits that found
+        the table full), samples [h,w] u32.  ns as matte's.  A camera with depth of field is refused.  Synchronises."""
+        x0, y0, x1, y1 = region
+        h, w = y1 - y0, x1 - x0
+        if ns is not None:
+            ns = np.ascontiguousarray(ns, dtype=np.uint32)
+            if ns.shape != (h, w):
+                raise ValueError(f"ns: shape {(h, w)} is expected, not {ns.shape}")
+        out = {"ids": np.zeros((h, w, QA_IDMATTE_SLOTS), np.int32), "counts": np.zeros((h, w, QA_IDMATTE_SLOTS), np.uint32),
+               "other": np.zeros((h, w), np.uint32), "samples": np.zeros((h, w), np.uint32)}
+        _check(lib().qa_idmatte_region(self._h, x0, y0, x1, y1, int(spp), _ptr(ns), _idmatte_key(key), *(out[k].ctypes.data for k in IDMATTE_PLANES)))
+        return out
+
+    def idmatte_device(self, region, spp, key="node", ns=None, ids=None, counts=None, other=None, samples=None, stream=None):
+        """qa_idmatte_region_device into torch CUDA tensors (see idmatte for the shapes; all four are int32 tensors, the unsigned
+        planes' bits; ns: an int32 / uint32 CUDA tensor [h,w] or None): the planes given are written; when none is given all four are
+        allocated.  -> dict name -> tensor.  Only enqueues (see render_region_device for the stream)."""
+        import torch
+        out, ptrs = _output_tensors(IDMATTE_PLANES, *_idmatte_planes(region), torch.device("cuda", self.device_id),
+                                    dict(ids=ids, counts=counts, other=other, samples=samples))
+        x0, y0, x1, y1 = region
+        if ns is not None:
+            assert ns.is_cuda and ns.is_contiguous() and ns.element_size() == 4 and not ns.dtype.is_floating_point and ns.numel() == (y1 - y0) * (x1 - x0), "ns"
+        nptr = None if ns is None else ns.data_ptr()
+        sptr = self._stream_arg(stream, next(iter(out.values())))
+        _check(lib().qa_idmatte_region_device(self._h, x0, y0, x1, y1, int(spp), nptr, _idmatte_key(key), *ptrs, sptr))
+        return out
+
+    def idmatte_select_device(self, ids, counts, samples, select, out=None, stream=None, out_bytes=None):
+        """qa_idmatte_select_device: the coverage plane of the ids of `select` (a sequence of at most QA_IDMATTE_MAX_SELECT ints) from
+        the planes idmatte_device wrote: per pixel the counts of the slots whose id is selected, summed, over the pixel's samples; 0
+        where it has none.  out: the float32 [h,w] tensor to write (None: a new one) -> out.  out_bytes: a uint8 [h,w] tensor that
+        also gets the plane's 8-bit grey picture (the byte display_device makes of the value without sRGB).  Only enqueues (see
+        render_region_device for the stream)."""
+        import torch
+        n = samples.numel()
+        for t, k in ((ids, QA_IDMATTE_SLOTS), (counts, QA_IDMATTE_SLOTS), (samples, 1)):
+            assert t.is_cuda and t.is_contiguous() and t.element_size() == 4 and not t.dtype.is_floating_point and t.numel() == k * n
+        sel = _idmatte_select_list(select)
+        if out is None:
+            out = torch.empty(tuple(samples.shape), dtype=torch.float32, device=ids.device)
+        assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and out.numel() == n
+        assert out_bytes is None or (out_bytes.is_cuda and out_bytes.is_contiguous() and out_bytes.dtype == torch.uint8 and out_bytes.numel() == n)
+        sptr = self._stream_arg(stream, ids)
+        _check(lib().qa_idmatte_select_device(self._h, ids.data_ptr(), counts.data_ptr(), samples.data_ptr(), n, sel.ctypes.data if sel.size else None,
+                                              sel.size, out.data_ptr(), _ptr(out_bytes), sptr))
         return out
 
     def rgba_device(self, rgb, backdrop, coverage, ns, srgb=True, out=None, stream=None):
@@ -1764,6 +1889,17 @@ class Progressive:
                                     dict(coverage=coverage, albedo=albedo, normal=normal, backdrop=backdrop))
         sptr = Context._stream_arg(stream, next(iter(out.values())))
         _check(lib().qa_progressive_matte_device(self._ctx._h, *ptrs, sptr))
+        return out
+
+    def idmatte_device(self, key="node", ids=None, counts=None, other=None, samples=None, stream=None):
+        """qa_progressive_idmatte_device: the id matte of the frame's region over the samples each pixel holds now, of the scene as it
+        now stands (see Context.idmatte_device: its planes for spp_max and the ns plane read() gives) -> dict name -> tensor; only
+        enqueues."""
+        import torch
+        out, ptrs = _output_tensors(IDMATTE_PLANES, *_idmatte_planes(self.region), torch.device("cuda", self._ctx.device_id),
+                                    dict(ids=ids, counts=counts, other=other, samples=samples))
+        sptr = Context._stream_arg(stream, next(iter(out.values())))
+        _check(lib().qa_progressive_idmatte_device(self._ctx._h, _idmatte_key(key), *ptrs, sptr))
         return out
 
     def reproject_device(self, history, prev_cam, hist_ids=None, out=None, out_length=None, params=None, depth_tolerance=None, max_history=None,

@@ -30,6 +30,7 @@ def lib():
         L.qa_host_scene_flatten.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
         L.qa_host_scene_set_camera.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float]
         L.qa_host_scene_camera.argtypes = [C.c_void_p, C.c_void_p]
+        L.qa_host_scene_node_index.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_int)]
         L.qa_host_free.argtypes = [C.c_void_p]
         L.qa_host_free.restype = None
         L.qa_fb_create.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_void_p)]
@@ -116,6 +117,15 @@ class HostScene:
             return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), shape=(n.value,)).copy()
         finally:
             lib().qa_host_free(p)
+
+    def node_index(self, name):
+        """-> the index flatten() gives the node whose XML name is `name` (its row of the blob's instance table, what the ids of
+        hip.Context.gbuffer and idmatte hold); the first in the flattener's order when several share it.  KeyError when none has it."""
+        i = C.c_int(-1)
+        _check(lib().qa_host_scene_node_index(self._h, os.fsencode(name), C.byref(i)))
+        if i.value < 0:
+            raise KeyError(name)
+        return i.value
 
     def close(self):
         if self._h:
