@@ -214,7 +214,7 @@
     ray.p = F3(0, 0, 0);
     ray.d = F3(0, 0, 1);
     f3 T = F3(0, 0, 0), L = F3(0, 0, 0);   // throughput, and the radiance this sample has gathered
-    int absorbMtl = -1, bounce = 0;
+    int bounce = 0;
     bool fromDiffuse = false;
 
     // ---- B. start the sample: camera ray (src/renderers/renderer.cpp:312-328) -------------------
@@ -237,7 +237,6 @@
       ray.d = normalize(cpt - campos);
       T = F3(1, 1, 1);
       L = F3(0, 0, 0);
-      absorbMtl = -1;
       bounce = rp.max_bounce;
       fromDiffuse = false;
       QA_TALLY(cnt.samples);
@@ -275,12 +274,9 @@
           QA_TACC(cnt.sl[10], tM)
         } else {
           // ---- D. shade: MtlBlinn_PhotonMap::Shade (MtlBlinn_PhotonMap.cpp:256-500) -----------
-          // Beer-Lambert attenuation when the ray arrives from inside (ComputeSecondaryRay :244-248)
-          if (!primary && !h.front && absorbMtl >= 0) {
-            const uint4 ab = mtlTable[6 * (size_t) absorbMtl + 5];
-            const f3 att = F3(qexpf(-asF(ab.x) * h.z), qexpf(-asF(ab.y) * h.z), qexpf(-asF(ab.z) * h.z));
-            T = T * att;
-          }
+          // (No Beer-Lambert attenuation of a ray that arrives from inside, ComputeSecondaryRay :244-248: PlanLastCast refuses every
+          // material whose absorption is not +0 or -0, so the factor would be qexpf(-+0 * h.z) with h.z finite and positive - exactly
+          // 1.0f - and T * 1.0f has T's bits: tests/cpp/absorb_identity_check.cpp.  The material a ray was spawned from is not kept.)
           const qa_instance &in = instAt<RES>(sc, h.node);
           int mi = -1;
           bool white = false;
@@ -308,7 +304,6 @@
               ray.p = p;
               ray.d = normalize(sf.nextDir);
               T = T * sf.bxdf;
-              absorbMtl = mi;
               bounce -= 1;
               fromDiffuse = sf.nextFromDiffuse;
               go = true;
