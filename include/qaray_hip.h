@@ -46,6 +46,8 @@
  *   qa_idmatte_select_device       coverage plane of a chosen set of ids made from it)
  *   qa_cast_rays*, qa_occluded*,   (no counterpart: Scene::TraceNodeNormal / TraceNodeShadow for rays of the caller's, and the camera
  *   qa_camera_rays_device          rays PixelRender starts from, handed out)       src/scene/scene.cpp:35-74
+ *   qa_ao_region*, qa_ao_points*,  (no counterpart: ambient occlusion - how many of K short rays over the facing side of what a pixel's
+ *   qa_progressive_ao_device       samples see, or of points of the caller's, meet nothing within a radius)
  *   qa_denoise_guided_device,      (no counterpart: the preview filter with those normal and albedo planes as two more
  *   qa_progressive_denoise_guided* edge-stopping guides)
  *   qa_denoise_variance_device     (no counterpart: that filter with a per-pixel variance of the caller's in place of its spatial guess)
@@ -474,6 +476,49 @@ int qa_progressive_idmatte_device(qa_ctx *ctx, int key, int32_t *d_ids, uint32_t
 int qa_idmatte_select_device(qa_ctx *ctx, const int32_t *d_ids, const uint32_t *d_counts, const uint32_t *d_samples, uint64_t npix,
                              const int32_t *select, uint32_t m, float *d_out, uint8_t *d_bytes, void *stream);
 
+/* Ambient occlusion of pixels [x0,x1) x [y0,y1), and of points of the caller's: how much of the hemisphere over a surface point is
+ * open within `radius`, as a count of open rays (the opening comment of qaray_amd/csrc/hip/qa_ao_dev.h is the specification: the
+ * counter-based direction generator, the facing normal, the counters).  A pixel takes the camera rays of samples first .. first + n - 1
+ * as qa_matte_region builds them: n = spp, or with a d_ns plane (region-local, one uint32 per pixel) n = min(max(ns - first, 0), spp).
+ * Each is cast as qa_cast_rays casts; from every hit K rays go out from the hit point, cosine-weighted about the normal turned
+ * towards the camera ray, with the counters s * K + k of the pixel's stream (y * width + x, as qa_camera_sample_rays_device's
+ * d_stream), each tested as qa_occluded tests a ray with tmax = radius (bias 0.005 included).  Region-local, row-major planes; every
+ * pointer may be NULL (not wanted), but not all of them:
+ *   open  1 uint32   the rays that met nothing
+ *   rays  1 uint32   the samples that hit something, times K
+ *   ao    1 float    rays ? (float) open / (float) rays : 1; a pixel with n = 0 writes 0, 0, 1
+ * The counts are integers and do not depend on the order in which rays are cast: the call equals the composition
+ * qa_camera_sample_rays_device -> qa_cast_rays_device -> qa_test_ao_face_normal_host / qa_test_ao_directions_host ->
+ * qa_occluded_device on every pixel (tests/test_gpu_ao.py).
+ *   qa_progressive_ao_device   the planes of the progressive frame's region with the frame's seed, first = 0 and n = the samples each
+ *                              pixel holds now, from the scene as it now stands (as qa_progressive_matte_device)
+ *   qa_ao_points_device        n points [n][3] with unit normals [n][3], world space, fp32: point i casts the K rays of the counters
+ *                              first + k of stream i, or d_stream_ids[i], about its normal as given.  d_open [n] uint32 and / or
+ *                              d_ao [n] float = (float) open / (float) K.  A point with a component (its normal's included) that is
+ *                              not finite, or with normal (0, 0, 0), is void: not walked, open = K, ao = 1.  n == 0 is QA_OK and
+ *                              launches nothing; n > 2^31 - 1, a NULL array or no output are QA_EINVAL as for the ray queries.
+ * The kernels only read the scene: no frame, progressive frame, counter (qa_get_counters) or kernel-time record changes.  Codes:
+ * QA_ENOSCENE; QA_EINVAL for an empty region, one outside the image, spp = 0, K = 0 or K > QA_AO_MAX_RAYS, (first + spp) * K (points:
+ * first + K) beyond 32 bits, a radius that is NaN or <= 0.005 (+inf is allowed: unbounded, taken as 1e30) or no plane at all;
+ * QA_EUNSUPPORTED for a camera with depth of field (dof > 0.1; the points form answers).  A refused call writes nothing.  Ordered as
+ * qa_matte_region_device: the device variants only enqueue on `stream` (a hipStream_t; NULL = the context's stream), behind the
+ * context's last frame and last edit, and a later edit waits for them; the progressive form first waits for the frame's last pass;
+ * the host variants (arrays in host memory) copy and synchronise.
+ *   qa_ao_grey_device          npix floats of a device plane -> one byte each in d_bytes: the plane's 8-bit grey picture, the byte
+ *                              qa_display_device makes of the value without sRGB.  Touches no state of the context; only enqueues.
+ *                              QA_EINVAL for npix = 0 or > 2^31 - 1 or a NULL buffer. */
+#define QA_AO_MAX_RAYS 256
+int qa_ao_region_device(qa_ctx *ctx, int x0, int y0, int x1, int y1, uint32_t first, uint32_t spp, const uint32_t *d_ns, uint32_t K,
+                        float radius, uint32_t seed, uint32_t *d_open, uint32_t *d_rays, float *d_ao, void *stream);
+int qa_ao_region(qa_ctx *ctx, int x0, int y0, int x1, int y1, uint32_t first, uint32_t spp, const uint32_t *ns, uint32_t K, float radius,
+                 uint32_t seed, uint32_t *open, uint32_t *rays, float *ao);
+int qa_progressive_ao_device(qa_ctx *ctx, uint32_t K, float radius, uint32_t *d_open, uint32_t *d_rays, float *d_ao, void *stream);
+int qa_ao_points_device(qa_ctx *ctx, uint64_t n, const float *d_points, const float *d_normals, const int32_t *d_stream_ids,
+                        uint32_t first, uint32_t K, float radius, uint32_t seed, uint32_t *d_open, float *d_ao, void *stream);
+int qa_ao_grey_device(qa_ctx *ctx, const float *d_ao, uint64_t npix, uint8_t *d_bytes, void *stream);
+int qa_ao_points(qa_ctx *ctx, uint64_t n, const float *points, const float *normals, const int32_t *stream_ids, uint32_t first,
+                 uint32_t K, float radius, uint32_t seed, uint32_t *open, float *ao);
+
 /* Ray queries: n rays of the caller's against the resident scene, through the integrators' own closest-hit and shadow walks (the
  * opening comment of qa_ray_query.hip is the specification).  Ray i has origin origins[3i .. 3i+2] and direction dirs[3i .. 3i+2],
  * world space, fp32, contiguous.  The direction is used as given and NOT normalised: t is the parameter along it (the hit is at
@@ -809,6 +854,16 @@ int qa_test_matte_rgba_host(const float *rgb, const float *backdrop, const float
 int qa_test_idmatte_accumulate_host(const uint8_t *hit, const int32_t *keys, uint32_t n, int32_t *ids, uint32_t *counts, uint32_t *other);
 int qa_test_idmatte_select_host(const int32_t *ids, const uint32_t *counts, const uint32_t *samples, uint64_t npix, const int32_t *select,
                                 uint32_t m, float *out);
+
+/* Self-test hooks for the ambient occlusion (qaray_amd/csrc/hip/qa_ao_dev.h): the source of qa_ao_region_device's and
+ * qa_ao_points_device's kernels compiled for the host (no GPU and no context needed).  directions: `count` rays - stream [count],
+ * c [count], the unit normals n [count][3] -> d [count][3].  face_normal: N [count][3] and camera-ray directions d [count][3] ->
+ * n [count][3].  sphere: the generator's inner step for the same keys -> the sphere points s [count][3] and whether all attempts
+ * failed, fallback [count] (either may be NULL).  direction_from: the outer step from sphere points given directly. */
+int qa_test_ao_directions_host(uint32_t seed, const uint32_t *stream, const uint32_t *c, const float *n, uint64_t count, float *d);
+int qa_test_ao_face_normal_host(const float *N, const float *d, uint64_t count, float *n);
+int qa_test_ao_sphere_host(uint32_t seed, const uint32_t *stream, const uint32_t *c, uint64_t count, float *s, uint8_t *fallback);
+int qa_test_ao_direction_from_host(const float *n, const float *s, uint64_t count, float *d);
 
 /* Self-test hook for the texel conversion (qaray_amd/csrc/hip/qa_texel_dev.h): the source of qa_scene_edit_texels' kernel and of an
  * upload's texel table compiled for the host: h rows of w RGB8 texels, `stride` bytes apart -> w * h entries {r, g, b, 0} / 255.0f

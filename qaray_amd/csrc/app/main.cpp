@@ -16,11 +16,16 @@
 // -matte-node NAME (may be given more than once; per NAME an image, <prefix>matte_NAME.png, 8-bit grey: the fraction of a pixel's samples
 // whose camera ray meets the node with that XML name first - an anti-aliased matte of the object; made on the device from the frame's own
 // sample counts (qa_idmatte_region_device, qa_idmatte_select_device); rewritten after each pass of -progressive; the other images do not
-// change.  Refused as -alpha is, and when no node has the name).
+// change.  Refused as -alpha is, and when no node has the name), -ao [K] and -ao-radius R (an image, <prefix>aoBuffer.png, 8-bit grey: the
+// ambient occlusion of what the frame's own samples see - of K rays, default 4, over the facing side of every camera hit the fraction
+// that meets nothing within R, default unbounded; made on the device with the frame's seed and sample counts (qa_ao_region_device,
+// qa_ao_grey_device); K is optional as -denoise's N is; rewritten after each pass of -progressive; the other images do not change.
+// Refused as -alpha is).
 // The reference's `-sppMax` sets sppMin by mistake (main.cpp:27-28); here it sets sppMax.
 // Flow: Init -> LoadScene -> ComputeScene -> Render -> Terminate (main.cpp:55-59).
 #include <cstdio>
 #include <cstdlib>
+#include <limits>
 #include <memory>
 #include <string>
 #include <vector>
@@ -38,6 +43,9 @@ int main(int argc, char **argv)
   int device = 0, w = -1, h = -1, devices = 0, progressive = 0, denoiseIterations = -1;
   bool denoise = false, denoiseGuided = false, alpha = false;
   std::vector<std::string> matteNodes;
+  int aoRays = 0;
+  float aoRadius = std::numeric_limits<float>::infinity();
+  bool aoRadiusGiven = false;
   if (argc < 2) { fprintf(stderr, "Error: insufficient input\n"); return -1; }
   for (int i = 1; i < argc; ++i) {
     const std::string s(argv[i]);
@@ -69,6 +77,17 @@ int main(int argc, char **argv)
     }
     else if (s == "-alpha") alpha = true;
     else if (s == "-matte-node") { if (i + 1 < argc) matteNodes.push_back(argv[++i]); else { fprintf(stderr, "Error: -matte-node needs a node's name\n"); return -1; } }
+    else if (s == "-ao") {   // the ray count is optional: taken when the next argument is a number
+      aoRays = 4;
+      if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9' && std::string(argv[i + 1]).find_first_not_of("0123456789") == std::string::npos)
+        aoRays = atoi(argv[++i]);
+      if (aoRays < 1 || aoRays > QA_AO_MAX_RAYS) { fprintf(stderr, "Error: -ao takes 1 .. %d rays per hit\n", QA_AO_MAX_RAYS); return -1; }
+    }
+    else if (s == "-ao-radius") {
+      aoRadius = (float) atof(next());
+      aoRadiusGiven = true;
+      if (!(aoRadius > 0.005f)) { fprintf(stderr, "Error: -ao-radius must exceed the renderer's bias, 0.005\n"); return -1; }
+    }
     else if (s == "-out") out = next();
     else if (s == "-root") root = next();
     else file = argv[i];
@@ -78,8 +97,12 @@ int main(int argc, char **argv)
   if (denoise && devices > 0) { fprintf(stderr, "Error: -denoise filters on one device and cannot be combined with -devices\n"); return -1; }
   if (alpha && devices > 0) { fprintf(stderr, "Error: -alpha makes its image on one device and cannot be combined with -devices\n"); return -1; }
   if (!matteNodes.empty() && devices > 0) { fprintf(stderr, "Error: -matte-node makes its images on one device and cannot be combined with -devices\n"); return -1; }
+  if (aoRays > 0 && devices > 0) { fprintf(stderr, "Error: -ao makes its image on one device and cannot be combined with -devices\n"); return -1; }
+  if (aoRadiusGiven && aoRays == 0) { fprintf(stderr, "Error: -ao-radius without -ao\n"); return -1; }
   try {
     Renderer renderer(param, device);
+    renderer.aoRays = aoRays;
+    renderer.aoRadius = aoRadius;
     renderer.alpha = alpha;
     renderer.denoise = denoise;
     renderer.denoiseIterations = denoiseIterations;
@@ -103,6 +126,10 @@ int main(int argc, char **argv)
     }
     if (!matteNodes.empty() && scene.camera.depthOfField > 0.1f) {   // (qa_idmatte_region_device refuses such a camera too)
       fprintf(stderr, "Error: -matte-node needs a pinhole camera: with depth of field the samples' camera rays cannot be cast again\n");
+      return 1;
+    }
+    if (aoRays > 0 && scene.camera.depthOfField > 0.1f) {   // (qa_ao_region_device refuses such a camera too)
+      fprintf(stderr, "Error: -ao needs a pinhole camera: with depth of field the samples' camera rays cannot be cast again\n");
       return 1;
     }
     for (const std::string &name : matteNodes) {

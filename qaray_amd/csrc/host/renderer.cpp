@@ -181,10 +181,10 @@ void Renderer::ThreadRender()
   if (tasking::has_stop_signal()) qa_request_stop(ctx);
   else qa_clear_stop(ctx);
   qa_reset_counters(ctx);
-  if (denoise || alpha || !matteNodes.empty()) {
-    // the frame stays on the device for the filter and the mattes (Render: SaveAlpha, SaveNodeMattes, SaveDenoised, after the timer has
+  if (denoise || alpha || !matteNodes.empty() || aoRays > 0) {
+    // the frame stays on the device for the filter and the mattes (Render: SaveAlpha, SaveNodeMattes, SaveAo, SaveDenoised, after the timer has
     // stopped); the FrameBuffer gets the same floats qa_render_region would have copied back
-    if (!multi.empty() || mpiSize != 1) throw std::runtime_error("-denoise, -alpha and -matte-node work on one device and cannot be combined with -devices");
+    if (!multi.empty() || mpiSize != 1) throw std::runtime_error("-denoise, -alpha, -matte-node and -ao work on one device and cannot be combined with -devices");
     const size_t n = (size_t) W * H;
     denoiseFrame.Alloc(n);
     if (qa_render_region_device(ctx, 0, 0, W, H, (int) param.sppMin, (int) param.sppMax, Material::maxBounce, param.seed, 0, denoiseFrame.rgb,
@@ -245,8 +245,9 @@ void Renderer::Render()
   // outside the timed span: the printed time and rate are the render's, with or without the flags
   if (alpha) SaveAlpha(denoiseFrame.rgb, denoiseFrame.ns, false);   // (first: the filter works in place)
   if (!matteNodes.empty()) SaveNodeMattes(denoiseFrame.ns, false);
+  if (aoRays > 0) SaveAo(denoiseFrame.ns, false);
   if (denoise) SaveDenoised(denoiseFrame.rgb, denoiseFrame.depth, denoiseFrame.ns);
-  if (denoise || alpha || !matteNodes.empty()) denoiseFrame.Free();
+  if (denoise || alpha || !matteNodes.empty() || aoRays > 0) denoiseFrame.Free();
 }
 
 // The batch counterpart of Renderer_GUI's progressive display (src/renderers/Renderer_GUI.cpp:37-97, which shows renderImage while
@@ -269,7 +270,7 @@ void Renderer::RenderProgressive(size_t passSpp)
   const size_t n = (size_t) W * H;
   std::vector<uint8_t> color(3 * n), count(n), zimg(n), countimg(n), mask(n);
   if (denoise || alpha) denoiseFrame.Alloc(n);   // -denoise: the preview of each pass, filtered in place; -alpha: its colour and sample counts
-                                                 // (-matte-node reads the frame's own slabs: qa_progressive_idmatte_device)
+                                                 // (-matte-node and -ao read the frame's own slabs: qa_progressive_idmatte_device, qa_progressive_ao_device)
   for (size_t spp = 0; spp < param.sppMax;) {
     spp = std::min(spp + passSpp, param.sppMax);
     const bool last = spp >= param.sppMax;
@@ -298,6 +299,7 @@ void Renderer::RenderProgressive(size_t passSpp)
       if (denoise) SaveDenoised(denoiseFrame.rgb, denoiseFrame.depth, denoiseFrame.ns);
     }
     if (!matteNodes.empty()) SaveNodeMattes(nullptr, true);
+    if (aoRays > 0) SaveAo(nullptr, true);
   }
   denoiseFrame.Free();
   qa_progressive_end(ctx);
@@ -418,6 +420,30 @@ void Renderer::SaveNodeMattes(const uint32_t *dNs, bool progressive)
     const std::string path = outputPrefix + "matte_" + node.first + ".png";
     if (!SavePNG(path.c_str(), grey.data(), (int) pixelW, (int) pixelH, 1)) throw std::runtime_error("-matte-node: " + path + " could not be written");
   }
+}
+
+// The ambient occlusion of exactly the samples each pixel holds (the progressive frame's own call while one is open, else the region
+// call with the frame's ns plane and seed), as 8-bit grey -> <prefix>aoBuffer.png.  Everything runs on the context's stream, behind the frame
+void Renderer::SaveAo(const uint32_t *dNs, bool progressive)
+{
+  if (!multi.empty() || mpiSize != 1) throw std::runtime_error("-ao makes its image on one device and cannot be combined with -devices");
+  const size_t n = pixelW * pixelH;
+  struct Bytes {   // (freed on every way out)
+    uint8_t *p = nullptr;
+    ~Bytes() { if (p) (void) hipFree(p); }
+  } dPlanes;
+  HIP_OR_THROW(hipMalloc((void **) &dPlanes.p, 5 * n));   // [ao 4 | grey 1] bytes per pixel
+  float *dAo = reinterpret_cast<float *>(dPlanes.p);
+  uint8_t *dGrey = reinterpret_cast<uint8_t *>(dAo + n);
+  const int rc = progressive ? qa_progressive_ao_device(ctx, (uint32_t) aoRays, aoRadius, nullptr, nullptr, dAo, nullptr)
+                             : qa_ao_region_device(ctx, 0, 0, (int) pixelW, (int) pixelH, 0, (uint32_t) param.sppMax, dNs, (uint32_t) aoRays, aoRadius,
+                                                   param.seed, nullptr, nullptr, dAo, nullptr);
+  if (rc != QA_OK || qa_ao_grey_device(ctx, dAo, n, dGrey, nullptr) != QA_OK) throw std::runtime_error(std::string("-ao: ") + qa_last_error());
+  qa_synchronize(ctx);
+  std::vector<uint8_t> grey(n);
+  HIP_OR_THROW(hipMemcpy(grey.data(), dGrey, n, hipMemcpyDeviceToHost));
+  const std::string path = outputPrefix + "aoBuffer.png";
+  if (!SavePNG(path.c_str(), grey.data(), (int) pixelW, (int) pixelH, 1)) throw std::runtime_error("-ao: " + path + " could not be written");
 }
 
 void Renderer::Terminate()

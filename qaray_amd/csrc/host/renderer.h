@@ -8,6 +8,7 @@
 // tasking::parallel_for loops over tiles and pixels (renderer.cpp:383-420) is one
 // qa_render_region / qa_render_strips call.
 #pragma once
+#include <limits>
 #include <cstddef>
 #include <cstdint>
 #include <string>
@@ -78,6 +79,11 @@ class Renderer {
   // ray meets that node first (qa_idmatte_region_device / qa_progressive_idmatte_device once, then qa_idmatte_select_device per
   // node).  (name, the flattener's index of the node: FindNodeIndex.)  One device only
   std::vector<std::pair<std::string, int>> matteNodes;
+  // -ao [K] (aoRays > 0) and -ao-radius R: another image, <prefix>aoBuffer.png, 8-bit grey: the ambient occlusion of what the frame's own
+  // samples see, K rays per hit within R (qa_ao_region_device / qa_progressive_ao_device with the frame's seed, then qa_ao_grey_device).
+  // One device only
+  int aoRays = 0;
+  float aoRadius = std::numeric_limits<float>::infinity();
 
  protected:
   RendererParam &param;
@@ -94,7 +100,8 @@ class Renderer {
   void SaveDenoised(float *dRgb, const float *dDepth, const uint32_t *dNs);   // the fourth; dRgb is filtered in place
   void SaveAlpha(const float *dRgb, const uint32_t *dNs, bool progressive);   // rgbaBuffer.png of the frame in device buffers
   void SaveNodeMattes(const uint32_t *dNs, bool progressive);                 // matte_NAME.png of every -matte-node
-  struct DeviceFrame {                                  // -denoise, -alpha, -matte-node: the frame's floats on the device, freed with the Renderer at the latest
+  void SaveAo(const uint32_t *dNs, bool progressive);                         // aoBuffer.png
+  struct DeviceFrame {                                  // -denoise, -alpha, -matte-node, -ao: the frame's floats on the device, freed with the Renderer at the latest
     float *rgb = nullptr, *depth = nullptr;
     uint32_t *ns = nullptr;
     void Alloc(size_t npix);

@@ -264,6 +264,9 @@ QA_IDMATTE_EMPTY = -2 ** 31   # the id of a free slot: no key has it
 QA_IDMATTE_NODE, QA_IDMATTE_MATERIAL = 0, 1
 QA_IDMATTE_MAX_SELECT = 256
 _IDMATTE_KEYS = {"node": QA_IDMATTE_NODE, "material": QA_IDMATTE_MATERIAL}
+# ambient occlusion (qa_ao_dev.h): open and rays uint32 [h,w], ao float32 [h,w], in the C ABI's order
+AO_PLANES = ("open", "rays", "ao")
+QA_AO_MAX_RAYS = 256
 QA_RAY_MISS = 1e30   # the t of a ray that hits nothing (exactly np.float32(1e30))
 RAY_OUTPUTS = ("t", "ids", "normal", "point")   # in the C ABI's order: float32 [n], int32 [n,2], float32 [n,3], [n,3]
 QA_MAX_RAYS = 2 ** 31 - 1
@@ -382,6 +385,16 @@ def lib():
         L.qa_idmatte_select_device.argtypes = [C.c_void_p] * 4 + [C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.qa_test_idmatte_accumulate_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32] + [C.c_void_p] * 3
         L.qa_test_idmatte_select_host.argtypes = [C.c_void_p] * 3 + [C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p]
+        L.qa_ao_region_device.argtypes = [C.c_void_p] + [C.c_int] * 4 + [C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_float, C.c_uint32] + [C.c_void_p] * 4
+        L.qa_ao_region.argtypes = [C.c_void_p] + [C.c_int] * 4 + [C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_float, C.c_uint32] + [C.c_void_p] * 3
+        L.qa_progressive_ao_device.argtypes = [C.c_void_p, C.c_uint32, C.c_float] + [C.c_void_p] * 4
+        L.qa_ao_points_device.argtypes = [C.c_void_p, C.c_uint64] + [C.c_void_p] * 3 + [C.c_uint32, C.c_uint32, C.c_float, C.c_uint32] + [C.c_void_p] * 3
+        L.qa_ao_points.argtypes = [C.c_void_p, C.c_uint64] + [C.c_void_p] * 3 + [C.c_uint32, C.c_uint32, C.c_float, C.c_uint32] + [C.c_void_p] * 2
+        L.qa_ao_grey_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+        L.qa_test_ao_directions_host.argtypes = [C.c_uint32] + [C.c_void_p] * 3 + [C.c_uint64, C.c_void_p]
+        L.qa_test_ao_face_normal_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+        L.qa_test_ao_sphere_host.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+        L.qa_test_ao_direction_from_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
         L.qa_cast_rays_device.argtypes = [C.c_void_p, C.c_uint64] + [C.c_void_p] * 7
         L.qa_cast_rays.argtypes = [C.c_void_p, C.c_uint64] + [C.c_void_p] * 6
         L.qa_occluded_device.argtypes = [C.c_void_p, C.c_uint64] + [C.c_void_p] * 5
@@ -515,6 +528,66 @@ def matte_rgba_host(rgb, backdrop, coverage, ns, srgb=True):
     out = np.zeros(coverage.shape + (4,), np.uint8)
     _check(lib().qa_test_matte_rgba_host(rgb.ctypes.data, backdrop.ctypes.data, coverage.ctypes.data, ns.ctypes.data, n, int(bool(srgb)), out.ctypes.data))
     return out
+
+
+def _ao_keys(stream, c):
+    """The (stream, counter) pairs of a hook call as two contiguous uint32 arrays of one length"""
+    stream = np.ascontiguousarray(stream, dtype=np.uint32).reshape(-1)
+    c = np.ascontiguousarray(c, dtype=np.uint32).reshape(-1)
+    if c.shape != stream.shape:
+        raise ValueError(f"c: shape {stream.shape} is expected, not {c.shape}")
+    return stream, c
+
+
+def _ao_vectors(name, v, count):
+    """(count, 3) contiguous float32 from (count, 3), or from one vector for every record"""
+    v = np.asarray(v, dtype=np.float32)
+    if v.shape == (3,):
+        v = np.broadcast_to(v, (count, 3))
+    if v.shape != (count, 3):
+        raise ValueError(f"{name}: shape ({count}, 3) or (3,) is expected, not {v.shape}")
+    return np.ascontiguousarray(v)
+
+
+def ao_directions_host(seed, stream, c, n):
+    """qa_test_ao_directions_host: the ambient-occlusion directions of the keys (seed, stream[i], c[i]) about the unit normals n
+    ((count, 3), or one (3,) for all) on the CPU, from the source the device kernels are compiled from -> float32 (count, 3).  No GPU
+    needed."""
+    stream, c = _ao_keys(stream, c)
+    n = _ao_vectors("n", n, len(c))
+    d = np.zeros((len(c), 3), np.float32)
+    _check(lib().qa_test_ao_directions_host(int(seed) & 0xFFFFFFFF, stream.ctypes.data, c.ctypes.data, n.ctypes.data, len(c), d.ctypes.data))
+    return d
+
+
+def ao_face_normal_host(N, d):
+    """qa_test_ao_face_normal_host: the normals N (count, 3) turned against the camera rays' directions d (count, 3) -> float32
+    (count, 3).  No GPU needed."""
+    N = np.ascontiguousarray(N, dtype=np.float32).reshape(-1, 3)
+    d = _ao_vectors("d", d, len(N))
+    out = np.zeros((len(N), 3), np.float32)
+    _check(lib().qa_test_ao_face_normal_host(N.ctypes.data, d.ctypes.data, len(N), out.ctypes.data))
+    return out
+
+
+def ao_sphere_host(seed, stream, c):
+    """qa_test_ao_sphere_host: the generator's inner step - the sphere points of the keys and whether all attempts failed -> (float32
+    (count, 3), bool (count,)).  No GPU needed."""
+    stream, c = _ao_keys(stream, c)
+    s = np.zeros((len(c), 3), np.float32)
+    fb = np.zeros(len(c), np.uint8)
+    _check(lib().qa_test_ao_sphere_host(int(seed) & 0xFFFFFFFF, stream.ctypes.data, c.ctypes.data, len(c), s.ctypes.data, fb.ctypes.data))
+    return s, fb.astype(bool)
+
+
+def ao_direction_from_host(n, s):
+    """qa_test_ao_direction_from_host: the generator's outer step from sphere points s (count, 3) given directly, about n ((count, 3) or
+    (3,)) -> float32 (count, 3).  No GPU needed."""
+    s = np.ascontiguousarray(s, dtype=np.float32).reshape(-1, 3)
+    n = _ao_vectors("n", n, len(s))
+    d = np.zeros((len(s), 3), np.float32)
+    _check(lib().qa_test_ao_direction_from_host(n.ctypes.data, s.ctypes.data, len(s), d.ctypes.data))
+    return d
 
 
 def _idmatte_key(key):
@@ -856,6 +929,15 @@ def _idmatte_planes(region):
     h, w = y1 - y0, x1 - x0
     shapes = {k: (h, w, QA_IDMATTE_SLOTS) if k in ("ids", "counts") else (h, w) for k in IDMATTE_PLANES}
     return shapes, {k: torch.int32 for k in IDMATTE_PLANES}
+
+
+def _ao_planes(region):
+    """Shapes and dtypes of the ambient-occlusion planes of a region (the unsigned planes are int32 tensors of the same bits, as the
+    id matte's)"""
+    import torch
+    x0, y0, x1, y1 = region
+    h, w = y1 - y0, x1 - x0
+    return {k: (h, w) for k in AO_PLANES}, {k: torch.float32 if k == "ao" else torch.int32 for k in AO_PLANES}
 
 
 def _ray_count(name, t):
@@ -1324,6 +1406,83 @@ class Context:
         sptr = self._stream_arg(stream, ids)
         _check(lib().qa_idmatte_select_device(self._h, ids.data_ptr(), counts.data_ptr(), samples.data_ptr(), n, sel.ctypes.data if sel.size else None,
                                               sel.size, out.data_ptr(), _ptr(out_bytes), sptr))
+        return out
+
+    def ao(self, region, spp, K=4, radius=float("inf"), first=0, ns=None, seed=DEFAULT_SEED):
+        """qa_ao_region: the ambient occlusion of a region (the opening comment of qa_ao_dev.h is the specification): from what the
+        camera rays of samples first .. first + spp - 1 of a pixel hit, K cosine-weighted rays over the facing side, each tested as
+        occluded() tests a ray of length radius -> dict of numpy arrays open [h,w] u32 (the rays that met nothing), rays [h,w] u32
+        (hit samples * K), ao [h,w] f32 (open / rays, 1 where rays is 0).  ns: [h,w] sample counts, a pixel then takes
+        min(max(ns - first, 0), spp) samples.  A camera with depth of field is refused.  Synchronises."""
+        x0, y0, x1, y1 = region
+        h, w = y1 - y0, x1 - x0
+        if ns is not None:
+            ns = np.ascontiguousarray(ns, dtype=np.uint32)
+            if ns.shape != (h, w):
+                raise ValueError(f"ns: shape {(h, w)} is expected, not {ns.shape}")
+        out = {"open": np.zeros((h, w), np.uint32), "rays": np.zeros((h, w), np.uint32), "ao": np.zeros((h, w), np.float32)}
+        _check(lib().qa_ao_region(self._h, x0, y0, x1, y1, int(first), int(spp), _ptr(ns), int(K), float(radius), int(seed) & 0xFFFFFFFF,
+                                  *(out[k].ctypes.data for k in AO_PLANES)))
+        return out
+
+    def ao_device(self, region, spp, K=4, radius=float("inf"), first=0, ns=None, seed=DEFAULT_SEED, open=None, rays=None, ao=None, stream=None):
+        """qa_ao_region_device into torch CUDA tensors (see ao for the planes; open and rays are int32 tensors, the unsigned planes'
+        bits; ns: an int32 / uint32 CUDA tensor [h,w] or None): the planes given are written; when none is given all three are
+        allocated.  -> dict name -> tensor.  Only enqueues (see render_region_device for the stream)."""
+        import torch
+        out, ptrs = _output_tensors(AO_PLANES, *_ao_planes(region), torch.device("cuda", self.device_id), dict(open=open, rays=rays, ao=ao))
+        x0, y0, x1, y1 = region
+        if ns is not None:
+            assert ns.is_cuda and ns.is_contiguous() and ns.element_size() == 4 and not ns.dtype.is_floating_point and ns.numel() == (y1 - y0) * (x1 - x0), "ns"
+        nptr = None if ns is None else ns.data_ptr()
+        sptr = self._stream_arg(stream, next(iter(out.values())))
+        _check(lib().qa_ao_region_device(self._h, x0, y0, x1, y1, int(first), int(spp), nptr, int(K), float(radius), int(seed) & 0xFFFFFFFF, *ptrs, sptr))
+        return out
+
+    def ao_grey_device(self, ao, out=None, stream=None):
+        """qa_ao_grey_device: the 8-bit grey picture of an ao plane (float32 CUDA tensor, any shape): the byte display_device makes of
+        the value without sRGB.  out: the uint8 tensor of that shape to write (None: a new one) -> out.  Only enqueues."""
+        import torch
+        dev = torch.device("cuda", self.device_id)
+        _ray_tensor("ao", ao, tuple(ao.shape) if isinstance(ao, torch.Tensor) else (), torch.float32, dev)
+        if out is None:
+            out = torch.empty(tuple(ao.shape), dtype=torch.uint8, device=dev)
+        _ray_tensor("out", out, tuple(ao.shape), torch.uint8, dev)
+        _check(lib().qa_ao_grey_device(self._h, ao.data_ptr(), ao.numel(), out.data_ptr(), self._stream_arg(stream, ao)))
+        return out
+
+    def ao_points_device(self, points, normals, K=16, radius=float("inf"), first=0, stream_ids=None, seed=DEFAULT_SEED, open=None, ao=None,
+                         stream=None):
+        """qa_ao_points_device: the ambient occlusion at n points of the caller's (mesh vertices, lightmap texels).  points, normals:
+        float32 [n,3] contiguous CUDA tensors, world space, the normals of unit length; point i casts the K rays of the counters
+        first .. first + K - 1 of stream i, or stream_ids[i] (int32 [n]).  Outputs: open int32 [n] (the unsigned count's bits), ao
+        float32 [n] = open / K; the ones given are written, and when none is given both are allocated.  A point with a component that
+        is not finite, or a zero normal, answers open = K, ao = 1.  -> dict name -> tensor.  Only enqueues."""
+        import torch
+        dev = torch.device("cuda", self.device_id)
+        n = _ray_count("points", points) if isinstance(points, torch.Tensor) else 0
+        _ray_tensor("points", points, (n, 3), torch.float32, dev)
+        _ray_tensor("normals", normals, (n, 3), torch.float32, dev)
+        if stream_ids is not None:
+            _ray_tensor("stream_ids", stream_ids, (n,), torch.int32, dev)
+        out, ptrs = _output_tensors(("open", "ao"), {"open": (n,), "ao": (n,)}, {"open": torch.int32, "ao": torch.float32}, dev, dict(open=open, ao=ao))
+        sptr = self._stream_arg(stream, points)
+        _check(lib().qa_ao_points_device(self._h, n, points.data_ptr(), normals.data_ptr(), None if stream_ids is None else stream_ids.data_ptr(),
+                                         int(first), int(K), float(radius), int(seed) & 0xFFFFFFFF, *ptrs, sptr))
+        return out
+
+    def ao_points(self, points, normals, K=16, radius=float("inf"), first=0, stream_ids=None, seed=DEFAULT_SEED):
+        """qa_ao_points: ao_points_device from and to host memory.  points, normals: [n,3], converted to float32; stream_ids: [n]
+        integers below 2^32 or None -> dict of numpy arrays open [n] u32, ao [n] f32.  Synchronises."""
+        p, nr, n = _ray_arrays(points, normals)
+        sid = None
+        if stream_ids is not None:
+            sid = np.ascontiguousarray(np.asarray(stream_ids).astype(np.uint32)).view(np.int32).reshape(-1)
+            if sid.shape != (n,):
+                raise ValueError(f"stream_ids: shape ({n},) is expected, not {sid.shape}")
+        out = {"open": np.zeros(n, np.uint32), "ao": np.zeros(n, np.float32)}
+        _check(lib().qa_ao_points(self._h, n, p.ctypes.data, nr.ctypes.data, _ptr(sid), int(first), int(K), float(radius), int(seed) & 0xFFFFFFFF,
+                                  out["open"].ctypes.data, out["ao"].ctypes.data))
         return out
 
     def rgba_device(self, rgb, backdrop, coverage, ns, srgb=True, out=None, stream=None):
@@ -1900,6 +2059,16 @@ class Progressive:
                                     dict(ids=ids, counts=counts, other=other, samples=samples))
         sptr = Context._stream_arg(stream, next(iter(out.values())))
         _check(lib().qa_progressive_idmatte_device(self._ctx._h, _idmatte_key(key), *ptrs, sptr))
+        return out
+
+    def ao_device(self, K=4, radius=float("inf"), open=None, rays=None, ao=None, stream=None):
+        """qa_progressive_ao_device: the ambient occlusion of the frame's region over the samples each pixel holds now, with the
+        frame's seed, of the scene as it now stands (see Context.ao_device: its planes for first 0, spp_max and the ns plane read()
+        gives) -> dict name -> tensor; only enqueues."""
+        import torch
+        out, ptrs = _output_tensors(AO_PLANES, *_ao_planes(self.region), torch.device("cuda", self._ctx.device_id), dict(open=open, rays=rays, ao=ao))
+        sptr = Context._stream_arg(stream, next(iter(out.values())))
+        _check(lib().qa_progressive_ao_device(self._ctx._h, int(K), float(radius), *ptrs, sptr))
         return out
 
     def reproject_device(self, history, prev_cam, hist_ids=None, out=None, out_length=None, params=None, depth_tolerance=None, max_history=None,
