@@ -48,6 +48,8 @@
  *   qa_camera_rays_device          rays PixelRender starts from, handed out)       src/scene/scene.cpp:35-74
  *   qa_ao_region*, qa_ao_points*,  (no counterpart: ambient occlusion - how many of K short rays over the facing side of what a pixel's
  *   qa_progressive_ao_device       samples see, or of points of the caller's, meet nothing within a radius)
+ *   qa_bake_texels*,               (no counterpart: the reference bakes nothing - the surface point of a node behind every texel of
+ *   qa_bake_dilate_device          a texture laid over it, and the gutter fill of a baked picture)
  *   qa_denoise_guided_device,      (no counterpart: the preview filter with those normal and albedo planes as two more
  *   qa_progressive_denoise_guided* edge-stopping guides)
  *   qa_denoise_variance_device     (no counterpart: that filter with a per-pixel variance of the caller's in place of its spatial guess)
@@ -519,6 +521,38 @@ int qa_ao_grey_device(qa_ctx *ctx, const float *d_ao, uint64_t npix, uint8_t *d_
 int qa_ao_points(qa_ctx *ctx, uint64_t n, const float *points, const float *normals, const int32_t *stream_ids, uint32_t first,
                  uint32_t K, float radius, uint32_t seed, uint32_t *open, float *ao);
 
+/* Bake maps: which surface point of a node lies behind each texel of a width x height texture laid over it, so that a lightmap or an
+ * occlusion map of an object can be made with the point queries above and written back with qa_scene_edit_texels_device (the opening
+ * comment of qaray_amd/csrc/hip/qa_bake_dev.h is the specification: the texel's sample, the inside rule and why charts have no cracks,
+ * the tiles, what a covered texel holds).  node: an instance index; a mesh with texture vertices or a plane (the built-in pair of
+ * faces); texmap: an index into the scene's texmaps whose transform the texture vertices go through as the renderer's lookup sends
+ * them, or -1 for the raw (u, v); mtl: only the faces with this qa_face::mtl, or -1 for all.  Row-major planes [height][width], row 0
+ * the top row as stored; every pointer may be NULL (not wanted), but not all of them:
+ *   point   3 floats   the surface point, world space
+ *   normal  3 floats   the interpolated shading normal, world space, unit (NaN where the mesh's normals cancel), never flipped
+ *   face    1 int32    the blob's face id (0 / 1 for a plane), -1 where no face covers the texel; the other planes then hold zeros
+ *   bary    2 floats   the weights of the face's first two vertices
+ * One sample per texel; where charts overlap the lowest face wins.  The kernel only reads the scene: no frame, progressive frame,
+ * counter (qa_get_counters) or kernel-time record changes.  Codes: QA_ENOSCENE; QA_EINVAL for a width or height of 0 or above 8192, no
+ * plane at all, a node out of range or without an object, a mesh without texture vertices, a texmap out of range or without a
+ * texture; QA_EUNSUPPORTED for a sphere node, for a map under which a face spans more than 4 tiles of the texture along an axis, and
+ * for a scene whose traversal stacks leave less than 15 KB of a workgroup's 64 KB of LDS (a stack depth near 50): the map's face
+ * chunk sits beside the dynamic LDS every scene kernel is launched with.
+ * A refused call writes nothing.  Ordered as qa_ao_points_device: the device variant only enqueues on `stream` (a hipStream_t; NULL =
+ * the context's stream), behind the context's last frame and last edit, and a later edit waits for it; the host variant copies and
+ * synchronises.
+ *   qa_bake_dilate_device   the gutter fill of a baked RGB8 picture [height][width][3]: a texel with d_face >= 0 keeps its bytes,
+ *                           another takes those of the nearest covered texel within `radius` (<= 8) texels per axis, wrapping at
+ *                           the borders as the lookup wraps; ties go to dy ascending, then dx ascending; with none in reach it keeps
+ *                           its own.  d_out must not overlap d_rgb8.  Touches no state of the context; only enqueues.  QA_EINVAL for
+ *                           a NULL buffer, a bad size or radius, or an overlap. */
+int qa_bake_texels_device(qa_ctx *ctx, int node, int texmap, int mtl, uint32_t width, uint32_t height, float *d_point, float *d_normal,
+                          int32_t *d_face, float *d_bary, void *stream);
+int qa_bake_texels(qa_ctx *ctx, int node, int texmap, int mtl, uint32_t width, uint32_t height, float *point, float *normal, int32_t *face,
+                   float *bary);
+int qa_bake_dilate_device(qa_ctx *ctx, const uint8_t *d_rgb8, const int32_t *d_face, uint32_t width, uint32_t height, uint32_t radius,
+                          uint8_t *d_out, void *stream);
+
 /* Ray queries: n rays of the caller's against the resident scene, through the integrators' own closest-hit and shadow walks (the
  * opening comment of qa_ray_query.hip is the specification).  Ray i has origin origins[3i .. 3i+2] and direction dirs[3i .. 3i+2],
  * world space, fp32, contiguous.  The direction is used as given and NOT normalised: t is the parameter along it (the hit is at
@@ -864,6 +898,13 @@ int qa_test_ao_directions_host(uint32_t seed, const uint32_t *stream, const uint
 int qa_test_ao_face_normal_host(const float *N, const float *d, uint64_t count, float *n);
 int qa_test_ao_sphere_host(uint32_t seed, const uint32_t *stream, const uint32_t *c, uint64_t count, float *s, uint8_t *fallback);
 int qa_test_ao_direction_from_host(const float *n, const float *s, uint64_t count, float *d);
+
+/* Self-test hooks for the bake maps (qaray_amd/csrc/hip/qa_bake_dev.h): the source of qa_bake_texels_device's and
+ * qa_bake_dilate_device's kernels compiled for the host (no GPU and no context needed).  texels: the call on a flat scene blob of
+ * nbytes in host memory, every refusal but QA_ENOSCENE included; dilate: the fill over host arrays. */
+int qa_test_bake_texels_host(const void *blob, uint64_t nbytes, int node, int texmap, int mtl, uint32_t width, uint32_t height, float *point,
+                             float *normal, int32_t *face, float *bary);
+int qa_test_bake_dilate_host(const uint8_t *rgb8, const int32_t *face, uint32_t width, uint32_t height, uint32_t radius, uint8_t *out);
 
 /* Self-test hook for the texel conversion (qaray_amd/csrc/hip/qa_texel_dev.h): the source of qa_scene_edit_texels' kernel and of an
  * upload's texel table compiled for the host: h rows of w RGB8 texels, `stride` bytes apart -> w * h entries {r, g, b, 0} / 255.0f

@@ -55,13 +55,19 @@ TEXMAP_DTYPE = np.dtype([("itm", np.float32, 9), ("pos", np.float32, 3), ("textu
 TEXTURE_DTYPE = np.dtype([("type", np.int32), ("width", np.int32), ("height", np.int32), ("pad0", np.int32), ("color1", np.float32, 3),
                           ("color2", np.float32, 3), ("off_texels", np.uint64), ("pad1", np.uint64)])
 MTLSET_DTYPE = np.dtype([("first", np.int32), ("count", np.int32), ("multi", np.int32), ("pad", np.int32)])
+MESH_DTYPE = np.dtype([("bmin", np.float32, 3), ("bmax", np.float32, 3), ("num_faces", np.uint32), ("num_vertices", np.uint32),
+                       ("num_normals", np.uint32), ("num_texcoords", np.uint32), ("num_bvh_nodes", np.uint32), ("pad", np.uint32),
+                       ("off_bvh_nodes", np.uint64), ("off_elements", np.uint64), ("off_faces", np.uint64), ("off_vertices", np.uint64),
+                       ("off_normals", np.uint64), ("off_texcoords", np.uint64)])
+FACE_DTYPE = np.dtype([("v", np.int32, 3), ("vn", np.int32, 3), ("vt", np.int32, 3), ("mtl", np.int32)])
 assert (CAMERA_DTYPE.itemsize, LIGHT_DTYPE.itemsize, MATERIAL_DTYPE.itemsize, INSTANCE_DTYPE.itemsize) == (76, 64, 112, 112)
 assert (TEXCOLOR_DTYPE.itemsize, TEXMAP_DTYPE.itemsize, TEXTURE_DTYPE.itemsize) == (16, 64, 56)
+assert (MESH_DTYPE.itemsize, FACE_DTYPE.itemsize) == (96, 40)
 QA_TEX_CHECKER, QA_TEX_FILE = 0, 1
 # qa_flat_header: byte offsets of the counts and table offsets the views below need
-_HEADER = {"camera": 16, "backdrop": 104, "instances": (136, 168), "mtlsets": (144, 184), "materials": (148, 192), "lights": (152, 200), "texmaps": (156, 208),
+_HEADER = {"camera": 16, "backdrop": 104, "instances": (136, 168), "meshes": (140, 176), "mtlsets": (144, 184), "materials": (148, 192), "lights": (152, 200), "texmaps": (156, 208),
            "textures": (160, 216)}
-_TABLE_DTYPES = {"instances": INSTANCE_DTYPE, "mtlsets": MTLSET_DTYPE, "materials": MATERIAL_DTYPE, "lights": LIGHT_DTYPE, "texmaps": TEXMAP_DTYPE,
+_TABLE_DTYPES = {"instances": INSTANCE_DTYPE, "meshes": MESH_DTYPE, "mtlsets": MTLSET_DTYPE, "materials": MATERIAL_DTYPE, "lights": LIGHT_DTYPE, "texmaps": TEXMAP_DTYPE,
                  "textures": TEXTURE_DTYPE}
 
 
@@ -85,9 +91,22 @@ def blob_texels(blob, i):
     return blob[off:off + 3 * w * h].reshape(h, w, 3)
 
 
+def blob_mesh_arrays(blob, mesh):
+    """The raw arrays of mesh `mesh` of a flat scene blob (numpy uint8) as writable views -> dict faces (FACE_DTYPE), vertices (nv, 3),
+    normals (nn, 3), texcoords (nt, 2) float32."""
+    m = blob_table(blob, "meshes")[mesh]
+
+    def view(off, count, dtype, width):
+        off, count = int(off), int(count)
+        a = blob[off:off + count * width * np.dtype(dtype).itemsize].view(dtype)
+        return a if width == 1 else a.reshape(count, width)
+    return {"faces": view(m["off_faces"], m["num_faces"], FACE_DTYPE, 1), "vertices": view(m["off_vertices"], m["num_vertices"], np.float32, 3),
+            "normals": view(m["off_normals"], m["num_normals"], np.float32, 3), "texcoords": view(m["off_texcoords"], m["num_texcoords"], np.float32, 2)}
+
+
 def blob_table(blob, which):
-    """The 'lights' / 'materials' / 'mtlsets' / 'instances' / 'texmaps' / 'textures' table of a flat scene blob (numpy uint8) as a writable
-    structured view."""
+    """The 'lights' / 'materials' / 'mtlsets' / 'instances' / 'meshes' / 'texmaps' / 'textures' table of a flat scene blob (numpy uint8) as a
+    writable structured view."""
     at_count, at_off = _HEADER[which]
     n = int(blob[at_count:at_count + 4].view(np.uint32)[0])
     off = int(blob[at_off:at_off + 8].view(np.uint64)[0])
@@ -267,6 +286,8 @@ _IDMATTE_KEYS = {"node": QA_IDMATTE_NODE, "material": QA_IDMATTE_MATERIAL}
 # ambient occlusion (qa_ao_dev.h): open and rays uint32 [h,w], ao float32 [h,w], in the C ABI's order
 AO_PLANES = ("open", "rays", "ao")
 QA_AO_MAX_RAYS = 256
+BAKE_PLANES = ("point", "normal", "face", "bary")   # in the C ABI's order: float32 [h,w,3], [h,w,3], int32 [h,w], float32 [h,w,2]
+QA_BAKE_MAX_DIM, QA_BAKE_MAX_RADIUS, QA_BAKE_MAX_TILES = 8192, 8, 4
 QA_RAY_MISS = 1e30   # the t of a ray that hits nothing (exactly np.float32(1e30))
 RAY_OUTPUTS = ("t", "ids", "normal", "point")   # in the C ABI's order: float32 [n], int32 [n,2], float32 [n,3], [n,3]
 QA_MAX_RAYS = 2 ** 31 - 1
@@ -395,6 +416,11 @@ def lib():
         L.qa_test_ao_face_normal_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
         L.qa_test_ao_sphere_host.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         L.qa_test_ao_direction_from_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+        L.qa_bake_texels_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint32] + [C.c_void_p] * 5
+        L.qa_bake_texels.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint32] + [C.c_void_p] * 4
+        L.qa_bake_dilate_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+        L.qa_test_bake_texels_host.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint32] + [C.c_void_p] * 4
+        L.qa_test_bake_dilate_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
         L.qa_cast_rays_device.argtypes = [C.c_void_p, C.c_uint64] + [C.c_void_p] * 7
         L.qa_cast_rays.argtypes = [C.c_void_p, C.c_uint64] + [C.c_void_p] * 6
         L.qa_occluded_device.argtypes = [C.c_void_p, C.c_uint64] + [C.c_void_p] * 5
@@ -588,6 +614,61 @@ def ao_direction_from_host(n, s):
     d = np.zeros((len(s), 3), np.float32)
     _check(lib().qa_test_ao_direction_from_host(n.ctypes.data, s.ctypes.data, len(s), d.ctypes.data))
     return d
+
+
+def _bake_size(width, height):
+    """(width, height) of a bake call as the C ABI takes them; the library refuses 0 and above QA_BAKE_MAX_DIM, a negative one is
+    refused here (it would wrap)"""
+    w, h = int(width), int(height)
+    if w < 0 or h < 0 or w > 0xFFFFFFFF or h > 0xFFFFFFFF:
+        raise ValueError(f"width, height: {w} x {h} texels")
+    return w, h
+
+
+def _bake_host_planes(w, h, want):
+    """The numpy planes of a host bake call: those named in `want` (all of BAKE_PLANES when it is None)"""
+    names = BAKE_PLANES if want is None else tuple(want)
+    bad = [k for k in names if k not in BAKE_PLANES]
+    if bad:
+        raise ValueError(f"planes: {bad} are not among {BAKE_PLANES}")
+    shapes = {"point": (h, w, 3), "normal": (h, w, 3), "face": (h, w), "bary": (h, w, 2)}
+    return {k: np.zeros(shapes[k], np.int32 if k == "face" else np.float32) for k in BAKE_PLANES if k in names}
+
+
+def bake_texels_host(blob, node, width, height, texmap=None, mtl=-1, planes=None):
+    """qa_test_bake_texels_host: Context.bake_texels on a flat scene blob (numpy uint8) on the CPU, from the source the device kernel
+    is compiled from (the opening comment of qa_bake_dev.h is the specification), every refusal but the missing scene's included
+    -> dict of numpy arrays point [h,w,3] f32, normal [h,w,3] f32, face [h,w] i32, bary [h,w,2] f32 (planes: the names wanted; None:
+    all four).  No GPU needed."""
+    blob = np.ascontiguousarray(blob, dtype=np.uint8)
+    w, h = _bake_size(width, height)
+    out = _bake_host_planes(w, h, planes)
+    _check(lib().qa_test_bake_texels_host(blob.ctypes.data, blob.size, int(node), -1 if texmap is None else int(texmap), int(mtl), w, h,
+                                          *(out[k].ctypes.data if k in out else None for k in BAKE_PLANES)))
+    return out
+
+
+def _dilate_arrays(rgb8, face):
+    rgb8 = np.ascontiguousarray(rgb8)
+    face = np.ascontiguousarray(face)
+    if rgb8.dtype != np.uint8 or rgb8.ndim != 3 or rgb8.shape[2] != 3:
+        raise ValueError("rgb8: a uint8 array of shape (h, w, 3) is expected")
+    if face.dtype != np.int32 or face.shape != rgb8.shape[:2]:
+        raise ValueError(f"face: an int32 array of shape {rgb8.shape[:2]} is expected")
+    return rgb8, face
+
+
+def bake_dilate_host(rgb8, face, radius=2, out=None):
+    """qa_test_bake_dilate_host: Context.bake_dilate_device over numpy arrays on the CPU, from the source the device kernel is compiled
+    from: rgb8 (h, w, 3) uint8, face (h, w) int32 -> uint8 (h, w, 3) (out: the array to write; it must not be rgb8).  No GPU needed."""
+    rgb8, face = _dilate_arrays(rgb8, face)
+    if out is None:
+        out = np.zeros_like(rgb8)
+    if not isinstance(out, np.ndarray) or out.dtype != np.uint8 or out.shape != rgb8.shape or not out.flags.c_contiguous:
+        raise ValueError(f"out: a contiguous uint8 array of shape {rgb8.shape} is expected")
+    h, w = face.shape
+    _check(lib().qa_test_bake_dilate_host(rgb8.ctypes.data, face.ctypes.data, w, h, int(radius), out.ctypes.data))
+    return out
 
 
 def _idmatte_key(key):
@@ -1037,6 +1118,7 @@ class Context:
         self.size = None
         self._photon_sizes = None
         self._tmax_fill = None   # occluded_device: the tensor a scalar tmax was broadcast into, kept until the next such call
+        self._bake_stream = None   # bake_ao: its side stream of torch's, made on first use, dropped by close()
 
     # -- scene ---------------------------------------------------------------------------------
     def upload_scene(self, blob):
@@ -1485,6 +1567,108 @@ class Context:
                                   out["open"].ctypes.data, out["ao"].ctypes.data))
         return out
 
+    # -- bake maps (qa_bake.hip) --------------------------------------------------------------------
+    def bake_texels_device(self, node, width, height, texmap=None, mtl=-1, point=None, normal=None, face=None, bary=None, stream=None):
+        """qa_bake_texels_device: the surface point of node `node` (a mesh with texture vertices, or a plane) behind every texel of a
+        width x height texture laid over it (the opening comment of qa_bake_dev.h is the specification).  texmap: the scene's texmap
+        whose transform the texture vertices go through (None: the raw uv); mtl: only the faces of that material index (-1: all).
+        Outputs, contiguous CUDA tensors, row 0 the top row as stored: point, normal float32 [h,w,3] (world space), face int32 [h,w]
+        (the blob's face id, -1 where nothing covers the texel: the other planes then hold zeros), bary float32 [h,w,2]; the ones
+        given are written, and when none is given all four are allocated.  -> dict name -> tensor.  Only enqueues (see
+        render_region_device for the stream)."""
+        import torch
+        dev = torch.device("cuda", self.device_id)
+        w, h = _bake_size(width, height)
+        shapes = {"point": (h, w, 3), "normal": (h, w, 3), "face": (h, w), "bary": (h, w, 2)}
+        dtypes = {k: torch.int32 if k == "face" else torch.float32 for k in BAKE_PLANES}
+        out, ptrs = _output_tensors(BAKE_PLANES, shapes, dtypes, dev, dict(point=point, normal=normal, face=face, bary=bary))
+        sptr = self._stream_arg(stream, next(iter(out.values())))
+        _check(lib().qa_bake_texels_device(self._h, int(node), -1 if texmap is None else int(texmap), int(mtl), w, h, *ptrs, sptr))
+        return out
+
+    def bake_texels(self, node, width, height, texmap=None, mtl=-1, planes=None):
+        """qa_bake_texels: bake_texels_device to host memory -> dict of numpy arrays point [h,w,3] f32, normal [h,w,3] f32, face
+        [h,w] i32, bary [h,w,2] f32 (planes: the names wanted; None: all four).  Synchronises."""
+        w, h = _bake_size(width, height)
+        out = _bake_host_planes(w, h, planes)
+        _check(lib().qa_bake_texels(self._h, int(node), -1 if texmap is None else int(texmap), int(mtl), w, h,
+                                    *(out[k].ctypes.data if k in out else None for k in BAKE_PLANES)))
+        return out
+
+    def bake_dilate_device(self, rgb8, face, radius=2, out=None, stream=None):
+        """qa_bake_dilate_device: the gutter fill of a baked picture.  rgb8 uint8 [h,w,3], face int32 [h,w] (bake_texels_device's
+        plane), contiguous CUDA tensors: a texel with face >= 0 keeps its bytes, another takes those of the nearest covered texel
+        within `radius` (<= 8) texels per axis, wrapping at the borders as the texture lookup wraps (ties: dy ascending, then dx);
+        with none in reach it keeps its own.  out: the uint8 [h,w,3] tensor to write, not rgb8 (None: a new one) -> out.  Only
+        enqueues."""
+        import torch
+        dev = torch.device("cuda", self.device_id)
+        shape = tuple(rgb8.shape) if isinstance(rgb8, torch.Tensor) else ()
+        if len(shape) != 3 or shape[2] != 3:
+            raise ValueError(f"rgb8: shape (h, w, 3) is expected, not {shape}")
+        _ray_tensor("rgb8", rgb8, shape, torch.uint8, dev)
+        _ray_tensor("face", face, shape[:2], torch.int32, dev)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device=dev)
+        _ray_tensor("out", out, shape, torch.uint8, dev)
+        _check(lib().qa_bake_dilate_device(self._h, rgb8.data_ptr(), face.data_ptr(), shape[1], shape[0], int(radius), out.data_ptr(),
+                                           self._stream_arg(stream, rgb8)))
+        return out
+
+    def bake_ao(self, node, texmap, K=64, radius=float("inf"), mtl=-1, dilate=2, seed=DEFAULT_SEED, stream=None):
+        """The ambient occlusion of node `node` baked into the file texture of texmap `texmap`, in place: the map of the texture's
+        texels (bake_texels_device at the texture's size, through the texmap), ao_points_device at the covered texels' points and
+        normals with stream_ids = iy * W + ix, ao_grey_device, the grey in all three channels; uncovered texels keep the texture's
+        bytes as they stand, then take their nearest covered neighbour's within `dilate` texels (bake_dilate_device; 0: no fill);
+        the picture then replaces the texture's texels (edit_texels).  A composition of those calls, all on one stream: the planes
+        stay on the device, only the texture's present bytes are read through download_scene.  -> dict of CUDA tensors ao [H,W]
+        f32 (1 where uncovered), face [H,W] i32, rgb8 [H,W,3] u8 (what the texture now holds).  QA_EINVAL for a texmap without a
+        file texture.  download_scene comes first (it synchronises where a texture was last edited from device memory, as after an
+        earlier bake_ao); the device work is then only enqueued, on `stream` (a HIP stream handle) or, with None, on a side stream
+        that torch's current stream is made to wait for."""
+        import torch
+        dev = torch.device("cuda", self.device_id)
+        blob = self.download_scene()
+        maps = blob_table(blob, "texmaps")
+        if texmap is None or not 0 <= int(texmap) < len(maps) or int(maps[int(texmap)]["texture"]) < 0:
+            raise HipError(-1, "bake_ao: the texmap is out of range or has no texture")
+        tex = int(maps[int(texmap)]["texture"])
+        rec = blob_table(blob, "textures")[tex]
+        if int(rec["type"]) != QA_TEX_FILE:
+            raise HipError(-1, "bake_ao: the texmap's texture is not a file texture")
+        W, H = int(rec["width"]), int(rec["height"])
+        # one stream for the library's calls and torch's own steps between them.  stream = None: a side stream of torch's (the
+        # context's own stream is not torch's to enqueue on) that starts behind torch's current stream, which in turn waits for it
+        cur = torch.cuda.current_stream(dev)
+        if stream:
+            ts = torch.cuda.ExternalStream(int(stream), device=dev)
+        else:
+            if self._bake_stream is None:
+                self._bake_stream = torch.cuda.Stream(dev)
+            ts = self._bake_stream
+            ts.wait_stream(cur)
+        sptr = ts.cuda_stream
+        with torch.cuda.stream(ts):
+            current = torch.from_numpy(blob_texels(blob, tex).copy()).to(dev)
+            m = self.bake_texels_device(node, W, H, texmap=texmap, mtl=mtl, point=torch.empty((H, W, 3), dtype=torch.float32, device=dev),
+                                        normal=torch.empty((H, W, 3), dtype=torch.float32, device=dev),
+                                        face=torch.empty((H, W), dtype=torch.int32, device=dev), stream=sptr)
+            ids = torch.arange(H * W, dtype=torch.int32, device=dev)
+            ao = self.ao_points_device(m["point"].reshape(-1, 3), m["normal"].reshape(-1, 3), K, radius, 0, ids, seed,
+                                       ao=torch.empty(H * W, dtype=torch.float32, device=dev), stream=sptr)["ao"].reshape(H, W)
+            covered = m["face"] >= 0   # (an uncovered texel's normal is zero: a void point, whose ao is 1)
+            grey = self.ao_grey_device(ao, stream=sptr)
+            rgb8 = torch.where(covered.unsqueeze(2), grey.unsqueeze(2).expand(H, W, 3), current).contiguous()
+            if int(dilate) > 0:
+                rgb8 = self.bake_dilate_device(rgb8, m["face"], int(dilate), stream=sptr)
+            self.edit_texels(tex, rgb8, stream=sptr)
+        out = {"ao": ao, "face": m["face"], "rgb8": rgb8}
+        if not stream:
+            cur.wait_stream(ts)
+            for t in out.values():
+                t.record_stream(cur)
+        return out
+
     def rgba_device(self, rgb, backdrop, coverage, ns, srgb=True, out=None, stream=None):
         """qa_matte_rgba_device: the straight-alpha 8-bit RGBA picture of a frame (rgb float32 [h,w,3] and ns int32 / uint32 [h,w] as
         render_region_device fills them, backdrop and coverage as matte_device(region, spp, ns=ns) does), what a PNG stores: the
@@ -1815,6 +1999,7 @@ class Context:
             lib().qa_ctx_destroy(self._h)   # (waits for the context's stream)
             self._h = C.c_void_p()
             self._tmax_fill = None
+            self._bake_stream = None   # (bake_ao's side stream)
 
     def __del__(self):
         try:
