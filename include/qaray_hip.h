@@ -63,6 +63,8 @@
  *   qa_radiance_rays*,             (no counterpart: PixelRender's path - Scene::TraceNodeNormal, Material::Shade, the lights - started
  *   qa_camera_sample_rays_device   from rays of the caller's instead of the camera ray, and the camera rays of every sample handed
  *                                  out)                                 src/renderers/renderer.cpp:312-341
+ *   qa_irradiance_points*          (no counterpart: MtlBlinn_PhotonMap::Shade of a white diffuse hit at a surface point of the
+ *                                  caller's - its lights, one diffuse bounce, the path behind it - with no ray leading there)
  *   qa_get_counters                (no counterpart: the reference only prints wall-clock)
  *   qa_get_kernel_time             Renderer::StartTimer/StopTimer       src/renderers/renderer.cpp:42-63
  */
@@ -988,6 +990,28 @@ int qa_radiance_rays(qa_ctx *ctx, uint64_t n, const float *origins, const float 
                      uint32_t *nsamples);
 int qa_camera_sample_rays_device(qa_ctx *ctx, int x0, int y0, int x1, int y1, int first, int count, float *d_origins, float *d_dirs,
                                  float *d_dx, float *d_dy, float *d_screen, uint32_t *d_stream, void *hip_stream);
+
+/* Irradiance queries: the light arriving at n surface points of the caller's, path-traced on the resident scene by the integrator
+ * of qa_render_region started from the points (qa_integrate_points: qa_kernel_body.h under POINTS; the opening comment of
+ * qaray_amd/csrc/hip/qa_irradiance.hip is the specification).  d_points, d_normals: [n][3] floats, world space, contiguous; the
+ * normal is used as given and NOT normalised.  Point q is shaded spp times as a hit there on a white diffuse material would be:
+ * the direct light at the point, one cosine-weighted bounce, the integrator as it stands behind it; a bounce that misses takes the
+ * environment.  kd * rgb is what a frame shows for a diffuse surface of colour kd at the point: the values are not scaled by pi,
+ * and every light weighs 1 / num_lights.  params: a qa_radiance_params whose flags are 0; d_stream: [n] uint32, point q draws from
+ * the random-number stream of pixel index d_stream[q] (NULL: q).  Outputs by point: d_rgb [n][3] the mean of the spp samples;
+ * d_nsamples [n] uint32 (may be NULL): zeroed first, spp for a finished point, 0 for one that qa_request_stop left unfinished.  A
+ * void point (a component of the point or the normal that is not finite, or normal (0, 0, 0)) draws no random number: its samples
+ * are black, and count.  The device form only enqueues on stream (NULL = the context's stream); qa_irradiance_points is the same
+ * from and to host memory through the queries' staging buffer (44 bytes per point), and synchronises.
+ * Ordered as a frame, as qa_radiance_rays_device: behind the context's last frame and last edit; qa_get_counters and
+ * qa_get_kernel_time move as for n * spp samples whose first segment casts nothing; frames before and after are untouched.
+ * Codes: QA_ENOSCENE without a scene; n == 0 is QA_OK and launches nothing; QA_EINVAL for n > 2^31 - 1 (and for
+ * (n + 63) / 64 * 64 >= 0xF0000000), a NULL point or normal array, rgb or params, spp < 1, max_bounce < 0, any flag bit;
+ * QA_EUNSUPPORTED for area lights with max_bounce > 7 and while photon maps are built.  A refused call writes nothing. */
+int qa_irradiance_points_device(qa_ctx *ctx, uint64_t n, const float *d_points, const float *d_normals, const uint32_t *d_stream,
+                                const qa_radiance_params *params, float *d_rgb, uint32_t *d_nsamples, void *stream);
+int qa_irradiance_points(qa_ctx *ctx, uint64_t n, const float *points, const float *normals, const uint32_t *stream_ids,
+                         const qa_radiance_params *params, float *rgb, uint32_t *nsamples);
 
 #ifdef __cplusplus
 }

@@ -1736,7 +1736,7 @@ struct Path {
 template <bool RES, bool LIGHTS, bool TEX, bool AREA, bool STATS, bool PHOTON = false>
 __global__ __launch_bounds__(QA_BLOCK, QA_WAVES_FOR(RES, LIGHTS)) void qa_integrate(const DScene sc, const RenderParams rp)
 {
-  constexpr bool RAYS = false;
+  constexpr bool RAYS = false, POINTS = false;
   const RayBatch rb = {};
 #include "qa_kernel_body.h"
 }
@@ -1757,7 +1757,18 @@ template <bool RES, bool LIGHTS, bool TEX, bool AREA>
 __global__ __launch_bounds__(QA_BLOCK, QA_WAVES_FOR(RES, LIGHTS)) void qa_integrate_rays(const DScene sc, const RenderParams rp, const RayBatch rb)
 {
   constexpr bool STATS = false, PHOTON = false;
-  constexpr bool RAYS = true;
+  constexpr bool RAYS = true, POINTS = false;
+#include "qa_kernel_body.h"
+}
+
+// qa_integrate_rays whose batch holds surface points and normals (rb.o, rb.d) in place of rays: a sample starts by shading its point
+// as a white diffuse surface and traces from there (qa_irradiance_points*; the opening comment of qa_irradiance.hip is the
+// specification): the third entry point over the body.  Instances: qa_irradiance.hip.
+template <bool RES, bool LIGHTS, bool TEX, bool AREA>
+__global__ __launch_bounds__(QA_BLOCK, QA_WAVES_FOR(RES, LIGHTS)) void qa_integrate_points(const DScene sc, const RenderParams rp, const RayBatch rb)
+{
+  constexpr bool STATS = false, PHOTON = false;
+  constexpr bool RAYS = true, POINTS = true;
 #include "qa_kernel_body.h"
 }
 

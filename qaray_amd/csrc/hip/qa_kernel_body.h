@@ -1,12 +1,16 @@
 // qa_kernel_body.h - the body of the per-lane megakernel (qa_kernel.h), included by its two entry points: qa_integrate and
-// qa_integrate_rays (qa_integrate_lastcast has a body of its own, qa_kernel_lastcast_body.h).  Not a header of its own: it is the text
-// of a function whose parameters are `sc` and `rp`, with the template parameters RES, LIGHTS, TEX, AREA, STATS, PHOTON, the constant
-// RAYS and the ray batch `rb` (RayBatch; empty unless RAYS) in scope.  (A text include rather than an inline function, as qa_kernel_cs_body.h: the shipped
+// qa_integrate_rays, and a third, qa_integrate_points (qa_integrate_lastcast has a body of its own, qa_kernel_lastcast_body.h).  Not a header of its own: it is the text
+// of a function whose parameters are `sc` and `rp`, with the template parameters RES, LIGHTS, TEX, AREA, STATS, PHOTON, the constants
+// RAYS and POINTS and the ray batch `rb` (RayBatch; empty unless RAYS) in scope.  (A text include rather than an inline function, as qa_kernel_cs_body.h: the shipped
 // instances keep exactly the code they had - through a function the kernel arguments are copied to scratch and the AREA variants
 // spill a thousand registers.)
 // RAYS (qa_integrate_rays; the opening comment of qa_radiance.hip is the specification): the paths start from the rays of `rb` and
 // not from the camera.  Only the work items (section A), the start of a sample (B), the first ray's miss (C) and the output sites
 // differ, each under `if constexpr (RAYS)`: with RAYS false the text below is the text the shipped kernels were compiled from.
+// POINTS (qa_integrate_points, RAYS with it; the opening comment of qa_irradiance.hip is the specification): `rb` holds surface
+// points and normals where a ray batch holds origins and directions, and a sample starts by shading its point instead of tracing
+// a first segment - one block ahead of the sweep of section C, under `if constexpr (POINTS)`; with POINTS false the text is
+// qa_integrate_rays'.
   extern __shared__ uint4 s_dyn[];
   SceneMem<RES> mem;
   mem.img = s_dyn;
@@ -306,6 +310,39 @@
           if (QA_GET_SIDX() == 0 && rp.depth) rp.depth[QA_GET_Q()] = QA_BIGFLOAT;
           done = true;
           sweep = false;
+        }
+      }
+      if constexpr (POINTS) {
+        // The first "hit" of a sample is the caller's point: path.ray holds (P, N) from section B, and nothing is traced to get there.
+        // Section D on a white diffuse material seen along the normal (V = N, front face): the lobe draw, the point's direct light
+        // (AREA: record 0 of the log, replayed last), one cosine-weighted bounce flagged fromDiffuse.  The bounce ray is swept below,
+        // in the same turn; a sample that spawns none (max_bounce 0, the roulette) ends here.
+        if (path.primary && sweep) {
+          const f3 p = path.ray.p, N = path.ray.d;
+          const uint4 white[6] = {make_uint4(0x3F800000u, 0x3F800000u, 0x3F800000u, 0u), make_uint4(0u, 0u, 0u, 0u), make_uint4(0u, 0u, 0u, 0u),
+                                  make_uint4(0u, 0u, 0u, 0u), make_uint4(0u, 0u, 0u, 0u), make_uint4(0u, 0u, 0u, 0u)};
+          const Surface sf = shadeSurface<false>(white, sc, tt, 0, N, N, true, th, path.bounce, path.fromDiffuse, rng);
+          QA_PUT_L(QA_GET_L() + QA_GET_T() * sf.emission)
+          if (LIGHTS && !AREA)
+            QA_PUT_L(QA_GET_L() + QA_GET_T() * directLight<RES, STATS>(mem, sc, p, N, N, sf.kd, sf.ks, sf.gloss, stack, cnt, rng))
+          if (AREA && nrec < QA_MAX_PATH) {
+            const f3 pT = QA_GET_T();
+            const float v[QA_REC_FLOATS] = {p.x, p.y, p.z, N.x, N.y, N.z, N.x, N.y, N.z, pT.x, pT.y, pT.z,
+                                            sf.kd.x, sf.kd.y, sf.kd.z, sf.ks.x, sf.ks.y, sf.ks.z, sf.gloss};
+            for (int f = 0; f < QA_REC_FLOATS; ++f) rec[(size_t) (nrec * QA_REC_FLOATS + f) * recStride] = v[f];
+            ++nrec;
+          }
+          if (sf.spawn) {
+            path.ray.d = normalize(sf.nextDir);
+            if (TEX) pathDiff.dx = pathDiff.dy = path.ray.d;
+            QA_PUT_T(QA_GET_T() * sf.bxdf)
+            path.bounce -= 1;
+            path.fromDiffuse = sf.nextFromDiffuse;
+            path.primary = false;
+          } else {
+            done = true;
+            sweep = false;
+          }
         }
       }
       if (sweep) {

@@ -53,7 +53,7 @@
 #include <cstring>
 
 #include "qa_firsthit.h"
-#include "qa_ctx.h"
+#include "qa_raybatch.h"
 
 static_assert(QA_RAYS_PER_SAMPLE == QA_RADIANCE_PER_SAMPLE && QA_RAYS_MISS_ENVIRONMENT == QA_RADIANCE_MISS_ENVIRONMENT, "RayBatch::flags are the C ABI's");
 
@@ -97,95 +97,10 @@ __global__ __launch_bounds__(QA_BLOCK) void qa_camera_sample_rays(const DCamera 
 
 }  // namespace qa
 
-// ---- the ten instances: the five shadings PickShading lists (qa_mega.hip), for scenes in LDS and in global memory
-typedef void (*RaysFn)(const DScene, const RenderParams, const RayBatch);
-template <bool RES>
-static RaysFn PickRaysShading(bool lights, bool tex, bool area)
-{
-  if (area) return tex ? (RaysFn) qa_integrate_rays<RES, true, true, true> : (RaysFn) qa_integrate_rays<RES, true, false, true>;
-  if (tex) return (RaysFn) qa_integrate_rays<RES, true, true, false>;
-  if (lights) return (RaysFn) qa_integrate_rays<RES, true, false, false>;
-  return (RaysFn) qa_integrate_rays<RES, false, false, false>;
-}
-// by the predicates SelectKernel hands to PickKernel: plan.resident, num_lights > 0, plan.textured, plan.area
-static RaysFn PickRays(const qa_ctx *c)
-{
-  const ScenePlan &p = c->plan;
-  const bool lights = c->ds.num_lights > 0;
-  return p.resident ? PickRaysShading<true>(lights, p.textured, p.area) : PickRaysShading<false>(lights, p.textured, p.area);
-}
+// ---- the ten instances: qa_integrate_rays<RES, LIGHTS, TEX, AREA> by the picker, the checks and the launch of qa_raybatch.h
+QA_DEFINE_RAYS_PICKER(PickRays, qa_integrate_rays)
 
-#define QA_MAX_RAYS 0x7FFFFFFFull
 #define QA_RADIANCE_FLAGS (QA_RADIANCE_PER_SAMPLE | QA_RADIANCE_MISS_ENVIRONMENT)
-
-// What the device and the host form refuse alike, before anything is sized by n.  QA_OK with n == 0: nothing to do
-static int RadianceChecks(qa_ctx *c, uint64_t n, bool rays, bool dx, bool dy, bool screen, const qa_radiance_params *p, bool rgb)
-{
-  if (!c->haveScene) return Fail(QA_ENOSCENE, "no scene uploaded");
-  if (n == 0) return QA_OK;
-  if (n > QA_MAX_RAYS) return Fail(QA_EINVAL, "more than 2^31 - 1 rays");
-  if ((n + 63) / 64 * 64 >= 0xF0000000ull) return Fail(QA_EINVAL, "too many rays for the 32-bit work counter");   // (every exiting wave adds 64 more)
-  if (!rays) return Fail(QA_EINVAL, "null ray array");
-  if (!rgb) return Fail(QA_EINVAL, "null rgb output");
-  if (!p) return Fail(QA_EINVAL, "null params");
-  if (p->spp < 1 || p->max_bounce < 0) return Fail(QA_EINVAL, "bad spp / bounce");
-  if (p->flags & ~QA_RADIANCE_FLAGS) return Fail(QA_EINVAL, "unknown flag bits");
-  if (dx != dy) return Fail(QA_EINVAL, "one differential array without the other");
-  if (c->plan.area && p->max_bounce + 1 > kMaxPath) return Fail(QA_EUNSUPPORTED, "area lights: maxBounce must be <= " + std::to_string(kMaxPath - 1));
-  if (c->photonReady) return Fail(QA_EUNSUPPORTED, "photon maps are built: no gathering instance of qa_integrate_rays is compiled (qa_photon_maps_clear first)");
-  if (c->plan.textured && c->ds.bgTexmap >= 0 && !screen && !(p->flags & QA_RADIANCE_MISS_ENVIRONMENT))
-    return Fail(QA_EINVAL, "the background has a texmap: give screen positions or QA_RADIANCE_MISS_ENVIRONMENT");
-  return QA_OK;
-}
-
-// One batch: the launch of a frame (qa_frame.hip LaunchSetup / LaunchFrame) without tiles, chunks, tile lists and photon maps
-static int Radiance(qa_ctx *c, uint64_t n, const RayBatch &rb, const qa_radiance_params &p, float *rgb, float *t, uint32_t *ns, hipStream_t s)
-{
-  HIP_TRY(c->lastFrame.WaitOn(s));
-  HIP_TRY(c->lastEdit.WaitOn(s));
-  if (ns) HIP_TRY(hipMemsetAsync(ns, 0, n * sizeof(uint32_t), s));   // rays skipped by a stop request read as "not finished"
-  unsigned int *work = c->dWork + c->workNext;
-  c->workNext = (c->workNext + 1) % qa_ctx::kCounterRing;
-  HIP_TRY(hipMemsetAsync(work, 0, sizeof(unsigned int), s));
-
-  RenderParams rp;
-  memset(&rp, 0, sizeof(rp));
-  rp.spp_min = rp.spp_max = p.spp;
-  rp.max_bounce = p.max_bounce;
-  rp.seed = p.seed;
-  rp.tile_row_step = 1;
-  rp.sync_samples = c->syncSamples < 0 ? c->plan.syncAuto : c->syncSamples;
-  rp.rgb = rgb; rp.depth = t; rp.ns = ns;
-  rp.work_counter = work;
-  rp.stop_flag = c->dStopAlias;
-  rp.counters = c->dCounters;
-  rp.num_chunks = 1;
-
-  const Integrator &mega = c->integ[kMega];   // the frames' LDS layout and stack depth (the tile lists' room stays unused)
-  DScene ds = c->ds;
-  ds.stackDepth = mega.stackDepth;
-  ds.walkZeroTerms = c->optWalkZeroTerms;
-  ds.lastCast = 0;
-  ds.lastCastGlow = c->plan.lastCastGlow;
-
-  const RaysFn fn = PickRays(c);
-  // persistent grid of what is resident at once, at most 8 workgroups per CU: the area-light log is sized for that (EnsurePlanSlab)
-  const long long needBlocks = (long long) ((n + QA_BLOCK - 1) / QA_BLOCK);
-  const long long blocks = std::max<long long>(1, std::min<long long>(needBlocks, (long long) c->numCUs * OccupancyBlocks((KernelFn) fn, mega.ldsBytes)));
-
-  EventPair ev;
-  if (!c->freeEvents.empty()) { ev = c->freeEvents.back(); c->freeEvents.pop_back(); }
-  else { HIP_TRY(hipEventCreate(&ev.a)); HIP_TRY(hipEventCreate(&ev.b)); }
-  HIP_TRY(hipEventRecord(ev.a, s));
-  hipLaunchKernelGGL(fn, dim3((unsigned) blocks), dim3(QA_BLOCK), (unsigned) mega.ldsBytes, s, ds, rp, rb);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(c->lastFrame.Record(s));
-  HIP_TRY(hipEventRecord(ev.b, s));
-  c->pending.push_back(ev);
-  c->launches++;
-  if (c->pending.size() > 256) return DrainEvents(c);
-  return QA_OK;
-}
 
 extern "C" {
 
@@ -204,17 +119,17 @@ int qa_radiance_rays_device(qa_ctx *c, uint64_t n, const float *d_origins, const
                             uint32_t *d_ns, void *hip_stream)
 {
   if (int rc = Enter(c)) return rc;
-  if (int rc = RadianceChecks(c, n, d_origins && d_dirs, d_dx != nullptr, d_dy != nullptr, d_screen != nullptr, params, d_rgb != nullptr)) return rc;
+  if (int rc = RayBatchChecks(c, n, d_origins && d_dirs, d_dx != nullptr, d_dy != nullptr, d_screen != nullptr, params, d_rgb != nullptr, QA_RADIANCE_FLAGS, true)) return rc;
   if (n == 0) return QA_OK;
   const RayBatch rb = {d_origins, d_dirs, d_dx, d_dy, d_screen, d_stream, (uint32_t) n, params->flags};
-  return Radiance(c, n, rb, *params, d_rgb, d_t, d_ns, StreamOf(c, hip_stream));
+  return LaunchRayBatch(c, PickRays(c), n, rb, *params, d_rgb, d_t, d_ns, StreamOf(c, hip_stream));
 }
 
 int qa_radiance_rays(qa_ctx *c, uint64_t n, const float *origins, const float *dirs, const float *dx, const float *dy, const float *screen,
                      const uint32_t *stream, const qa_radiance_params *params, float *rgb, float *t, uint32_t *ns)
 {
   if (int rc = Enter(c)) return rc;
-  if (int rc = RadianceChecks(c, n, origins && dirs, dx != nullptr, dy != nullptr, screen != nullptr, params, rgb != nullptr)) return rc;
+  if (int rc = RayBatchChecks(c, n, origins && dirs, dx != nullptr, dy != nullptr, screen != nullptr, params, rgb != nullptr, QA_RADIANCE_FLAGS, true)) return rc;
   if (n == 0) return QA_OK;
   // staging, in floats per ray: [rgb 3 | t 1 | ns 1 | stream 1] then per record [origins 3 | dirs 3 | dx 3 | dy 3 | screen 2]
   const uint64_t r = n * ((params->flags & QA_RADIANCE_PER_SAMPLE) ? (uint64_t) params->spp : 1ull);
@@ -231,7 +146,7 @@ int qa_radiance_rays(qa_ctx *c, uint64_t n, const float *origins, const float *d
   if (screen) HIP_TRY(hipMemcpyAsync(dScreen, screen, r * 8, hipMemcpyHostToDevice, c->stream));
   if (stream) HIP_TRY(hipMemcpyAsync(dStream, stream, n * 4, hipMemcpyHostToDevice, c->stream));
   const RayBatch rb = {dO, dD, dx ? dDx : nullptr, dx ? dDy : nullptr, screen ? dScreen : nullptr, stream ? dStream : nullptr, (uint32_t) n, params->flags};
-  if (int rc = Radiance(c, n, rb, *params, dRgb, t ? dT : nullptr, ns ? dNs : nullptr, c->stream)) return rc;
+  if (int rc = LaunchRayBatch(c, PickRays(c), n, rb, *params, dRgb, t ? dT : nullptr, ns ? dNs : nullptr, c->stream)) return rc;
   HIP_TRY(hipMemcpyAsync(rgb, dRgb, n * 12, hipMemcpyDeviceToHost, c->stream));
   if (t) HIP_TRY(hipMemcpyAsync(t, dT, n * 4, hipMemcpyDeviceToHost, c->stream));
   if (ns) HIP_TRY(hipMemcpyAsync(ns, dNs, n * 4, hipMemcpyDeviceToHost, c->stream));

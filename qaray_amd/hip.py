@@ -430,6 +430,8 @@ def lib():
         L.qa_radiance_rays_device.argtypes = [C.c_void_p, C.c_uint64] + [C.c_void_p] * 6 + [C.POINTER(RadianceParams)] + [C.c_void_p] * 4
         L.qa_radiance_rays.argtypes = [C.c_void_p, C.c_uint64] + [C.c_void_p] * 6 + [C.POINTER(RadianceParams)] + [C.c_void_p] * 3
         L.qa_camera_sample_rays_device.argtypes = [C.c_void_p] + [C.c_int] * 6 + [C.c_void_p] * 7
+        L.qa_irradiance_points_device.argtypes = [C.c_void_p, C.c_uint64] + [C.c_void_p] * 3 + [C.POINTER(RadianceParams)] + [C.c_void_p] * 3
+        L.qa_irradiance_points.argtypes = [C.c_void_p, C.c_uint64] + [C.c_void_p] * 3 + [C.POINTER(RadianceParams)] + [C.c_void_p] * 2
         L.qa_scene_edit_camera.argtypes = [C.c_void_p, C.c_void_p]
         for name in ("qa_scene_edit_lights", "qa_scene_edit_materials", "qa_scene_edit_instances"):
             getattr(L, name).argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
@@ -1669,6 +1671,59 @@ class Context:
                 t.record_stream(cur)
         return out
 
+    def bake_light(self, node, texmap, spp=64, max_bounce=5, scale=1.0, mtl=-1, dilate=2, seed=DEFAULT_SEED, stream=None):
+        """The light arriving at node `node` baked into the file texture of texmap `texmap`, in place - a light map, composed as
+        bake_ao composes its map: the map of the texture's texels (bake_texels_device at the texture's size, through the texmap),
+        irradiance_points_device at the texels' points and normals with stream_ids = iy * W + ix (an uncovered texel's normal is
+        zero: a void point, black), ao_grey_device of light * scale - linear bytes, which the texel table decodes by / 255
+        (texels_host) - uncovered texels keep the texture's bytes as they stand, then take their nearest covered neighbour's within
+        `dilate` texels (bake_dilate_device; 0: no fill); the picture then replaces the texture's texels (edit_texels).  The baked
+        value is what a frame shows for a white diffuse surface there (kd * light for another colour): not scaled by pi, every
+        light weighted 1 / num_lights; values above 1 / scale clip.  The limit: paths that return to the node read its texture as
+        it stands during the bake, not the light map being made.  All on one stream, as bake_ao.  -> dict of CUDA tensors light
+        [H,W,3] f32 (0 where uncovered), face [H,W] i32, rgb8 [H,W,3] u8 (what the texture now holds).  QA_EINVAL for a texmap
+        without a file texture."""
+        import torch
+        dev = torch.device("cuda", self.device_id)
+        blob = self.download_scene()
+        maps = blob_table(blob, "texmaps")
+        if texmap is None or not 0 <= int(texmap) < len(maps) or int(maps[int(texmap)]["texture"]) < 0:
+            raise HipError(-1, "bake_light: the texmap is out of range or has no texture")
+        tex = int(maps[int(texmap)]["texture"])
+        rec = blob_table(blob, "textures")[tex]
+        if int(rec["type"]) != QA_TEX_FILE:
+            raise HipError(-1, "bake_light: the texmap's texture is not a file texture")
+        W, H = int(rec["width"]), int(rec["height"])
+        cur = torch.cuda.current_stream(dev)   # (the streams: see bake_ao)
+        if stream:
+            ts = torch.cuda.ExternalStream(int(stream), device=dev)
+        else:
+            if self._bake_stream is None:
+                self._bake_stream = torch.cuda.Stream(dev)
+            ts = self._bake_stream
+            ts.wait_stream(cur)
+        sptr = ts.cuda_stream
+        with torch.cuda.stream(ts):
+            current = torch.from_numpy(blob_texels(blob, tex).copy()).to(dev)
+            m = self.bake_texels_device(node, W, H, texmap=texmap, mtl=mtl, point=torch.empty((H, W, 3), dtype=torch.float32, device=dev),
+                                        normal=torch.empty((H, W, 3), dtype=torch.float32, device=dev),
+                                        face=torch.empty((H, W), dtype=torch.int32, device=dev), stream=sptr)
+            ids = torch.arange(H * W, dtype=torch.int32, device=dev)
+            light = self.irradiance_points_device(m["point"].reshape(-1, 3), m["normal"].reshape(-1, 3), spp, max_bounce, seed, ids,
+                                                  stream=sptr)[0].reshape(H, W, 3)
+            covered = m["face"] >= 0
+            grey = self.ao_grey_device(light * float(scale), stream=sptr)
+            rgb8 = torch.where(covered.unsqueeze(2), grey, current).contiguous()
+            if int(dilate) > 0:
+                rgb8 = self.bake_dilate_device(rgb8, m["face"], int(dilate), stream=sptr)
+            self.edit_texels(tex, rgb8, stream=sptr)
+        out = {"light": light, "face": m["face"], "rgb8": rgb8}
+        if not stream:
+            cur.wait_stream(ts)
+            for t in out.values():
+                t.record_stream(cur)
+        return out
+
     def rgba_device(self, rgb, backdrop, coverage, ns, srgb=True, out=None, stream=None):
         """qa_matte_rgba_device: the straight-alpha 8-bit RGBA picture of a frame (rgb float32 [h,w,3] and ns int32 / uint32 [h,w] as
         render_region_device fills them, backdrop and coverage as matte_device(region, spp, ns=ns) does), what a PNG stores: the
@@ -1848,6 +1903,51 @@ class Context:
         _check(lib().qa_radiance_rays(self._h, n, ptr(o), ptr(arrs["dirs"]), ptr(arrs["dx"]), ptr(arrs["dy"]), ptr(arrs["screen"]), ptr(sid),
                                       C.byref(p), ptr(rgb), ptr(t), ptr(ns)))
         return rgb, t, ns
+
+    # -- irradiance queries (qa_irradiance.hip) ----------------------------------------------------
+    def irradiance_points_device(self, points, normals, spp=16, max_bounce=5, seed=DEFAULT_SEED, stream_ids=None, rgb=None, ns=None, stream=None):
+        """qa_irradiance_points_device: the light arriving at n surface points of the caller's (lightmap texels, mesh vertices),
+        path-traced by the renderer's integrator started at the points, spp samples each: the direct light at the point, one
+        cosine-weighted bounce, and the integrator as it stands behind it.  kd * rgb is what a frame shows for a diffuse surface
+        of colour kd there (not scaled by pi; every light weighs 1 / num_lights).  points, normals: float32 [n,3] contiguous CUDA
+        tensors, world space, the normals of unit length (used as given).  stream_ids: int32 or uint32 [n], the random-number
+        stream of each point (None: the point's index).  A point with a component that is not finite, or a zero normal, is black.
+        Outputs (given, or allocated): rgb float32 [n,3], ns int32 [n] (spp for a finished point) -> (rgb, ns).  Only enqueues
+        (see render_region_device for the stream)."""
+        import torch
+        dev = torch.device("cuda", self.device_id)
+        if not isinstance(points, torch.Tensor):
+            raise TypeError(f"points: a torch tensor is expected, not {type(points).__name__}")
+        n = _ray_count("points", points)
+        _ray_tensor("points", points, (n, 3), torch.float32, dev)
+        _ray_tensor("normals", normals, (n, 3), torch.float32, dev)
+        if stream_ids is not None:
+            if isinstance(stream_ids, torch.Tensor) and stream_ids.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)):
+                raise TypeError(f"stream_ids: dtype torch.int32 or torch.uint32 is expected, not {stream_ids.dtype}")
+            _ray_tensor("stream_ids", stream_ids, (n,), getattr(stream_ids, "dtype", None), dev)
+        rgb = torch.empty((n, 3), dtype=torch.float32, device=dev) if rgb is None else rgb
+        ns = torch.empty((n,), dtype=torch.int32, device=dev) if ns is None else ns
+        _ray_tensor("rgb", rgb, (n, 3), torch.float32, dev)
+        _ray_tensor("ns", ns, (n,), torch.int32, dev)
+        p = RadianceParams.of(spp, max_bounce, seed)
+        sptr = self._stream_arg(stream, points)
+        ptr = lambda a: None if a is None else (a.data_ptr() or None)   # noqa: E731
+        _check(lib().qa_irradiance_points_device(self._h, n, ptr(points), ptr(normals), ptr(stream_ids), C.byref(p), ptr(rgb), ptr(ns), sptr))
+        return rgb, ns
+
+    def irradiance_points(self, points, normals, spp=16, max_bounce=5, seed=DEFAULT_SEED, stream_ids=None):
+        """qa_irradiance_points: irradiance_points_device from and to host memory.  points, normals: [n,3], converted to float32;
+        stream_ids: [n] integers below 2^32 or None -> (rgb [n,3] f32, ns [n] u32) numpy arrays.  Synchronises."""
+        p, nr, n = _ray_arrays(points, normals)
+        sid = None
+        if stream_ids is not None:
+            sid = np.ascontiguousarray(stream_ids, dtype=np.uint32)
+            if sid.shape != (n,):
+                raise ValueError(f"stream_ids: shape ({n},) is expected, not {sid.shape}")
+        rgb, ns = np.zeros((n, 3), np.float32), np.zeros(n, np.uint32)
+        _check(lib().qa_irradiance_points(self._h, n, p.ctypes.data, nr.ctypes.data, _ptr(sid), C.byref(RadianceParams.of(spp, max_bounce, seed)),
+                                          rgb.ctypes.data, ns.ctypes.data))
+        return rgb, ns
 
     def camera_sample_rays_device(self, region, first=0, count=1, outputs=CAMERA_SAMPLE_OUTPUTS, stream=None, **given):
         """qa_camera_sample_rays_device: samples [first, first + count) of the camera rays of the pixels of a region, exactly as a
