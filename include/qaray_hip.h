@@ -950,6 +950,12 @@ int qa_test_reproject_moments_host(const qa_camera *prev_cam, const qa_camera *c
  *                                 n records, every sample of ray q starts from record q
  *     QA_RADIANCE_MISS_ENVIRONMENT a first ray that misses takes the environment by direction, as a bounce ray does; without it
  *                                 the background, as a frame's camera ray does
+ *     QA_RADIANCE_PHOTON_MAPS     (bit 3; qa_irradiance_points* take it too) the batch runs with Scene::usePhotonMap = true, exactly
+ *                                 as a frame does once qa_photon_maps_build has run: diffuse hits gather from the caustics map, and
+ *                                 from the photon map behind a diffuse bounce (qa_integrate_rays_pm / qa_integrate_points_pm).  The
+ *                                 gathers draw no random number.  Opt-in: a frame changes silently when maps are built, a batch says
+ *                                 what it wants - without the flag a context whose maps are built refuses the batch
+ *                                 (QA_EUNSUPPORTED), with it a context without maps does (QA_ENOSCENE, "no photon maps built")
  *   qa_radiance_params_default  spp 1, max_bounce 5, seed 0x51A7A7, flags 0.  Needs no context.
  *   qa_radiance_rays_device     d_dx, d_dy: the ray's differential directions for the texture filter, both or neither (NULL: a ray
  *                               of no width, the first hit's textures are looked up unfiltered); d_screen: [records][2] the position
@@ -976,10 +982,11 @@ int qa_test_reproject_moments_host(const qa_camera *prev_cam, const qa_camera *c
  * for (n + 63) / 64 * 64 >= 0xF0000000: the work counter is 32 bits), a NULL ray array, rgb or params, spp < 1, max_bounce < 0,
  * unknown flag bits, one of d_dx / d_dy without the other, a textured background without d_screen and without
  * QA_RADIANCE_MISS_ENVIRONMENT; QA_EUNSUPPORTED for area lights with max_bounce > 7 (as qa_render_region) and while photon maps
- * are built (no gathering instance is compiled).  A refused call writes nothing.  Every mesh is walked per lane, rays are taken
- * in the caller's order. */
+ * are built unless QA_RADIANCE_PHOTON_MAPS is set; QA_ENOSCENE for QA_RADIANCE_PHOTON_MAPS without maps.  A refused call writes
+ * nothing.  Every mesh is walked per lane, rays are taken in the caller's order. */
 #define QA_RADIANCE_PER_SAMPLE       1u
 #define QA_RADIANCE_MISS_ENVIRONMENT 2u
+#define QA_RADIANCE_PHOTON_MAPS      8u
 typedef struct qa_radiance_params { int spp, max_bounce; uint32_t seed, flags; } qa_radiance_params;
 int qa_radiance_params_default(qa_radiance_params *params);
 int qa_radiance_rays_device(qa_ctx *ctx, uint64_t n, const float *d_origins, const float *d_dirs, const float *d_dx, const float *d_dy,
@@ -997,7 +1004,9 @@ int qa_camera_sample_rays_device(qa_ctx *ctx, int x0, int y0, int x1, int y1, in
  * normal is used as given and NOT normalised.  Point q is shaded spp times as a hit there on a white diffuse material would be:
  * the direct light at the point, one cosine-weighted bounce, the integrator as it stands behind it; a bounce that misses takes the
  * environment.  kd * rgb is what a frame shows for a diffuse surface of colour kd at the point: the values are not scaled by pi,
- * and every light weighs 1 / num_lights.  params: a qa_radiance_params whose flags are 0; d_stream: [n] uint32, point q draws from
+ * and every light weighs 1 / num_lights.  params: a qa_radiance_params whose flags are 0 or QA_RADIANCE_PHOTON_MAPS (the point then
+ * gathers from the caustics map ahead of its direct light, and the paths behind its bounce gather as a frame's do: the opening
+ * comment of qaray_amd/csrc/hip/qa_irradiance_pm.hip); d_stream: [n] uint32, point q draws from
  * the random-number stream of pixel index d_stream[q] (NULL: q).  Outputs by point: d_rgb [n][3] the mean of the spp samples;
  * d_nsamples [n] uint32 (may be NULL): zeroed first, spp for a finished point, 0 for one that qa_request_stop left unfinished.  A
  * void point (a component of the point or the normal that is not finite, or normal (0, 0, 0)) draws no random number: its samples
@@ -1006,8 +1015,9 @@ int qa_camera_sample_rays_device(qa_ctx *ctx, int x0, int y0, int x1, int y1, in
  * Ordered as a frame, as qa_radiance_rays_device: behind the context's last frame and last edit; qa_get_counters and
  * qa_get_kernel_time move as for n * spp samples whose first segment casts nothing; frames before and after are untouched.
  * Codes: QA_ENOSCENE without a scene; n == 0 is QA_OK and launches nothing; QA_EINVAL for n > 2^31 - 1 (and for
- * (n + 63) / 64 * 64 >= 0xF0000000), a NULL point or normal array, rgb or params, spp < 1, max_bounce < 0, any flag bit;
- * QA_EUNSUPPORTED for area lights with max_bounce > 7 and while photon maps are built.  A refused call writes nothing. */
+ * (n + 63) / 64 * 64 >= 0xF0000000), a NULL point or normal array, rgb or params, spp < 1, max_bounce < 0, any other flag bit;
+ * QA_EUNSUPPORTED for area lights with max_bounce > 7 and while photon maps are built unless QA_RADIANCE_PHOTON_MAPS is set;
+ * QA_ENOSCENE for QA_RADIANCE_PHOTON_MAPS without maps.  A refused call writes nothing. */
 int qa_irradiance_points_device(qa_ctx *ctx, uint64_t n, const float *d_points, const float *d_normals, const uint32_t *d_stream,
                                 const qa_radiance_params *params, float *d_rgb, uint32_t *d_nsamples, void *stream);
 int qa_irradiance_points(qa_ctx *ctx, uint64_t n, const float *points, const float *normals, const uint32_t *stream_ids,

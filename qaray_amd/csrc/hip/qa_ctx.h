@@ -276,6 +276,21 @@ int CheckFrame(qa_ctx *c, const FrameArgs &a);
 int LaunchSetup(qa_ctx *c, Launch &L, const FrameArgs &a, int ownRows, unsigned int *work, bool resume);
 int LaunchFrame(qa_ctx *c, Launch &L, bool staged, hipStream_t s);
 int DrainEvents(qa_ctx *c);
+// Scene::usePhotonMap for one launch: the tables of both maps and the heap slab, as qa_photon_maps_build left them (c->photonReady),
+// for the frames' PHOTON variants (LaunchSetup) and the gathering batch kernels (qa_raybatch.h)
+inline void SetPhotonParams(const qa_ctx *c, RenderParams &rp)
+{
+  for (int k = 0; k < 2; ++k) {
+    const qa_photon_map_params &mp = k ? c->photonParams.caustics : c->photonParams.photon;
+    rp.pm[k].node = static_cast<const uint4 *>(c->dPmTables[k][0]);
+    rp.pm[k].dir = static_cast<const float4 *>(c->dPmTables[k][1]);
+    rp.pm[k].power = static_cast<const float4 *>(c->dPmTables[k][2]);
+    rp.pm[k].count = mp.size;
+    rp.pm[k].half = (int32_t) (mp.size / 2) - 1;   // halfStoredPhotons = (photons.size() - 1) / 2 - 1, cyPhotonMap.h:291
+    rp.pm[k].radius = mp.radius;
+  }
+  rp.heap = static_cast<uint2 *>(c->dHeap);
+}
 // qa_capi.hip, for the edits that live elsewhere (qa_texture_edit.hip): bytes of the pinned edit ring; the waits an edit's device
 // work begins with (and statBytesCopied = 0); what every edit ends with
 int EditStageReserve(qa_ctx *c, size_t need, unsigned char **at);

@@ -180,18 +180,7 @@ int LaunchSetup(qa_ctx *c, Launch &L, const FrameArgs &a, int ownRows, unsigned 
   const bool pmOn = c->photonReady;
   memset(rp.pm, 0, sizeof(rp.pm));
   rp.heap = nullptr;
-  if (pmOn) {
-    for (int k = 0; k < 2; ++k) {
-      const qa_photon_map_params &mp = k ? c->photonParams.caustics : c->photonParams.photon;
-      rp.pm[k].node = static_cast<const uint4 *>(c->dPmTables[k][0]);
-      rp.pm[k].dir = static_cast<const float4 *>(c->dPmTables[k][1]);
-      rp.pm[k].power = static_cast<const float4 *>(c->dPmTables[k][2]);
-      rp.pm[k].count = mp.size;
-      rp.pm[k].half = (int32_t) (mp.size / 2) - 1;   // halfStoredPhotons = (photons.size() - 1) / 2 - 1, cyPhotonMap.h:291
-      rp.pm[k].radius = mp.radius;
-    }
-    rp.heap = static_cast<uint2 *>(c->dHeap);
-  }
+  if (pmOn) SetPhotonParams(c, rp);
   const bool stats = a.flags & QA_RENDER_STATS, cs = c->integ[kCs].fn && !pmOn && !stats;
   // (the textured cooperative variants carry the chunk code already: a progressive pass runs them as they are)
   L.slot = PickSlot(pmOn, stats, cs, resume && !c->plan.textured);

@@ -31,8 +31,10 @@
 //   Outputs, indexed by point: rgb [n][3] the mean over the spp samples (the body's own running mean); ns [n] uint32 (optional) the
 //     samples taken: zeroed first, spp once the point is finished - a point that a stop request left unfinished reads 0, and its
 //     rgb is not written.  There is no t output.
-//   spp is fixed: no adaptive stop.  The camera is not read.  Area lights: max_bounce <= 7, as for a frame.  Photon maps: a
-//     context whose maps are built is refused (QA_EUNSUPPORTED): no gathering instance is compiled.  flags must be 0.
+//   spp is fixed: no adaptive stop.  The camera is not read.  Area lights: max_bounce <= 7, as for a frame.  flags must be 0 or
+//     QA_RADIANCE_PHOTON_MAPS.  Photon maps: with the flag the batch runs with Scene::usePhotonMap = true on the gathering instances
+//     of qa_irradiance_pm.hip (whose opening comment specifies the gather at the point); without it a context whose maps are built
+//     is refused (QA_EUNSUPPORTED), with it one without maps (QA_ENOSCENE).
 //   State: as qa_radiance_rays_device - ordered as a frame is (behind the context's last frame and last edit, one at a time per
 //     context), adds to qa_get_counters (samples += n * spp and the casts of its paths: a sample's first segment casts nothing) and
 //     to qa_get_kernel_time (one launch), and leaves qa_get_kernel_name, progressive frames and the frames' slabs alone.
@@ -51,8 +53,10 @@
 // ---- the ten instances: qa_integrate_points<RES, LIGHTS, TEX, AREA> by the picker, the checks and the launch of qa_raybatch.h
 QA_DEFINE_RAYS_PICKER(PickPoints, qa_integrate_points)
 
-// (the checks are the rays' with no differentials or screen positions, no flag known and no first segment that could miss into a
+// (the checks are the rays' with no differentials or screen positions, no flag known but QA_RADIANCE_PHOTON_MAPS - which picks the
+// gathering family, qa_irradiance_pm.hip, and never reaches RayBatch::flags - and no first segment that could miss into a
 // background image)
+static RaysFn PickFor(const qa_ctx *c, const qa_radiance_params *p) { return WantsPhotonMaps(p) ? PickPointsPm(c) : PickPoints(c); }
 
 extern "C" {
 
@@ -60,17 +64,17 @@ int qa_irradiance_points_device(qa_ctx *c, uint64_t n, const float *d_points, co
                                 const qa_radiance_params *params, float *d_rgb, uint32_t *d_nsamples, void *stream)
 {
   if (int rc = Enter(c)) return rc;
-  if (int rc = RayBatchChecks(c, n, d_points && d_normals, false, false, false, params, d_rgb != nullptr, 0u, false)) return rc;
+  if (int rc = RayBatchChecks(c, n, d_points && d_normals, false, false, false, params, d_rgb != nullptr, QA_RADIANCE_PHOTON_MAPS, false)) return rc;
   if (n == 0) return QA_OK;
   const RayBatch rb = {d_points, d_normals, nullptr, nullptr, nullptr, d_stream, (uint32_t) n, 0u};
-  return LaunchRayBatch(c, PickPoints(c), n, rb, *params, d_rgb, nullptr, d_nsamples, StreamOf(c, stream));
+  return LaunchRayBatch(c, PickFor(c, params), n, rb, *params, d_rgb, nullptr, d_nsamples, StreamOf(c, stream));
 }
 
 int qa_irradiance_points(qa_ctx *c, uint64_t n, const float *points, const float *normals, const uint32_t *stream_ids, const qa_radiance_params *params,
                          float *rgb, uint32_t *nsamples)
 {
   if (int rc = Enter(c)) return rc;
-  if (int rc = RayBatchChecks(c, n, points && normals, false, false, false, params, rgb != nullptr, 0u, false)) return rc;
+  if (int rc = RayBatchChecks(c, n, points && normals, false, false, false, params, rgb != nullptr, QA_RADIANCE_PHOTON_MAPS, false)) return rc;
   if (n == 0) return QA_OK;
   // staging, in floats per point: [rgb 3 | ns 1 | stream 1 | points 3 | normals 3]
   HIP_TRY(c->stageQuery.Reserve((size_t) n * 11 * sizeof(float)));
@@ -81,7 +85,7 @@ int qa_irradiance_points(qa_ctx *c, uint64_t n, const float *points, const float
   HIP_TRY(hipMemcpyAsync(dN, normals, n * 12, hipMemcpyHostToDevice, c->stream));
   if (stream_ids) HIP_TRY(hipMemcpyAsync(dStream, stream_ids, n * 4, hipMemcpyHostToDevice, c->stream));
   const RayBatch rb = {dP, dN, nullptr, nullptr, nullptr, stream_ids ? dStream : nullptr, (uint32_t) n, 0u};
-  if (int rc = LaunchRayBatch(c, PickPoints(c), n, rb, *params, dRgb, nullptr, nsamples ? dNs : nullptr, c->stream)) return rc;
+  if (int rc = LaunchRayBatch(c, PickFor(c, params), n, rb, *params, dRgb, nullptr, nsamples ? dNs : nullptr, c->stream)) return rc;
   HIP_TRY(hipMemcpyAsync(rgb, dRgb, n * 12, hipMemcpyDeviceToHost, c->stream));
   if (nsamples) HIP_TRY(hipMemcpyAsync(nsamples, dNs, n * 4, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));

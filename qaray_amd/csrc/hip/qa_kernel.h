@@ -1772,4 +1772,24 @@ __global__ __launch_bounds__(QA_BLOCK, QA_WAVES_FOR(RES, LIGHTS)) void qa_integr
 #include "qa_kernel_body.h"
 }
 
+// The gathering siblings of the two batch kernels (QA_RADIANCE_PHOTON_MAPS: Scene::usePhotonMap for a batch, as qa_integrate's
+// PHOTON variants for a frame): kernels of their own names, so that every instance above keeps its symbol and its code.  A map
+// needs a point light, so LIGHTS is true; rp.pm and rp.heap are filled as for a frame (qa_ctx.h SetPhotonParams).  Instances:
+// qa_radiance_pm.hip, qa_irradiance_pm.hip (whose opening comment specifies the gather at the point itself).
+template <bool RES, bool TEX, bool AREA>
+__global__ __launch_bounds__(QA_BLOCK, QA_WAVES_FOR(RES, true)) void qa_integrate_rays_pm(const DScene sc, const RenderParams rp, const RayBatch rb)
+{
+  constexpr bool LIGHTS = true, STATS = false, PHOTON = true;
+  constexpr bool RAYS = true, POINTS = false;
+#include "qa_kernel_body.h"
+}
+
+template <bool RES, bool TEX, bool AREA>
+__global__ __launch_bounds__(QA_BLOCK, QA_WAVES_FOR(RES, true)) void qa_integrate_points_pm(const DScene sc, const RenderParams rp, const RayBatch rb)
+{
+  constexpr bool LIGHTS = true, STATS = false, PHOTON = true;
+  constexpr bool RAYS = true, POINTS = true;
+#include "qa_kernel_body.h"
+}
+
 }  // namespace qa

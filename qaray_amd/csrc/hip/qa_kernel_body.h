@@ -323,6 +323,14 @@
                                   make_uint4(0u, 0u, 0u, 0u), make_uint4(0u, 0u, 0u, 0u), make_uint4(0u, 0u, 0u, 0u)};
           const Surface sf = shadeSurface<false>(white, sc, tt, 0, N, N, true, th, path.bounce, path.fromDiffuse, rng);
           QA_PUT_L(QA_GET_L() + QA_GET_T() * sf.emission)
+          if constexpr (PHOTON) {
+            // section D's gather at the point itself (qa_integrate_points_pm): the point's path has fromDiffuse = false, so the
+            // caustics map alone, ahead of the point's direct light or its log record; the heap is the lane's, as in section D
+            if (sf.selDiffuse) {
+              uint2 *heap = rp.heap + ((size_t) blockIdx.x * QA_BLOCK + threadIdx.x) * (QA_PHOTON_GATHER + 1);
+              QA_PUT_L(QA_GET_L() + QA_GET_T() * photonGather(rp.pm[1], p, N, N, sf.kd, sf.ks, sf.gloss, stack, heap))
+            }
+          }
           if (LIGHTS && !AREA)
             QA_PUT_L(QA_GET_L() + QA_GET_T() * directLight<RES, STATS>(mem, sc, p, N, N, sf.kd, sf.ks, sf.gloss, stack, cnt, rng))
           if (AREA && nrec < QA_MAX_PATH) {

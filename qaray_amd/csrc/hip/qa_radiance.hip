@@ -30,8 +30,9 @@
 //     on a miss and for a void ray; ns [n] uint32 (optional) the samples taken: zeroed first, spp once the ray is finished - a ray
 //     that a stop request left unfinished reads 0, and its rgb is not written.
 //   spp is fixed: no adaptive stop (the running variance of a batch ray stops nothing).
-//   The camera is not read.  Area lights: max_bounce <= 7, as for a frame.  Photon maps: a context whose maps are built is refused
-//     (QA_EUNSUPPORTED): no gathering instance is compiled.
+//   The camera is not read.  Area lights: max_bounce <= 7, as for a frame.  Photon maps: with QA_RADIANCE_PHOTON_MAPS the batch runs
+//     with Scene::usePhotonMap = true on the gathering instances of qa_radiance_pm.hip (whose opening comment says the rest); without
+//     the flag a context whose maps are built is refused (QA_EUNSUPPORTED), with it one without maps (QA_ENOSCENE).
 //   State: the call is ordered as a frame is (behind the context's last frame and last edit, one at a time per context), adds to
 //     qa_get_counters (samples += n * spp, the casts of its paths) and to qa_get_kernel_time (one launch) as a frame does, and
 //     leaves qa_get_kernel_name, progressive frames and the frames' slabs alone.
@@ -100,7 +101,10 @@ __global__ __launch_bounds__(QA_BLOCK) void qa_camera_sample_rays(const DCamera 
 // ---- the ten instances: qa_integrate_rays<RES, LIGHTS, TEX, AREA> by the picker, the checks and the launch of qa_raybatch.h
 QA_DEFINE_RAYS_PICKER(PickRays, qa_integrate_rays)
 
-#define QA_RADIANCE_FLAGS (QA_RADIANCE_PER_SAMPLE | QA_RADIANCE_MISS_ENVIRONMENT)
+// (QA_RADIANCE_PHOTON_MAPS: the batch runs on the gathering family, qa_radiance_pm.hip; RayBatch::flags keeps the two bits it knows)
+#define QA_RADIANCE_FLAGS (QA_RADIANCE_PER_SAMPLE | QA_RADIANCE_MISS_ENVIRONMENT | QA_RADIANCE_PHOTON_MAPS)
+#define QA_RAYBATCH_FLAGS (QA_RADIANCE_PER_SAMPLE | QA_RADIANCE_MISS_ENVIRONMENT)
+static RaysFn PickFor(const qa_ctx *c, const qa_radiance_params *p) { return WantsPhotonMaps(p) ? PickRaysPm(c) : PickRays(c); }
 
 extern "C" {
 
@@ -121,8 +125,8 @@ int qa_radiance_rays_device(qa_ctx *c, uint64_t n, const float *d_origins, const
   if (int rc = Enter(c)) return rc;
   if (int rc = RayBatchChecks(c, n, d_origins && d_dirs, d_dx != nullptr, d_dy != nullptr, d_screen != nullptr, params, d_rgb != nullptr, QA_RADIANCE_FLAGS, true)) return rc;
   if (n == 0) return QA_OK;
-  const RayBatch rb = {d_origins, d_dirs, d_dx, d_dy, d_screen, d_stream, (uint32_t) n, params->flags};
-  return LaunchRayBatch(c, PickRays(c), n, rb, *params, d_rgb, d_t, d_ns, StreamOf(c, hip_stream));
+  const RayBatch rb = {d_origins, d_dirs, d_dx, d_dy, d_screen, d_stream, (uint32_t) n, params->flags & QA_RAYBATCH_FLAGS};
+  return LaunchRayBatch(c, PickFor(c, params), n, rb, *params, d_rgb, d_t, d_ns, StreamOf(c, hip_stream));
 }
 
 int qa_radiance_rays(qa_ctx *c, uint64_t n, const float *origins, const float *dirs, const float *dx, const float *dy, const float *screen,
@@ -145,8 +149,8 @@ int qa_radiance_rays(qa_ctx *c, uint64_t n, const float *origins, const float *d
   }
   if (screen) HIP_TRY(hipMemcpyAsync(dScreen, screen, r * 8, hipMemcpyHostToDevice, c->stream));
   if (stream) HIP_TRY(hipMemcpyAsync(dStream, stream, n * 4, hipMemcpyHostToDevice, c->stream));
-  const RayBatch rb = {dO, dD, dx ? dDx : nullptr, dx ? dDy : nullptr, screen ? dScreen : nullptr, stream ? dStream : nullptr, (uint32_t) n, params->flags};
-  if (int rc = LaunchRayBatch(c, PickRays(c), n, rb, *params, dRgb, t ? dT : nullptr, ns ? dNs : nullptr, c->stream)) return rc;
+  const RayBatch rb = {dO, dD, dx ? dDx : nullptr, dx ? dDy : nullptr, screen ? dScreen : nullptr, stream ? dStream : nullptr, (uint32_t) n, params->flags & QA_RAYBATCH_FLAGS};
+  if (int rc = LaunchRayBatch(c, PickFor(c, params), n, rb, *params, dRgb, t ? dT : nullptr, ns ? dNs : nullptr, c->stream)) return rc;
   HIP_TRY(hipMemcpyAsync(rgb, dRgb, n * 12, hipMemcpyDeviceToHost, c->stream));
   if (t) HIP_TRY(hipMemcpyAsync(t, dT, n * 4, hipMemcpyDeviceToHost, c->stream));
   if (ns) HIP_TRY(hipMemcpyAsync(ns, dNs, n * 4, hipMemcpyDeviceToHost, c->stream));

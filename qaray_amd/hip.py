@@ -138,6 +138,7 @@ class DenoiseParams(C.Structure):   # qa_denoise_params; DenoiseParams.default()
 
 QA_DENOISE_GUIDE_NORMAL, QA_DENOISE_GUIDE_ALBEDO = 1, 2
 QA_RADIANCE_PER_SAMPLE, QA_RADIANCE_MISS_ENVIRONMENT = 1, 2
+QA_RADIANCE_PHOTON_MAPS = 8   # (bit 3: the batch gathers from the built photon maps, as a frame does)
 
 
 class RadianceParams(C.Structure):   # qa_radiance_params; RadianceParams.default() = qa_radiance_params_default
@@ -150,7 +151,7 @@ class RadianceParams(C.Structure):   # qa_radiance_params; RadianceParams.defaul
         return p
 
     @classmethod
-    def of(cls, spp=None, max_bounce=None, seed=None, per_sample=False, miss_environment=False):
+    def of(cls, spp=None, max_bounce=None, seed=None, per_sample=False, miss_environment=False, photon_maps=False):
         """The library's defaults with the arguments that are given written over them."""
         p = cls.default()
         if spp is not None:
@@ -159,8 +160,17 @@ class RadianceParams(C.Structure):   # qa_radiance_params; RadianceParams.defaul
             p.max_bounce = int(max_bounce)
         if seed is not None:
             p.seed = int(seed) & 0xFFFFFFFF
-        p.flags = (QA_RADIANCE_PER_SAMPLE if per_sample else 0) | (QA_RADIANCE_MISS_ENVIRONMENT if miss_environment else 0)
+        p.flags = ((QA_RADIANCE_PER_SAMPLE if per_sample else 0) | (QA_RADIANCE_MISS_ENVIRONMENT if miss_environment else 0) |
+                   (QA_RADIANCE_PHOTON_MAPS if photon_maps else 0))
         return p
+
+
+def _photon_maps_option(call, options):
+    """The one keyword the point queries and bake_light take beyond their listed parameters: photon_maps (default False)."""
+    unknown = sorted(set(options) - {"photon_maps"})
+    if unknown:
+        raise TypeError(f"{call}() got an unexpected keyword argument '{unknown[0]}'")
+    return bool(options.get("photon_maps", False))
 
 
 class DenoiseGuidedParams(C.Structure):   # qa_denoise_guided_params; .default() = qa_denoise_guided_params_default
@@ -1671,7 +1681,7 @@ class Context:
                 t.record_stream(cur)
         return out
 
-    def bake_light(self, node, texmap, spp=64, max_bounce=5, scale=1.0, mtl=-1, dilate=2, seed=DEFAULT_SEED, stream=None):
+    def bake_light(self, node, texmap, spp=64, max_bounce=5, scale=1.0, mtl=-1, dilate=2, seed=DEFAULT_SEED, stream=None, **options):
         """The light arriving at node `node` baked into the file texture of texmap `texmap`, in place - a light map, composed as
         bake_ao composes its map: the map of the texture's texels (bake_texels_device at the texture's size, through the texmap),
         irradiance_points_device at the texels' points and normals with stream_ids = iy * W + ix (an uncovered texel's normal is
@@ -1682,8 +1692,12 @@ class Context:
         light weighted 1 / num_lights; values above 1 / scale clip.  The limit: paths that return to the node read its texture as
         it stands during the bake, not the light map being made.  All on one stream, as bake_ao.  -> dict of CUDA tensors light
         [H,W,3] f32 (0 where uncovered), face [H,W] i32, rgb8 [H,W,3] u8 (what the texture now holds).  QA_EINVAL for a texmap
-        without a file texture."""
+        without a file texture.  One more keyword, photon_maps=False: the same composition with the flag on its point query
+        (irradiance_points_device), so that the light map holds the caustics a frame with maps shows; the maps must be built.  The
+        last step, edit_texels, drops the maps as every texel edit does: the caller rebuilds them afterwards
+        (build_photon_maps), and photon_maps_info() raises until then."""
         import torch
+        photon_maps = _photon_maps_option("bake_light", options)
         dev = torch.device("cuda", self.device_id)
         blob = self.download_scene()
         maps = blob_table(blob, "texmaps")
@@ -1710,7 +1724,7 @@ class Context:
                                         face=torch.empty((H, W), dtype=torch.int32, device=dev), stream=sptr)
             ids = torch.arange(H * W, dtype=torch.int32, device=dev)
             light = self.irradiance_points_device(m["point"].reshape(-1, 3), m["normal"].reshape(-1, 3), spp, max_bounce, seed, ids,
-                                                  stream=sptr)[0].reshape(H, W, 3)
+                                                  stream=sptr, photon_maps=photon_maps)[0].reshape(H, W, 3)
             covered = m["face"] >= 0
             grey = self.ao_grey_device(light * float(scale), stream=sptr)
             rgb8 = torch.where(covered.unsqueeze(2), grey, current).contiguous()
@@ -1831,7 +1845,7 @@ class Context:
 
     # -- radiance queries (qa_radiance.hip) --------------------------------------------------------
     def radiance_rays_device(self, origins, dirs, spp=1, max_bounce=5, seed=DEFAULT_SEED, dx=None, dy=None, screen=None, stream_ids=None,
-                             miss_environment=False, rgb=None, t=None, ns=None, stream=None):
+                             miss_environment=False, rgb=None, t=None, ns=None, stream=None, photon_maps=False):
         """qa_radiance_rays_device: n rays of the caller's path-traced by the renderer's integrator, spp samples each.  origins, dirs:
         float32 contiguous CUDA tensors, [n,3] (every sample of ray q starts from ray q) or [n,spp,3] (rays per sample:
         QA_RADIANCE_PER_SAMPLE); dirs are used as given (unit length is assumed).  Optional, shaped as origins: dx, dy the
@@ -1839,7 +1853,10 @@ class Context:
         [...,2] where a missed first ray looks a background image up (pixels).  stream_ids: int32 or uint32 [n], the random-number
         stream of each ray (None: the ray's index).  miss_environment: a missed first ray takes the environment by direction
         and not the background.  Outputs (given, or allocated): rgb float32 [n,3], t float32 [n] (QA_RAY_MISS on a miss), ns
-        int32 [n] (spp for a finished ray) -> (rgb, t, ns).  Only enqueues (see render_region_device for the stream)."""
+        int32 [n] (spp for a finished ray) -> (rgb, t, ns).  photon_maps (QA_RADIANCE_PHOTON_MAPS): the paths gather from the
+        photon and caustics maps build_photon_maps made, exactly as a frame does while they are built; opt-in - without it a
+        context with maps refuses the call (QA_EUNSUPPORTED), with it one without maps does (QA_ENOSCENE).  Only enqueues (see
+        render_region_device for the stream)."""
         import torch
         dev = torch.device("cuda", self.device_id)
         if not isinstance(origins, torch.Tensor):
@@ -1864,7 +1881,7 @@ class Context:
         _ray_tensor("rgb", rgb, (n, 3), torch.float32, dev)
         _ray_tensor("t", t, (n,), torch.float32, dev)
         _ray_tensor("ns", ns, (n,), torch.int32, dev)
-        p = RadianceParams.of(spp, max_bounce, seed, per_sample, miss_environment)
+        p = RadianceParams.of(spp, max_bounce, seed, per_sample, miss_environment, photon_maps)
         sptr = self._stream_arg(stream, origins)
         ptr = lambda a: None if a is None else (a.data_ptr() or None)   # noqa: E731
         _check(lib().qa_radiance_rays_device(self._h, n, ptr(origins), ptr(dirs), ptr(dx), ptr(dy), ptr(screen), ptr(stream_ids), C.byref(p),
@@ -1872,9 +1889,9 @@ class Context:
         return rgb, t, ns
 
     def radiance_rays(self, origins, dirs, spp=1, max_bounce=5, seed=DEFAULT_SEED, dx=None, dy=None, screen=None, stream_ids=None,
-                      miss_environment=False):
+                      miss_environment=False, photon_maps=False):
         """qa_radiance_rays: radiance_rays_device from and to host memory.  Arrays as there, converted to float32 (stream_ids to
-        uint32) -> (rgb [n,3] f32, t [n] f32, ns [n] u32) numpy arrays.  Synchronises."""
+        uint32); photon_maps as there -> (rgb [n,3] f32, t [n] f32, ns [n] u32) numpy arrays.  Synchronises."""
         spp = int(spp)
         o = np.ascontiguousarray(origins, dtype=np.float32)
         n, per_sample = _radiance_shape("origins", o, spp)
@@ -1898,23 +1915,28 @@ class Context:
             if sid.shape != (n,):
                 raise ValueError(f"stream_ids: shape ({n},) is expected, not {sid.shape}")
         rgb, t, ns = np.zeros((n, 3), np.float32), np.zeros(n, np.float32), np.zeros(n, np.uint32)
-        p = RadianceParams.of(spp, max_bounce, seed, per_sample, miss_environment)
+        p = RadianceParams.of(spp, max_bounce, seed, per_sample, miss_environment, photon_maps)
         ptr = lambda a: None if a is None else a.ctypes.data   # noqa: E731
         _check(lib().qa_radiance_rays(self._h, n, ptr(o), ptr(arrs["dirs"]), ptr(arrs["dx"]), ptr(arrs["dy"]), ptr(arrs["screen"]), ptr(sid),
                                       C.byref(p), ptr(rgb), ptr(t), ptr(ns)))
         return rgb, t, ns
 
     # -- irradiance queries (qa_irradiance.hip) ----------------------------------------------------
-    def irradiance_points_device(self, points, normals, spp=16, max_bounce=5, seed=DEFAULT_SEED, stream_ids=None, rgb=None, ns=None, stream=None):
+    def irradiance_points_device(self, points, normals, spp=16, max_bounce=5, seed=DEFAULT_SEED, stream_ids=None, rgb=None, ns=None, stream=None,
+                                 **options):
         """qa_irradiance_points_device: the light arriving at n surface points of the caller's (lightmap texels, mesh vertices),
         path-traced by the renderer's integrator started at the points, spp samples each: the direct light at the point, one
         cosine-weighted bounce, and the integrator as it stands behind it.  kd * rgb is what a frame shows for a diffuse surface
         of colour kd there (not scaled by pi; every light weighs 1 / num_lights).  points, normals: float32 [n,3] contiguous CUDA
         tensors, world space, the normals of unit length (used as given).  stream_ids: int32 or uint32 [n], the random-number
         stream of each point (None: the point's index).  A point with a component that is not finite, or a zero normal, is black.
-        Outputs (given, or allocated): rgb float32 [n,3], ns int32 [n] (spp for a finished point) -> (rgb, ns).  Only enqueues
-        (see render_region_device for the stream)."""
+        Outputs (given, or allocated): rgb float32 [n,3], ns int32 [n] (spp for a finished point) -> (rgb, ns).  One more
+        keyword, photon_maps=False (QA_RADIANCE_PHOTON_MAPS): the point gathers from the caustics map ahead of its direct light,
+        and the paths behind its bounce gather from both maps as a frame's do while build_photon_maps' maps are built; opt-in -
+        without it a context with maps refuses the call (QA_EUNSUPPORTED), with it one without maps does (QA_ENOSCENE).  Only
+        enqueues (see render_region_device for the stream)."""
         import torch
+        photon_maps = _photon_maps_option("irradiance_points_device", options)
         dev = torch.device("cuda", self.device_id)
         if not isinstance(points, torch.Tensor):
             raise TypeError(f"points: a torch tensor is expected, not {type(points).__name__}")
@@ -1929,15 +1951,17 @@ class Context:
         ns = torch.empty((n,), dtype=torch.int32, device=dev) if ns is None else ns
         _ray_tensor("rgb", rgb, (n, 3), torch.float32, dev)
         _ray_tensor("ns", ns, (n,), torch.int32, dev)
-        p = RadianceParams.of(spp, max_bounce, seed)
+        p = RadianceParams.of(spp, max_bounce, seed, photon_maps=photon_maps)
         sptr = self._stream_arg(stream, points)
         ptr = lambda a: None if a is None else (a.data_ptr() or None)   # noqa: E731
         _check(lib().qa_irradiance_points_device(self._h, n, ptr(points), ptr(normals), ptr(stream_ids), C.byref(p), ptr(rgb), ptr(ns), sptr))
         return rgb, ns
 
-    def irradiance_points(self, points, normals, spp=16, max_bounce=5, seed=DEFAULT_SEED, stream_ids=None):
+    def irradiance_points(self, points, normals, spp=16, max_bounce=5, seed=DEFAULT_SEED, stream_ids=None, **options):
         """qa_irradiance_points: irradiance_points_device from and to host memory.  points, normals: [n,3], converted to float32;
-        stream_ids: [n] integers below 2^32 or None -> (rgb [n,3] f32, ns [n] u32) numpy arrays.  Synchronises."""
+        stream_ids: [n] integers below 2^32 or None; the keyword photon_maps=False as there -> (rgb [n,3] f32, ns [n] u32) numpy
+        arrays.  Synchronises."""
+        photon_maps = _photon_maps_option("irradiance_points", options)
         p, nr, n = _ray_arrays(points, normals)
         sid = None
         if stream_ids is not None:
@@ -1945,8 +1969,8 @@ class Context:
             if sid.shape != (n,):
                 raise ValueError(f"stream_ids: shape ({n},) is expected, not {sid.shape}")
         rgb, ns = np.zeros((n, 3), np.float32), np.zeros(n, np.uint32)
-        _check(lib().qa_irradiance_points(self._h, n, p.ctypes.data, nr.ctypes.data, _ptr(sid), C.byref(RadianceParams.of(spp, max_bounce, seed)),
-                                          rgb.ctypes.data, ns.ctypes.data))
+        par = RadianceParams.of(spp, max_bounce, seed, photon_maps=photon_maps)
+        _check(lib().qa_irradiance_points(self._h, n, p.ctypes.data, nr.ctypes.data, _ptr(sid), C.byref(par), rgb.ctypes.data, ns.ctypes.data))
         return rgb, ns
 
     def camera_sample_rays_device(self, region, first=0, count=1, outputs=CAMERA_SAMPLE_OUTPUTS, stream=None, **given):
