@@ -65,7 +65,9 @@
  *                                  out)                                 src/renderers/renderer.cpp:312-341
  *   qa_irradiance_points*          (no counterpart: MtlBlinn_PhotonMap::Shade of a white diffuse hit at a surface point of the
  *                                  caller's - its lights, one diffuse bounce, the path behind it - with no ray leading there)
- *   qa_get_counters                (no counterpart: the reference only prints wall-clock)
+ *   qa_probe_sh*, qa_probe_shade_device,   (no counterpart: PixelRender's path along the directions of a cube map around a point in
+ *   qa_probe_grid_shade_device     free space, projected onto spherical harmonics - the light a moving object there receives)
+ *   qa_get_counters               (no counterpart: the reference only prints wall-clock)
  *   qa_get_kernel_time             Renderer::StartTimer/StopTimer       src/renderers/renderer.cpp:42-63
  */
 #ifndef QARAY_HIP_H
@@ -1022,6 +1024,73 @@ int qa_irradiance_points_device(qa_ctx *ctx, uint64_t n, const float *d_points, 
                                 const qa_radiance_params *params, float *d_rgb, uint32_t *d_nsamples, void *stream);
 int qa_irradiance_points(qa_ctx *ctx, uint64_t n, const float *points, const float *normals, const uint32_t *stream_ids,
                          const qa_radiance_params *params, float *rgb, uint32_t *nsamples);
+
+/* Light probes: the light arriving at n points in free space - where a moving object, a character or a particle will be - as the
+ * nine coefficients per colour of the real spherical harmonics of order 2, and their evaluation at shading points (the opening
+ * comment of qaray_amd/csrc/hip/qa_lightprobe_dev.h is the specification of every number below).  A probe holds what a camera at
+ * its point would see in every direction: emitters, the environment, and the surfaces around it under their own direct and bounced
+ * light.  It does NOT hold the direct term of point, spot and directional lights at the point itself - no ray can meet them; a shader
+ * adds them analytically, as it does for any dynamic object.
+ *   qa_probe_params             m: the probe is a cube map of m x m texels per face, 1 <= m <= 128, K = 6 m^2 directions through the
+ *                               texel centres, each weighted by its texel's solid angle; spp, max_bounce, seed as qa_radiance_params';
+ *                               flags: QA_PROBE_JITTER (the directions are jittered inside their texels by counter-based words of
+ *                               (seed, the probe's stream id, k)) and QA_RADIANCE_PHOTON_MAPS (passed through to the rays), every
+ *                               other bit is refused; chunk_rays: the probes are traced max(1, chunk_rays / K) at a time (0: 2^20
+ *                               rays), which bounds the scratch and changes no result.
+ *   qa_probe_params_default     m 16, spp 1, max_bounce 5, seed 0x51A7A7, flags 0, chunk_rays 0.  Needs no context.
+ *   qa_probe_sh_device          d_points [n][3] floats, world space; d_stream [n] uint32 the probe's stream id S (NULL: its index).
+ *                               Ray (q, k) is a ray of qa_radiance_rays_device from point q along direction k with
+ *                               QA_RADIANCE_MISS_ENVIRONMENT, spp samples and the random-number stream of pixel index
+ *                               (S * K + k) mod 2^32.  Outputs by probe: d_sh [n][9][3] the coefficients (order: 1; y, z, x; xy, yz,
+ *                               3z^2 - 1, xz, x^2 - y^2), the projection normalised by 4 pi over the summed weights; d_cube
+ *                               [n][6][m][m][3] (may be NULL) the rays' rgb, faces +x, -x, +y, -y, +z, -z; d_hits [n] uint32 (may be
+ *                               NULL) the rays with t < QA_RAY_MISS; d_tmin [n] (may be NULL) the least t - a probe inside a wall or
+ *                               against one shows there.  A probe with a component that is not finite is void: all outputs 0,
+ *                               d_tmin QA_RAY_MISS.  A result depends on the point, S, m, flags, seed, spp and max_bounce alone.
+ *                               Only enqueues on stream (NULL = the context's stream); the rays of a chunk live in a scratch buffer
+ *                               of the context's that only grows (44 bytes per ray of the largest chunk so far).
+ *   qa_probe_sh                 the same from and to host memory through the queries' staging buffer (132 bytes per probe, and the
+ *                               cube when asked for); synchronises.
+ *   qa_probe_shade_device       shading point i takes probe d_index[i] (int32; NULL: i) of d_sh [probes][9][3] and its normal
+ *                               d_normals[i] (unit length assumed) -> d_rgb [n][3] = max(0, sum_c A_c sh_c Y_c(N)), A = 1, 2/3, 1/4 by
+ *                               band: the units of qa_irradiance_points, not scaled by pi, kd * rgb is a diffuse colour.  An index
+ *                               outside [0, probes) is clamped into it (the array is the device's: nothing is refused by content); a
+ *                               normal that is not finite shades to 0.  Needs no scene; only enqueues.
+ *   qa_probe_grid_shade_device  the same from a regular grid: origin[3], spacing[3] > 0, counts[3] >= 1 in host memory, probe
+ *                               (iz * ny + iy) * nx + ix of d_sh at origin + (ix, iy, iz) * spacing; the point's 27 coefficients
+ *                               are interpolated trilinearly (x, then y, then z) between the probes of its cell, points outside
+ *                               the grid take the nearest cell's edge.  A point or normal that is not finite shades to 0.
+ * qa_probe_sh_device is ordered as its chunks are, as qa_radiance_rays_device: behind the context's last frame and last edit, and a
+ * later edit waits for it; qa_get_counters moves as for n * K * spp samples, qa_get_kernel_time by one launch per chunk.  The two
+ * shading calls read only the caller's arrays and order nothing.
+ * Codes: qa_probe_sh*: QA_ENOSCENE without a scene; n == 0 is QA_OK and launches nothing; QA_EINVAL for n > 2^31 - 1, a NULL point
+ * array, sh or params, m outside 1 .. 128, an unknown flag bit, and whatever qa_radiance_rays_device refuses of a chunk: more than
+ * 2^31 - 1 rays in one chunk (the limit is per chunk, not per batch), spp < 1, max_bounce < 0; QA_EUNSUPPORTED for area lights with
+ * max_bounce > 7 and while photon maps are built unless QA_RADIANCE_PHOTON_MAPS is set; QA_ENOSCENE for that flag without maps.
+ * The shading calls: QA_EINVAL for n > 2^31 - 1, a NULL array, probes == 0, probes < n without an index, a grid whose origin or
+ * spacing is not finite, spacing <= 0, a count < 1 or more than 2^31 - 1 probes.  A refused call writes nothing. */
+#define QA_PROBE_JITTER 16u
+typedef struct qa_probe_params { int m, spp, max_bounce; uint32_t seed, flags; uint64_t chunk_rays; } qa_probe_params;
+int qa_probe_params_default(qa_probe_params *params);
+int qa_probe_sh_device(qa_ctx *ctx, uint64_t n, const float *d_points, const uint32_t *d_stream, const qa_probe_params *params,
+                       float *d_sh, float *d_cube, uint32_t *d_hits, float *d_tmin, void *stream);
+int qa_probe_sh(qa_ctx *ctx, uint64_t n, const float *points, const uint32_t *stream_ids, const qa_probe_params *params, float *sh,
+                float *cube, uint32_t *hits, float *tmin);
+int qa_probe_shade_device(qa_ctx *ctx, uint64_t n, const float *d_sh, uint64_t probes, const float *d_normals, const int32_t *d_index,
+                          float *d_rgb, void *stream);
+int qa_probe_grid_shade_device(qa_ctx *ctx, uint64_t n, const float *d_sh, const float *origin, const float *spacing,
+                               const int32_t *counts, const float *d_points, const float *d_normals, float *d_rgb, void *stream);
+/* Self-test hooks for the light probes (qaray_amd/csrc/hip/qa_lightprobe_dev.h): the source of the kernels above compiled for the
+ * host (no GPU and no context needed).  directions: n probes with stream ids stream [n] -> d [n][K][3], w [n][K], ray_stream [n][K]
+ * (each may be NULL, not all); flags: 0 or QA_PROBE_JITTER.  project: one probe's K rays - d [K][3], w [K], rgb [K][3], t [K] - reduced
+ * as the wave reduces them -> sh [27], hits [1], tmin [1] (the last two may be NULL).  shade, grid_shade: the calls over host arrays. */
+int qa_test_probe_directions_host(int m, uint32_t seed, uint32_t flags, const uint32_t *stream, uint64_t n, float *d, float *w,
+                                  uint32_t *ray_stream);
+int qa_test_probe_project_host(uint64_t K, const float *d, const float *w, const float *rgb, const float *t, float *sh, uint32_t *hits,
+                               float *tmin);
+int qa_test_probe_shade_host(uint64_t n, const float *sh, uint64_t probes, const float *normals, const int32_t *index, float *rgb);
+int qa_test_probe_grid_shade_host(uint64_t n, const float *sh, const float *origin, const float *spacing, const int32_t *counts,
+                                  const float *points, const float *normals, float *rgb);
 
 #ifdef __cplusplus
 }

@@ -155,7 +155,7 @@ int qa_ctx_destroy(qa_ctx *c)
     if (p) (void) hipFree(p);
   for (void *p : {(void *) c->hEditStage, (void *) c->hStop})
     if (p) (void) hipHostFree(p);
-  for (DevBuf *b : {&c->pixState, &c->tileProgress, &c->stageRgb, &c->stageDepth, &c->stageNs, &c->stageQuery, &c->displayStage, &c->denoisePlanes, &c->reprojectIds}) b->Free();
+  for (DevBuf *b : {&c->pixState, &c->tileProgress, &c->stageRgb, &c->stageDepth, &c->stageNs, &c->stageQuery, &c->displayStage, &c->denoisePlanes, &c->reprojectIds, &c->probeScratch}) b->Free();
   for (StreamFence *f : {&c->lastFrame, &c->lastEdit, &c->lastDisplay, &c->lastDenoise, &c->lastReproject, &c->texSource, &c->prog.done})
     if (f->ev) (void) hipEventDestroy(f->ev);
   if (c->stream) (void) hipStreamDestroy(c->stream);

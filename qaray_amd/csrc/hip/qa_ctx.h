@@ -263,6 +263,9 @@ struct qa_ctx {
   // qa_progressive_reproject_device's ids plane of the current frame (qa_reproject.hip): 8 bytes per pixel of the largest frame so far
   DevBuf reprojectIds;
   StreamFence lastReproject{"lastReproject"};    // one per context: a call on another stream waits
+  // qa_probe_sh*'s rays of one chunk of probes (qa_lightprobe.hip): 44 bytes per ray of the largest chunk so far.  One per context:
+  // the call that writes it waits for lastFrame and records it behind its last reduction
+  DevBuf probeScratch;
 };
 
 void FreePhotonMaps(qa_ctx *c);  // qa_photon.hip

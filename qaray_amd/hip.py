@@ -165,6 +165,36 @@ class RadianceParams(C.Structure):   # qa_radiance_params; RadianceParams.defaul
         return p
 
 
+QA_PROBE_JITTER = 16   # (beside the radiance bits: QA_RADIANCE_PHOTON_MAPS is passed through)
+QA_PROBE_MAX_M = 128
+
+
+class ProbeParams(C.Structure):   # qa_probe_params; ProbeParams.default() = qa_probe_params_default
+    _fields_ = [("m", C.c_int), ("spp", C.c_int), ("max_bounce", C.c_int), ("seed", C.c_uint32), ("flags", C.c_uint32), ("chunk_rays", C.c_uint64)]
+
+    @classmethod
+    def default(cls):
+        p = cls()
+        _check(lib().qa_probe_params_default(C.byref(p)))
+        return p
+
+    @classmethod
+    def of(cls, m=None, spp=None, max_bounce=None, seed=None, jitter=False, photon_maps=False, chunk_rays=0):
+        """The library's defaults with the arguments that are given written over them."""
+        p = cls.default()
+        if m is not None:
+            p.m = int(m)
+        if spp is not None:
+            p.spp = int(spp)
+        if max_bounce is not None:
+            p.max_bounce = int(max_bounce)
+        if seed is not None:
+            p.seed = int(seed) & 0xFFFFFFFF
+        p.flags = (QA_PROBE_JITTER if jitter else 0) | (QA_RADIANCE_PHOTON_MAPS if photon_maps else 0)
+        p.chunk_rays = int(chunk_rays)
+        return p
+
+
 def _photon_maps_option(call, options):
     """The one keyword the point queries and bake_light take beyond their listed parameters: photon_maps (default False)."""
     unknown = sorted(set(options) - {"photon_maps"})
@@ -442,6 +472,15 @@ def lib():
         L.qa_camera_sample_rays_device.argtypes = [C.c_void_p] + [C.c_int] * 6 + [C.c_void_p] * 7
         L.qa_irradiance_points_device.argtypes = [C.c_void_p, C.c_uint64] + [C.c_void_p] * 3 + [C.POINTER(RadianceParams)] + [C.c_void_p] * 3
         L.qa_irradiance_points.argtypes = [C.c_void_p, C.c_uint64] + [C.c_void_p] * 3 + [C.POINTER(RadianceParams)] + [C.c_void_p] * 2
+        L.qa_probe_params_default.argtypes = [C.POINTER(ProbeParams)]
+        L.qa_probe_sh_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(ProbeParams)] + [C.c_void_p] * 5
+        L.qa_probe_sh.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(ProbeParams)] + [C.c_void_p] * 4
+        L.qa_probe_shade_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64] + [C.c_void_p] * 4
+        L.qa_probe_grid_shade_device.argtypes = [C.c_void_p, C.c_uint64] + [C.c_void_p] * 8
+        L.qa_test_probe_directions_host.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64] + [C.c_void_p] * 3
+        L.qa_test_probe_project_host.argtypes = [C.c_uint64] + [C.c_void_p] * 7
+        L.qa_test_probe_shade_host.argtypes = [C.c_uint64, C.c_void_p, C.c_uint64] + [C.c_void_p] * 3
+        L.qa_test_probe_grid_shade_host.argtypes = [C.c_uint64] + [C.c_void_p] * 7
         L.qa_scene_edit_camera.argtypes = [C.c_void_p, C.c_void_p]
         for name in ("qa_scene_edit_lights", "qa_scene_edit_materials", "qa_scene_edit_instances"):
             getattr(L, name).argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
@@ -626,6 +665,79 @@ def ao_direction_from_host(n, s):
     d = np.zeros((len(s), 3), np.float32)
     _check(lib().qa_test_ao_direction_from_host(n.ctypes.data, s.ctypes.data, len(s), d.ctypes.data))
     return d
+
+
+def probe_directions_host(m, stream_ids=(0,), seed=DEFAULT_SEED, jitter=False):
+    """qa_test_probe_directions_host: the K = 6 m^2 directions of a light probe's cube map, their weights (the texels' solid angles)
+    and the random-number streams of their rays, for the probes with the given stream ids, on the CPU from the source the device
+    kernels are compiled from -> (d float32 (n, K, 3), w float32 (n, K), ray_stream uint32 (n, K)).  No GPU needed."""
+    s = np.ascontiguousarray(stream_ids, dtype=np.uint32).reshape(-1)
+    m = int(m)
+    if not 1 <= m <= QA_PROBE_MAX_M:
+        raise ValueError(f"m: 1 .. {QA_PROBE_MAX_M} is expected, not {m}")
+    K = 6 * m * m
+    d, w, rs = np.zeros((len(s), K, 3), np.float32), np.zeros((len(s), K), np.float32), np.zeros((len(s), K), np.uint32)
+    _check(lib().qa_test_probe_directions_host(m, int(seed) & 0xFFFFFFFF, QA_PROBE_JITTER if jitter else 0, s.ctypes.data, len(s), d.ctypes.data,
+                                               w.ctypes.data, rs.ctypes.data))
+    return d, w, rs
+
+
+def probe_project_host(d, w, rgb, t):
+    """qa_test_probe_project_host: one probe's K rays - directions d (K, 3), weights w (K,), radiance rgb (K, 3), hit parameters t
+    (K,) - projected as a wave of the device kernel projects them -> (sh float32 (9, 3), hits int, tmin float32).  No GPU needed."""
+    d = np.ascontiguousarray(d, dtype=np.float32).reshape(-1, 3)
+    K = len(d)
+    w, t = (np.ascontiguousarray(a, dtype=np.float32).reshape(-1) for a in (w, t))
+    rgb = np.ascontiguousarray(rgb, dtype=np.float32).reshape(-1, 3)
+    if w.shape != (K,) or t.shape != (K,) or rgb.shape != (K, 3):
+        raise ValueError(f"w, t: shape ({K},) and rgb: shape ({K}, 3) are expected, not {w.shape}, {t.shape}, {rgb.shape}")
+    sh, hits, tmin = np.zeros((9, 3), np.float32), np.zeros(1, np.uint32), np.zeros(1, np.float32)
+    _check(lib().qa_test_probe_project_host(K, d.ctypes.data, w.ctypes.data, rgb.ctypes.data, t.ctypes.data, sh.ctypes.data, hits.ctypes.data, tmin.ctypes.data))
+    return sh, int(hits[0]), tmin[0]
+
+
+def _probe_sh_array(sh):
+    sh = np.ascontiguousarray(sh, dtype=np.float32)
+    if sh.ndim < 2 or sh.shape[-2:] != (9, 3):
+        raise ValueError(f"sh: shape (..., 9, 3) is expected, not {sh.shape}")
+    return sh.reshape(-1, 9, 3)
+
+
+def probe_shade_host(sh, normals, index=None):
+    """qa_test_probe_shade_host: Context.probe_shade_device over host arrays - sh (probes, 9, 3), normals (n, 3), index (n,) int32 or
+    None (shading point i takes probe i) -> rgb float32 (n, 3).  No GPU needed."""
+    sh = _probe_sh_array(sh)
+    nr = np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
+    n = len(nr)
+    if index is not None:
+        index = np.ascontiguousarray(index, dtype=np.int32)
+        if index.shape != (n,):
+            raise ValueError(f"index: shape ({n},) is expected, not {index.shape}")
+    rgb = np.zeros((n, 3), np.float32)
+    _check(lib().qa_test_probe_shade_host(n, sh.ctypes.data, len(sh), nr.ctypes.data, None if index is None else index.ctypes.data, rgb.ctypes.data))
+    return rgb
+
+
+def _probe_grid_args(origin, spacing, counts):
+    """The three host arrays of a grid call"""
+    o, sp = (np.ascontiguousarray(a, dtype=np.float32) for a in (origin, spacing))
+    cn = np.ascontiguousarray(counts, dtype=np.int32)
+    if o.shape != (3,) or sp.shape != (3,) or cn.shape != (3,):
+        raise ValueError("origin, spacing and counts hold three values each")
+    return o, sp, cn
+
+
+def probe_grid_shade_host(sh, origin, spacing, counts, points, normals):
+    """qa_test_probe_grid_shade_host: ProbeGrid.shade_device over host arrays - sh (nz * ny * nx, 9, 3) of the grid (origin, spacing,
+    counts), points and normals (n, 3) -> rgb float32 (n, 3).  No GPU needed."""
+    sh = _probe_sh_array(sh)
+    o, sp, cn = _probe_grid_args(origin, spacing, counts)
+    if (cn >= 1).all() and len(sh) != int(np.prod(cn.astype(np.int64))):
+        raise ValueError(f"sh: {int(np.prod(cn.astype(np.int64)))} probes are expected, not {len(sh)}")
+    p, nr, n = _ray_arrays(points, normals)
+    rgb = np.zeros((n, 3), np.float32)
+    _check(lib().qa_test_probe_grid_shade_host(n, sh.ctypes.data, o.ctypes.data, sp.ctypes.data, cn.ctypes.data, p.ctypes.data, nr.ctypes.data, rgb.ctypes.data))
+    return rgb
 
 
 def _bake_size(width, height):
@@ -1973,6 +2085,105 @@ class Context:
         _check(lib().qa_irradiance_points(self._h, n, p.ctypes.data, nr.ctypes.data, _ptr(sid), C.byref(par), rgb.ctypes.data, ns.ctypes.data))
         return rgb, ns
 
+    # -- light probes (qa_lightprobe.hip) ----------------------------------------------------------
+    def probe_sh_device(self, points, m=16, spp=1, max_bounce=5, seed=DEFAULT_SEED, jitter=False, photon_maps=False, stream_ids=None, sh=None,
+                        cube=None, hits=None, tmin=None, chunk_rays=0, stream=None):
+        """qa_probe_sh_device: the light arriving at n points in free space, as order-2 spherical harmonics.  A probe is a cube map
+        of m x m texels per face around its point: K = 6 m^2 rays through the texel centres (jitter: jittered inside the texels),
+        each path-traced by the renderer's integrator as radiance_rays_device traces a ray (miss_environment, spp samples, the
+        stream (S * K + k) mod 2^32 for the probe's stream id S), weighted by its texel's solid angle and projected on the device.
+        It holds what a camera at the point would see in every direction - emitters, the environment, the surfaces around it under
+        their own direct and bounced light - and not the direct term of point, spot and directional lights at the point itself: a
+        shader adds those analytically.  points: float32 [n,3] contiguous CUDA tensor; stream_ids: int32 or uint32 [n] (None: the
+        probe's index).  Outputs (given, or allocated; cube only when given or cube=True): sh float32 [n,9,3], cube float32
+        [n,6,m,m,3] the rays' rgb, hits int32 [n] the rays that hit something, tmin float32 [n] the nearest hit (QA_RAY_MISS for
+        none) -> dict of them.  A point that is not finite gives zeros.  photon_maps as radiance_rays_device's; chunk_rays: the
+        rays traced at a time (0: 2^20), which bounds the scratch and changes no result.  Only enqueues (see render_region_device
+        for the stream)."""
+        import torch
+        dev = torch.device("cuda", self.device_id)
+        if not isinstance(points, torch.Tensor):
+            raise TypeError(f"points: a torch tensor is expected, not {type(points).__name__}")
+        n = _ray_count("points", points)
+        _ray_tensor("points", points, (n, 3), torch.float32, dev)
+        m = int(m)
+        if not 1 <= m <= QA_PROBE_MAX_M:
+            raise ValueError(f"m: 1 .. {QA_PROBE_MAX_M} is expected, not {m}")
+        if stream_ids is not None:
+            if isinstance(stream_ids, torch.Tensor) and stream_ids.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)):
+                raise TypeError(f"stream_ids: dtype torch.int32 or torch.uint32 is expected, not {stream_ids.dtype}")
+            _ray_tensor("stream_ids", stream_ids, (n,), getattr(stream_ids, "dtype", None), dev)
+        sh = torch.empty((n, 9, 3), dtype=torch.float32, device=dev) if sh is None else sh
+        hits = torch.empty((n,), dtype=torch.int32, device=dev) if hits is None else hits
+        tmin = torch.empty((n,), dtype=torch.float32, device=dev) if tmin is None else tmin
+        if cube is True:
+            cube = torch.empty((n, 6, m, m, 3), dtype=torch.float32, device=dev)
+        _ray_tensor("sh", sh, (n, 9, 3), torch.float32, dev)
+        _ray_tensor("hits", hits, (n,), torch.int32, dev)
+        _ray_tensor("tmin", tmin, (n,), torch.float32, dev)
+        if cube is not None:
+            _ray_tensor("cube", cube, (n, 6, m, m, 3), torch.float32, dev)
+        p = ProbeParams.of(m, spp, max_bounce, seed, jitter, photon_maps, chunk_rays)
+        sptr = self._stream_arg(stream, points)
+        ptr = lambda a: None if a is None else (a.data_ptr() or None)   # noqa: E731
+        _check(lib().qa_probe_sh_device(self._h, n, ptr(points), ptr(stream_ids), C.byref(p), ptr(sh), ptr(cube), ptr(hits), ptr(tmin), sptr))
+        out = {"sh": sh, "hits": hits, "tmin": tmin}
+        if cube is not None:
+            out["cube"] = cube
+        return out
+
+    def probe_sh(self, points, m=16, spp=1, max_bounce=5, seed=DEFAULT_SEED, jitter=False, photon_maps=False, stream_ids=None, cube=False,
+                 chunk_rays=0):
+        """qa_probe_sh: probe_sh_device from and to host memory.  points: [n,3], converted to float32; stream_ids: [n] integers below
+        2^32 or None -> dict of numpy arrays sh [n,9,3] f32, hits [n] u32, tmin [n] f32, and cube [n,6,m,m,3] f32 with cube=True.
+        Synchronises."""
+        p = np.ascontiguousarray(points, dtype=np.float32)
+        n = _ray_count("points", p)
+        m = int(m)
+        if not 1 <= m <= QA_PROBE_MAX_M:
+            raise ValueError(f"m: 1 .. {QA_PROBE_MAX_M} is expected, not {m}")
+        sid = None
+        if stream_ids is not None:
+            sid = np.ascontiguousarray(stream_ids, dtype=np.uint32)
+            if sid.shape != (n,):
+                raise ValueError(f"stream_ids: shape ({n},) is expected, not {sid.shape}")
+        out = {"sh": np.zeros((n, 9, 3), np.float32), "hits": np.zeros(n, np.uint32), "tmin": np.zeros(n, np.float32)}
+        if cube:
+            out["cube"] = np.zeros((n, 6, m, m, 3), np.float32)
+        par = ProbeParams.of(m, spp, max_bounce, seed, jitter, photon_maps, chunk_rays)
+        _check(lib().qa_probe_sh(self._h, n, p.ctypes.data, _ptr(sid), C.byref(par), out["sh"].ctypes.data, _ptr(out.get("cube")), out["hits"].ctypes.data,
+                                 out["tmin"].ctypes.data))
+        return out
+
+    def probe_shade_device(self, sh, normals, index=None, out=None, stream=None):
+        """qa_probe_shade_device: the diffuse light of probes at shading points.  sh: float32 [probes,9,3] contiguous CUDA tensor
+        (probe_sh_device's); normals: float32 [n,3], unit length; index: int32 [n] the probe of each shading point (None: point i
+        takes probe i, probes >= n), an index outside [0, probes) is clamped into it -> out float32 [n,3] (given, or allocated) =
+        max(0, sum_c A_c sh_c Y_c(N)): the units of irradiance_points_device, kd * out is a diffuse colour.  A normal that is not
+        finite shades to 0.  Only enqueues."""
+        import torch
+        dev = torch.device("cuda", self.device_id)
+        if not isinstance(sh, torch.Tensor):
+            raise TypeError(f"sh: a torch tensor is expected, not {type(sh).__name__}")
+        if sh.ndim != 3 or tuple(sh.shape[1:]) != (9, 3):
+            raise ValueError(f"sh: shape (probes, 9, 3) is expected, not {tuple(sh.shape)}")
+        probes = int(sh.shape[0])
+        _ray_tensor("sh", sh, (probes, 9, 3), torch.float32, dev)
+        if not isinstance(normals, torch.Tensor):
+            raise TypeError(f"normals: a torch tensor is expected, not {type(normals).__name__}")
+        n = _ray_count("normals", normals)
+        _ray_tensor("normals", normals, (n, 3), torch.float32, dev)
+        if index is not None:
+            _ray_tensor("index", index, (n,), torch.int32, dev)
+        elif probes < n:
+            raise ValueError(f"sh: {n} probes are expected without an index, not {probes}")
+        out = torch.empty((n, 3), dtype=torch.float32, device=dev) if out is None else out
+        _ray_tensor("out", out, (n, 3), torch.float32, dev)
+        sptr = self._stream_arg(stream, normals)
+        ptr = lambda a: None if a is None else (a.data_ptr() or None)   # noqa: E731
+        _check(lib().qa_probe_shade_device(self._h, n, ptr(sh), probes, ptr(normals), ptr(index), ptr(out), sptr))
+        return out
+
     def camera_sample_rays_device(self, region, first=0, count=1, outputs=CAMERA_SAMPLE_OUTPUTS, stream=None, **given):
         """qa_camera_sample_rays_device: samples [first, first + count) of the camera rays of the pixels of a region, exactly as a
         frame builds them -> dict name -> CUDA tensor for the names in `outputs` (or the tensors passed by name): origins, dirs, dx,
@@ -2558,3 +2769,57 @@ class TemporalPreview:
         self._cam = cam
         self._at = nxt
         return self._rgb[nxt], self._length[nxt]
+
+
+class ProbeGrid:
+    """A regular grid of light probes over a Context's scene: probe (iz * ny + iy) * nx + ix stands at origin + (ix, iy, iz) *
+    spacing.  bake() traces and projects them (Context.probe_sh_device) and keeps sh, hits and tmin on the device; shade_device()
+    gives the diffuse light at any points from the trilinearly interpolated coefficients - what a viewer asks for the nodes it
+    moves with edit_instances.  hits and tmin tell which probes sit inside a wall or against one."""
+
+    def __init__(self, ctx, origin, spacing, counts):
+        self.ctx = ctx
+        self.origin, self.spacing, self.counts = _probe_grid_args(origin, spacing, counts)
+        if not (np.isfinite(self.origin).all() and np.isfinite(self.spacing).all() and (self.spacing > 0).all() and (self.counts >= 1).all()):
+            raise ValueError("a grid has a finite origin, spacing > 0 and counts >= 1")
+        self.probes = int(np.prod(self.counts.astype(np.int64)))
+        if self.probes > QA_MAX_RAYS:
+            raise ValueError("more than 2^31 - 1 probes")
+        self.sh = self.hits = self.tmin = None
+
+    def points(self):
+        """-> the probes' positions, float32 (nz * ny * nx, 3) numpy, in the grid's order: origin + (ix, iy, iz) * spacing in fp32"""
+        nx, ny, nz = (int(v) for v in self.counts)
+        iz, iy, ix = np.meshgrid(np.arange(nz), np.arange(ny), np.arange(nx), indexing="ij")
+        idx = np.stack([ix, iy, iz], axis=-1).reshape(-1, 3).astype(np.float32)
+        return (self.origin + (idx * self.spacing).astype(np.float32)).astype(np.float32)
+
+    def bake(self, **kw):
+        """probe_sh_device on the grid's points (its keywords: m, spp, max_bounce, seed, jitter, photon_maps, chunk_rays, stream);
+        the results stay on the device as .sh [probes,9,3], .hits [probes] and .tmin [probes] -> self.  Only enqueues."""
+        import torch
+        pts = torch.from_numpy(self.points()).to(torch.device("cuda", self.ctx.device_id))
+        out = self.ctx.probe_sh_device(pts, **kw)
+        self.sh, self.hits, self.tmin = out["sh"], out["hits"], out["tmin"]
+        return self
+
+    def shade_device(self, points, normals, out=None, stream=None):
+        """qa_probe_grid_shade_device: the diffuse light at points (float32 [n,3] CUDA tensor) with unit normals [n,3] from the baked
+        grid: the 27 coefficients interpolated trilinearly between the probes of the point's cell (points outside take the
+        nearest cell's edge), shaded as Context.probe_shade_device shades -> out float32 [n,3] (given, or allocated).  A point
+        or normal that is not finite shades to 0.  Only enqueues."""
+        import torch
+        if self.sh is None:
+            raise ValueError("the grid is not baked: bake() first")
+        dev = torch.device("cuda", self.ctx.device_id)
+        if not isinstance(points, torch.Tensor):
+            raise TypeError(f"points: a torch tensor is expected, not {type(points).__name__}")
+        n = _ray_count("points", points)
+        _ray_tensor("points", points, (n, 3), torch.float32, dev)
+        _ray_tensor("normals", normals, (n, 3), torch.float32, dev)
+        out = torch.empty((n, 3), dtype=torch.float32, device=dev) if out is None else out
+        _ray_tensor("out", out, (n, 3), torch.float32, dev)
+        sptr = Context._stream_arg(stream, points)
+        _check(lib().qa_probe_grid_shade_device(self.ctx._h, n, self.sh.data_ptr(), self.origin.ctypes.data, self.spacing.ctypes.data, self.counts.ctypes.data,
+                                                points.data_ptr() or None, normals.data_ptr() or None, out.data_ptr() or None, sptr))
+        return out
