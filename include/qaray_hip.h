@@ -67,6 +67,8 @@
  *                                  caller's - its lights, one diffuse bounce, the path behind it - with no ray leading there)
  *   qa_probe_sh*, qa_probe_shade_device,   (no counterpart: PixelRender's path along the directions of a cube map around a point in
  *   qa_probe_grid_shade_device     free space, projected onto spherical harmonics - the light a moving object there receives)
+ *   qa_probevis_sh*,               (no counterpart: the distances those rays travelled as two moments per direction cell, and a grid
+ *   qa_probevis_grid_shade_device  shading that weighs each probe by whether it sees the shading point - no light through walls)
  *   qa_get_counters               (no counterpart: the reference only prints wall-clock)
  *   qa_get_kernel_time             Renderer::StartTimer/StopTimer       src/renderers/renderer.cpp:42-63
  */
@@ -1091,6 +1093,44 @@ int qa_test_probe_project_host(uint64_t K, const float *d, const float *w, const
 int qa_test_probe_shade_host(uint64_t n, const float *sh, uint64_t probes, const float *normals, const int32_t *index, float *rgb);
 int qa_test_probe_grid_shade_host(uint64_t n, const float *sh, const float *origin, const float *spacing, const int32_t *counts,
                                   const float *points, const float *normals, float *rgb);
+
+/* Probe visibility: the distances a probe's rays travelled, kept as two moments per direction cell, and a grid shading that weighs
+ * each of a cell's eight probes by whether it can see the shading point - so that a wall between them stops the light (the opening
+ * comment of qaray_amd/csrc/hip/qa_probevis_dev.h is the specification of every number below).  No ray is traced beyond those of
+ * qa_probe_sh_device.
+ *   qa_probevis_params            d: the moments are a cube map of d x d cells per face, 1 <= d <= m and m % d == 0, each pooling
+ *                                 (m / d)^2 texels; dmax > 0, finite: a ray's t is clamped to it (a miss becomes dmax); normal_bias,
+ *                                 finite: the shading point is moved by normal_bias * N before the visibility test.
+ *   qa_probevis_params_default    d 8, dmax 0, normal_bias 0.  dmax 0 is refused below: the caller sets it (ProbeGrid of the Python
+ *                                 layer takes 1.5 |spacing|).  Needs no context.
+ *   qa_probevis_sh_device         qa_probe_sh_device and, from the same rays, d_moments [n][6][d][d][2] (mean of t, mean of t^2 per
+ *                                 cell; +0 for a void probe).  d_moments is required, d_sh may be NULL here; d_cube, d_hits, d_tmin
+ *                                 as there.  The outputs it shares with qa_probe_sh_device have that call's bits.
+ *   qa_probevis_sh                the same from and to host memory.
+ *   qa_probevis_grid_shade_device qa_probe_grid_shade_device with d_moments [probes][6][d][d][2] of the grid's probes: the eight
+ *                                 probes of the point's cell are weighed by trilinear weight x wrapped cosine x Chebyshev visibility
+ *                                 and normalised.  d says the layout of d_moments (1 .. 128); of params only normal_bias is read.
+ * qa_probevis_sh_device is ordered, counted and refused exactly as qa_probe_sh_device on the same arguments (one more kernel per
+ * chunk pools the chunk's t before the next chunk overwrites it: qa_get_kernel_time counts the chunks as before), and QA_EINVAL
+ * also for NULL vis params or d_moments, d < 1, d > m, m % d != 0, dmax <= 0 or not finite, normal_bias not finite.  The shading
+ * call reads only the caller's arrays and orders nothing; QA_EINVAL as qa_probe_grid_shade_device and for NULL d_moments or params,
+ * d outside 1 .. 128, normal_bias not finite.  A refused call writes nothing. */
+typedef struct qa_probevis_params { int d; float dmax, normal_bias; } qa_probevis_params;
+int qa_probevis_params_default(qa_probevis_params *params);
+int qa_probevis_sh_device(qa_ctx *ctx, uint64_t n, const float *d_points, const uint32_t *d_stream, const qa_probe_params *params,
+                          const qa_probevis_params *vis, float *d_sh, float *d_cube, uint32_t *d_hits, float *d_tmin, float *d_moments,
+                          void *stream);
+int qa_probevis_sh(qa_ctx *ctx, uint64_t n, const float *points, const uint32_t *stream_ids, const qa_probe_params *params,
+                   const qa_probevis_params *vis, float *sh, float *cube, uint32_t *hits, float *tmin, float *moments);
+int qa_probevis_grid_shade_device(qa_ctx *ctx, uint64_t n, const float *d_sh, const float *d_moments, int d, const float *origin,
+                                  const float *spacing, const int32_t *counts, const float *d_points, const float *d_normals,
+                                  const qa_probevis_params *params, float *d_rgb, void *stream);
+/* Self-test hooks (qaray_amd/csrc/hip/qa_probevis_dev.h compiled for the host; no GPU and no context needed).  moments: one probe's
+ * K = 6 m^2 hit parameters t -> out [6][d][d][2].  grid_shade: the call above over host arrays. */
+int qa_test_probevis_moments_host(int m, int d, float dmax, const float *t, float *out);
+int qa_test_probevis_grid_shade_host(uint64_t n, const float *sh, const float *moments, int d, const float *origin, const float *spacing,
+                                     const int32_t *counts, const float *points, const float *normals,
+                                     const qa_probevis_params *params, float *rgb);
 
 #ifdef __cplusplus
 }

@@ -11,7 +11,11 @@
 //
 // What a probe holds: emitters, the environment, and the surfaces around it under their own direct and bounced light.  It does not
 // hold the direct term of point, spot and directional lights at P itself - no ray can meet them; a shader adds them analytically.
+//
+// Visibility (qa_probevis_*, specified in qa_probevis_dev.h): the same batch with one more kernel per chunk, which pools the chunk's t
+// from the scratch into two distance moments per direction cell, and a grid shading that weighs the probes of a cell by them.
 #include "qa_lightprobe_dev.h"
+#include "qa_probevis_dev.h"
 #include "qa_raybatch.h"
 
 namespace qa {
@@ -61,7 +65,7 @@ __global__ __launch_bounds__(256) void qa_probe_project(const ProbeReduce g)
   if (local >= g.count) return;
   const uint64_t q = g.first + local;
   if (probeVoid(g.points[3 * q], g.points[3 * q + 1], g.points[3 * q + 2])) {
-    if (lane < 27) g.sh[27 * q + lane] = 0.f;
+    if (g.sh && lane < 27) g.sh[27 * q + lane] = 0.f;
     if (lane == 0) {
       if (g.hits) g.hits[q] = 0u;
       if (g.tmin) g.tmin[q] = QA_AO_MAX_T;
@@ -92,7 +96,7 @@ __global__ __launch_bounds__(256) void qa_probe_project(const ProbeReduce g)
   // switch tree of a dozen masked stores)
   float mine = sh[0];
   for (int i = 1; i < 27; ++i) mine = (lane == (uint32_t) i) ? sh[i] : mine;
-  if (lane < 27) g.sh[27 * q + lane] = mine;
+  if (g.sh && lane < 27) g.sh[27 * q + lane] = mine;
   if (lane == 0) {
     if (g.hits) g.hits[q] = acc.hits;
     if (g.tmin) g.tmin[q] = acc.tmin;
@@ -117,6 +121,43 @@ __global__ __launch_bounds__(256) void qa_probe_grid_shade(uint64_t n, const Pro
   const float P[3] = {points[3 * i], points[3 * i + 1], points[3 * i + 2]}, N[3] = {normals[3 * i], normals[3 * i + 1], normals[3 * i + 2]};
   float out[3];
   probeGridShade(grid, sh, P, N, out);
+  rgb[3 * i] = out[0]; rgb[3 * i + 1] = out[1]; rgb[3 * i + 2] = out[2];
+}
+
+// ---- visibility (qa_probevis_*; the opening comment of qa_probevis_dev.h is the specification)
+
+struct ProbeVisPool {
+  const float *points;
+  uint64_t first, count;    // the chunk's probes
+  uint32_t m, K, d;
+  float dmax;
+  const float *t;           // the chunk's rays
+  float *moments;           // output of the whole batch [n][6][d][d][2]
+};
+
+// One thread per cell of the chunk's probes: the chunk's t is read before the next chunk's rays overwrite it
+__global__ __launch_bounds__(256) void qa_probevis_moments(const ProbeVisPool g)
+{
+  const uint32_t cells = 6u * g.d * g.d;
+  const uint64_t i = (uint64_t) blockIdx.x * 256 + threadIdx.x;
+  if (i >= g.count * cells) return;
+  const uint64_t local = i / cells, q = g.first + local;
+  const uint32_t cell = (uint32_t) (i % cells);
+  float out[2] = {0.f, 0.f};
+  if (!probeVoid(g.points[3 * q], g.points[3 * q + 1], g.points[3 * q + 2])) probeVisMoments(g.m, g.d, g.dmax, g.t + local * g.K, cell, out);
+  g.moments[2 * (q * cells + cell)] = out[0];
+  g.moments[2 * (q * cells + cell) + 1] = out[1];
+}
+
+// One thread per shading point
+__global__ __launch_bounds__(256) void qa_probevis_grid_shade(uint64_t n, const ProbeGrid grid, const float *sh, const float *moments, int d, float normal_bias,
+                                                              const float *points, const float *normals, float *rgb)
+{
+  const uint64_t i = (uint64_t) blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const float P[3] = {points[3 * i], points[3 * i + 1], points[3 * i + 2]}, N[3] = {normals[3 * i], normals[3 * i + 1], normals[3 * i + 2]};
+  float out[3];
+  probeVisGridShade(grid, sh, moments, d, normal_bias, P, N, out);
   rgb[3 * i] = out[0]; rgb[3 * i + 1] = out[1]; rgb[3 * i + 2] = out[2];
 }
 
@@ -156,7 +197,7 @@ static int ProbeChecks(qa_ctx *c, uint64_t n, bool points, const qa_probe_params
 
 // The batch, chunk after chunk on stream s (behind ProbeChecks; every array is the device's)
 static int ProbeBatch(qa_ctx *c, uint64_t n, const float *points, const uint32_t *stream, const qa_probe_params *p, float *sh, float *cube,
-                      uint32_t *hits, float *tmin, hipStream_t s)
+                      uint32_t *hits, float *tmin, hipStream_t s, const qa_probevis_params *vis = nullptr, float *moments = nullptr)
 {
   const uint64_t K = 6ull * p->m * p->m, per = ChunkProbes(p, n, K), rays = per * K;
   const qa_radiance_params rp = RadianceOf(p);
@@ -175,6 +216,11 @@ static int ProbeBatch(qa_ctx *c, uint64_t n, const float *points, const uint32_t
     const ProbeReduce red = {points, stream, first, count, (uint32_t) p->m, (uint32_t) K, p->seed, p->flags & QA_PROBE_JITTER, rgb, dT, cube ? rgb : nullptr, sh, hits, tmin};
     hipLaunchKernelGGL(qa_probe_project, dim3((unsigned) ((count + 3) / 4)), dim3(256), 0, s, red);
     HIP_TRY(hipGetLastError());
+    if (moments) {
+      const ProbeVisPool pool = {points, first, count, (uint32_t) p->m, (uint32_t) K, (uint32_t) vis->d, vis->dmax, dT, moments};
+      hipLaunchKernelGGL(qa_probevis_moments, dim3((unsigned) ((count * 6 * vis->d * vis->d + 255) / 256)), dim3(256), 0, s, pool);
+      HIP_TRY(hipGetLastError());
+    }
   }
   HIP_TRY(c->lastFrame.Record(s));
   return QA_OK;
@@ -196,6 +242,19 @@ static ProbeGrid GridOf(const float *origin, const float *spacing, const int32_t
   ProbeGrid g;
   for (int e = 0; e < 3; ++e) { g.origin[e] = origin[e]; g.spacing[e] = spacing[e]; g.counts[e] = counts[e]; }
   return g;
+}
+
+// qa_probevis_sh*: what qa_probe_sh* refuses, in its order and with its codes (sh is optional here), then the moments' own rules
+static int ProbeVisChecks(qa_ctx *c, uint64_t n, bool points, const qa_probe_params *p, const qa_probevis_params *v, bool moments)
+{
+  if (int rc = ProbeChecks(c, n, points, p, true)) return rc;
+  if (n == 0) return QA_OK;
+  if (!v) return Fail(QA_EINVAL, "null visibility params");
+  if (!moments) return Fail(QA_EINVAL, "null moments output");
+  if (v->d < 1 || v->d > p->m || p->m % v->d) return Fail(QA_EINVAL, "d must be 1 .. m and divide m");
+  if (!(v->dmax > 0.f) || !std::isfinite(v->dmax)) return Fail(QA_EINVAL, "dmax must be positive and finite");
+  if (!std::isfinite(v->normal_bias)) return Fail(QA_EINVAL, "normal_bias must be finite");
+  return QA_OK;
 }
 
 extern "C" {
@@ -274,7 +333,88 @@ int qa_probe_grid_shade_device(qa_ctx *c, uint64_t n, const float *d_sh, const f
   return QA_OK;
 }
 
+// ---- visibility: the moments beside the coefficients, and the shading that uses them
+
+int qa_probevis_params_default(qa_probevis_params *params)
+{
+  if (!params) return Fail(QA_EINVAL, "null argument");
+  params->d = 8;
+  params->dmax = 0.f;   // (refused as it stands: the caller says how far a probe looks)
+  params->normal_bias = 0.f;
+  return QA_OK;
+}
+
+int qa_probevis_sh_device(qa_ctx *c, uint64_t n, const float *d_points, const uint32_t *d_stream, const qa_probe_params *params,
+                          const qa_probevis_params *vis, float *d_sh, float *d_cube, uint32_t *d_hits, float *d_tmin, float *d_moments, void *stream)
+{
+  if (int rc = Enter(c)) return rc;
+  if (int rc = ProbeVisChecks(c, n, d_points != nullptr, params, vis, d_moments != nullptr)) return rc;
+  if (n == 0) return QA_OK;
+  return ProbeBatch(c, n, d_points, d_stream, params, d_sh, d_cube, d_hits, d_tmin, StreamOf(c, stream), vis, d_moments);
+}
+
+int qa_probevis_sh(qa_ctx *c, uint64_t n, const float *points, const uint32_t *stream_ids, const qa_probe_params *params,
+                   const qa_probevis_params *vis, float *sh, float *cube, uint32_t *hits, float *tmin, float *moments)
+{
+  if (int rc = Enter(c)) return rc;
+  if (int rc = ProbeVisChecks(c, n, points != nullptr, params, vis, moments != nullptr)) return rc;
+  if (n == 0) return QA_OK;
+  // qa_probe_sh's staging and, in floats per probe, 12 d^2 of moments behind it
+  const uint64_t K = 6ull * params->m * params->m, cells = 12ull * vis->d * vis->d;
+  HIP_TRY(c->stageQuery.Reserve((size_t) n * (33 + cells + (cube ? 3 * K : 0)) * sizeof(float)));
+  float *dSh = (float *) c->stageQuery.p;
+  uint32_t *dHits = (uint32_t *) (dSh + 27 * n);
+  float *dTmin = (float *) (dHits + n);
+  uint32_t *dStream = (uint32_t *) (dTmin + n);
+  float *dP = (float *) (dStream + n), *dMoments = dP + 3 * n, *dCube = cube ? dMoments + cells * n : nullptr;
+  HIP_TRY(hipMemcpyAsync(dP, points, n * 12, hipMemcpyHostToDevice, c->stream));
+  if (stream_ids) HIP_TRY(hipMemcpyAsync(dStream, stream_ids, n * 4, hipMemcpyHostToDevice, c->stream));
+  if (int rc = ProbeBatch(c, n, dP, stream_ids ? dStream : nullptr, params, dSh, dCube, dHits, dTmin, c->stream, vis, dMoments)) return rc;
+  if (sh) HIP_TRY(hipMemcpyAsync(sh, dSh, n * 108, hipMemcpyDeviceToHost, c->stream));
+  if (cube) HIP_TRY(hipMemcpyAsync(cube, dCube, n * K * 12, hipMemcpyDeviceToHost, c->stream));
+  if (hits) HIP_TRY(hipMemcpyAsync(hits, dHits, n * 4, hipMemcpyDeviceToHost, c->stream));
+  if (tmin) HIP_TRY(hipMemcpyAsync(tmin, dTmin, n * 4, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(moments, dMoments, n * cells * 4, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return DrainEvents(c);
+}
+
+int qa_probevis_grid_shade_device(qa_ctx *c, uint64_t n, const float *d_sh, const float *d_moments, int d, const float *origin, const float *spacing,
+                                  const int32_t *counts, const float *d_points, const float *d_normals, const qa_probevis_params *params,
+                                  float *d_rgb, void *stream)
+{
+  if (int rc = Enter(c)) return rc;
+  if (!GridOk(origin, spacing, counts)) return Fail(QA_EINVAL, "bad grid: finite origin, spacing > 0, counts >= 1, at most 2^31 - 1 probes");
+  if (!params || !std::isfinite(params->normal_bias)) return Fail(QA_EINVAL, "null params or a normal_bias that is not finite");
+  if (d < 1 || d > QA_PROBE_MAX_M) return Fail(QA_EINVAL, "d must be 1 .. 128");
+  if (n == 0) return QA_OK;
+  if (n > QA_MAX_RAYS) return Fail(QA_EINVAL, "more than 2^31 - 1 shading points");
+  if (!d_sh || !d_moments || !d_points || !d_normals || !d_rgb) return Fail(QA_EINVAL, "null array");
+  hipLaunchKernelGGL(qa_probevis_grid_shade, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, StreamOf(c, stream), n, GridOf(origin, spacing, counts), d_sh,
+                     d_moments, d, params->normal_bias, d_points, d_normals, d_rgb);
+  HIP_TRY(hipGetLastError());
+  return QA_OK;
+}
+
 // ---- the same source on the CPU (no GPU and no context needed)
+
+int qa_test_probevis_moments_host(int m, int d, float dmax, const float *t, float *out)
+{
+  if (m < 1 || m > QA_PROBE_MAX_M || d < 1 || d > m || m % d || !(dmax > 0.f) || !std::isfinite(dmax) || !t || !out) return QA_EINVAL;
+  for (uint32_t cell = 0; cell < 6u * (uint32_t) d * (uint32_t) d; ++cell) probeVisMoments((uint32_t) m, (uint32_t) d, dmax, t, cell, out + 2 * cell);
+  return QA_OK;
+}
+
+int qa_test_probevis_grid_shade_host(uint64_t n, const float *sh, const float *moments, int d, const float *origin, const float *spacing, const int32_t *counts,
+                                     const float *points, const float *normals, const qa_probevis_params *params, float *rgb)
+{
+  if (!GridOk(origin, spacing, counts) || !params || !std::isfinite(params->normal_bias) || d < 1 || d > QA_PROBE_MAX_M) return QA_EINVAL;
+  if (n == 0) return QA_OK;
+  if (!sh || !moments || !points || !normals || !rgb) return QA_EINVAL;
+  const ProbeGrid g = GridOf(origin, spacing, counts);
+  for (uint64_t i = 0; i < n; ++i) probeVisGridShade(g, sh, moments, d, params->normal_bias, points + 3 * i, normals + 3 * i, rgb + 3 * i);
+  return QA_OK;
+}
 
 // the n probes with stream ids stream [n]: d [n][K][3], w [n][K], ray_stream [n][K] (each may be null, not all)
 int qa_test_probe_directions_host(int m, uint32_t seed, uint32_t flags, const uint32_t *stream, uint64_t n, float *d, float *w, uint32_t *ray_stream)

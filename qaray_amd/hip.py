@@ -195,6 +195,29 @@ class ProbeParams(C.Structure):   # qa_probe_params; ProbeParams.default() = qa_
         return p
 
 
+class ProbeVisParams(C.Structure):   # qa_probevis_params; ProbeVisParams.default() = qa_probevis_params_default
+    _fields_ = [("d", C.c_int), ("dmax", C.c_float), ("normal_bias", C.c_float)]
+
+    @classmethod
+    def default(cls):
+        p = cls()
+        _check(lib().qa_probevis_params_default(C.byref(p)))
+        return p
+
+    @classmethod
+    def of(cls, d=None, dmax=None, normal_bias=None):
+        """The library's defaults (d 8, dmax 0 - which the calls refuse - normal_bias 0) with the arguments that are given written
+        over them."""
+        p = cls.default()
+        if d is not None:
+            p.d = int(d)
+        if dmax is not None:
+            p.dmax = float(dmax)
+        if normal_bias is not None:
+            p.normal_bias = float(normal_bias)
+        return p
+
+
 def _photon_maps_option(call, options):
     """The one keyword the point queries and bake_light take beyond their listed parameters: photon_maps (default False)."""
     unknown = sorted(set(options) - {"photon_maps"})
@@ -481,6 +504,12 @@ def lib():
         L.qa_test_probe_project_host.argtypes = [C.c_uint64] + [C.c_void_p] * 7
         L.qa_test_probe_shade_host.argtypes = [C.c_uint64, C.c_void_p, C.c_uint64] + [C.c_void_p] * 3
         L.qa_test_probe_grid_shade_host.argtypes = [C.c_uint64] + [C.c_void_p] * 7
+        L.qa_probevis_params_default.argtypes = [C.POINTER(ProbeVisParams)]
+        L.qa_probevis_sh_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(ProbeParams), C.POINTER(ProbeVisParams)] + [C.c_void_p] * 6
+        L.qa_probevis_sh.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(ProbeParams), C.POINTER(ProbeVisParams)] + [C.c_void_p] * 5
+        L.qa_probevis_grid_shade_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.POINTER(ProbeVisParams)] + [C.c_void_p] * 2
+        L.qa_test_probevis_moments_host.argtypes = [C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p]
+        L.qa_test_probevis_grid_shade_host.argtypes = [C.c_uint64, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.POINTER(ProbeVisParams), C.c_void_p]
         L.qa_scene_edit_camera.argtypes = [C.c_void_p, C.c_void_p]
         for name in ("qa_scene_edit_lights", "qa_scene_edit_materials", "qa_scene_edit_instances"):
             getattr(L, name).argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
@@ -737,6 +766,47 @@ def probe_grid_shade_host(sh, origin, spacing, counts, points, normals):
     p, nr, n = _ray_arrays(points, normals)
     rgb = np.zeros((n, 3), np.float32)
     _check(lib().qa_test_probe_grid_shade_host(n, sh.ctypes.data, o.ctypes.data, sp.ctypes.data, cn.ctypes.data, p.ctypes.data, nr.ctypes.data, rgb.ctypes.data))
+    return rgb
+
+
+def probevis_moments_host(t, m, d, dmax):
+    """qa_test_probevis_moments_host: the hit parameters t (6 m^2,) of one probe's rays (probe_directions_host's order; a miss is
+    QA_RAY_MISS) -> float32 (6, d, d, 2): per direction cell the mean of min(t, dmax) and of its square over the (m / d)^2 texels
+    the cell pools.  No GPU needed."""
+    m, d = int(m), int(d)
+    t = np.ascontiguousarray(t, dtype=np.float32).reshape(-1)
+    if not 1 <= m <= QA_PROBE_MAX_M or not 1 <= d <= m or m % d:
+        raise ValueError(f"1 <= d <= m <= {QA_PROBE_MAX_M} with m % d == 0 is expected, not m {m}, d {d}")
+    if t.shape != (6 * m * m,):
+        raise ValueError(f"t: {6 * m * m} values are expected, not {t.shape}")
+    out = np.zeros((6, d, d, 2), np.float32)
+    _check(lib().qa_test_probevis_moments_host(m, d, float(dmax), t.ctypes.data, out.ctypes.data))
+    return out
+
+
+def _probevis_moments_array(moments, probes):
+    mo = np.ascontiguousarray(moments, dtype=np.float32)
+    if mo.ndim != 5 or mo.shape[1] != 6 or mo.shape[2] != mo.shape[3] or mo.shape[4] != 2 or not 1 <= mo.shape[2] <= QA_PROBE_MAX_M:
+        raise ValueError(f"moments: shape (probes, 6, d, d, 2) is expected, not {mo.shape}")
+    if len(mo) != probes:
+        raise ValueError(f"moments: {probes} probes are expected, not {len(mo)}")
+    return mo, int(mo.shape[2])
+
+
+def probevis_grid_shade_host(sh, moments, origin, spacing, counts, points, normals, normal_bias=0.0):
+    """qa_test_probevis_grid_shade_host: ProbeGrid.shade_device(visibility=True) over host arrays - sh (nz * ny * nx, 9, 3) and
+    moments (nz * ny * nx, 6, d, d, 2) of the grid (origin, spacing, counts), points and normals (n, 3) -> rgb float32 (n, 3).  No
+    GPU needed."""
+    sh = _probe_sh_array(sh)
+    o, sp, cn = _probe_grid_args(origin, spacing, counts)
+    if (cn >= 1).all() and len(sh) != int(np.prod(cn.astype(np.int64))):
+        raise ValueError(f"sh: {int(np.prod(cn.astype(np.int64)))} probes are expected, not {len(sh)}")
+    mo, d = _probevis_moments_array(moments, len(sh))
+    p, nr, n = _ray_arrays(points, normals)
+    rgb = np.zeros((n, 3), np.float32)
+    par = ProbeVisParams.of(d, None, normal_bias)
+    _check(lib().qa_test_probevis_grid_shade_host(n, sh.ctypes.data, mo.ctypes.data, d, o.ctypes.data, sp.ctypes.data, cn.ctypes.data, p.ctypes.data,
+                                                  nr.ctypes.data, C.byref(par), rgb.ctypes.data))
     return rgb
 
 
@@ -2100,6 +2170,11 @@ class Context:
         none) -> dict of them.  A point that is not finite gives zeros.  photon_maps as radiance_rays_device's; chunk_rays: the
         rays traced at a time (0: 2^20), which bounds the scratch and changes no result.  Only enqueues (see render_region_device
         for the stream)."""
+        return self._probe_sh_device(points, m, spp, max_bounce, seed, jitter, photon_maps, stream_ids, sh, cube, hits, tmin, chunk_rays, stream)
+
+    def _probe_sh_device(self, points, m, spp, max_bounce, seed, jitter, photon_maps, stream_ids, sh, cube, hits, tmin, chunk_rays, stream, vis=None,
+                         moments=None):
+        """probe_sh_device, and with vis (ProbeVisParams) probevis_sh_device: the same arguments, checks and outputs, and the moments"""
         import torch
         dev = torch.device("cuda", self.device_id)
         if not isinstance(points, torch.Tensor):
@@ -2126,11 +2201,35 @@ class Context:
         p = ProbeParams.of(m, spp, max_bounce, seed, jitter, photon_maps, chunk_rays)
         sptr = self._stream_arg(stream, points)
         ptr = lambda a: None if a is None else (a.data_ptr() or None)   # noqa: E731
-        _check(lib().qa_probe_sh_device(self._h, n, ptr(points), ptr(stream_ids), C.byref(p), ptr(sh), ptr(cube), ptr(hits), ptr(tmin), sptr))
+        if vis is None:
+            _check(lib().qa_probe_sh_device(self._h, n, ptr(points), ptr(stream_ids), C.byref(p), ptr(sh), ptr(cube), ptr(hits), ptr(tmin), sptr))
+        else:
+            d = int(vis.d)
+            if not 1 <= d <= m or m % d:
+                raise ValueError(f"d: a divisor of m = {m} is expected, not {d}")
+            moments = torch.empty((n, 6, d, d, 2), dtype=torch.float32, device=dev) if moments is None else moments
+            _ray_tensor("moments", moments, (n, 6, d, d, 2), torch.float32, dev)
+            _check(lib().qa_probevis_sh_device(self._h, n, ptr(points), ptr(stream_ids), C.byref(p), C.byref(vis), ptr(sh), ptr(cube), ptr(hits), ptr(tmin),
+                                               ptr(moments), sptr))
         out = {"sh": sh, "hits": hits, "tmin": tmin}
         if cube is not None:
             out["cube"] = cube
+        if vis is not None:
+            out["moments"] = moments
         return out
+
+    def probevis_sh_device(self, points, d=8, dmax=None, m=16, spp=1, max_bounce=5, seed=DEFAULT_SEED, jitter=False, photon_maps=False, stream_ids=None,
+                           sh=None, cube=None, hits=None, tmin=None, chunk_rays=0, stream=None, moments=None):
+        """qa_probevis_sh_device: probe_sh_device (its arguments, its outputs, their bits) and, from the same rays, the probes'
+        distance moments for ProbeGrid.shade_device(visibility=True): moments float32 [n,6,d,d,2] (given, or allocated), a cube map
+        of d x d cells per face (d divides m), each holding the mean of min(t, dmax) and of its square over the (m / d)^2 rays it
+        pools; a miss counts as dmax, a void probe stores zeros.  dmax > 0 is the caller's: how far a probe needs to see (a grid
+        takes 1.5 times its cell's diagonal).  No ray is traced beyond probe_sh_device's.  -> its dict and "moments".  Only
+        enqueues."""
+        if dmax is None:
+            raise ValueError("dmax: how far a probe looks is expected (ProbeGrid.bake(visibility=True) takes 1.5 |spacing|)")
+        return self._probe_sh_device(points, m, spp, max_bounce, seed, jitter, photon_maps, stream_ids, sh, cube, hits, tmin, chunk_rays, stream,
+                                     ProbeVisParams.of(d, dmax), moments)
 
     def probe_sh(self, points, m=16, spp=1, max_bounce=5, seed=DEFAULT_SEED, jitter=False, photon_maps=False, stream_ids=None, cube=False,
                  chunk_rays=0):
@@ -2153,6 +2252,32 @@ class Context:
         par = ProbeParams.of(m, spp, max_bounce, seed, jitter, photon_maps, chunk_rays)
         _check(lib().qa_probe_sh(self._h, n, p.ctypes.data, _ptr(sid), C.byref(par), out["sh"].ctypes.data, _ptr(out.get("cube")), out["hits"].ctypes.data,
                                  out["tmin"].ctypes.data))
+        return out
+
+    def probevis_sh(self, points, d=8, dmax=None, m=16, spp=1, max_bounce=5, seed=DEFAULT_SEED, jitter=False, photon_maps=False, stream_ids=None,
+                    cube=False, chunk_rays=0):
+        """qa_probevis_sh: probevis_sh_device from and to host memory -> probe_sh's dict and moments [n,6,d,d,2] f32.  Synchronises."""
+        if dmax is None:
+            raise ValueError("dmax: how far a probe looks is expected (ProbeGrid.bake(visibility=True) takes 1.5 |spacing|)")
+        p = np.ascontiguousarray(points, dtype=np.float32)
+        n = _ray_count("points", p)
+        m, d = int(m), int(d)
+        if not 1 <= m <= QA_PROBE_MAX_M:
+            raise ValueError(f"m: 1 .. {QA_PROBE_MAX_M} is expected, not {m}")
+        if not 1 <= d <= m or m % d:
+            raise ValueError(f"d: a divisor of m = {m} is expected, not {d}")
+        sid = None
+        if stream_ids is not None:
+            sid = np.ascontiguousarray(stream_ids, dtype=np.uint32)
+            if sid.shape != (n,):
+                raise ValueError(f"stream_ids: shape ({n},) is expected, not {sid.shape}")
+        out = {"sh": np.zeros((n, 9, 3), np.float32), "hits": np.zeros(n, np.uint32), "tmin": np.zeros(n, np.float32),
+               "moments": np.zeros((n, 6, d, d, 2), np.float32)}
+        if cube:
+            out["cube"] = np.zeros((n, 6, m, m, 3), np.float32)
+        par, vis = ProbeParams.of(m, spp, max_bounce, seed, jitter, photon_maps, chunk_rays), ProbeVisParams.of(d, dmax)
+        _check(lib().qa_probevis_sh(self._h, n, p.ctypes.data, _ptr(sid), C.byref(par), C.byref(vis), out["sh"].ctypes.data, _ptr(out.get("cube")),
+                                    out["hits"].ctypes.data, out["tmin"].ctypes.data, out["moments"].ctypes.data))
         return out
 
     def probe_shade_device(self, sh, normals, index=None, out=None, stream=None):
@@ -2775,7 +2900,9 @@ class ProbeGrid:
     """A regular grid of light probes over a Context's scene: probe (iz * ny + iy) * nx + ix stands at origin + (ix, iy, iz) *
     spacing.  bake() traces and projects them (Context.probe_sh_device) and keeps sh, hits and tmin on the device; shade_device()
     gives the diffuse light at any points from the trilinearly interpolated coefficients - what a viewer asks for the nodes it
-    moves with edit_instances.  hits and tmin tell which probes sit inside a wall or against one."""
+    moves with edit_instances.  hits and tmin tell which probes sit inside a wall or against one.  bake(visibility=True) also keeps
+    the probes' distance moments, and shade_device(visibility=True) then weighs each probe by whether it can see the point, so
+    that a wall between them stops the light."""
 
     def __init__(self, ctx, origin, spacing, counts):
         self.ctx = ctx
@@ -2785,7 +2912,7 @@ class ProbeGrid:
         self.probes = int(np.prod(self.counts.astype(np.int64)))
         if self.probes > QA_MAX_RAYS:
             raise ValueError("more than 2^31 - 1 probes")
-        self.sh = self.hits = self.tmin = None
+        self.sh = self.hits = self.tmin = self.moments = self.d = self.dmax = None
 
     def points(self):
         """-> the probes' positions, float32 (nz * ny * nx, 3) numpy, in the grid's order: origin + (ix, iy, iz) * spacing in fp32"""
@@ -2794,23 +2921,38 @@ class ProbeGrid:
         idx = np.stack([ix, iy, iz], axis=-1).reshape(-1, 3).astype(np.float32)
         return (self.origin + (idx * self.spacing).astype(np.float32)).astype(np.float32)
 
-    def bake(self, **kw):
+    def bake(self, visibility=False, d=8, dmax=None, **kw):
         """probe_sh_device on the grid's points (its keywords: m, spp, max_bounce, seed, jitter, photon_maps, chunk_rays, stream);
-        the results stay on the device as .sh [probes,9,3], .hits [probes] and .tmin [probes] -> self.  Only enqueues."""
+        the results stay on the device as .sh [probes,9,3], .hits [probes] and .tmin [probes] -> self.  visibility=True bakes with
+        probevis_sh_device and keeps .moments [probes,6,d,d,2] for shade_device(visibility=True); dmax=None becomes 1.5 |spacing|
+        (fp32: 1.5 times the cell's diagonal) and is kept as .dmax.  Without it .moments is None.  Only enqueues."""
         import torch
         pts = torch.from_numpy(self.points()).to(torch.device("cuda", self.ctx.device_id))
-        out = self.ctx.probe_sh_device(pts, **kw)
+        if visibility:
+            if dmax is None:
+                sp = self.spacing
+                dmax = np.float32(1.5) * np.sqrt(((sp[0] * sp[0] + sp[1] * sp[1]).astype(np.float32) + sp[2] * sp[2]).astype(np.float32)).astype(np.float32)
+            out = self.ctx.probevis_sh_device(pts, d=d, dmax=float(np.float32(dmax)), **kw)
+            self.moments, self.d, self.dmax = out["moments"], int(d), np.float32(dmax)
+        else:
+            out = self.ctx.probe_sh_device(pts, **kw)
+            self.moments = self.d = self.dmax = None
         self.sh, self.hits, self.tmin = out["sh"], out["hits"], out["tmin"]
         return self
 
-    def shade_device(self, points, normals, out=None, stream=None):
+    def shade_device(self, points, normals, out=None, stream=None, visibility=False, normal_bias=0.0):
         """qa_probe_grid_shade_device: the diffuse light at points (float32 [n,3] CUDA tensor) with unit normals [n,3] from the baked
         grid: the 27 coefficients interpolated trilinearly between the probes of the point's cell (points outside take the
         nearest cell's edge), shaded as Context.probe_shade_device shades -> out float32 [n,3] (given, or allocated).  A point
-        or normal that is not finite shades to 0.  Only enqueues."""
+        or normal that is not finite shades to 0.  visibility=True (qa_probevis_grid_shade_device; the grid was baked with
+        visibility=True) weighs each of the cell's eight probes by its trilinear weight, a wrapped cosine towards the probe and
+        the Chebyshev bound, from the probe's distance moments, on what it sees at the point's distance - a probe behind a wall
+        keeps a floor of 0.05 - and normalises; the point is moved by normal_bias * normal for that test.  Only enqueues."""
         import torch
         if self.sh is None:
             raise ValueError("the grid is not baked: bake() first")
+        if visibility and self.moments is None:
+            raise ValueError("the grid has no moments: bake(visibility=True) first")
         dev = torch.device("cuda", self.ctx.device_id)
         if not isinstance(points, torch.Tensor):
             raise TypeError(f"points: a torch tensor is expected, not {type(points).__name__}")
@@ -2820,6 +2962,12 @@ class ProbeGrid:
         out = torch.empty((n, 3), dtype=torch.float32, device=dev) if out is None else out
         _ray_tensor("out", out, (n, 3), torch.float32, dev)
         sptr = Context._stream_arg(stream, points)
+        if visibility:
+            par = ProbeVisParams.of(self.d, float(self.dmax), normal_bias)
+            _check(lib().qa_probevis_grid_shade_device(self.ctx._h, n, self.sh.data_ptr(), self.moments.data_ptr(), self.d, self.origin.ctypes.data,
+                                                       self.spacing.ctypes.data, self.counts.ctypes.data, points.data_ptr() or None,
+                                                       normals.data_ptr() or None, C.byref(par), out.data_ptr() or None, sptr))
+            return out
         _check(lib().qa_probe_grid_shade_device(self.ctx._h, n, self.sh.data_ptr(), self.origin.ctypes.data, self.spacing.ctypes.data, self.counts.ctypes.data,
                                                 points.data_ptr() or None, normals.data_ptr() or None, out.data_ptr() or None, sptr))
         return out
