@@ -69,6 +69,9 @@
  *   qa_probe_grid_shade_device     free space, projected onto spherical harmonics - the light a moving object there receives)
  *   qa_probevis_sh*,               (no counterpart: the distances those rays travelled as two moments per direction cell, and a grid
  *   qa_probevis_grid_shade_device  shading that weighs each probe by whether it sees the shading point - no light through walls)
+ *   qa_reflprobe_prefilter_device, (no counterpart: a probe's cube map convolved with Phong lobes into a chain of ever smaller cube
+ *   qa_reflprobe_shade_device,     maps, and the lookup of a direction at a level in it, in one probe or blended over a grid's cell -
+ *   qa_reflprobe_grid_shade_device what a glossy Blinn material sees of its surroundings)
  *   qa_get_counters               (no counterpart: the reference only prints wall-clock)
  *   qa_get_kernel_time             Renderer::StartTimer/StopTimer       src/renderers/renderer.cpp:42-63
  */
@@ -1131,6 +1134,48 @@ int qa_test_probevis_moments_host(int m, int d, float dmax, const float *t, floa
 int qa_test_probevis_grid_shade_host(uint64_t n, const float *sh, const float *moments, int d, const float *origin, const float *spacing,
                                      const int32_t *counts, const float *points, const float *normals,
                                      const qa_probevis_params *params, float *rgb);
+
+/* Reflection probes: a probe's cube map (d_cube of qa_probe_sh_device) prefiltered for glossy reflection - convolved with Phong lobes
+ * of decreasing sharpness into a chain of ever smaller cube maps - and the lookup of a direction at a level of that chain (the opening
+ * comment of qaray_amd/csrc/hip/qa_reflprobe_dev.h is the specification of every number below).  No ray is traced here.
+ *   qa_reflprobe_layout            m: the cube's texels per face edge, a power of two in 1 .. 128, lg = log2 m; levels: 1 .. lg + 1.
+ *                                  Level l has res[l] = m >> l texels per face edge and starts at texel offset[l] of a probe's chain;
+ *                                  level 0 is the cube itself, level l >= 1 the cube convolved with max(0, dot)^(2^squarings[l]),
+ *                                  squarings[l] = max(0, 2 (lg - l) - 1) (squarings[0] = 0: nothing is convolved there); *texels = T,
+ *                                  the chain's texels.  The three arrays hold `levels` entries; each output may be NULL.  Needs no
+ *                                  context.
+ *   qa_reflprobe_prefilter_device  d_cube [n][6][m][m][3] -> d_chain [n][T][3]: level 0 copied bit for bit, every texel of the others
+ *                                  the lobe-weighted, solid-angle-weighted mean of all 6 m^2 source texels, summed in ascending order.
+ *                                  A NaN texel reaches exactly the outputs whose lobe covers it; zeros stay zeros.
+ *   qa_reflprobe_shade_device      lookup i takes probe d_index[i] (int32; NULL: i; clamped into [0, probes)) of d_chain
+ *                                  [probes][T][3], the direction d_dirs[i] (any length) and the level d_level[i] (a float, clamped to
+ *                                  [0, levels - 1]) -> d_rgb [n][3]: bilinear inside the direction's face (coordinates clamp at the
+ *                                  face's edge), linear between the two levels.  A direction that is zero or not finite, or a level
+ *                                  that is NaN, answers 0.
+ *   qa_reflprobe_grid_shade_device the same from a regular grid (as qa_probe_grid_shade_device's: origin, spacing, counts in host
+ *                                  memory, d_chain in the grid's order): the lookups in the eight probes of the point's cell blended
+ *                                  trilinearly (x, then y, then z); a point on a probe takes that probe's answer.  A point that is not
+ *                                  finite answers 0.  No parallax correction, no visibility weighting.
+ * The three device calls read and write only arrays of the caller's and order nothing, as qa_probe_shade_device; they need no scene
+ * and only enqueue on stream (NULL = the context's stream).  A caller who prefilters a cube that qa_probe_sh_device is still writing
+ * puts both on one stream.
+ * Codes: n == 0 is QA_OK and launches nothing; QA_EINVAL for a NULL array, an m that is not a power of two in 1 .. 128, levels outside
+ * 1 .. lg + 1, n or probes beyond 2^31 - 1, probes == 0, probes < n without an index, or a bad grid (as qa_probe_grid_shade_device).  A
+ * refused call writes nothing. */
+int qa_reflprobe_layout(int m, int levels, uint32_t *offset, uint32_t *res, uint32_t *squarings, uint64_t *texels);
+int qa_reflprobe_prefilter_device(qa_ctx *ctx, uint64_t n, const float *d_cube, int m, int levels, float *d_chain, void *stream);
+int qa_reflprobe_shade_device(qa_ctx *ctx, uint64_t n, const float *d_chain, uint64_t probes, int m, int levels, const float *d_dirs,
+                              const float *d_level, const int32_t *d_index, float *d_rgb, void *stream);
+int qa_reflprobe_grid_shade_device(qa_ctx *ctx, uint64_t n, const float *d_chain, int m, int levels, const float *origin,
+                                   const float *spacing, const int32_t *counts, const float *d_points, const float *d_dirs,
+                                   const float *d_level, float *d_rgb, void *stream);
+/* Self-test hooks (qaray_amd/csrc/hip/qa_reflprobe_dev.h compiled for the host; no GPU and no context needed): the three calls above
+ * over host arrays, refusing what they refuse. */
+int qa_test_reflprobe_prefilter_host(uint64_t n, const float *cube, int m, int levels, float *chain);
+int qa_test_reflprobe_shade_host(uint64_t n, const float *chain, uint64_t probes, int m, int levels, const float *dirs, const float *level,
+                                 const int32_t *index, float *rgb);
+int qa_test_reflprobe_grid_shade_host(uint64_t n, const float *chain, int m, int levels, const float *origin, const float *spacing,
+                                      const int32_t *counts, const float *points, const float *dirs, const float *level, float *rgb);
 
 #ifdef __cplusplus
 }

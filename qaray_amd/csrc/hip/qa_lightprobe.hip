@@ -226,24 +226,6 @@ static int ProbeBatch(qa_ctx *c, uint64_t n, const float *points, const uint32_t
   return QA_OK;
 }
 
-static bool GridOk(const float *origin, const float *spacing, const int32_t *counts)
-{
-  if (!origin || !spacing || !counts) return false;
-  uint64_t total = 1;
-  for (int e = 0; e < 3; ++e) {
-    if (!std::isfinite(origin[e]) || !std::isfinite(spacing[e]) || !(spacing[e] > 0.f) || counts[e] < 1) return false;
-    total *= (uint64_t) counts[e];
-    if (total > QA_MAX_RAYS) return false;
-  }
-  return true;
-}
-static ProbeGrid GridOf(const float *origin, const float *spacing, const int32_t *counts)
-{
-  ProbeGrid g;
-  for (int e = 0; e < 3; ++e) { g.origin[e] = origin[e]; g.spacing[e] = spacing[e]; g.counts[e] = counts[e]; }
-  return g;
-}
-
 // qa_probevis_sh*: what qa_probe_sh* refuses, in its order and with its codes (sh is optional here), then the moments' own rules
 static int ProbeVisChecks(qa_ctx *c, uint64_t n, bool points, const qa_probe_params *p, const qa_probevis_params *v, bool moments)
 {

@@ -200,6 +200,25 @@ struct ProbeGrid {
   float origin[3], spacing[3];
   int32_t counts[3];
 };
+// a grid as the entry points take it - three host arrays - checked (finite origin, spacing > 0, counts >= 1, at most 2^31 - 1
+// probes) and packed: what the grid calls of qa_lightprobe.hip and qa_reflprobe.hip share
+inline bool GridOk(const float *origin, const float *spacing, const int32_t *counts)
+{
+  if (!origin || !spacing || !counts) return false;
+  uint64_t total = 1;
+  for (int e = 0; e < 3; ++e) {
+    if (!isfinite(origin[e]) || !isfinite(spacing[e]) || !(spacing[e] > 0.f) || counts[e] < 1) return false;
+    total *= (uint64_t) counts[e];
+    if (total > 0x7FFFFFFFull) return false;
+  }
+  return true;
+}
+inline ProbeGrid GridOf(const float *origin, const float *spacing, const int32_t *counts)
+{
+  ProbeGrid g;
+  for (int e = 0; e < 3; ++e) { g.origin[e] = origin[e]; g.spacing[e] = spacing[e]; g.counts[e] = counts[e]; }
+  return g;
+}
 // the shading of normal N at point P from the grid's coefficients sh [nz * ny * nx][27]
 __host__ __device__ __forceinline__ void probeGridShade(const ProbeGrid &G, const float *sh, const float P[3], const float N[3], float rgb[3])
 {

@@ -510,6 +510,13 @@ def lib():
         L.qa_probevis_grid_shade_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.POINTER(ProbeVisParams)] + [C.c_void_p] * 2
         L.qa_test_probevis_moments_host.argtypes = [C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p]
         L.qa_test_probevis_grid_shade_host.argtypes = [C.c_uint64, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.POINTER(ProbeVisParams), C.c_void_p]
+        L.qa_reflprobe_layout.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 4
+        L.qa_reflprobe_prefilter_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.qa_reflprobe_shade_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.c_int] + [C.c_void_p] * 5
+        L.qa_reflprobe_grid_shade_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 8
+        L.qa_test_reflprobe_prefilter_host.argtypes = [C.c_uint64, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        L.qa_test_reflprobe_shade_host.argtypes = [C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.c_int] + [C.c_void_p] * 4
+        L.qa_test_reflprobe_grid_shade_host.argtypes = [C.c_uint64, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 7
         L.qa_scene_edit_camera.argtypes = [C.c_void_p, C.c_void_p]
         for name in ("qa_scene_edit_lights", "qa_scene_edit_materials", "qa_scene_edit_instances"):
             getattr(L, name).argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
@@ -807,6 +814,95 @@ def probevis_grid_shade_host(sh, moments, origin, spacing, counts, points, norma
     par = ProbeVisParams.of(d, None, normal_bias)
     _check(lib().qa_test_probevis_grid_shade_host(n, sh.ctypes.data, mo.ctypes.data, d, o.ctypes.data, sp.ctypes.data, cn.ctypes.data, p.ctypes.data,
                                                   nr.ctypes.data, C.byref(par), rgb.ctypes.data))
+    return rgb
+
+
+def reflprobe_layout(m, levels=None):
+    """qa_reflprobe_layout: the chain of a reflection probe of m x m texels per face (a power of two in 1 .. 128) with `levels` levels
+    (None: log2 m + 1, down to one texel per face) -> dict: levels, offset uint32 (levels,) the first texel of each level, res uint32
+    (levels,) its texels per face edge m >> l, squarings uint32 (levels,) s with the level's Phong exponent 2^s (level 0 is the cube
+    itself: 0 there), texels T of a probe's chain.  No GPU needed."""
+    m = int(m)
+    if m < 1 or m > QA_PROBE_MAX_M or m & (m - 1):
+        raise ValueError(f"m: a power of two in 1 .. {QA_PROBE_MAX_M} is expected, not {m}")
+    lg = m.bit_length() - 1
+    levels = lg + 1 if levels is None else int(levels)
+    if not 1 <= levels <= lg + 1:
+        raise ValueError(f"levels: 1 .. {lg + 1} is expected for m = {m}, not {levels}")
+    offset, res, sq = (np.zeros(levels, np.uint32) for _ in range(3))
+    texels = C.c_uint64(0)
+    _check(lib().qa_reflprobe_layout(m, levels, offset.ctypes.data, res.ctypes.data, sq.ctypes.data, C.addressof(texels)))
+    return {"levels": levels, "offset": offset, "res": res, "squarings": sq, "texels": int(texels.value)}
+
+
+def reflprobe_level(glossiness, m, levels=None):
+    """The level of a chain at which a Blinn material of that glossiness looks: level l holds the Phong exponent 2^(2 (lg - l) - 1), and
+    a Blinn exponent alpha is about the Phong exponent alpha / 4 around the mirror direction, so
+    level = lg - (log2(glossiness / 4) + 1) / 2, clamped to [0, levels - 1] -> float32 array like glossiness.  An approximation for
+    choosing the argument of reflprobe_shade_device, not part of its specification.  numpy, host only."""
+    lay = reflprobe_layout(m, levels)
+    lg = int(m).bit_length() - 1
+    with np.errstate(all="ignore"):
+        g = np.asarray(glossiness, np.float64)
+        level = lg - (np.log2(g / 4.0) + 1.0) / 2.0
+    return np.clip(np.nan_to_num(level, nan=0.0), 0.0, lay["levels"] - 1).astype(np.float32)
+
+
+def _reflprobe_chain_array(chain, m, levels):
+    """A host chain (probes, T, 3) checked against its layout -> (chain, levels)"""
+    lay = reflprobe_layout(m, levels)
+    chain = np.ascontiguousarray(chain, dtype=np.float32)
+    if chain.ndim != 3 or chain.shape[1:] != (lay["texels"], 3):
+        raise ValueError(f"chain: shape (probes, {lay['texels']}, 3) is expected, not {chain.shape}")
+    return chain, lay["levels"]
+
+
+def _reflprobe_lookup_arrays(dirs, level):
+    d = np.ascontiguousarray(dirs, dtype=np.float32)
+    n = _ray_count("dirs", d)
+    lv = np.ascontiguousarray(np.broadcast_to(np.asarray(level, np.float32), (n,)))
+    return d, lv, n
+
+
+def reflprobe_prefilter_host(cube, levels=None):
+    """qa_test_reflprobe_prefilter_host: Context.reflprobe_prefilter_device over a host array - cube (n, 6, m, m, 3) -> chain float32
+    (n, T, 3).  No GPU needed."""
+    cube = np.ascontiguousarray(cube, dtype=np.float32)
+    if cube.ndim != 5 or cube.shape[1] != 6 or cube.shape[2] != cube.shape[3] or cube.shape[4] != 3:
+        raise ValueError(f"cube: shape (n, 6, m, m, 3) is expected, not {cube.shape}")
+    n, m = int(cube.shape[0]), int(cube.shape[2])
+    lay = reflprobe_layout(m, levels)
+    chain = np.zeros((n, lay["texels"], 3), np.float32)
+    _check(lib().qa_test_reflprobe_prefilter_host(n, cube.ctypes.data, m, lay["levels"], chain.ctypes.data))
+    return chain
+
+
+def reflprobe_shade_host(chain, m, dirs, level, levels=None, index=None):
+    """qa_test_reflprobe_shade_host: Context.reflprobe_shade_device over host arrays - chain (probes, T, 3), dirs (n, 3), level (n,) or a
+    number, index (n,) int32 or None (lookup i takes probe i) -> rgb float32 (n, 3).  No GPU needed."""
+    chain, levels = _reflprobe_chain_array(chain, m, levels)
+    d, lv, n = _reflprobe_lookup_arrays(dirs, level)
+    if index is not None:
+        index = np.ascontiguousarray(index, dtype=np.int32)
+        if index.shape != (n,):
+            raise ValueError(f"index: shape ({n},) is expected, not {index.shape}")
+    rgb = np.zeros((n, 3), np.float32)
+    _check(lib().qa_test_reflprobe_shade_host(n, chain.ctypes.data, len(chain), int(m), levels, d.ctypes.data, lv.ctypes.data, _ptr(index), rgb.ctypes.data))
+    return rgb
+
+
+def reflprobe_grid_shade_host(chain, m, origin, spacing, counts, points, dirs, level, levels=None):
+    """qa_test_reflprobe_grid_shade_host: ProbeGrid.reflect_device over host arrays - chain (nz * ny * nx, T, 3) of the grid (origin,
+    spacing, counts), points and dirs (n, 3), level (n,) or a number -> rgb float32 (n, 3).  No GPU needed."""
+    chain, levels = _reflprobe_chain_array(chain, m, levels)
+    o, sp, cn = _probe_grid_args(origin, spacing, counts)
+    if (cn >= 1).all() and len(chain) != int(np.prod(cn.astype(np.int64))):
+        raise ValueError(f"chain: {int(np.prod(cn.astype(np.int64)))} probes are expected, not {len(chain)}")
+    p, d, n = _ray_arrays(points, dirs)
+    lv = np.ascontiguousarray(np.broadcast_to(np.asarray(level, np.float32), (n,)))
+    rgb = np.zeros((n, 3), np.float32)
+    _check(lib().qa_test_reflprobe_grid_shade_host(n, chain.ctypes.data, int(m), levels, o.ctypes.data, sp.ctypes.data, cn.ctypes.data, p.ctypes.data,
+                                                   d.ctypes.data, lv.ctypes.data, rgb.ctypes.data))
     return rgb
 
 
@@ -2309,6 +2405,62 @@ class Context:
         _check(lib().qa_probe_shade_device(self._h, n, ptr(sh), probes, ptr(normals), ptr(index), ptr(out), sptr))
         return out
 
+    # -- reflection probes (qa_reflprobe.hip) ------------------------------------------------------
+    def reflprobe_prefilter_device(self, cube, levels=None, chain=None, stream=None):
+        """qa_reflprobe_prefilter_device: probe cubes prefiltered for glossy reflection.  cube: float32 [n,6,m,m,3] contiguous CUDA
+        tensor (probe_sh_device's cube; m a power of two); levels: 1 .. log2 m + 1 (None: all, down to one texel per face) -> chain
+        float32 [n,T,3] (given, or allocated; hip.reflprobe_layout says where each level lies): level 0 is the cube bit for bit,
+        level l the cube at m >> l texels per face edge convolved with the Phong lobe of exponent 2^(2 (log2 m - l) - 1).  Reads and
+        writes only these arrays and orders nothing: after probe_sh_device, pass its stream.  Only enqueues."""
+        import torch
+        dev = torch.device("cuda", self.device_id)
+        if not isinstance(cube, torch.Tensor):
+            raise TypeError(f"cube: a torch tensor is expected, not {type(cube).__name__}")
+        if cube.ndim != 5 or tuple(cube.shape[1:2]) != (6,) or cube.shape[2] != cube.shape[3] or cube.shape[4] != 3:
+            raise ValueError(f"cube: shape (n, 6, m, m, 3) is expected, not {tuple(cube.shape)}")
+        n, m = int(cube.shape[0]), int(cube.shape[2])
+        if n > QA_MAX_RAYS:
+            raise ValueError("cube: more than 2^31 - 1 probes")
+        lay = reflprobe_layout(m, levels)
+        _ray_tensor("cube", cube, (n, 6, m, m, 3), torch.float32, dev)
+        chain = torch.empty((n, lay["texels"], 3), dtype=torch.float32, device=dev) if chain is None else chain
+        _ray_tensor("chain", chain, (n, lay["texels"], 3), torch.float32, dev)
+        sptr = self._stream_arg(stream, cube)
+        _check(lib().qa_reflprobe_prefilter_device(self._h, n, cube.data_ptr() or None, m, lay["levels"], chain.data_ptr() or None, sptr))
+        return chain
+
+    def reflprobe_shade_device(self, chain, m, dirs, level, levels=None, index=None, out=None, stream=None):
+        """qa_reflprobe_shade_device: what a glossy surface sees in probes.  chain: float32 [probes,T,3] (reflprobe_prefilter_device's,
+        of cubes of m x m texels with `levels` levels, None: all); dirs: float32 [n,3] the reflected directions, any length; level:
+        float32 [n], clamped to [0, levels - 1] (hip.reflprobe_level gives it for a glossiness); index: int32 [n] the probe of each
+        lookup (None: lookup i takes probe i, probes >= n), clamped into [0, probes) -> out float32 [n,3] (given, or allocated):
+        bilinear inside the direction's face, linear between the two levels.  A direction that is zero or not finite, or a level
+        that is NaN, gives 0.  Only enqueues."""
+        import torch
+        dev = torch.device("cuda", self.device_id)
+        lay = reflprobe_layout(m, levels)
+        if not isinstance(chain, torch.Tensor):
+            raise TypeError(f"chain: a torch tensor is expected, not {type(chain).__name__}")
+        if chain.ndim != 3 or tuple(chain.shape[1:]) != (lay["texels"], 3):
+            raise ValueError(f"chain: shape (probes, {lay['texels']}, 3) is expected, not {tuple(chain.shape)}")
+        probes = int(chain.shape[0])
+        _ray_tensor("chain", chain, (probes, lay["texels"], 3), torch.float32, dev)
+        if not isinstance(dirs, torch.Tensor):
+            raise TypeError(f"dirs: a torch tensor is expected, not {type(dirs).__name__}")
+        n = _ray_count("dirs", dirs)
+        _ray_tensor("dirs", dirs, (n, 3), torch.float32, dev)
+        _ray_tensor("level", level, (n,), torch.float32, dev)
+        if index is not None:
+            _ray_tensor("index", index, (n,), torch.int32, dev)
+        elif probes < n:
+            raise ValueError(f"chain: {n} probes are expected without an index, not {probes}")
+        out = torch.empty((n, 3), dtype=torch.float32, device=dev) if out is None else out
+        _ray_tensor("out", out, (n, 3), torch.float32, dev)
+        sptr = self._stream_arg(stream, dirs)
+        ptr = lambda a: None if a is None else (a.data_ptr() or None)   # noqa: E731
+        _check(lib().qa_reflprobe_shade_device(self._h, n, ptr(chain), probes, int(m), lay["levels"], ptr(dirs), ptr(level), ptr(index), ptr(out), sptr))
+        return out
+
     def camera_sample_rays_device(self, region, first=0, count=1, outputs=CAMERA_SAMPLE_OUTPUTS, stream=None, **given):
         """qa_camera_sample_rays_device: samples [first, first + count) of the camera rays of the pixels of a region, exactly as a
         frame builds them -> dict name -> CUDA tensor for the names in `outputs` (or the tensors passed by name): origins, dirs, dx,
@@ -2902,7 +3054,8 @@ class ProbeGrid:
     gives the diffuse light at any points from the trilinearly interpolated coefficients - what a viewer asks for the nodes it
     moves with edit_instances.  hits and tmin tell which probes sit inside a wall or against one.  bake(visibility=True) also keeps
     the probes' distance moments, and shade_device(visibility=True) then weighs each probe by whether it can see the point, so
-    that a wall between them stops the light."""
+    that a wall between them stops the light.  bake(reflections=True) also keeps the probes' prefiltered cube chains,
+    and reflect_device() gives what a glossy surface at a point sees in a direction."""
 
     def __init__(self, ctx, origin, spacing, counts):
         self.ctx = ctx
@@ -2912,7 +3065,7 @@ class ProbeGrid:
         self.probes = int(np.prod(self.counts.astype(np.int64)))
         if self.probes > QA_MAX_RAYS:
             raise ValueError("more than 2^31 - 1 probes")
-        self.sh = self.hits = self.tmin = self.moments = self.d = self.dmax = None
+        self.sh = self.hits = self.tmin = self.moments = self.d = self.dmax = self.chain = self.m = self.levels = None
 
     def points(self):
         """-> the probes' positions, float32 (nz * ny * nx, 3) numpy, in the grid's order: origin + (ix, iy, iz) * spacing in fp32"""
@@ -2921,13 +3074,21 @@ class ProbeGrid:
         idx = np.stack([ix, iy, iz], axis=-1).reshape(-1, 3).astype(np.float32)
         return (self.origin + (idx * self.spacing).astype(np.float32)).astype(np.float32)
 
-    def bake(self, visibility=False, d=8, dmax=None, **kw):
+    def bake(self, visibility=False, d=8, dmax=None, reflections=False, levels=None, **kw):
         """probe_sh_device on the grid's points (its keywords: m, spp, max_bounce, seed, jitter, photon_maps, chunk_rays, stream);
         the results stay on the device as .sh [probes,9,3], .hits [probes] and .tmin [probes] -> self.  visibility=True bakes with
         probevis_sh_device and keeps .moments [probes,6,d,d,2] for shade_device(visibility=True); dmax=None becomes 1.5 |spacing|
-        (fp32: 1.5 times the cell's diagonal) and is kept as .dmax.  Without it .moments is None.  Only enqueues."""
+        (fp32: 1.5 times the cell's diagonal) and is kept as .dmax.  Without it .moments is None.  reflections=True asks the same
+        bake for the cubes (m a power of two), prefilters them on the same stream (reflprobe_prefilter_device, `levels` levels, None:
+        all) and keeps .chain [probes,T,3], .m and .levels for reflect_device(); the cubes are dropped, level 0 being their copy.
+        Without it .chain is None.  The two combine, and neither changes a bit of the other outputs.  Only enqueues."""
         import torch
         pts = torch.from_numpy(self.points()).to(torch.device("cuda", self.ctx.device_id))
+        if reflections:
+            if kw.get("cube") is not None:
+                raise ValueError("cube: bake(reflections=True) asks for the cubes itself")
+            lay = reflprobe_layout(kw.get("m", 16), levels)   # (refused before anything is traced)
+            kw = dict(kw, cube=True)
         if visibility:
             if dmax is None:
                 sp = self.spacing
@@ -2938,6 +3099,11 @@ class ProbeGrid:
             out = self.ctx.probe_sh_device(pts, **kw)
             self.moments = self.d = self.dmax = None
         self.sh, self.hits, self.tmin = out["sh"], out["hits"], out["tmin"]
+        if reflections:
+            self.chain = self.ctx.reflprobe_prefilter_device(out["cube"], lay["levels"], stream=kw.get("stream"))
+            self.m, self.levels = int(kw.get("m", 16)), lay["levels"]
+        else:
+            self.chain = self.m = self.levels = None
         return self
 
     def shade_device(self, points, normals, out=None, stream=None, visibility=False, normal_bias=0.0):
@@ -2970,4 +3136,29 @@ class ProbeGrid:
             return out
         _check(lib().qa_probe_grid_shade_device(self.ctx._h, n, self.sh.data_ptr(), self.origin.ctypes.data, self.spacing.ctypes.data, self.counts.ctypes.data,
                                                 points.data_ptr() or None, normals.data_ptr() or None, out.data_ptr() or None, sptr))
+        return out
+
+    def reflect_device(self, points, dirs, level, out=None, stream=None):
+        """qa_reflprobe_grid_shade_device: what a glossy surface at points (float32 [n,3] CUDA tensor) sees along dirs [n,3] (the
+        reflected directions, any length) at level [n] (float32; hip.reflprobe_level gives it for a glossiness) from the grid baked
+        with reflections=True: Context.reflprobe_shade_device's lookup in each of the eight probes of the point's cell, blended
+        trilinearly (points outside take the nearest cell's edge) -> out float32 [n,3] (given, or allocated).  A point on a probe
+        takes that probe's answer; a point or direction that is not finite, a zero direction or a NaN level gives 0.  Every probe is
+        asked for the same direction (no parallax correction), and a probe behind a wall counts as any other.  Only enqueues."""
+        import torch
+        if self.chain is None:
+            raise ValueError("the grid has no chains: bake(reflections=True) first")
+        dev = torch.device("cuda", self.ctx.device_id)
+        if not isinstance(points, torch.Tensor):
+            raise TypeError(f"points: a torch tensor is expected, not {type(points).__name__}")
+        n = _ray_count("points", points)
+        _ray_tensor("points", points, (n, 3), torch.float32, dev)
+        _ray_tensor("dirs", dirs, (n, 3), torch.float32, dev)
+        _ray_tensor("level", level, (n,), torch.float32, dev)
+        out = torch.empty((n, 3), dtype=torch.float32, device=dev) if out is None else out
+        _ray_tensor("out", out, (n, 3), torch.float32, dev)
+        sptr = Context._stream_arg(stream, points)
+        _check(lib().qa_reflprobe_grid_shade_device(self.ctx._h, n, self.chain.data_ptr(), self.m, self.levels, self.origin.ctypes.data,
+                                                    self.spacing.ctypes.data, self.counts.ctypes.data, points.data_ptr() or None, dirs.data_ptr() or None,
+                                                    level.data_ptr() or None, out.data_ptr() or None, sptr))
         return out
