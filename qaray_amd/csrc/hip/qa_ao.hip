@@ -19,6 +19,7 @@
 #include "qa_ctx.h"
 #include "qa_ao_dev.h"
 #include "qa_display_dev.h"
+#include "qa_stage.h"
 
 namespace qa {
 
@@ -244,20 +245,15 @@ int qa_ao_region(qa_ctx *c, int x0, int y0, int x1, int y1, uint32_t first, uint
   if (int rc = Enter(c)) return rc;
   const AoPlanes host = {open, rays, ao};
   if (int rc = CheckAo(c, x0, y0, x1, y1, first, spp, K, radius, host)) return rc;   // before anything is sized by the region
-  // staging [open 4 | rays 4 | ao 4 | ns 4] bytes per pixel: only grows, and is only used synchronously
   const size_t npix = (size_t) (x1 - x0) * (size_t) (y1 - y0);
-  HIP_TRY(c->stageQuery.Reserve(npix * 16));
-  uint32_t *dO = (uint32_t *) c->stageQuery.p, *dR = dO + npix;
-  float *dA = (float *) (dR + npix);
-  uint32_t *dS = (uint32_t *) (dA + npix);
-  if (ns) HIP_TRY(hipMemcpyAsync(dS, ns, npix * 4, hipMemcpyHostToDevice, c->stream));
-  const AoPlanes dev = {open ? dO : nullptr, rays ? dR : nullptr, ao ? dA : nullptr};
-  if (int rc = AoRegion(c, x0, y0, x1, y1, first, spp, ns ? dS : nullptr, nullptr, K, radius, seed, dev, c->stream)) return rc;
-  if (open) HIP_TRY(hipMemcpyAsync(open, dO, npix * 4, hipMemcpyDeviceToHost, c->stream));
-  if (rays) HIP_TRY(hipMemcpyAsync(rays, dR, npix * 4, hipMemcpyDeviceToHost, c->stream));
-  if (ao) HIP_TRY(hipMemcpyAsync(ao, dA, npix * 4, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return QA_OK;
+  QueryStage st(c);
+  const auto dS = st.In(ns, npix);
+  const auto dO = st.Out(open, npix), dR = st.Out(rays, npix);
+  const auto dA = st.Out(ao, npix);
+  if (int rc = st.Begin()) return rc;
+  const AoPlanes dev = {st(dO), st(dR), st(dA)};
+  if (int rc = AoRegion(c, x0, y0, x1, y1, first, spp, st(dS), nullptr, K, radius, seed, dev, c->stream)) return rc;
+  return st.End();
 }
 
 int qa_progressive_ao_device(qa_ctx *c, uint32_t K, float radius, uint32_t *d_open, uint32_t *d_rays, float *d_ao, void *stream)
@@ -286,20 +282,14 @@ int qa_ao_points(qa_ctx *c, uint64_t n, const float *points, const float *normal
   if (int rc = Enter(c)) return rc;
   if (int rc = CheckAoPoints(c, n, points && normals, open || ao, first, K, radius)) return rc;   // before anything is sized by n
   if (n == 0) return QA_OK;
-  // staging [points 12 | normals 12 | stream ids 4 | open 4 | ao 4] bytes per point
-  HIP_TRY(c->stageQuery.Reserve((size_t) n * 36));
-  float *dP = (float *) c->stageQuery.p, *dN = dP + 3 * n;
-  int32_t *dS = (int32_t *) (dN + 3 * n);
-  uint32_t *dO = (uint32_t *) (dS + n);
-  float *dA = (float *) (dO + n);
-  HIP_TRY(hipMemcpyAsync(dP, points, n * 12, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(dN, normals, n * 12, hipMemcpyHostToDevice, c->stream));
-  if (stream_ids) HIP_TRY(hipMemcpyAsync(dS, stream_ids, n * 4, hipMemcpyHostToDevice, c->stream));
-  if (int rc = AoPoints(c, n, dP, dN, stream_ids ? dS : nullptr, first, K, radius, seed, open ? dO : nullptr, ao ? dA : nullptr, c->stream)) return rc;
-  if (open) HIP_TRY(hipMemcpyAsync(open, dO, n * 4, hipMemcpyDeviceToHost, c->stream));
-  if (ao) HIP_TRY(hipMemcpyAsync(ao, dA, n * 4, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return QA_OK;
+  QueryStage st(c);
+  const auto dP = st.In(points, 3 * n), dN = st.In(normals, 3 * n);
+  const auto dS = st.In(stream_ids, n);
+  const auto dO = st.Out(open, n);
+  const auto dA = st.Out(ao, n);
+  if (int rc = st.Begin()) return rc;
+  if (int rc = AoPoints(c, n, st(dP), st(dN), st(dS), first, K, radius, seed, st(dO), st(dA), c->stream)) return rc;
+  return st.End();
 }
 
 int qa_ao_grey_device(qa_ctx *c, const float *d_ao, uint64_t npix, uint8_t *d_bytes, void *stream)

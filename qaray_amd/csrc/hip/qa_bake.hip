@@ -17,6 +17,7 @@
 
 #include "qa_ctx.h"
 #include "qa_bake_dev.h"
+#include "qa_stage.h"
 
 namespace qa {
 
@@ -305,20 +306,15 @@ int qa_bake_texels(qa_ctx *c, int node, int texmap, int mtl, uint32_t width, uin
   if (int rc = Enter(c)) return rc;
   BakeCall call;
   if (int rc = BakeCheck(c, node, texmap, mtl, width, height, point || normal || face || bary, call)) return rc;   // before anything is sized
-  // staging [point 12 | normal 12 | face 4 | bary 8] bytes per texel, the planes asked for only
   const size_t n = (size_t) width * height;
-  const size_t offN = point ? 12 * n : 0, offF = offN + (normal ? 12 * n : 0), offB = offF + (face ? 4 * n : 0), total = offB + (bary ? 8 * n : 0);
-  HIP_TRY(c->stageQuery.Reserve(total));
-  unsigned char *st = (unsigned char *) c->stageQuery.p;
-  const BakePlanes dev = {point ? (float *) st : nullptr, normal ? (float *) (st + offN) : nullptr, face ? (int32_t *) (st + offF) : nullptr,
-                          bary ? (float *) (st + offB) : nullptr};
+  QueryStage st(c);
+  const auto dP = st.Out(point, 3 * n), dN = st.Out(normal, 3 * n);
+  const auto dF = st.Out(face, n);
+  const auto dB = st.Out(bary, 2 * n);
+  if (int rc = st.Begin()) return rc;
+  const BakePlanes dev = {st(dP), st(dN), st(dF), st(dB)};
   if (int rc = BakeTexels(c, call, node, width, height, dev, c->stream)) return rc;
-  if (point) HIP_TRY(hipMemcpyAsync(point, dev.point, 12 * n, hipMemcpyDeviceToHost, c->stream));
-  if (normal) HIP_TRY(hipMemcpyAsync(normal, dev.normal, 12 * n, hipMemcpyDeviceToHost, c->stream));
-  if (face) HIP_TRY(hipMemcpyAsync(face, dev.face, 4 * n, hipMemcpyDeviceToHost, c->stream));
-  if (bary) HIP_TRY(hipMemcpyAsync(bary, dev.bary, 8 * n, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return QA_OK;
+  return st.End();
 }
 
 static int CheckDilate(const uint8_t *rgb8, const int32_t *face, uint32_t W, uint32_t H, uint32_t radius, const uint8_t *out)

@@ -190,8 +190,8 @@ struct qa_ctx {
   DCounters *dCounters = nullptr;
   // host-variant staging
   DevBuf stageRgb, stageDepth, stageNs;
-  DevBuf stageQuery;              // the host forms of the guide planes, the matte planes, the ray queries and the radiance queries: one buffer, sized
-                                  // for the largest call so far - each of them ends with hipStreamSynchronize(stream), so no two use it at once
+  DevBuf stageQuery;              // the host forms of every query: one buffer, carved by QueryStage (qa_stage.h) and by nothing else, sized for the
+                                  // largest call so far - each of them ends with hipStreamSynchronize(stream), so no two use it at once
   // timing
   std::vector<EventPair> pending, freeEvents;
   double totalMs = 0;

@@ -11,6 +11,7 @@
 
 #include "qa_firsthit.h"
 #include "qa_ctx.h"
+#include "qa_stage.h"
 
 namespace qa {
 
@@ -115,19 +116,13 @@ int qa_gbuffer_region(qa_ctx *c, int x0, int y0, int x1, int y1, uint32_t seed, 
   if (int rc = Enter(c)) return rc;
   if (int rc = CheckRegion(c, x0, y0, x1, y1)) return rc;   // (as GBuffer does) before anything is sized by the region
   if (!normal && !albedo && !depth && !ids) return Fail(QA_EINVAL, "no output plane");
-  // staging [normal 12 | albedo 12 | depth 4 | ids 8] bytes per pixel: only grows, and is only used synchronously
   const size_t npix = (size_t) (x1 - x0) * (size_t) (y1 - y0);
-  HIP_TRY(c->stageQuery.Reserve(npix * 36));
-  float *dN = (float *) c->stageQuery.p, *dA = dN + 3 * npix, *dZ = dA + 3 * npix;
-  int32_t *dI = (int32_t *) (dZ + npix);
-  if (int rc = GBuffer(c, x0, y0, x1, y1, seed, normal ? dN : nullptr, albedo ? dA : nullptr, depth ? dZ : nullptr, ids ? dI : nullptr, c->stream))
-    return rc;
-  if (normal) HIP_TRY(hipMemcpyAsync(normal, dN, npix * 12, hipMemcpyDeviceToHost, c->stream));
-  if (albedo) HIP_TRY(hipMemcpyAsync(albedo, dA, npix * 12, hipMemcpyDeviceToHost, c->stream));
-  if (depth) HIP_TRY(hipMemcpyAsync(depth, dZ, npix * 4, hipMemcpyDeviceToHost, c->stream));
-  if (ids) HIP_TRY(hipMemcpyAsync(ids, dI, npix * 8, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return QA_OK;
+  QueryStage st(c);
+  const auto dN = st.Out(normal, 3 * npix), dA = st.Out(albedo, 3 * npix), dZ = st.Out(depth, npix);
+  const auto dI = st.Out(ids, 2 * npix);
+  if (int rc = st.Begin()) return rc;
+  if (int rc = GBuffer(c, x0, y0, x1, y1, seed, st(dN), st(dA), st(dZ), st(dI), c->stream)) return rc;
+  return st.End();
 }
 
 int qa_progressive_gbuffer_device(qa_ctx *c, float *d_normal, float *d_albedo, float *d_depth, int32_t *d_ids, void *hip_stream)

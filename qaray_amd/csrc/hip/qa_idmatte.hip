@@ -13,6 +13,7 @@
 #include "qa_ctx.h"
 #include "qa_idmatte_dev.h"
 #include "qa_matte_dev.h"
+#include "qa_stage.h"
 
 namespace qa {
 
@@ -199,20 +200,15 @@ int qa_idmatte_region(qa_ctx *c, int x0, int y0, int x1, int y1, uint32_t spp, c
   if (int rc = Enter(c)) return rc;
   const IdMattePlanes host = {ids, counts, other, samples};
   if (int rc = CheckIdMatte(c, x0, y0, x1, y1, spp, key, host, false)) return rc;   // before anything is sized by the region
-  // staging [ids 32 | counts 32 | other 4 | samples 4 | ns 4] bytes per pixel: only grows, and is only used synchronously
   const size_t npix = (size_t) (x1 - x0) * (size_t) (y1 - y0);
-  HIP_TRY(c->stageQuery.Reserve(npix * 76));
-  int32_t *dI = (int32_t *) c->stageQuery.p;
-  uint32_t *dC = (uint32_t *) (dI + 8 * npix), *dO = dC + 8 * npix, *dN = dO + npix, *dS = dN + npix;
-  if (ns) HIP_TRY(hipMemcpyAsync(dS, ns, npix * 4, hipMemcpyHostToDevice, c->stream));
-  const IdMattePlanes dev = {ids ? dI : nullptr, counts ? dC : nullptr, other ? dO : nullptr, samples ? dN : nullptr};
-  if (int rc = IdMatte(c, x0, y0, x1, y1, spp, ns ? dS : nullptr, nullptr, key, dev, c->stream)) return rc;
-  if (ids) HIP_TRY(hipMemcpyAsync(ids, dI, npix * 32, hipMemcpyDeviceToHost, c->stream));
-  if (counts) HIP_TRY(hipMemcpyAsync(counts, dC, npix * 32, hipMemcpyDeviceToHost, c->stream));
-  if (other) HIP_TRY(hipMemcpyAsync(other, dO, npix * 4, hipMemcpyDeviceToHost, c->stream));
-  if (samples) HIP_TRY(hipMemcpyAsync(samples, dN, npix * 4, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return QA_OK;
+  QueryStage st(c);   // (every plane starts on a multiple of 16 bytes: what IdMatte asks of ids and counts)
+  const auto dS = st.In(ns, npix);
+  const auto dI = st.Out(ids, 8 * npix);
+  const auto dC = st.Out(counts, 8 * npix), dO = st.Out(other, npix), dN = st.Out(samples, npix);
+  if (int rc = st.Begin()) return rc;
+  const IdMattePlanes dev = {st(dI), st(dC), st(dO), st(dN)};
+  if (int rc = IdMatte(c, x0, y0, x1, y1, spp, st(dS), nullptr, key, dev, c->stream)) return rc;
+  return st.End();
 }
 
 int qa_progressive_idmatte_device(qa_ctx *c, int key, int32_t *d_ids, uint32_t *d_counts, uint32_t *d_other, uint32_t *d_samples, void *stream)

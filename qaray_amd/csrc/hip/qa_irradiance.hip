@@ -49,6 +49,7 @@
 // walked per lane.  A lightmap's rows against the frame's 8 x 8 tiles may cost coherence; recorded, not tuned.
 #include "qa_firsthit.h"
 #include "qa_raybatch.h"
+#include "qa_stage.h"
 
 // ---- the ten instances: qa_integrate_points<RES, LIGHTS, TEX, AREA> by the picker, the checks and the launch of qa_raybatch.h
 QA_DEFINE_RAYS_PICKER(PickPoints, qa_integrate_points)
@@ -76,19 +77,15 @@ int qa_irradiance_points(qa_ctx *c, uint64_t n, const float *points, const float
   if (int rc = Enter(c)) return rc;
   if (int rc = RayBatchChecks(c, n, points && normals, false, false, false, params, rgb != nullptr, QA_RADIANCE_PHOTON_MAPS, false)) return rc;
   if (n == 0) return QA_OK;
-  // staging, in floats per point: [rgb 3 | ns 1 | stream 1 | points 3 | normals 3]
-  HIP_TRY(c->stageQuery.Reserve((size_t) n * 11 * sizeof(float)));
-  float *dRgb = (float *) c->stageQuery.p;
-  uint32_t *dNs = (uint32_t *) (dRgb + 3 * n), *dStream = dNs + n;
-  float *dP = (float *) (dStream + n), *dN = dP + 3 * n;
-  HIP_TRY(hipMemcpyAsync(dP, points, n * 12, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(dN, normals, n * 12, hipMemcpyHostToDevice, c->stream));
-  if (stream_ids) HIP_TRY(hipMemcpyAsync(dStream, stream_ids, n * 4, hipMemcpyHostToDevice, c->stream));
-  const RayBatch rb = {dP, dN, nullptr, nullptr, nullptr, stream_ids ? dStream : nullptr, (uint32_t) n, 0u};
-  if (int rc = LaunchRayBatch(c, PickFor(c, params), n, rb, *params, dRgb, nullptr, nsamples ? dNs : nullptr, c->stream)) return rc;
-  HIP_TRY(hipMemcpyAsync(rgb, dRgb, n * 12, hipMemcpyDeviceToHost, c->stream));
-  if (nsamples) HIP_TRY(hipMemcpyAsync(nsamples, dNs, n * 4, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
+  QueryStage st(c);
+  const auto dP = st.In(points, 3 * n), dN = st.In(normals, 3 * n);
+  const auto dStream = st.In(stream_ids, n);
+  const auto dRgb = st.Out(rgb, 3 * n);
+  const auto dNs = st.Out(nsamples, n);
+  if (int rc = st.Begin()) return rc;
+  const RayBatch rb = {st(dP), st(dN), nullptr, nullptr, nullptr, st(dStream), (uint32_t) n, 0u};
+  if (int rc = LaunchRayBatch(c, PickFor(c, params), n, rb, *params, st(dRgb), nullptr, st(dNs), c->stream)) return rc;
+  if (int rc = st.End()) return rc;
   return DrainEvents(c);   // the batch is complete: fold its event pair into the kernel time
 }
 

@@ -17,6 +17,7 @@
 #include "qa_lightprobe_dev.h"
 #include "qa_probevis_dev.h"
 #include "qa_raybatch.h"
+#include "qa_stage.h"
 
 namespace qa {
 
@@ -239,6 +240,24 @@ static int ProbeVisChecks(qa_ctx *c, uint64_t n, bool points, const qa_probe_par
   return QA_OK;
 }
 
+// What both host forms do behind their checks (n > 0): stage, run the batch on the context's stream, copy back.  vis and moments are
+// null for the plain call
+static int ProbeHost(qa_ctx *c, uint64_t n, const float *points, const uint32_t *stream_ids, const qa_probe_params *params, const qa_probevis_params *vis,
+                     float *sh, float *cube, uint32_t *hits, float *tmin, float *moments)
+{
+  const uint64_t K = 6ull * params->m * params->m, cells = vis ? 12ull * vis->d * vis->d : 0;
+  QueryStage st(c);
+  const auto dP = st.In(points, 3 * n);
+  const auto dStream = st.In(stream_ids, n);
+  const auto dSh = st.Out(sh, 27 * n), dCube = st.Out(cube, 3 * K * n);
+  const auto dHits = st.Out(hits, n);
+  const auto dTmin = st.Out(tmin, n), dMoments = st.Out(moments, cells * n);
+  if (int rc = st.Begin()) return rc;
+  if (int rc = ProbeBatch(c, n, st(dP), st(dStream), params, st(dSh), st(dCube), st(dHits), st(dTmin), c->stream, vis, st(dMoments))) return rc;
+  if (int rc = st.End()) return rc;
+  return DrainEvents(c);   // the chunks are complete: fold their event pairs into the kernel time
+}
+
 extern "C" {
 
 int qa_probe_params_default(qa_probe_params *params)
@@ -259,7 +278,7 @@ int qa_probe_sh_device(qa_ctx *c, uint64_t n, const float *d_points, const uint3
   if (int rc = Enter(c)) return rc;
   if (int rc = ProbeChecks(c, n, d_points != nullptr, params, d_sh != nullptr)) return rc;
   if (n == 0) return QA_OK;
-  return ProbeBatch(c, n, d_points, d_stream, params, d_sh, d_cube, d_hits, d_tmin, StreamOf(c, stream));
+  return ProbeBatch(c, n, d_points, d_stream, params, d_sh, d_cube, d_hits, d_tmin, StreamOf(c, stream), nullptr, nullptr);
 }
 
 int qa_probe_sh(qa_ctx *c, uint64_t n, const float *points, const uint32_t *stream_ids, const qa_probe_params *params, float *sh, float *cube,
@@ -268,23 +287,7 @@ int qa_probe_sh(qa_ctx *c, uint64_t n, const float *points, const uint32_t *stre
   if (int rc = Enter(c)) return rc;
   if (int rc = ProbeChecks(c, n, points != nullptr, params, sh != nullptr)) return rc;
   if (n == 0) return QA_OK;
-  // staging, in floats per probe: [sh 27 | hits 1 | tmin 1 | stream 1 | point 3] and, with a cube, 3 K more
-  const uint64_t K = 6ull * params->m * params->m;
-  HIP_TRY(c->stageQuery.Reserve((size_t) n * (33 + (cube ? 3 * K : 0)) * sizeof(float)));
-  float *dSh = (float *) c->stageQuery.p;
-  uint32_t *dHits = (uint32_t *) (dSh + 27 * n);
-  float *dTmin = (float *) (dHits + n);
-  uint32_t *dStream = (uint32_t *) (dTmin + n);
-  float *dP = (float *) (dStream + n), *dCube = cube ? dP + 3 * n : nullptr;
-  HIP_TRY(hipMemcpyAsync(dP, points, n * 12, hipMemcpyHostToDevice, c->stream));
-  if (stream_ids) HIP_TRY(hipMemcpyAsync(dStream, stream_ids, n * 4, hipMemcpyHostToDevice, c->stream));
-  if (int rc = ProbeBatch(c, n, dP, stream_ids ? dStream : nullptr, params, dSh, dCube, dHits, dTmin, c->stream)) return rc;
-  HIP_TRY(hipMemcpyAsync(sh, dSh, n * 108, hipMemcpyDeviceToHost, c->stream));
-  if (cube) HIP_TRY(hipMemcpyAsync(cube, dCube, n * K * 12, hipMemcpyDeviceToHost, c->stream));
-  if (hits) HIP_TRY(hipMemcpyAsync(hits, dHits, n * 4, hipMemcpyDeviceToHost, c->stream));
-  if (tmin) HIP_TRY(hipMemcpyAsync(tmin, dTmin, n * 4, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return DrainEvents(c);   // the chunks are complete: fold their event pairs into the kernel time
+  return ProbeHost(c, n, points, stream_ids, params, nullptr, sh, cube, hits, tmin, nullptr);
 }
 
 int qa_probe_shade_device(qa_ctx *c, uint64_t n, const float *d_sh, uint64_t probes, const float *d_normals, const int32_t *d_index,
@@ -341,24 +344,7 @@ int qa_probevis_sh(qa_ctx *c, uint64_t n, const float *points, const uint32_t *s
   if (int rc = Enter(c)) return rc;
   if (int rc = ProbeVisChecks(c, n, points != nullptr, params, vis, moments != nullptr)) return rc;
   if (n == 0) return QA_OK;
-  // qa_probe_sh's staging and, in floats per probe, 12 d^2 of moments behind it
-  const uint64_t K = 6ull * params->m * params->m, cells = 12ull * vis->d * vis->d;
-  HIP_TRY(c->stageQuery.Reserve((size_t) n * (33 + cells + (cube ? 3 * K : 0)) * sizeof(float)));
-  float *dSh = (float *) c->stageQuery.p;
-  uint32_t *dHits = (uint32_t *) (dSh + 27 * n);
-  float *dTmin = (float *) (dHits + n);
-  uint32_t *dStream = (uint32_t *) (dTmin + n);
-  float *dP = (float *) (dStream + n), *dMoments = dP + 3 * n, *dCube = cube ? dMoments + cells * n : nullptr;
-  HIP_TRY(hipMemcpyAsync(dP, points, n * 12, hipMemcpyHostToDevice, c->stream));
-  if (stream_ids) HIP_TRY(hipMemcpyAsync(dStream, stream_ids, n * 4, hipMemcpyHostToDevice, c->stream));
-  if (int rc = ProbeBatch(c, n, dP, stream_ids ? dStream : nullptr, params, dSh, dCube, dHits, dTmin, c->stream, vis, dMoments)) return rc;
-  if (sh) HIP_TRY(hipMemcpyAsync(sh, dSh, n * 108, hipMemcpyDeviceToHost, c->stream));
-  if (cube) HIP_TRY(hipMemcpyAsync(cube, dCube, n * K * 12, hipMemcpyDeviceToHost, c->stream));
-  if (hits) HIP_TRY(hipMemcpyAsync(hits, dHits, n * 4, hipMemcpyDeviceToHost, c->stream));
-  if (tmin) HIP_TRY(hipMemcpyAsync(tmin, dTmin, n * 4, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(moments, dMoments, n * cells * 4, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return DrainEvents(c);
+  return ProbeHost(c, n, points, stream_ids, params, vis, sh, cube, hits, tmin, moments);
 }
 
 int qa_probevis_grid_shade_device(qa_ctx *c, uint64_t n, const float *d_sh, const float *d_moments, int d, const float *origin, const float *spacing,

@@ -13,6 +13,7 @@
 #include "qa_firsthit.h"
 #include "qa_ctx.h"
 #include "qa_matte_dev.h"
+#include "qa_stage.h"
 
 namespace qa {
 
@@ -174,20 +175,14 @@ int qa_matte_region(qa_ctx *c, int x0, int y0, int x1, int y1, uint32_t spp, con
   if (int rc = Enter(c)) return rc;
   const MattePlanes host = {coverage, albedo, normal, backdrop};
   if (int rc = CheckMatte(c, x0, y0, x1, y1, spp, host)) return rc;   // before anything is sized by the region
-  // staging [coverage 4 | albedo 12 | normal 12 | backdrop 12 | ns 4] bytes per pixel: only grows, and is only used synchronously
   const size_t npix = (size_t) (x1 - x0) * (size_t) (y1 - y0);
-  HIP_TRY(c->stageQuery.Reserve(npix * 44));
-  float *dC = (float *) c->stageQuery.p, *dA = dC + npix, *dN = dA + 3 * npix, *dB = dN + 3 * npix;
-  uint32_t *dS = (uint32_t *) (dB + 3 * npix);
-  if (ns) HIP_TRY(hipMemcpyAsync(dS, ns, npix * 4, hipMemcpyHostToDevice, c->stream));
-  const MattePlanes dev = {coverage ? dC : nullptr, albedo ? dA : nullptr, normal ? dN : nullptr, backdrop ? dB : nullptr};
-  if (int rc = Matte(c, x0, y0, x1, y1, spp, ns ? dS : nullptr, nullptr, dev, c->stream)) return rc;
-  if (coverage) HIP_TRY(hipMemcpyAsync(coverage, dC, npix * 4, hipMemcpyDeviceToHost, c->stream));
-  if (albedo) HIP_TRY(hipMemcpyAsync(albedo, dA, npix * 12, hipMemcpyDeviceToHost, c->stream));
-  if (normal) HIP_TRY(hipMemcpyAsync(normal, dN, npix * 12, hipMemcpyDeviceToHost, c->stream));
-  if (backdrop) HIP_TRY(hipMemcpyAsync(backdrop, dB, npix * 12, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return QA_OK;
+  QueryStage st(c);
+  const auto dS = st.In(ns, npix);
+  const auto dC = st.Out(coverage, npix), dA = st.Out(albedo, 3 * npix), dN = st.Out(normal, 3 * npix), dB = st.Out(backdrop, 3 * npix);
+  if (int rc = st.Begin()) return rc;
+  const MattePlanes dev = {st(dC), st(dA), st(dN), st(dB)};
+  if (int rc = Matte(c, x0, y0, x1, y1, spp, st(dS), nullptr, dev, c->stream)) return rc;
+  return st.End();
 }
 
 int qa_progressive_matte_device(qa_ctx *c, float *d_coverage, float *d_albedo, float *d_normal, float *d_backdrop, void *hip_stream)

@@ -55,6 +55,7 @@
 
 #include "qa_firsthit.h"
 #include "qa_raybatch.h"
+#include "qa_stage.h"
 
 static_assert(QA_RAYS_PER_SAMPLE == QA_RADIANCE_PER_SAMPLE && QA_RAYS_MISS_ENVIRONMENT == QA_RADIANCE_MISS_ENVIRONMENT, "RayBatch::flags are the C ABI's");
 
@@ -135,26 +136,17 @@ int qa_radiance_rays(qa_ctx *c, uint64_t n, const float *origins, const float *d
   if (int rc = Enter(c)) return rc;
   if (int rc = RayBatchChecks(c, n, origins && dirs, dx != nullptr, dy != nullptr, screen != nullptr, params, rgb != nullptr, QA_RADIANCE_FLAGS, true)) return rc;
   if (n == 0) return QA_OK;
-  // staging, in floats per ray: [rgb 3 | t 1 | ns 1 | stream 1] then per record [origins 3 | dirs 3 | dx 3 | dy 3 | screen 2]
+  // the ray arrays hold a record per ray, or per ray and sample; dx and dy come both or neither (RayBatchChecks)
   const uint64_t r = n * ((params->flags & QA_RADIANCE_PER_SAMPLE) ? (uint64_t) params->spp : 1ull);
-  HIP_TRY(c->stageQuery.Reserve((size_t) (n * 6 + r * 14) * sizeof(float)));
-  float *dRgb = (float *) c->stageQuery.p, *dT = dRgb + 3 * n;
-  uint32_t *dNs = (uint32_t *) (dT + n), *dStream = dNs + n;
-  float *dO = (float *) (dStream + n), *dD = dO + 3 * r, *dDx = dD + 3 * r, *dDy = dDx + 3 * r, *dScreen = dDy + 3 * r;
-  HIP_TRY(hipMemcpyAsync(dO, origins, r * 12, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(dD, dirs, r * 12, hipMemcpyHostToDevice, c->stream));
-  if (dx) {
-    HIP_TRY(hipMemcpyAsync(dDx, dx, r * 12, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(dDy, dy, r * 12, hipMemcpyHostToDevice, c->stream));
-  }
-  if (screen) HIP_TRY(hipMemcpyAsync(dScreen, screen, r * 8, hipMemcpyHostToDevice, c->stream));
-  if (stream) HIP_TRY(hipMemcpyAsync(dStream, stream, n * 4, hipMemcpyHostToDevice, c->stream));
-  const RayBatch rb = {dO, dD, dx ? dDx : nullptr, dx ? dDy : nullptr, screen ? dScreen : nullptr, stream ? dStream : nullptr, (uint32_t) n, params->flags & QA_RAYBATCH_FLAGS};
-  if (int rc = LaunchRayBatch(c, PickFor(c, params), n, rb, *params, dRgb, t ? dT : nullptr, ns ? dNs : nullptr, c->stream)) return rc;
-  HIP_TRY(hipMemcpyAsync(rgb, dRgb, n * 12, hipMemcpyDeviceToHost, c->stream));
-  if (t) HIP_TRY(hipMemcpyAsync(t, dT, n * 4, hipMemcpyDeviceToHost, c->stream));
-  if (ns) HIP_TRY(hipMemcpyAsync(ns, dNs, n * 4, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
+  QueryStage st(c);
+  const auto dO = st.In(origins, 3 * r), dD = st.In(dirs, 3 * r), dDx = st.In(dx, 3 * r), dDy = st.In(dy, 3 * r), dScreen = st.In(screen, 2 * r);
+  const auto dStream = st.In(stream, n);
+  const auto dRgb = st.Out(rgb, 3 * n), dT = st.Out(t, n);
+  const auto dNs = st.Out(ns, n);
+  if (int rc = st.Begin()) return rc;
+  const RayBatch rb = {st(dO), st(dD), st(dDx), st(dDy), st(dScreen), st(dStream), (uint32_t) n, params->flags & QA_RAYBATCH_FLAGS};
+  if (int rc = LaunchRayBatch(c, PickFor(c, params), n, rb, *params, st(dRgb), st(dT), st(dNs), c->stream)) return rc;
+  if (int rc = st.End()) return rc;
   return DrainEvents(c);   // the batch is complete: fold its event pair into the kernel time
 }
 

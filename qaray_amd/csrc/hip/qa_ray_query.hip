@@ -35,6 +35,7 @@
 
 #include "qa_firsthit.h"
 #include "qa_ctx.h"
+#include "qa_stage.h"
 
 namespace qa {
 
@@ -194,19 +195,13 @@ int qa_cast_rays(qa_ctx *c, uint64_t n, const float *origins, const float *dirs,
   if (int rc = Enter(c)) return rc;
   if (int rc = QueryChecks(c, n, origins && dirs, t || ids || normal || point)) return rc;   // before anything is sized by n
   if (n == 0) return QA_OK;
-  // staging [origins 12 | dirs 12 | normal 12 | point 12 | t 4 | ids 8] bytes per ray
-  HIP_TRY(c->stageQuery.Reserve((size_t) n * 60));
-  float *dO = (float *) c->stageQuery.p, *dD = dO + 3 * n, *dN = dD + 3 * n, *dP = dN + 3 * n, *dT = dP + 3 * n;
-  int32_t *dI = (int32_t *) (dT + n);
-  HIP_TRY(hipMemcpyAsync(dO, origins, n * 12, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(dD, dirs, n * 12, hipMemcpyHostToDevice, c->stream));
-  if (int rc = CastRays(c, n, dO, dD, t ? dT : nullptr, ids ? dI : nullptr, normal ? dN : nullptr, point ? dP : nullptr, c->stream)) return rc;
-  if (t) HIP_TRY(hipMemcpyAsync(t, dT, n * 4, hipMemcpyDeviceToHost, c->stream));
-  if (ids) HIP_TRY(hipMemcpyAsync(ids, dI, n * 8, hipMemcpyDeviceToHost, c->stream));
-  if (normal) HIP_TRY(hipMemcpyAsync(normal, dN, n * 12, hipMemcpyDeviceToHost, c->stream));
-  if (point) HIP_TRY(hipMemcpyAsync(point, dP, n * 12, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return QA_OK;
+  QueryStage st(c);
+  const auto dO = st.In(origins, 3 * n), dD = st.In(dirs, 3 * n);
+  const auto dT = st.Out(t, n), dN = st.Out(normal, 3 * n), dP = st.Out(point, 3 * n);
+  const auto dI = st.Out(ids, 2 * n);
+  if (int rc = st.Begin()) return rc;
+  if (int rc = CastRays(c, n, st(dO), st(dD), st(dT), st(dI), st(dN), st(dP), c->stream)) return rc;
+  return st.End();
 }
 
 int qa_occluded_device(qa_ctx *c, uint64_t n, const float *d_origins, const float *d_dirs, const float *d_tmax, uint8_t *d_out, void *hip_stream)
@@ -220,17 +215,12 @@ int qa_occluded(qa_ctx *c, uint64_t n, const float *origins, const float *dirs, 
   if (int rc = Enter(c)) return rc;
   if (int rc = QueryChecks(c, n, origins && dirs && tmax, out != nullptr)) return rc;
   if (n == 0) return QA_OK;
-  // staging [origins 12 | dirs 12 | tmax 4 | out 1] bytes per ray
-  HIP_TRY(c->stageQuery.Reserve((size_t) n * 29));
-  float *dO = (float *) c->stageQuery.p, *dD = dO + 3 * n, *dT = dD + 3 * n;
-  uint8_t *dOut = (uint8_t *) (dT + n);
-  HIP_TRY(hipMemcpyAsync(dO, origins, n * 12, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(dD, dirs, n * 12, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(dT, tmax, n * 4, hipMemcpyHostToDevice, c->stream));
-  if (int rc = Occluded(c, n, dO, dD, dT, dOut, c->stream)) return rc;
-  HIP_TRY(hipMemcpyAsync(out, dOut, n, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return QA_OK;
+  QueryStage st(c);
+  const auto dO = st.In(origins, 3 * n), dD = st.In(dirs, 3 * n), dT = st.In(tmax, n);
+  const auto dOut = st.Out(out, n);
+  if (int rc = st.Begin()) return rc;
+  if (int rc = Occluded(c, n, st(dO), st(dD), st(dT), st(dOut), c->stream)) return rc;
+  return st.End();
 }
 
 int qa_camera_rays_device(qa_ctx *c, int x0, int y0, int x1, int y1, uint32_t seed, float *d_origins, float *d_dirs, void *hip_stream)
